@@ -10,6 +10,8 @@ A step = ONE decode of one batch of synthetic LLRs (already resident in HBM) thr
 hot path: T iterations of check + variable updates, syndrome, hard decisions out.
 Default workload = BASELINE.json configs[1]: (1998,1512) code, BasicMinSumDecoder factor 0.7,
 fp32, 10 iterations, batch 65536 per GPU, SNR 2.0 dB, fixed iterations (early_stop=False).
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy: the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one process per GPU.  Started bare (`python bench.py --gpus N`, no WORLD_SIZE in the
 environment) the script spawns its N ranks itself as child processes BEFORE anything touches the
@@ -85,7 +87,13 @@ def parse_args(argv=None):
                     help="total codewords of the strong-scaling config-5 leg of a multi-rank run (BASELINE.json: 262144)")
     ap.add_argument("--config5-max-per-gpu", type=int, default=262144,
                     help="skip that leg when total / N exceeds this many codewords per GPU (memory: ~0.42 MB per codeword)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32, the posterior in "
+                         "the engine's dtype; a fixed, seeded sample of rows, at most 64 MB in all) -- compares builds output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ----------------------------------------------------------------------------------- self-launch
@@ -653,6 +661,43 @@ class ShardedRun:
         self.torch.cuda.empty_cache()
 
 
+DUMP_BYTES = 64_000_000       # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 20251015           # the row sample depends on this and the shapes only, never on the data
+
+
+def dump_outputs(path, res, gathered):
+    """--dump-outputs: the arrays the timed step handed its caller in its last step (DecodeResult fields; with a process
+    group also the all-gathered bit-packed hard decisions) -> path/<name>.npy.  Integers and flags as float32 (exact), the
+    posterior in the engine's dtype.  When the batch is larger than the budget, ONE seeded sample of rows is taken for all
+    per-codeword arrays (rows.npy holds its indices; gathered_rows.npy those of the gathered array)."""
+    import numpy as np
+    import torch
+    B = res.iterations.shape[0]
+    per = {"bits": res.bits, "posterior": res.posterior, "iterations": res.iterations, "success": res.success}
+    per = {k: v for k, v in per.items() if v is not None}
+    row_bytes = 8 + sum((v[0].numel() if v.dim() > 1 else 1) * (8 if v.dtype == torch.float64 else 4) for v in per.values())
+    G = 0 if gathered is None else gathered.shape[0]
+    if G:
+        row_bytes += 8 + 4 * gathered.shape[1]
+    k = max(1, min(B, (DUMP_BYTES - 16 * 4096) // row_bytes))      # 4 KB per file for the headers, 16 files at most
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.arange(B) if k == B else np.sort(rng.choice(B, size=k, replace=False))
+    out = {"rows": rows.astype(np.float64)}
+    idx = torch.from_numpy(rows).to(res.iterations.device)
+    for name, v in per.items():
+        a = v.index_select(0, idx).cpu().numpy()
+        out[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    if G:
+        grows = np.arange(G) if min(k, G) == G else np.sort(rng.choice(G, size=k, replace=False))
+        out["gathered_rows"] = grows.astype(np.float64)
+        out["gathered_packed_bits"] = gathered.index_select(0, torch.from_numpy(grows).to(gathered.device)).cpu().numpy().astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": path, "rows": int(k), "of": int(B), "files": sorted(n + ".npy" for n in out),
+            "bytes": int(sum(os.path.getsize(os.path.join(path, n + ".npy")) for n in out))}
+
+
 def max_over_ranks(x, ctx):
     if not ctx["use_dist"]:
         return float(x)
@@ -759,6 +804,7 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = B * world * args.steps / elapsed
     ver = main_run.verify()                                       # nothing skipped; gathered == the ranks' shards
+    dumped = dump_outputs(args.dump_outputs, main_run.res, main_run.gathered) if args.dump_outputs and rank == 0 else None
     inventory = rank_inventory(ctx)
     allgather = main_run.gather_alone()
 
@@ -778,6 +824,8 @@ def main():
                                  "config is defined on fp32 (BASELINE.json north_star, SURVEY 8d) -- the float64 kernels "
                                  "run as the `basic_f64` leg; fp32-vs-fp64 decision mismatch rates are in BASELINE.md"},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if use_dist:
         out["distributed"] = {**inventory, "allgather": allgather, "gather_check": ver.get("gather_check"),
                               "step": "decode of this rank's shard, then all_gather_into_tensor of uint8[B, ceil(n/8)]; "
