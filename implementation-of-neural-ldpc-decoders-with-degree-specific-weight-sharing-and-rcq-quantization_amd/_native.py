@@ -19,7 +19,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libldpc_hip.so"
-LIB_PATH = os.environ.get("LDPC_HIP_LIB") or os.path.join(_HERE, LIB_NAME)   # override: A/B kernel variants
+LIB_PATH = os.environ.get("LDPC_HIP_LIB") or os.path.join(_HERE, LIB_NAME)   # override: load another build
 CSRC = os.path.join(_HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "ldpc_hip.h")
 DEBUG_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ldpc_hip_debug.h")
@@ -80,7 +80,7 @@ def is_stale(target: Optional[str] = None, defines=()) -> bool:
 def build_native(force: bool = False, verbose: bool = False, defines=(), out: Optional[str] = None) -> str:
     """hipcc cross-compile of csrc/ldpc_hip.hip for gfx950 into the package dir; skipped when the library on disk was
     built from exactly these sources with exactly this recipe (content hash embedded in the library, not file times).
-    `defines`/`out` build tuning variants (tools/sweep_variants.py)."""
+    `defines` (extra -D macros) and `out` (another target path) build the same sources with a modified recipe."""
     srcs = _source_files()
     target = out or os.path.join(_HERE, LIB_NAME)
     want = source_hash(defines)

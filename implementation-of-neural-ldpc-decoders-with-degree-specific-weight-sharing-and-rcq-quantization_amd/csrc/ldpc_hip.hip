@@ -136,9 +136,6 @@ bool use_gather(const ldpc_decoder *d) { return d->gat_ok && !use_pair(d) && d->
 // VEC 1 for latency-mode batches <= 64; fp64: VEC 2 / 1.
 int pick_vec(const ldpc_decoder *d, int64_t batch)
 {
-#ifdef LDPC_RESIDENT_PROBES                          // tuning builds: LDPC_STREAM_VEC=1 forces 64-codeword tiles
-    { const char *ev = getenv("LDPC_STREAM_VEC"); if (ev && atoi(ev) == 1) return 1; }
-#endif
     if (batch <= 64) return 1;
     if (d->schedule != LDPC_SCHED_FLOODING) return 1;      // layered: one dependent chain per wave, as many waves as possible
     return d->dtype == LDPC_F64 ? 2 : 4;
@@ -328,7 +325,7 @@ int launch_vn(const ldpc_decoder *d, const Workspace &w, int it, bool last, bool
             const int lut_cur = codes ? d->q_of_iter[row] * lut_stride : 0;
             const size_t shmem = vn_rows_stage_bytes() + (size_t)lut_total * sizeof(float);
             const int vb = (g.n + kRowsVars - 1) / kRowsVars;
-            const dim3 grid((unsigned)((size_t)w.tiles * rows_grid_chunks(vb, LDPC_ROWS_XCD != 0))), block(kRowsThreads);
+            const dim3 grid((unsigned)((size_t)w.tiles * rows_grid_chunks(vb, true))), block(kRowsThreads);
             const uint64_t *done = use_done ? w.done : nullptr;
 #define LDPC_VR(CODES)                                                                                          \
     do {                                                                                                        \
@@ -442,16 +439,16 @@ int launch_vn_q(const ldpc_decoder *d, const Workspace &w, int it, bool use_done
     hipLaunchKernelGGL((vn_sweep_q<VEC, NL_>), grid, block, shmem, s, g, (const uint8_t *)w.c2v, (const float *)w.llrT, \
                        (uint8_t *)w.v2c, alpha_row, (const int *)d->alpha_slot, lut_cur, lut_entries, beta_next,        \
                        (const int *)d->beta_slot, thr_next, d->n_levels, w.bitsT, done, vb)
-    const int vb4 = (g.n + kWavesPerBlock * LDPC_VNQ_VPW - 1) / (kWavesPerBlock * LDPC_VNQ_VPW);
+    const int vb4 = (g.n + kWavesPerBlock * kVnqVpw - 1) / (kWavesPerBlock * kVnqVpw);
     const dim3 grid4((unsigned)((size_t)w.tiles * vb4));
 #define LDPC_VQ4(NL_, ES_)                                                                                            \
-    hipLaunchKernelGGL((vn_sweep_q4<NL_, ES_, LDPC_VNQ_VPW>), grid4, block, shmem, s, g, (const uint8_t *)w.c2v,         \
+    hipLaunchKernelGGL((vn_sweep_q4<NL_, ES_, kVnqVpw>), grid4, block, shmem, s, g, (const uint8_t *)w.c2v,         \
                        (const float *)w.llrT, (uint8_t *)w.v2c, alpha_row, (const int *)d->alpha_slot, lut_cur,         \
                        lut_entries, beta_next, (const int *)d->beta_slot, thr_next, d->n_levels, w.bitsT, done, vb4)
     if (init) {
         if (!pair_q4<VEC>(d)) return fail(LDPC_ERR_ARG, "internal: code-pair initial pass on a decoder without vn_sweep_q4");
 #define LDPC_VQI(NL_)                                                                                                 \
-    hipLaunchKernelGGL((vn_sweep_q4<NL_, false, LDPC_VNQ_VPW, true>), grid4, block, 0, s, g, (const uint8_t *)w.c2v,     \
+    hipLaunchKernelGGL((vn_sweep_q4<NL_, false, kVnqVpw, true>), grid4, block, 0, s, g, (const uint8_t *)w.c2v,     \
                        (const float *)w.llrT, (uint8_t *)w.v2c, alpha_row, (const int *)d->alpha_slot, lut_cur,         \
                        lut_entries, beta_next, (const int *)d->beta_slot, thr_next, d->n_levels, w.bitsT, done, vb4)
         if (d->key_float4) LDPC_VQI(kKeyFloat4); else if (d->n_levels == 4) LDPC_VQI(4); else LDPC_VQI(0);
@@ -480,12 +477,9 @@ int launch_gather(const ldpc_decoder *d, const Workspace &w, int it, bool use_do
     if (cb == 0 || g.E == 0) return LDPC_OK;
     // XCD-affine tile mapping when the rows one tile touches (LLRs + both code buffers) fit an XCD's 4 MiB L2: the re-reads
     // then hit there instead of going through the fabric (measured, (1998,1512) RCQ: 6.28 -> 5.85 ms per decode; on the
-    // (16200,7200) code, 29 MB per tile, it costs 3 %: gpurun_out/xcd1)
+    // (16200,7200) code, 29 MB per tile, it costs 3 %)
     constexpr int W = 64 * VEC;
-    int xcd_tiles = (w.tiles >= 16 && ((size_t)4 * g.n + 2 * (size_t)g.E) * W <= (4u << 20)) ? w.tiles : 0;
-#ifdef LDPC_RESIDENT_PROBES                          // tuning builds: LDPC_GATHER_XCD=0/1 overrides
-    { const char *ex = getenv("LDPC_GATHER_XCD"); if (ex) xcd_tiles = atoi(ex) > 0 ? w.tiles : 0; }
-#endif
+    const int xcd_tiles = (w.tiles >= 16 && ((size_t)4 * g.n + 2 * (size_t)g.E) * W <= (4u << 20)) ? w.tiles : 0;
     const size_t tiles_padded = xcd_tiles ? (size_t)((w.tiles + 7) / 8) * 8 : (size_t)w.tiles;
     const dim3 grid((unsigned)(tiles_padded * cb)), block(kBlock);
     const float *beta_row = (const float *)d->beta + (size_t)it * d->n_beta;
@@ -496,7 +490,7 @@ int launch_gather(const ldpc_decoder *d, const Workspace &w, int it, bool use_do
     const size_t shmem = (size_t)lut_entries * sizeof(float);
     const uint64_t *done = use_done ? w.done : nullptr;
 #define LDPC_GA(NL_, BPC_, CPW_)                                                                                     \
-    hipLaunchKernelGGL((cn_gather<VEC, NL_, BPC_, CPW_, LDPC_GATHER_GRP>), grid, block, shmem, s, g,                  \
+    hipLaunchKernelGGL((cn_gather<VEC, NL_, BPC_, CPW_, kGatherGrp>), grid, block, shmem, s, g,                  \
                        (const int4 *)d->gat_meta, (const int *)d->gat_nbr, (const float *)w.llrT, (const uint8_t *)cin, \
                        (uint8_t *)cout, beta_row, (const int *)d->beta_slot, alpha_prev, thr, d->n_levels, lut_prev,   \
                        lut_entries, done, cb, xcd_tiles)
@@ -857,10 +851,6 @@ struct LaneCost {
 void optimise_lane_order(std::vector<int> &order, const std::vector<std::vector<int>> &vs, int G)
 {
     if (G != 1 && G != 2) return;
-#ifdef LDPC_RESIDENT_PROBES                         // tuning builds only (tools/): the product library reads no environment
-    const char *off = getenv("LDPC_RESIDENT_NO_LANE_OPT");
-    if (off && atoi(off)) return;
-#endif
     LaneCost lc{vs, order, 32, 32, G == 2 ? 16 : 32, G == 2 ? 16 : 32};
     const int n = (int)order.size();
     std::vector<std::pair<int, int>> classes;
@@ -935,17 +925,11 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     // the other's phase -- measured best on the (1998,1512) code; larger codes fall back to one workgroup
     // per CU or G = 1.  A row stride of 512 slots (instead of m) lets LDS instructions carry t*stride as an
     // immediate offset; it is taken when it costs neither G nor workgroups per CU.
-    // LDPC_RESIDENT_G / _NT override for tuning (read only by -DLDPC_RESIDENT_PROBES builds).
     auto geometry = [&](int stride, int &G_out, int &blocks_out) {
         const long long S_ = (long long)max_sub * stride;
         const int mp = is_pow2(stride) ? m : 0;           // parity words of the early-stop syndrome (power-of-two strides)
         if (S_ > 65535 || !resident_fits(d, S_, 1, 1, mp)) return false;
-        int G_ = 0;
-#ifdef LDPC_RESIDENT_PROBES
-        const char *eg = getenv("LDPC_RESIDENT_G");
-        if (eg) G_ = atoi(eg);
-#endif
-        if (!((G_ == 1 || G_ == 2) && resident_fits(d, S_, G_, 1, mp))) G_ = resident_fits(d, S_, 2, 1, mp) ? 2 : 1;
+        const int G_ = resident_fits(d, S_, 2, 1, mp) ? 2 : 1;
         int b_ = 1;
         while (b_ < 8 && resident_fits(d, S_, G_, b_ + 1, mp)) ++b_;
         G_out = G_; blocks_out = b_;
@@ -959,11 +943,7 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
         if (geometry(512, G5, b5) && G5 == G && std::min(b5, 2) == std::min(blocks, 2)) { mstride = 512; blocks = b5; }
     }
     const long long S = (long long)max_sub * mstride;
-    int NT = 0;
-#ifdef LDPC_RESIDENT_PROBES
-    { const char *en = getenv("LDPC_RESIDENT_NT"); if (en) NT = atoi(en); }
-#endif
-    if (NT < 64 || NT > 1024 || NT % 64) NT = blocks >= 2 ? 512 : 1024;
+    const int NT = blocks >= 2 ? 512 : 1024;
 
     std::vector<int> perm_v(n), pos_v(n);
     for (int j = 0; j < n; ++j) perm_v[j] = j;
@@ -1055,7 +1035,7 @@ int allow_full_lds(const void *kfn, int device)
 template <int G>
 int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
 {
-    size_t lds = d->res_lds;
+    const size_t lds = d->res_lds;
     if (d->dtype == LDPC_F64) {                       // one fp64 codeword per workgroup in the slots of a float pair
         if (G != 2 || !d->res.bslot_c) return fail(LDPC_ERR_ARG, "internal: fp64 resident geometry");
         const unsigned blocks64 = (unsigned)a.batch;
@@ -1075,9 +1055,6 @@ int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
         return LDPC_OK;
     }
     const unsigned blocks = (unsigned)((a.batch + G - 1) / G);
-#ifdef LDPC_RESIDENT_PROBES
-    { const char *pad = getenv("LDPC_RES_LDS_PAD"); if (pad && atoi(pad) > 0) lds = std::min<size_t>(lds + atoi(pad), 160 * 1024); }  // occupancy experiments
-#endif
 #define LDPC_RES_MS(FORM, NL, MS, SPLIT)                                                                 \
     do {                                                                                                 \
         auto kfn = d->res.bslot_c ? (a.early_stop ? resident_decode<G, FORM, true, NL, MS, 1, float, SPLIT>     \
@@ -1119,9 +1096,6 @@ int decode_resident(const ldpc_decoder *d, const void *llr, int64_t batch, int32
     a.bits = bits; a.posterior = (float *)posterior; a.iterations = iterations; a.success = success;
     a.packed = packed_bits;
     a.dbg_c2v = dbg_c2v;
-#ifdef LDPC_RESIDENT_PROBES                          // phase-timing probes of tools/resident_probe*.sh; never in the product build
-    { const char *dbg = getenv("LDPC_RES_DEBUG"); a.debug_skip = dbg ? atoi(dbg) : 0; }
-#endif
     a.alpha_in_lds = resident_alpha_floats(d) > 0;
     a.unit_alpha = d->unit_alpha; a.rcq_zero0 = d->rcq_zero0;
     hipStream_t rs = (hipStream_t)stream;
@@ -1154,34 +1128,15 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
         const int e0 = g->h_check_ptr[row], dc = g->h_check_ptr[row + 1] - e0, k = t - (lw - dc);
         return k >= 0 ? g->h_var_idx[e0 + k] : -1;
     };
-    std::vector<char> group_late((size_t)m_pad / kLayPf, 0);
-    group_late[0] = 1;                                                // its first row follows the previous iteration's last check
     for (int i = 0; i < m_pad; ++i) {
         const int dc = i < g->m ? g->h_check_ptr[i + 1] - g->h_check_ptr[i] : 0;
         deg1 = deg1 || dc == 1;
-        // dependence on the previous plan row
-        const int p = (i + m_pad - 1) % m_pad;
-        int shared = 0, src_lane = -1, dst_lane = -1;
-        for (int t = 0; t < lw; ++t) {
-            const int v = var_at(i, t);
-            if (v < 0) continue;
-            for (int u = 0; u < lw; ++u)
-                if (var_at(p, u) == v) { ++shared; src_lane = u; dst_lane = t; }
-        }
-        // one common variable whose lane in this row is the lower neighbour of its lane in the previous row: forwarded by a
-        // DPP row_shl:1 (row = 16 lanes; the pair must not straddle a DPP row).  Right-aligned ascending order makes the
-        // parity chain of staircase codes exactly that.  Anything else with a common variable: LATE (its whole group).
-        const bool fwd = shared == 1 && src_lane == dst_lane + 1 && (src_lane / 16 == dst_lane / 16);
-        if (shared > 0 && !fwd) group_late[(size_t)i / kLayPf] = 1;
         for (int t = 0; t < lw; ++t) {
             const int v = var_at(i, t);
             const uint32_t o = v >= 0 ? (uint32_t)v * 4u : none;
-            off[(size_t)i * lw + t] = o | ((fwd && t == dst_lane) ? kLayFwdBit : 0u) | (dc == 1 ? kLayDeg1Bit : 0u);
+            off[(size_t)i * lw + t] = o | (dc == 1 ? kLayDeg1Bit : 0u);
         }
     }
-    for (size_t gi = 0; gi < group_late.size(); ++gi)
-        if (group_late[gi])
-            for (int t = 0; t < lw; ++t) off[gi * kLayPf * lw + t] |= kLayLateBit;
     // magnitude 0 reconstructs to 0 under every quantiser (rcq_decoder.py:79-85, :107-119): tau_0 == 0 and no later
     // threshold <= 0 -- true for the reference's C * (j / (2^(bc-1) - 1))^gamma with gamma > 0
     bool zero0 = true;
@@ -1323,9 +1278,6 @@ static int graph_create_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, 
     std::vector<int> wide;
     for (int i = 0; i < m; ++i)
         if (check_ptr[i + 1] - check_ptr[i] > kWideCheck) wide.push_back(i);
-#ifdef LDPC_NO_WIDE_KERNEL                            // A/B timing builds of tools/time_wide.py only
-    wide.clear();
-#endif
     g->n_wide = (int)wide.size();
     if (!rc && g->n_wide) rc = upload(&g->wide_checks, wide.data(), wide.size());
     if (rc) {
@@ -1492,7 +1444,7 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
                 if (!(t > 0.0f) || (k > 1 && t < desc->thresholds[(size_t)q * d->n_levels + k - 1])) { sorted = false; break; }
             }
         d->pair_ok = sorted;
-        bool in_range = sorted && d->n_levels == 4 && LDPC_KEY_FLOAT != 0;
+        bool in_range = sorted && d->n_levels == 4;
         for (int q = 0; q < d->n_quant && in_range; ++q)
             for (int k = 1; k < d->n_levels; ++k) {
                 const float t = desc->thresholds[(size_t)q * d->n_levels + k];

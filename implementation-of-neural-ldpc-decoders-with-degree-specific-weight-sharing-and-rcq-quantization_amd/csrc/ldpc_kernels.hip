@@ -42,35 +42,19 @@ struct alignas(sizeof(T) * V) Pack {
 };
 
 // Message rows are streamed exactly once per sweep (a sweep moves GBs, far beyond the 256 MiB
-// Infinity Cache), so loads/stores may carry the non-temporal hint; knobs for A/B timing.
-#ifndef LDPC_NT_LOAD
-#define LDPC_NT_LOAD 1
-#endif
-#ifndef LDPC_NT_STORE
-#define LDPC_NT_STORE 1
-#endif
-#ifndef LDPC_CN_UNROLL
-#define LDPC_CN_UNROLL 4
-#endif
-#ifndef LDPC_GATHER_GRP
-#define LDPC_GATHER_GRP 2      // edges per load group of the fused RCQ iteration kernel (cn_gather); measured on the
-                               // (16200,7200) code: 2 edges / 5 waves 2.22 ms per launch, 3/4: 2.40, 4/4: 2.43, 4/3: 2.87,
-                               // 6/2: 3.85, 8/2: 3.94 (occupancy beats deeper groups: the kernel is issue- and latency-bound)
-#endif
-#ifndef LDPC_GATHER_WAVES
-#define LDPC_GATHER_WAVES 5    // waves per SIMD the register allocation of cn_gather must leave room for
-#endif
+// Infinity Cache), so loads/stores carry the non-temporal hint.
+constexpr int kCnUnroll = 4;         // unroll of the edge loops of the check sweeps
+constexpr int kGatherGrp = 2;        // edges per load group of the fused RCQ iteration kernel (cn_gather); measured on the
+                                     // (16200,7200) code: 2 edges / 5 waves 2.22 ms per launch, 3/4: 2.40, 4/4: 2.43, 4/3: 2.87,
+                                     // 6/2: 3.85, 8/2: 3.94 (occupancy beats deeper groups: the kernel is issue- and latency-bound)
+constexpr int kGatherWaves = 5;      // waves per SIMD the register allocation of cn_gather must leave room for
 
 template <typename T, int V>
 __device__ __forceinline__ Pack<T, V> ld(const T *p)
 {
     typedef T VT __attribute__((ext_vector_type(V)));
     union { VT v; Pack<T, V> k; } u;
-#if LDPC_NT_LOAD
     u.v = __builtin_nontemporal_load(reinterpret_cast<const VT *>(p));
-#else
-    u.v = *reinterpret_cast<const VT *>(p);
-#endif
     return u.k;
 }
 template <typename T, int V>
@@ -79,11 +63,7 @@ __device__ __forceinline__ void st(T *p, const Pack<T, V> &v)
     typedef T VT __attribute__((ext_vector_type(V)));
     union { VT v; Pack<T, V> k; } u;
     u.k = v;
-#if LDPC_NT_STORE
     __builtin_nontemporal_store(u.v, reinterpret_cast<VT *>(p));
-#else
-    *reinterpret_cast<VT *>(p) = u.v;
-#endif
 }
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -241,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void cn_sweep(GraphDev g, const T *__restri
         m1[c] = inf_of<T>(); m2[c] = inf_of<T>(); idx[c] = 0; sm[c] = 0; zm[c] = 0; par[c] = 0; nz[c] = 0;
     }
 
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
     for (int t = 0; t < dc; ++t) {
         const T *row = FIRST ? in_base + (size_t)g.var_idx[e0 + t] * W : in_base + (size_t)t * W;
         Pack<T, VEC> v = ld<T, VEC>(row);
@@ -297,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void cn_sweep(GraphDev g, const T *__restri
             cc1[c] = (l1 + (s1 ? z1 : 0u)) | ((l1 + (s1 ? 0u : z1)) << 8);
             cc2[c] = (l2 + (s2 ? z2 : 0u)) | ((l2 + (s2 ? 0u : z2)) << 8);
         }
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
         for (int t = 0; t < dc; ++t) {
             Pack<T, VEC> re;
             if (wide) {
@@ -316,7 +296,7 @@ __global__ __launch_bounds__(kBlock) void cn_sweep(GraphDev g, const T *__restri
         }
         continue;
     }
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
     for (int t = 0; t < dc; ++t) {
         const T b = beta_row[beta_slot[e0 + t]];
         T oa = (T)0;
@@ -442,11 +422,9 @@ __device__ __forceinline__ void cn_f4_check(const GraphDev &g, int e0, const flo
     }
 }
 
-#ifndef LDPC_CNF4_WAVES
-#define LDPC_CNF4_WAVES 5          // waves per SIMD the register allocation leaves room for (16 rows x 4 floats are held per lane)
-#endif
+constexpr int kCnf4Waves = 5;      // waves per SIMD the register allocation leaves room for (16 rows x 4 floats are held per lane)
 template <bool FIRST, bool BPC, bool ES>
-__global__ __launch_bounds__(kBlock, LDPC_CNF4_WAVES) void cn_sweep_f4(GraphDev g, const float *__restrict__ src, float *__restrict__ c2v_out,
+__global__ __launch_bounds__(kBlock, kCnf4Waves) void cn_sweep_f4(GraphDev g, const float *__restrict__ src, float *__restrict__ c2v_out,
                                                       const float *__restrict__ beta_row, const int *__restrict__ beta_slot,
                                                       const uint64_t *__restrict__ done, int check_blocks)
 {
@@ -932,19 +910,12 @@ template <typename V, typename T> __device__ __forceinline__ void vec_set(V &v, 
 
 constexpr int kRowsVars = 64;
 constexpr int kRowsStride = kRowsVars + 1;
-#ifndef LDPC_ROWS_XCD
-#define LDPC_ROWS_XCD 1              // vn_last_rows: the variable chunks of a tile are dealt to the XCDs in CONTIGUOUS ranges (workgroups go
-                                     // round-robin over the 8 XCDs, each with its own L2): a caller row is 4n bytes, not a multiple of the
-                                     // 128-byte line, so every chunk boundary splits a line between two workgroups -- on the same XCD the
-                                     // two halves meet in one L2, written with plain (temporal) stores.  Config 5, per launch
-                                     // (tools/experiments/rows_xcd_round.sh and the r03 profiles): plain order + non-temporal 2.20 ms,
-                                     // XCD-contiguous + non-temporal 2.16, XCD-contiguous + temporal 1.96, plain order + temporal 2.40.
-                                     // transpose_in_q4 keeps the plain order (1.16 ms; XCD-contiguous 1.31: its tile-row writes lose
-                                     // their order).
-#endif
-#ifndef LDPC_ROWS_NT_STORE
-#define LDPC_ROWS_NT_STORE 0         // caller rows of vn_last_rows with non-temporal stores (A/B knob; see above)
-#endif
+// vn_last_rows deals the variable chunks of a tile to the XCDs in CONTIGUOUS ranges (workgroups go round-robin over the 8
+// XCDs, each with its own L2): a caller row is 4n bytes, not a multiple of the 128-byte line, so every chunk boundary splits a
+// line between two workgroups -- on the same XCD the two halves meet in one L2, written with plain (temporal) stores.  Config
+// 5, per launch: plain order + non-temporal 2.20 ms, XCD-contiguous + non-temporal 2.16, XCD-contiguous + temporal 1.96, plain
+// order + temporal 2.40.  transpose_in_q4 keeps the plain order (1.16 ms; XCD-contiguous 1.31: its tile-row writes lose
+// their order).
 // blockIdx -> (tile, variable chunk) of the two boundary kernels; the grid is tiles x rows_grid_chunks(var_blocks, xcd)
 __host__ __device__ inline int rows_grid_chunks(int var_blocks, bool xcd) { return xcd ? (var_blocks + 7) / 8 * 8 : var_blocks; }
 template <bool XCD>
@@ -955,15 +926,6 @@ __device__ __forceinline__ bool rows_block(int var_blocks, int &tile, int &chunk
     const int k = uni((int)(blockIdx.x % gc));
     chunk = XCD ? (k % 8) * (gc / 8) + k / 8 : k;                   // XCD x (= k % 8) owns chunks [x * gc/8, (x + 1) * gc/8)
     return chunk < var_blocks;
-}
-template <typename V>
-__device__ __forceinline__ void rows_store(V v, V *p)
-{
-#if LDPC_ROWS_NT_STORE
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 constexpr int kRowsThreads = 1024;   // 16 waves x 4 variables: the staging tile (66.5 KB) admits two blocks per CU, and the first
                                      // phase needs every wave slot of the CU to keep enough row loads in flight (with 256-thread
@@ -1021,7 +983,7 @@ __global__ __launch_bounds__(kRowsThreads, 8) void vn_last_rows(GraphDev g, cons
     }
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     int tile, chunk;
-    if (!rows_block<LDPC_ROWS_XCD != 0>(var_blocks, tile, chunk)) return;   // block-uniform (padding blocks of the XCD-contiguous grid)
+    if (!rows_block<true>(var_blocks, tile, chunk)) return;   // block-uniform (padding blocks of the XCD-contiguous grid)
     const int j0 = chunk * kRowsVars;
 
     Frozen<VEC> fz;
@@ -1108,8 +1070,8 @@ __global__ __launch_bounds__(kRowsThreads, 8) void vn_last_rows(GraphDev g, cons
             vec_set<IV, int>(d, q, src[q] < 0.0f ? 1 : 0);
         }
         const size_t o = (size_t)b * g.n + j0 + jq;
-        if (posterior) rows_store(v, reinterpret_cast<FV *>(posterior + o));
-        if (bits) rows_store(d, reinterpret_cast<IV *>(bits + o));
+        if (posterior) *reinterpret_cast<FV *>(posterior + o) = v;
+        if (bits) *reinterpret_cast<IV *>(bits + o) = d;
     }
 }
 
@@ -1320,7 +1282,7 @@ __global__ __launch_bounds__(kBlock) void cn_sweep_q(GraphDev g, const uint8_t *
                 }
             }
         } else {
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
             for (int t = 0; t < dc; ++t) {
                 const Pack<uint8_t, VEC> v = ld<uint8_t, VEC>(in_base + (size_t)t * W);
 #pragma unroll
@@ -1353,7 +1315,7 @@ __global__ __launch_bounds__(kBlock) void cn_sweep_q(GraphDev g, const uint8_t *
             for (int t = 0; t < DCMAX; ++t)
                 if (t < dc) emit(t, in[t]);
         } else {
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
             for (int t = 0; t < dc; ++t) emit(t, ld<uint8_t, VEC>(in_base + (size_t)t * W));
         }
     }
@@ -1409,7 +1371,7 @@ __device__ __forceinline__ void cn_q4_check(int dc, const uint8_t *__restrict__ 
         for (int t = 0; t < R; ++t)
             if (live(t)) absorb(in[t]);
     } else {
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
         for (int t = 0; t < dc; ++t) absorb(row(in_base + (size_t)t * W));
     }
     if (DC == 1 || (DC == 0 && dc == 1)) { m2l = m1l; m2h = m1h; }       // "min2_val = min_val" (rcq_decoder.py:233-234)
@@ -1435,7 +1397,7 @@ __device__ __forceinline__ void cn_q4_check(int dc, const uint8_t *__restrict__ 
         for (int t = 0; t < R; ++t)
             if (live(t)) emit(t, in[t]);
     } else {
-#pragma unroll LDPC_CN_UNROLL
+#pragma unroll kCnUnroll
         for (int t = 0; t < dc; ++t) emit(t, row(in_base + (size_t)t * W));
     }
 }
@@ -1521,9 +1483,6 @@ __device__ __forceinline__ unsigned key_of(float val, float b, const unsigned (&
 //   least ulp(prev(t)) * K >= 1 (the host admits thresholds in [2^-50, 2^50] to this form), else it is <= 0;
 //   [m > 0] = clamp(|G| * K) (m >= 2^-149 -> >= 2);  NaN -> every bracket 0 (DX10 clamp), as the compare form's squash.
 constexpr int kKeyFloat4 = 104;
-#ifndef LDPC_KEY_FLOAT
-#define LDPC_KEY_FLOAT 1          // 0: 4-level decoders keep the compare chain (A/B builds)
-#endif
 struct KeyTab {
     unsigned tb[8];               // compare forms: threshold bit patterns (NaN padding)
     float K, c1, c2, c3;          // float form: 2^75 and prev(t_q) * 2^75
@@ -1684,14 +1643,10 @@ __device__ __forceinline__ void vn_q4_body(const GraphDev &g, int tile, int j, i
 // Variable sweep, VEC = 4, degrees <= 8, at most 8 levels (the host launches vn_sweep_q<4> otherwise).
 // VPW consecutive variables per wave: a degree-2 variable is ~300 instructions of work, less than the wave's prologue
 // (kernel arguments, LUT staging + barrier, thresholds) -- unlike the fp32 sweeps this kernel is not HBM-bound.
-#ifndef LDPC_VNQ_VPW
-#define LDPC_VNQ_VPW 8
-#endif
-#ifndef LDPC_VNQ_WAVES
-#define LDPC_VNQ_WAVES 8          // waves per SIMD the register allocation must leave room for
-#endif
+constexpr int kVnqVpw = 8;
+constexpr int kVnqWaves = 8;        // waves per SIMD the register allocation must leave room for
 template <int NL, bool ES, int VPW, bool INIT = false>
-__global__ __launch_bounds__(kBlock, LDPC_VNQ_WAVES) void vn_sweep_q4(GraphDev g, const uint8_t *__restrict__ c2v,
+__global__ __launch_bounds__(kBlock, kVnqWaves) void vn_sweep_q4(GraphDev g, const uint8_t *__restrict__ c2v,
                                                       const float *__restrict__ llrT, uint8_t *__restrict__ v2c,
                                                       const float *__restrict__ alpha_row, const int *__restrict__ alpha_slot,
                                                       const float *__restrict__ lut_cur, int lut_entries,
@@ -1776,7 +1731,7 @@ __global__ __launch_bounds__(kRowsThreads, 8) void transpose_in_q4(GraphDev g, c
     typedef float F4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     int tile, chunk;
-    if (!rows_block<false>(var_blocks, tile, chunk)) return;        // plain chunk order (see LDPC_ROWS_XCD)
+    if (!rows_block<false>(var_blocks, tile, chunk)) return;        // plain chunk order (see rows_block)
     const int j0 = chunk * kRowsVars;
     {
         const int jq = (threadIdx.x % kTpr) * 4, l = threadIdx.x / kTpr;       // codeword 4 * l + c of the tile
@@ -1886,7 +1841,7 @@ __device__ __forceinline__ Pack<float, VEC> gather_v2c(const Pack<uint8_t, VEC> 
 // consumed.  The kernel is bound by memory latency, not bandwidth (its reads are L2/MALL hits of 256 B - 1 KiB rows):
 // one exposed round trip per GRP edges instead of one per edge.
 template <int VEC, int NL, bool BPC, int CPW, int GRP>
-__global__ __launch_bounds__(kBlock, LDPC_GATHER_WAVES) void cn_gather(GraphDev g, const int4 *__restrict__ gat_meta,
+__global__ __launch_bounds__(kBlock, kGatherWaves) void cn_gather(GraphDev g, const int4 *__restrict__ gat_meta,
                                                     const int *__restrict__ gat_nbr, const float *__restrict__ llrT,
                                                     const uint8_t *__restrict__ codes_in,
                                                     uint8_t *__restrict__ codes_out,

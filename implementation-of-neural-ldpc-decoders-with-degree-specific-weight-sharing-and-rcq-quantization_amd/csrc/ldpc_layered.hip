@@ -23,18 +23,10 @@
 // (tools/probes/valu_latency_probe.hip) -- so the quantise/select tail is scheduled by hand (ten instructions, no hazard
 // padding) and the step is bounded by VALU time, not by the LDS round trip.
 //
-// A/B form (-DLDPC_LAY_EARLY=1, measured slower at full occupancy, see the macro below): the LDS round trip taken OFF the
-// chain where the graph allows it -- the posteriors of check i+1 are read one step
-// EARLY (before check i has written), which is exact for every lane whose variable check i does not touch.  The host knows
-// which lanes those are; per plan row it records how the row depends on the previous one:
-//   NONE  no common variable                         -> the early values are the values
-//   FWD   exactly one common variable, sitting in the LAST lane of the previous row and the last-but-one of this row (edges
-//         are laid out right-aligned in ascending variable order, so this is the dual-diagonal parity chain of IRA /
-//         DVB-S2-like codes: check i = {..., p_i-1, p_i})  -> that lane takes the value the previous step just wrote from
-//         its neighbour lane (one DPP move), all others keep the early value
-//   LATE  anything else                              -> the row is read again after the previous write (the plain in-order form;
-//         decided per GROUP of four rows so that the fast groups carry no test and no branch per step)
-// (the plan always carries these flags; the default in-order form ignores them).
+// Every row is read after the previous row's write.  Reading the next row one step early (exact where the rows share no
+// variable, a DPP forward for the parity chain) was measured slower at full occupancy: (1998,1512), 65536 codewords, T = 10:
+// in order 8.87-8.90 ms, early 9.23-9.25 ms -- a step is bounded by the VALU time of its ~19 DPP operations, not by the LDS
+// round trip, and the in-order form's LDS waits are what the fifth wave of a CU fills.
 //
 // Arithmetic is that of layered_rcq (same helpers): results are identical to the streaming kernel's.
 #pragma once
@@ -55,26 +47,14 @@ struct LayeredPlan {
                                    //          i (edges right-aligned, ascending variable order); lanes without an
                                    //          edge point at word n of the codeword's vector, which holds +inf for ever (it
                                    //          is neutral for min and parity, and inf + message = inf is written back);
-                                   //          bit 31 (kLayFwdBit): THIS lane takes its value from its upper neighbour lane of the
-                                   //          previous step (FWD rows: the one receiving lane); bit 30 (kLayLateBit), on every lane
-                                   //          of the FIRST row of a group of kLayPf rows: some row of the group must be read after
-                                   //          the previous row's write (the whole group then runs in order; group 0 always);
                                    //          bit 29 (kLayDeg1Bit) on the entries of a degree-1 check ("min2 = min", :312-313);
                                    //          no-op rows up to m_pad (inf in, inf out), then 2 * kLayPf more that only the
                                    //          prefetch past the last check reads
 };
 
 constexpr int kLayPf = 4;          // plan entries in flight ahead of the check being processed (= the unroll of the walk)
-#ifndef LDPC_LAY_EARLY
-#define LDPC_LAY_EARLY 0           // 1: early reads + DPP forwarding of the parity chain (header); 0: every row is read after the previous
-                                   // write.  Same-box A/B on the (1998,1512) code, 65536 codewords, T = 10
-                                   // (profiles/r03_layered_variants.txt): in order 8.87-8.90 ms, early form 9.23-9.25 ms (both 0.66-0.68 ms
-                                   // at 4096 codewords, where a wave has its SIMD to itself): a step is bounded by the VALU time of its
-                                   // ~19 DPP operations, not by the LDS round trip, and the in-order form's LDS waits are what the
-                                   // fifth wave of a CU fills.
-#endif
 constexpr uint32_t kLayOffMask = 0x1fffffffu;
-constexpr uint32_t kLayFwdBit = 0x80000000u, kLayLateBit = 0x40000000u, kLayDeg1Bit = 0x20000000u;
+constexpr uint32_t kLayDeg1Bit = 0x20000000u;
 
 // LDS bytes of one codeword: n posteriors + the +inf word
 __host__ __device__ inline size_t lay_row_bytes(int n) { return ((size_t)n + 1) * 4; }
@@ -200,34 +180,11 @@ __global__ __launch_bounds__(kWave) void layered_lds(LayeredPlan pl, const float
             else th[q] = (q < n_levels) ? thr[q] : __builtin_nanf("");
             asm volatile("" : "+v"(th[q]));                         // in VGPRs for the whole walk (a select takes one scalar operand: its mask)
         }
-        // one check: o = this lane's plan entry, on = its entry of the NEXT row (whose posteriors are requested here, one step
-        // early); xe = this row's early value, upd_prev = what this lane wrote in the previous step
-        float xe = 0.0f, upd_prev = 0.0f;
-        auto step = [&](uint32_t o, uint32_t on, auto late_tag) {
-            constexpr bool kLate = decltype(late_tag)::value;
+        // one check: o = this lane's plan entry.  The second argument (its entry of the NEXT row) is not read; the call
+        // still passes it because dropping it changes the code the compiler generates for this kernel.
+        auto step = [&](uint32_t o, uint32_t /*next*/) {
             const unsigned addr = lds_addr(o);
-            // the NEXT row's posteriors first -- before this row's write, a whole step before they are needed (the scheduling
-            // barrier keeps the compiler from sinking the request towards its use)
-#if LDPC_LAY_EARLY
-            const float x_early = xe;
-            xe = lay_lds_ld(lds_addr(on));
-            __builtin_amdgcn_sched_barrier(0);
-            float x = x_early;
-#else
-            (void)on;
-            float x = lay_lds_ld(addr);                             // in order: after the previous row's write
-#endif
-            if constexpr (!LDPC_LAY_EARLY) {
-            } else if constexpr (kLate) {
-                // a group with a LATE row (or the first group of an iteration): every row of it is read after the previous
-                // write.  The wait sits INSIDE the asm, so the compiler's own counters -- and with them the fast groups --
-                // never drain the LDS queue.
-                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(x) : "v"(addr) : "memory");
-            } else if (LW >= 2) {
-                // FWD: the flagged lane <- its upper neighbour's value of the previous step (row_shl:1)
-                const float f = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(upd_prev), 0x101, 0xf, 0xf, true));
-                x = ((int)o < 0) ? f : x;
-            }
+            const float x = lay_lds_ld(addr);                       // in order: after the previous row's write
             const unsigned xb = __float_as_uint(x), a = xb & 0x7fffffffu;
             unsigned m1 = a, m2 = 0x7f800000u, par = xb;
             lay_step<1, LW>(m1, m2, par); lay_step<2, LW>(m1, m2, par); lay_step<4, LW>(m1, m2, par);
@@ -286,10 +243,8 @@ __global__ __launch_bounds__(kWave) void layered_lds(LayeredPlan pl, const float
             float upd = x + msg;                                    // "posteriors[j] += c2v_messages[i, j]" (:337-338)
             if (ES) upd = frozen ? x : upd;                         // a stopped codeword keeps its posteriors
             lay_lds_st(addr, upd);
-            upd_prev = upd;
         };
-        // Plan entries are requested a group ahead: rows 1.. of the NEXT group, and row 0 of the group after it (row 0 of the
-        // next group is needed already by the LAST step of this one, for its early read -- it was requested a group ago).
+        // Plan entries are requested a group ahead: rows 1.. of the NEXT group, and row 0 of the group after it.
         // m is a multiple of kLayPf and 2 * kLayPf more rows follow: no bounds tests.
         uint32_t cur[kLayPf], nxt[kLayPf], nn0;
 #pragma unroll
@@ -300,15 +255,8 @@ __global__ __launch_bounds__(kWave) void layered_lds(LayeredPlan pl, const float
 #pragma unroll
             for (int k = 1; k < kLayPf; ++k) nxt[k] = nx[(size_t)k * LW];
             nn0 = nx[(size_t)kLayPf * LW];
-            // one wave-uniform test per GROUP: the host flags the first row of a group that holds a LATE row (and group 0:
-            // its first row follows the previous iteration's last check); such a group runs the in-order form
-            if (LDPC_LAY_EARLY && (__builtin_amdgcn_readfirstlane(cur[0]) & kLayLateBit)) {
 #pragma unroll
-                for (int k = 0; k < kLayPf; ++k) step(cur[k], k + 1 < kLayPf ? cur[k + 1] : nxt[0], std::true_type{});
-            } else {
-#pragma unroll
-                for (int k = 0; k < kLayPf; ++k) step(cur[k], k + 1 < kLayPf ? cur[k + 1] : nxt[0], std::false_type{});
-            }
+            for (int k = 0; k < kLayPf; ++k) step(cur[k], k + 1 < kLayPf ? cur[k + 1] : nxt[0]);
 #pragma unroll
             for (int k = 0; k < kLayPf; ++k) cur[k] = nxt[k];
             nxt[0] = nn0;

@@ -74,42 +74,11 @@ struct ResidentArgs {
     int alpha_in_lds;             // T * n_alpha floats staged in LDS
     int unit_alpha;               // every alpha == 1.0f (Basic, RCQ, sharing types 1/3): the multiply is skipped
     int rcq_zero0;                // every quantiser has tau_0 == 0 (true for gamma > 0): per-check quantisation
-    int debug_skip;               // phase-timing probes, compiled in only with -DLDPC_RESIDENT_PROBES (tools/resident_probe*.sh)
     void *dbg_c2v;                // [batch][E] or null: C2V values of every codeword's last executed iteration, CSR edge
                                   // order (include/ldpc_hip_debug.h; lets the tests compare per-edge RCQ codes on this engine)
 };
 
 constexpr int kResAlphaMax = 1024;   // floats of alpha table kept in LDS
-constexpr int kResHeld = 16;         // check degrees up to this keep their values in registers between the two passes
-#ifndef LDPC_RES_CHECK_MODE
-#define LDPC_RES_CHECK_MODE 0        // 0 per-lane form only | 1 scalar form for single-degree waves | 2 one scalar pass per degree
-                                     // (measured on one box, (1998,1512) Basic / RCQ: 0: 3.10 / 3.30 ms, 1: 3.13 / 3.33, 2: 3.20 / 3.48;
-                                     //  LDPC_RES_VAR_MODE 1 costs another 0.15-0.25 ms: DESIGN.md 5)
-#endif
-#ifndef LDPC_RES_FINAL_SCATTER
-#define LDPC_RES_FINAL_SCATTER 1      // fixed T: final syndrome by parity scatter (0: decisions through the dead message slots)
-#endif
-#ifndef LDPC_RES_NO_PLAN_PREFETCH
-#define LDPC_RES_NO_PLAN_PREFETCH 0
-#endif
-#ifndef LDPC_RES_SELECT4
-#define LDPC_RES_SELECT4 1           // pass 2 of the check phase in hand-scheduled groups of four values (0: the compiler's form)
-#endif
-#ifndef LDPC_RES_PLAN_U32
-#define LDPC_RES_PLAN_U32 1          // plan prefetch addressed with 32-bit offsets against a scalar base (-0.3 % fp32, measured)
-#endif
-#ifndef LDPC_RES_F64_MINMAX
-#define LDPC_RES_F64_MINMAX 1        // float64 check phase: branch-free min1/min2, products hoisted, pass 2 in groups of four edges
-#endif
-#ifndef LDPC_RES_VAR_MODE
-#define LDPC_RES_VAR_MODE 0          // 0 per-lane dispatch | 1 one scalar pass per distinct degree
-#endif
-
-#ifdef LDPC_RESIDENT_PROBES
-#define LDPC_PROBE(a, bit) ((a).debug_skip & (bit))
-#else
-#define LDPC_PROBE(a, bit) 0
-#endif
 
 // LDS access by byte offset.  The dynamic LDS block is this kernel's only LDS object (no static
 // __shared__), so it starts at LDS address 0 and a message slot's byte offset IS its LDS address:
@@ -139,27 +108,10 @@ __device__ __forceinline__ void lds_store(unsigned byte_off, const X &v)
 
 // LLRs in and decisions out are touched once per codeword: non-temporal, so that they do not evict the plan (the index data
 // every iteration re-reads) from the CU's L1
-#ifndef LDPC_RES_NT_IO
-#define LDPC_RES_NT_IO 1
-#endif
 template <typename X>
-__device__ __forceinline__ X res_stream_load(const X *p)
-{
-#if LDPC_RES_NT_IO
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ X res_stream_load(const X *p) { return __builtin_nontemporal_load(p); }
 template <typename X>
-__device__ __forceinline__ void res_stream_store(X *p, X v)
-{
-#if LDPC_RES_NT_IO
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+__device__ __forceinline__ void res_stream_store(X *p, X v) { __builtin_nontemporal_store(v, p); }
 
 __device__ __forceinline__ void lds_atomic_xor(unsigned byte_off, unsigned v)
 {
@@ -327,87 +279,16 @@ __device__ __forceinline__ void res_select4_f64(double (&x)[4], double m1, doubl
     for (int i = 0; i < 4; ++i) x[i] = __longlong_as_double((long long)(((unsigned long long)rh[i] << 32) | rl[i]));
 }
 
-// Check update of ONE degree, fully unrolled (fp32, one beta per check): the DC values are read once, stay in registers
-// for both passes and are written back in place -- one LDS read and one LDS write per edge instead of two reads and a
-// write, no load-to-use wait in the second pass, no loop control.  Entered through a scalar switch on the wave's degree.
-template <int G, int FORM, int NL, int DC>
-__device__ __forceinline__ void res_check_held(unsigned base, unsigned stride, float b_check, const float (&th)[8],
-                                               const float *__restrict__ thr, int n_levels)
-{
-    using P = Pack<float, G>;
-    P v[DC];
-#pragma unroll
-    for (int t = 0; t < DC; ++t) v[t] = lds_load<P>(base + t * stride);
-    float m1[G], m2[G];
-    uint32_t sacc[G];
-    float ninf = -inf_of<float>();
-    asm volatile("" : "+v"(ninf));                    // opaque to constant folding: min as ONE v_med3
-#pragma unroll
-    for (int g = 0; g < G; ++g) { m1[g] = inf_of<float>(); m2[g] = inf_of<float>(); sacc[g] = 0; }
-#pragma unroll
-    for (int t = 0; t < DC; ++t) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            sacc[g] ^= __float_as_uint(v[t].x[g]);
-            m2[g] = __builtin_amdgcn_fmed3f(__builtin_fabsf(v[t].x[g]), m1[g], m2[g]);
-            m1[g] = __builtin_amdgcn_fmed3f(__builtin_fabsf(v[t].x[g]), m1[g], ninf);
-        }
-    }
-    if (DC == 1) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) m2[g] = m1[g];     // "min2_val = min_val" for a degree-1 check
-    }
-    uint32_t o1[G], o2[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        float w1 = b_check * m1[g], w2 = b_check * m2[g];
-        if (FORM == FORM_RCQ) {
-            // value = (1 - 2*(w < 0)) * tau[level(|w|)]; with tau_0 == 0 a zero magnitude reconstructs to +-0, so
-            // applying the edge sign afterwards is value-identical to the reference's order
-            const float r1 = res_quant_rec<NL>(__builtin_fabsf(w1), th, thr, n_levels);
-            const float r2 = res_quant_rec<NL>(__builtin_fabsf(w2), th, thr, n_levels);
-            w1 = flip_sign<float>(r1, (w1 < 0.0f) ? 1u : 0u);
-            w2 = flip_sign<float>(r2, (w2 < 0.0f) ? 1u : 0u);
-        }
-        const uint32_t par = sacc[g] & 0x80000000u;
-        o1[g] = __float_as_uint(w1) ^ par;
-        o2[g] = __float_as_uint(w2) ^ par;
-        asm volatile("" : "+v"(o1[g]), "+v"(o2[g]));  // keep the two per-check values materialised (see the generic form)
-    }
-    int t0 = 0;
-    if constexpr (G == 2 && LDPC_RES_SELECT4 != 0) {
-        uint32_t sign_v = 0x80000000u;
-        asm volatile("" : "+v"(sign_v));
-#pragma unroll
-        for (int t = 0; t + 1 < DC; t += 2) {
-            res_select4(v[t].x[0], v[t].x[1], v[t + 1].x[0], v[t + 1].x[1], m1[0], m1[1], o1[0], o2[0], o1[1], o2[1], sign_v);
-            lds_store<P>(base + t * stride, v[t]);
-            lds_store<P>(base + (t + 1) * stride, v[t + 1]);
-        }
-        t0 = DC & ~1;
-    }
-#pragma unroll
-    for (int t = t0; t < DC; ++t) {
-        P o;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const uint32_t sel = (__builtin_fabsf(v[t].x[g]) == m1[g]) ? o2[g] : o1[g];
-            o.x[g] = __uint_as_float(__builtin_amdgcn_bitop3_b32(sel, __float_as_uint(v[t].x[g]), 0x80000000u, 0x78));
-        }
-        lds_store<P>(base + t * stride, o);
-    }
-}
-
-template <int G, int FORM, bool BPC, bool UNI, int NL, int MS, typename T, bool SPLIT = false>
-__device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned char *smem, int p, int dc, int dcw,
+template <int G, int FORM, bool BPC, int NL, int MS, typename T, bool SPLIT = false>
+__device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned char *smem, int p, int dc,
                                                T b_check, const T *__restrict__ beta_row,
                                                const T *__restrict__ oa_row, const float (&th)[8],
                                                const float *__restrict__ thr, int n_levels, bool rcq_zero0, int gs = 1)
 {
-    // UNI: every lane of the wave has the degree dcw (scalar loops).  !UNI: per-lane degrees, and the lanes of a group
-    // (gs > 1) hold the pieces of ONE wide check: their partials are combined between the two passes.
+    // Per-lane degrees; with SPLIT the lanes of a group (gs > 1) hold the pieces of ONE wide check: their partials are
+    // combined between the two passes.
     constexpr int kEl = G * (int)sizeof(T);
-    const int trip = UNI ? dcw : dc;
+    const int trip = dc;
     const unsigned stride = (MS > 0 ? (unsigned)MS : (unsigned)pl.mstride) * kEl;   // compile-time when MS > 0
     const unsigned base = (unsigned)p * kEl;
     if constexpr (!std::is_same<T, float>::value) {
@@ -423,7 +304,6 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 par[g] ^= signbit_of<T>(v.x[g]);
-#if LDPC_RES_F64_MINMAX
                 // "if a < min1: (min2, min1) = (min1, a) elif a < min2: min2 = a" (ldpc_decoder.py:96-101) without branches:
                 // min2' = max(min(a, min2), min1), min1' = min(a, min1) -- the same values for every ordered input, and a NaN
                 // is skipped by both forms (v_min/v_max_f64 return the other operand for a quiet NaN; the initial pass
@@ -434,11 +314,6 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
                 asm("v_min_f64 %0, |%1|, %2" : "=v"(m1n) : "v"(v.x[g]), "v"(m1[g]));
                 asm("v_max_f64 %0, %1, %2" : "=v"(m2[g]) : "v"(lo), "v"(m1[g]));
                 m1[g] = m1n;
-#else
-                const T a = abs_of<T>(v.x[g]);
-                if (a < m1[g]) { m2[g] = m1[g]; m1[g] = a; }
-                else if (a < m2[g]) { m2[g] = a; }
-#endif
             }
         };
         {
@@ -451,7 +326,7 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
             }
             for (; t < trip; ++t) absorb(lds_load<PD>(base + t * stride));
         }
-        if constexpr (!UNI && SPLIT) {
+        if constexpr (SPLIT) {
             unsigned nzd[G];
 #pragma unroll
             for (int g = 0; g < G; ++g) nzd[g] = 0;
@@ -463,12 +338,9 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
             if (trip == 1 && gs == 1) m2[g] = m1[g];        // "min2_val = min_val" for a degree-1 check
             o1[g] = flip_sign<T>(b_check * m1[g], par[g]);
             o2[g] = flip_sign<T>(b_check * m2[g], par[g]);
-#if LDPC_RES_F64_MINMAX
             asm volatile("" : "+v"(o1[g]), "+v"(o2[g]));   // two products per check, not one v_mul_f64 per edge (see the fp32 form)
-#endif
         }
         int t = 0;
-#if LDPC_RES_F64_MINMAX
         if constexpr (G == 1) {
             uint32_t sign_v = 0x80000000u;
             asm volatile("" : "+v"(sign_v));
@@ -482,7 +354,6 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
                 for (int i = 0; i < 4; ++i) { PD o; o.x[0] = x[i]; lds_store<PD>(addr + i * stride, o); }
             }
         }
-#endif
 #pragma unroll 4
         for (; t < trip; ++t) {
             const unsigned addr = base + t * stride;
@@ -505,20 +376,6 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
     for (int g = 0; g < G; ++g) {
         m1[g] = inf_of<float>(); m2[g] = inf_of<float>(); sacc[g] = 0; nz[g] = 0;
     }
-#if LDPC_RES_CHECK_MODE != 0
-    constexpr bool kPerCheck = BPC && (FORM == FORM_NMS || FORM == FORM_RCQ);
-    if (kPerCheck && UNI && trip <= kResHeld && (FORM == FORM_NMS || rcq_zero0)) {
-        // The common case -- one beta per check and a wave-uniform degree of at most kResHeld edges: one scalar jump
-        // into straight-line code for exactly that degree, the check's values held in registers between the passes.
-#define LDPC_RH(D) case D: res_check_held<G, FORM, NL, D>(base, stride, b_check, th, thr, n_levels); return;
-        switch (trip) {
-            LDPC_RH(1) LDPC_RH(2) LDPC_RH(3) LDPC_RH(4) LDPC_RH(5) LDPC_RH(6) LDPC_RH(7) LDPC_RH(8)
-            LDPC_RH(9) LDPC_RH(10) LDPC_RH(11) LDPC_RH(12) LDPC_RH(13) LDPC_RH(14) LDPC_RH(15) LDPC_RH(16)
-        default: return;                              // trip == 0: nothing to do
-        }
-#undef LDPC_RH
-    }
-#endif
     // generic form (any degree, per-lane trip counts, per-edge beta, OMS): pass 1 streams the slots, pass 2 re-reads them
 #pragma unroll 4
     for (int t = 0; t < trip; ++t) {
@@ -534,7 +391,7 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
                                                                            // canonicalise + v_min: 3 ops)
         }
     }
-    if constexpr (!UNI && SPLIT) group_combine<G, float>(gs, m1, m2, sacc, nz);
+    if constexpr (SPLIT) group_combine<G, float>(gs, m1, m2, sacc, nz);
     if (trip == 1 && gs == 1) {
 #pragma unroll
         for (int g = 0; g < G; ++g) m2[g] = m1[g];     // "min2_val = min_val" for a degree-1 check
@@ -564,7 +421,7 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
             asm volatile("" : "+v"(o1[g]), "+v"(o2[g]));
         }
         int t = 0;
-        if constexpr (G == 2 && LDPC_RES_SELECT4 != 0) {
+        if constexpr (G == 2) {
             uint32_t sign_v = 0x80000000u;
             asm volatile("" : "+v"(sign_v));              // the constant in a VGPR (see res_select4)
             for (; t + 3 < trip; t += 4) {
@@ -667,48 +524,14 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
             // passes needs every lane of a group at the same point of the program
             const int gs = pl.gsz[p];
             if (__ballot(gs > 1) != 0ull) {
-                res_check_body<G, FORM, BPC, false, NL, MS, T, true>(pl, smem, p, dc, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0, gs);
+                res_check_body<G, FORM, BPC, NL, MS, T, true>(pl, smem, p, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0, gs);
                 continue;
             }
         }
-#if LDPC_RES_CHECK_MODE == 2
-        // One pass per DISTINCT degree in the wave (nodes are sorted by degree: all but the class-boundary waves make one
-        // pass), each with a scalar trip count.  The loop itself is uniform -- it runs on the scalar mask of lanes not yet
-        // served, every lane stays in it -- and the degree is handed to the body as an opaque scalar copy made BEFORE the
-        // comparison: inside `if (dc == dcw)` the optimiser would otherwise substitute the per-lane dc for the scalar and
-        // turn the edge loops back into exec-masked vector loops.  (A `for (pending) { rfl; if (==) {...} }` waterfall is not
-        // safe here: with the readfirstlane hoisted, lanes of another degree would spin forever, which the optimiser is
-        // entitled to assume never happens -- it then drops the comparison and runs every lane with the first lane's degree.)
-        for (unsigned long long todo = __ballot(true); todo;) {
-            const int dcw = __builtin_amdgcn_readlane(dc, __ffsll((long long)todo) - 1);
-            int trip = dcw;
-            asm volatile("" : "+s"(trip));
-            const bool mine = dc == dcw;
-            if (mine)
-                res_check_body<G, FORM, BPC, true, NL, MS, T>(pl, smem, p, dc, trip, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
-            todo &= ~__ballot(mine);
-        }
-#elif LDPC_RES_CHECK_MODE == 1
-        // A wave whose lanes all have one degree (nodes are sorted by degree: all but the class-boundary waves) runs the
-        // scalar form -- trip count in an SGPR, for the common forms straight-line code of exactly that degree with the
-        // values held in registers; a class-boundary wave runs the per-lane form once for all its lanes (exec-masked
-        // loops over per-lane trip counts).  The scalar is an opaque copy: were it derived from `dc` visibly, the optimiser
-        // would put the per-lane value back (it knows dc == dcw in that branch).
-        {
-            const int dcw = __builtin_amdgcn_readfirstlane(dc);
-            int trip = dcw;
-            asm volatile("" : "+s"(trip));
-            if (__ballot(dc != dcw) == 0ull)
-                res_check_body<G, FORM, BPC, true, NL, MS, T>(pl, smem, p, dc, trip, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
-            else
-                res_check_body<G, FORM, BPC, false, NL, MS, T>(pl, smem, p, dc, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
-        }
-#else
         // every lane runs the edge loops with ITS degree as trip count (exec-masked vector loops): one pass per wave
-        // whatever the mix of degrees.  Measured fastest (see LDPC_RES_CHECK_MODE above): the phase is bound by VALU issue
-        // -- six instructions per edge and codeword, which the scalar forms do not reduce -- not by loop control.
-        res_check_body<G, FORM, BPC, false, NL, MS, T>(pl, smem, p, dc, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
-#endif
+        // whatever the mix of degrees.  Measured fastest against scalar per-degree forms: the phase is bound
+        // by VALU issue -- six instructions per edge and codeword, which the scalar forms do not reduce -- not by loop control.
+        res_check_body<G, FORM, BPC, NL, MS, T>(pl, smem, p, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
     }
 }
 
@@ -835,50 +658,20 @@ __device__ __forceinline__ void res_var_phase(const ResidentPlan &pl, unsigned c
         const int qn = q + nt;
         unsigned metan;
         uint2 plon, phin;
-#if !LDPC_RES_NO_PLAN_PREFETCH                        // tuning builds with more waves per SIMD trade the prefetch for registers
         {
-#if LDPC_RES_PLAN_U32
             // 32-bit byte offsets against the scalar base (global_load ... v_off, s[base]): one shift per load instead of a
             // sign extension and a 64-bit add each
             const unsigned qc = (unsigned)min(qn, n - 1), qh = min(qc, (unsigned)hi_last);
             metan = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(pl.vmeta) + (size_t)(qc << 2));
             plon = *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(pl.vslot_lo) + (size_t)(qc << 3));
             phin = *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(pl.vslot_hi) + (size_t)(qh << 3));
-#else
-            const int qc = min(qn, n - 1);
-            metan = pl.vmeta[qc];
-            plon = pl.vslot_lo[qc];
-            phin = pl.vslot_hi[min(qc, hi_last)];
-#endif
         }
-#endif
         const int dv = (int)(meta & 0xffu);
         const uint4 slo = plan_unpack(plo), shi = plan_unpack(phi);
         T a = (T)0;                                                      // LDS copy of the table when small
         if (MODE == 0 || MODE == 4) a = alpha_lds ? alpha_lds[meta >> 8] : alpha_glb[meta >> 8];
-        // one scalar branch into the body of the wave's degree; a class-boundary wave (two or three degrees)
-        // goes round once per distinct degree with the other lanes masked off
-#if LDPC_RES_VAR_MODE == 1
-        for (unsigned long long todo = __ballot(true); todo;) {      // uniform loop, scalar degree (see res_check_phase)
-            const int dvw = __builtin_amdgcn_readlane(dv, __ffsll((long long)todo) - 1);
-            int dsel = dvw;
-            asm volatile("" : "+s"(dsel));
-            const bool mine = dv == dvw;
-            if (mine) res_var_dispatch<G, MODE, T>(smem, llr_s, bits_s, q, dsel, slo, shi, a, emask, ps);
-            todo &= ~__ballot(mine);
-        }
-#else
         // every lane jumps to the compile-time body of ITS degree (exec-masked dispatch): one pass per wave whatever the mix
         res_var_dispatch<G, MODE, T>(smem, llr_s, bits_s, q, dv, slo, shi, a, emask, ps);
-#endif
-#if LDPC_RES_NO_PLAN_PREFETCH
-        {
-            const int qc = min(qn, n - 1);
-            metan = pl.vmeta[qc];
-            plon = pl.vslot_lo[qc];
-            phin = pl.vslot_hi[min(qc, hi_last)];
-        }
-#endif
         q = qn; meta = metan; plo = plon; phi = phin;
     }
 }
@@ -1062,12 +855,10 @@ __host__ __device__ inline size_t res_lds_total(int S, int n, int G, int n_alpha
 
 // ES: 0 = fixed-iteration kernel, 1 = early-stop kernel (kept apart so that the fixed-T kernel does not carry
 // the posterior/syndrome/emit code of the stop rule: the extra code cost the hot loop ~4 % when merged)
-#ifndef LDPC_RES_MAX_THREADS
-#define LDPC_RES_MAX_THREADS 1024      // launch bounds of resident_decode: threads per workgroup, waves per SIMD the
-#define LDPC_RES_MIN_WAVES 4           // register allocation must leave room for (tuning builds trade registers for waves)
-#endif
+constexpr int kResMaxThreads = 1024;   // launch bounds of resident_decode: threads per workgroup, waves per SIMD the
+constexpr int kResMinWaves = 4;        // register allocation must leave room for
 template <int G, int FORM, bool BPC, int NL, int MS, int ES, typename T = float, bool SPLIT = false>
-__global__ __launch_bounds__(LDPC_RES_MAX_THREADS, LDPC_RES_MIN_WAVES) void resident_decode(ResidentPlan pl, ResidentArgs a)
+__global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(ResidentPlan pl, ResidentArgs a)
 {
     extern __shared__ __align__(16) unsigned char res_smem[];     // the only LDS object: msg starts at offset 0
     if (__builtin_amdgcn_groupstaticsize() != 0) __builtin_trap();  // lds_load/lds_store rely on that (folds away)
@@ -1095,31 +886,28 @@ __global__ __launch_bounds__(LDPC_RES_MAX_THREADS, LDPC_RES_MIN_WAVES) void resi
     const int tid = threadIdx.x, nt = blockDim.x, n = pl.n;
     const long long b0 = (long long)blockIdx.x * G;
     constexpr unsigned kAll = (1u << G) - 1u;
-    if (LDPC_PROBE(a, 64)) return;                       // launch-overhead probe
 
     // LLRs: coalesced rows from HBM, scattered into degree-sorted order; padding codewords get +1.
     // All loads of a batch of kPro positions are issued before the first LDS store: one HBM round trip per
     // batch instead of one per element (the plain loop waits for every load before it issues the next).
     constexpr int kPro = 4;
-    if (!LDPC_PROBE(a, 16)) {
-        for (int j0 = tid; j0 < n; j0 += kPro * nt) {
-            unsigned ip[kPro];
-            P v[kPro];
+    for (int j0 = tid; j0 < n; j0 += kPro * nt) {
+        unsigned ip[kPro];
+        P v[kPro];
 #pragma unroll
-            for (int k = 0; k < kPro; ++k) {
-                const int j = j0 + k * nt;
-                ip[k] = 0;
-                if (j < n) {
-                    ip[k] = pl.inv_perm_v[j];
+        for (int k = 0; k < kPro; ++k) {
+            const int j = j0 + k * nt;
+            ip[k] = 0;
+            if (j < n) {
+                ip[k] = pl.inv_perm_v[j];
 #pragma unroll
-                    for (int g = 0; g < G; ++g)
-                        v[k].x[g] = (b0 + g < a.batch) ? res_stream_load(&g_llr[(size_t)(b0 + g) * n + j]) : (T)1;
-                }
+                for (int g = 0; g < G; ++g)
+                    v[k].x[g] = (b0 + g < a.batch) ? res_stream_load(&g_llr[(size_t)(b0 + g) * n + j]) : (T)1;
             }
-#pragma unroll
-            for (int k = 0; k < kPro; ++k)
-                if (j0 + k * nt < n) reinterpret_cast<P *>(llr_s)[ip[k]] = v[k];
         }
+#pragma unroll
+        for (int k = 0; k < kPro; ++k)
+            if (j0 + k * nt < n) reinterpret_cast<P *>(llr_s)[ip[k]] = v[k];
     }
     for (int k = tid; k < (a.alpha_in_lds ? a.T * a.n_alpha : 0); k += nt) alpha_s[k] = g_alpha[k];
     if (tid == 0) { sh_unsat[0] = 0; sh_unsat[1] = 0; }
@@ -1128,7 +916,7 @@ __global__ __launch_bounds__(LDPC_RES_MAX_THREADS, LDPC_RES_MIN_WAVES) void resi
     // "initialise v2c with the channel LLRs" (T == 0: c2v = 0, the loop never runs)
     {
         const P *L = reinterpret_cast<const P *>(llr_s);
-        for (int q0 = tid; q0 < n && !LDPC_PROBE(a, 32); q0 += kPro * nt) {
+        for (int q0 = tid; q0 < n; q0 += kPro * nt) {
             int dvk[kPro];
             uint2 plo[kPro], phi[kPro];
 #pragma unroll
@@ -1181,12 +969,11 @@ __global__ __launch_bounds__(LDPC_RES_MAX_THREADS, LDPC_RES_MIN_WAVES) void resi
         const float *thr = FORM == FORM_RCQ ? a.thr + (size_t)a.q_of_iter[it] * a.n_levels : nullptr;
         const T *alpha_lds = a.alpha_in_lds ? alpha_s + it * a.n_alpha : nullptr;
         const T *alpha_glb = g_alpha + (size_t)it * a.n_alpha;
-        if (!LDPC_PROBE(a, 1))
-            res_check_phase<G, FORM, BPC, NL, MS, T, SPLIT>(pl, res_smem, beta_row, oa_row, thr, a.n_levels, a.rcq_zero0 != 0,
-                                                  dc_pre, b_pre, tid, nt);
+        res_check_phase<G, FORM, BPC, NL, MS, T, SPLIT>(pl, res_smem, beta_row, oa_row, thr, a.n_levels, a.rcq_zero0 != 0,
+                                              dc_pre, b_pre, tid, nt);
         if (BPC && tid < pl.m && it + 1 < a.T)           // next iteration's beta: in flight across the phases below
             b_pre = g_beta[(size_t)(it + 1) * a.n_beta + pl.bslot_c[tid]];
-        if (!LDPC_PROBE(a, 128)) __syncthreads();   // probe 128: timing without the two barriers of an iteration (results are then wrong)
+        __syncthreads();
         if (ES && !a.posterior) {
             // reference stop rule without a second gather pass: the variable phase also yields this iteration's
             // hard decisions (the posterior shares the gathered C2V values); outputs are bits only
@@ -1232,10 +1019,10 @@ __global__ __launch_bounds__(LDPC_RES_MAX_THREADS, LDPC_RES_MIN_WAVES) void resi
                 __syncthreads();
             }
         }
-        if (it != a.T - 1 && !LDPC_PROBE(a, 2)) {
+        if (it != a.T - 1) {
             if (a.unit_alpha) res_var_phase<G, 2, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt);
             else res_var_phase<G, 0, T>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt);
-            if (!LDPC_PROBE(a, 128)) __syncthreads();   // probe 128: timing without the two barriers of an iteration (results are then wrong)
+            __syncthreads();
         }
     }
 
@@ -1257,21 +1044,18 @@ __global__ __launch_bounds__(LDPC_RES_MAX_THREADS, LDPC_RES_MIN_WAVES) void resi
     // fixed-T mode: success = final syndrome is zero.  With parity words (power-of-two stride) the posterior pass scatters the
     // decisions into them (one LDS atomic per edge, then m words are read); otherwise the decisions go into the dead message
     // slots and every check reads its row of them back (MODE 8 / res_syndrome_slots)
-    const bool scatter = LDPC_RES_FINAL_SCATTER && !ES && psf.par_off != 0;
-    if (!LDPC_PROBE(a, 8)) {
-        if (ES) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt);
-        else if (scatter) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, psf);
-        else res_var_phase<G, 8, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt);
-    }
+    const bool scatter = !ES && psf.par_off != 0;
+    if (ES) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt);
+    else if (scatter) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, psf);
+    else res_var_phase<G, 8, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt);
     __syncthreads();
     unsigned unsat = kAll;
-    if (!ES && !LDPC_PROBE(a, 8)) {
+    if (!ES) {
         if (scatter) res_parity_reduce<G, SPLIT>(pl, psf.par_off, sh_unsat, tid, nt);
         else res_syndrome_slots<G, T, SPLIT>(pl, sh_unsat, tid, nt);
         __syncthreads();
         unsat = *sh_unsat;
     }
-    if (LDPC_PROBE(a, 4)) return;
     res_emit<G, T>(pl, a, llr_s, b0, open, a.T, unsat, tid, nt);
 }
 

@@ -1256,7 +1256,7 @@ def _random_code(rng, T):
 
 
 import os as _os
-_FUZZ_SEEDS = int(_os.environ.get("LDPC_FUZZ_SEEDS", "12"))     # tools/fuzz_round.sh runs the same property over hundreds of seeds
+_FUZZ_SEEDS = int(_os.environ.get("LDPC_FUZZ_SEEDS", "12"))     # LDPC_FUZZ_SEEDS widens the campaign
 
 
 @pytest.mark.parametrize("seed", range(_FUZZ_SEEDS))

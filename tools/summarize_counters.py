@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/<tag>/ctr_<workload>_p*/ (tools/gpu_round.sh) -> profiles/<tag>_<name>_counters.csv: per-launch averages of the
+"""rocprofv3 --pmc output (<tag>/ctr_<workload>_p*/ of the run-output directory, one pass each) -> profiles/<tag>_<name>_counters.csv: per-launch averages of the
 SQ / LDS counters of one kernel plus a few derived ratios.
 
     python tools/summarize_counters.py <tag> <workload> <kernel substring> <name>

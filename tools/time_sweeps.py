@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Time one decode and the individual CN / VN sweeps of a workload with HIP events.
-Used for A/B timing of kernel variants: LDPC_HIP_LIB=<variant .so> python tools/time_sweeps.py"""
+"""Time one decode and the individual CN / VN sweeps of a workload with HIP events."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
