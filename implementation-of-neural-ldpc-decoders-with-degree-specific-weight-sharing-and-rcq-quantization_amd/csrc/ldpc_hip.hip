@@ -115,11 +115,14 @@ struct ldpc_decoder {
     bool key_float4 = false;       // ... with 4 levels and every threshold 1.. in [2^-50, 2^50]: the float form of the key (kKeyFloat4)
     int4 *gat_meta = nullptr;      // [E + 1]
     int *gat_nbr = nullptr;        // [sum dv(dv-1) + 8]
-    // LDS-resident layered decode (ldpc_layered.hip): LDPC_SCHED_LAYERED_REF on codes whose posteriors fit LDS
+    // LDS-resident layered decode (ldpc_layered.hip): both layered schedules on codes whose state fits LDS
     bool lay_ok = false;
     LayeredPlan lay{};
     uint32_t *lay_off = nullptr;
     size_t lay_lds = 0;
+    int *lay_slot = nullptr;       // LDPC_SCHED_LAYERED: beta slot of each plan entry (-1: none), [m_pad + 2 * kLayPf][lw]
+    float *lay_beta = nullptr;     // ... and beta in plan order, [T][m_pad + 2 * kLayPf][lw] (lay_beta_gather)
+    bool beta_unit = false;        // every beta is 1.0 (fp32): the layered kernels skip the weight
 };
 
 namespace {
@@ -608,11 +611,12 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
             if (d->schedule == LDPC_SCHED_LAYERED)
                 hipLaunchKernelGGL((layered_rcq<VEC, true>), dim3(w.tiles), dim3(kWave), 0, s, g, (float *)w.llrT, d->thresholds,
                                    d->n_levels, (const int *)d->q_of_iter_dev, T_it, early_stop ? 1 : 0, w.bitsT, w.done, w.iters,
-                                   d->g->max_dc, (uint8_t *)w.c2v);
+                                   d->g->max_dc, (uint8_t *)w.c2v, d->beta_unit ? nullptr : (const float *)d->beta,
+                                   d->beta_slot, d->n_beta);
             else
                 hipLaunchKernelGGL((layered_rcq<VEC, false>), dim3(w.tiles), dim3(kWave), 0, s, g, (float *)w.llrT, d->thresholds,
                                    d->n_levels, (const int *)d->q_of_iter_dev, T_it, early_stop ? 1 : 0, w.bitsT, w.done, w.iters,
-                                   d->g->max_dc, (uint8_t *)nullptr);
+                                   d->g->max_dc, (uint8_t *)nullptr, nullptr, nullptr, 0);
             HIP_TRY(hipGetLastError());
             if (early_stop && T_it == 0) HIP_TRY(hipMemsetAsync(w.done, 0, (size_t)w.tiles * VEC * sizeof(uint64_t), s));
             if (bits || posterior) layout_out((const T *)w.llrT);
@@ -774,6 +778,15 @@ void resident_table_flags(ldpc_decoder *d, const void *alpha_host, const float *
         for (int q = 0; q < d->n_quant; ++q) z = z && thr_host[(size_t)q * d->n_levels] == 0.0f;
         d->rcq_zero0 = z;
     }
+}
+
+// every beta is 1.0: the layered schedules then run their unweighted form (same results, no weight loads)
+void beta_table_flags(ldpc_decoder *d, const void *beta_host)
+{
+    bool unit = d->dtype == LDPC_F32;
+    const size_t cnt = (size_t)std::max(d->T, 0) * d->n_beta;
+    for (size_t k = 0; k < cnt && unit; ++k) unit = ((const float *)beta_host)[k] == 1.0f;
+    d->beta_unit = unit;
 }
 
 // ---- LDS-resident engine: plan (host) ---------------------------------------------------------
@@ -1106,18 +1119,49 @@ int decode_resident(const ldpc_decoder *d, const void *llr, int64_t batch, int32
 }
 
 // ---- LDS-resident layered decode: plan (host) and launch -----------------------------------------------------
+// LDPC_SCHED_LAYERED: the decoder's beta table in plan order (d->lay_beta), enqueued on `s` after the table's upload
+int gather_layered_beta(const ldpc_decoder *d, hipStream_t s)
+{
+    if (!d->lay_beta || d->T == 0) return LDPC_OK;
+    const int entries = (d->lay.m_pad + 2 * kLayPf) * d->lay.lw;
+    const long long cnt = (long long)entries * d->T;
+    hipLaunchKernelGGL(lay_beta_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, (const float *)d->beta, d->n_beta,
+                       (const int *)d->lay_slot, entries, d->T, d->lay_beta);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+constexpr size_t kLayPaperMinWaves = 4;           // LDPC_SCHED_LAYERED takes the LDS kernel only with a wave per SIMD
 int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
 {
     const ldpc_graph *g = d->g;
     d->lay_ok = false;
-    if (d->schedule != LDPC_SCHED_LAYERED_REF || d->form != LDPC_C2V_RCQ || d->dtype != LDPC_F32) return LDPC_OK;
+    if (d->schedule == LDPC_SCHED_FLOODING || d->form != LDPC_C2V_RCQ || d->dtype != LDPC_F32) return LDPC_OK;
     if (g->E == 0 || g->m == 0 || g->max_dc > 64) return LDPC_OK;     // a check wider than a wavefront: streaming kernel
+    const bool paper = d->schedule == LDPC_SCHED_LAYERED;
     int lw = 1;
     while (lw < g->max_dc) lw <<= 1;
-    int cw = 64 / lw;
-    while (cw > 1 && (size_t)cw * lay_row_bytes(g->n) > kLdsBytes) cw >>= 1;
-    if ((size_t)cw * lay_row_bytes(g->n) > kLdsBytes) return LDPC_OK;  // one codeword's posteriors exceed LDS
     const int m_pad = (g->m + kLayPf - 1) / kLayPf * kLayPf;
+    // LDPC_SCHED_LAYERED also keeps one code byte per plan entry of the codeword's walk after its posteriors
+    const size_t code_off = lay_row_bytes(g->n);
+    const size_t row_bytes = paper ? code_off + ((size_t)m_pad * lw + 3) / 4 * 4 : lay_row_bytes(g->n);
+    int cw = 64 / lw;
+    while (cw > 1 && (size_t)cw * row_bytes > kLdsBytes) cw >>= 1;
+    if ((size_t)cw * row_bytes > kLdsBytes) return LDPC_OK;           // one codeword's state exceeds LDS
+    if (paper) {
+        // the codes make a codeword's state large: a full wave of codewords may leave SIMDs without a wave ((1998,1512):
+        // 4 x 15.8 KB -> two workgroups per CU).  Take the codewords per wave that put the most codewords on a CU, the
+        // fuller wave on a tie (4 -> 8, 3 -> 9, 2 -> 10, 1 -> 10 codewords per CU there).
+        int best = cw, best_cu = 0;
+        for (int c = cw; c >= 1; --c) {
+            const int per_cu = c * (int)(kLdsBytes / ((size_t)c * row_bytes));
+            if (per_cu > best_cu) { best = c; best_cu = per_cu; }
+        }
+        cw = best;
+        // fewer than one wave per SIMD loses to the streaming kernel: (16200,7200) keeps one 137 KB codeword per CU and ran
+        // 3.5x slower than layered_rcq (1872 vs 528 ms at 32768 codewords, T = 10) -- it stays on the streaming kernel
+        if (kLdsBytes / ((size_t)cw * row_bytes) < kLayPaperMinWaves) return LDPC_OK;
+    }
     if ((size_t)g->n * 4u + 4u > kLayOffMask) return LDPC_OK;
     const uint32_t none = (uint32_t)g->n * 4u;                        // the codeword's +inf word
     std::vector<uint32_t> off((size_t)(m_pad + 2 * kLayPf) * lw, none);
@@ -1156,8 +1200,23 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     // leave room for only four workgroups per CU instead of five and put the four rows of a wave on the same LDS banks
     // ((1998,1512): 11.2 vs 9.6 ms, profiles/r03_layered_variants.txt).  The kernel keeps the template flag for A/B builds.
     const int row_shift = 0;
-    d->lay = LayeredPlan{g->n, g->m, lw, cw, m_pad, deg1 ? 1 : 0, zero0 ? 1 : 0, sorted ? 1 : 0, row_shift, d->lay_off};
-    d->lay_lds = row_shift ? ((size_t)cw << row_shift) : (size_t)cw * lay_row_bytes(g->n);
+    d->lay = LayeredPlan{g->n, g->m, lw, cw, m_pad, deg1 ? 1 : 0, zero0 ? 1 : 0, sorted ? 1 : 0, row_shift, d->lay_off,
+                         (unsigned)row_bytes, (unsigned)code_off, nullptr};
+    d->lay_lds = row_shift ? ((size_t)cw << row_shift) : (size_t)cw * row_bytes;
+    if (paper) {
+        // beta of every plan entry, per iteration: gathered on the device from the decoder's table (again on set_weights)
+        std::vector<int> slot((size_t)(m_pad + 2 * kLayPf) * lw, -1);
+        for (int i = 0; i < g->m; ++i) {
+            const int e0 = g->h_check_ptr[i], dc = g->h_check_ptr[i + 1] - e0;
+            for (int k = 0; k < dc; ++k) slot[(size_t)i * lw + (lw - dc) + k] = desc->beta_slot[e0 + k];
+        }
+        rc = upload(&d->lay_slot, slot.data(), slot.size());
+        if (!rc) rc = upload(&d->lay_beta, (const float *)nullptr, slot.size() * (size_t)std::max(d->T, 1));
+        if (!rc) rc = gather_layered_beta(d, nullptr);
+        if (!rc) HIP_TRY(hipStreamSynchronize(nullptr));
+        if (rc) return rc;
+        d->lay.beta_lay = d->lay_beta;
+    }
     d->lay_ok = true;
     return LDPC_OK;
 }
@@ -1169,6 +1228,39 @@ int decode_layered_lds(const ldpc_decoder *d, const void *llr, int64_t batch, in
     hipStream_t s = (hipStream_t)stream;
     const LayeredPlan &pl = d->lay;
     const unsigned blocks = (unsigned)((batch + pl.cw - 1) / pl.cw);
+    if (d->schedule == LDPC_SCHED_LAYERED) {
+#define LDPC_PAP_K(LW_, NL_, ES_, WB_)                                                                               \
+    do {                                                                                                             \
+        auto kfn = layered_paper_lds<LW_, NL_, ES_, WB_>;                                                            \
+        if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                                   \
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kWave), d->lay_lds, s, pl, (const float *)llr, (long long)batch, \
+                           (const float *)d->thresholds, d->n_levels, (const int *)d->q_of_iter_dev, capped_T(d),   \
+                           bits, (float *)posterior, iterations, success, packed_bits);                             \
+    } while (0)
+#define LDPC_PAP_NL(LW_, ES_, WB_)                                                                                   \
+    do {                                                                                                             \
+        if (d->n_levels == 4) LDPC_PAP_K(LW_, 4, ES_, WB_); else LDPC_PAP_K(LW_, 0, ES_, WB_);                      \
+    } while (0)
+#define LDPC_PAP_LW(LW_)                                                                                             \
+    do {                                                                                                             \
+        if (early_stop) { if (d->beta_unit) LDPC_PAP_NL(LW_, true, false); else LDPC_PAP_NL(LW_, true, true); }       \
+        else { if (d->beta_unit) LDPC_PAP_NL(LW_, false, false); else LDPC_PAP_NL(LW_, false, true); }                \
+    } while (0)
+        switch (pl.lw) {
+        case 1: LDPC_PAP_LW(1); break;
+        case 2: LDPC_PAP_LW(2); break;
+        case 4: LDPC_PAP_LW(4); break;
+        case 8: LDPC_PAP_LW(8); break;
+        case 16: LDPC_PAP_LW(16); break;
+        case 32: LDPC_PAP_LW(32); break;
+        default: LDPC_PAP_LW(64); break;
+        }
+#undef LDPC_PAP_LW
+#undef LDPC_PAP_NL
+#undef LDPC_PAP_K
+        HIP_TRY(hipGetLastError());
+        return LDPC_OK;
+    }
 #define LDPC_LAY_K(LW_, NL_, ES_, D1_, Z0_, SO_)                                                                     \
     do {                                                                                                             \
         auto kfn = pl.row_shift ? layered_lds<LW_, NL_, ES_, D1_, Z0_, SO_, true> : layered_lds<LW_, NL_, ES_, D1_, Z0_, SO_, false>; \
@@ -1453,6 +1545,7 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
         d->key_float4 = in_range;
     }
     resident_table_flags(d, desc->alpha, d->form == LDPC_C2V_RCQ ? desc->thresholds : nullptr);
+    beta_table_flags(d, desc->beta);
     if (!rc && d->schedule == LDPC_SCHED_FLOODING) rc = build_resident_plan(d, desc);
     if (!rc) rc = build_layered_plan(d, desc);
     if (rc) {
@@ -1503,7 +1596,11 @@ int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alph
     DeviceGuard guard(d->g->device);
     hipStream_t s = (hipStream_t)stream;
     const size_t es = d->elem(), rows = (size_t)d->T;
-    if (beta) HIP_TRY(hipMemcpyAsync(d->beta, beta, rows * d->n_beta * es, hipMemcpyHostToDevice, s));
+    if (beta) {
+        HIP_TRY(hipMemcpyAsync(d->beta, beta, rows * d->n_beta * es, hipMemcpyHostToDevice, s));
+        beta_table_flags(d, beta);
+        if (int rc = gather_layered_beta(d, s)) return rc;
+    }
     if (alpha) {
         HIP_TRY(hipMemcpyAsync(d->alpha, alpha, rows * d->n_alpha * es, hipMemcpyHostToDevice, s));
         resident_table_flags(d, alpha, nullptr);
@@ -1524,6 +1621,7 @@ void ldpc_decoder_destroy(ldpc_decoder *d)
     (void)hipFree(d->thresholds); (void)hipFree(d->lut); (void)hipFree(d->q_of_iter_dev);
     for (void *p : d->res_bufs) (void)hipFree(p);
     (void)hipFree(d->gat_meta); (void)hipFree(d->gat_nbr); (void)hipFree(d->lay_off);
+    (void)hipFree(d->lay_slot); (void)hipFree(d->lay_beta);
     (void)hipFree(d->beta_inv_ptr); (void)hipFree(d->beta_inv_items); (void)hipFree(d->alpha_inv_ptr);
     (void)hipFree(d->alpha_inv_items); (void)hipFree(d->oms_inv_ptr); (void)hipFree(d->oms_inv_items);
     delete d;

@@ -2189,13 +2189,16 @@ __global__ __launch_bounds__(kBlock) void syndrome_latch_chunks(GraphDev g, cons
 //                the check's previous message (its 1-byte code, kept per edge in `codes`, reconstructed with the
 //                quantiser of the iteration that produced it) is subtracted from the posterior before the update,
 //                the new one is added and its code stored.  Nothing in the reference executes this: parity unpinned.
+//                With `beta` (WeightedRCQDecoder(layered="paper")) the check output is weighted as in the flooding W-RCQ
+//                check sweep: w = +-(beta_t[beta_slot[e]] * min), same fp32 product; beta == NULL: unweighted (beta 1, no load).
 template <int VEC, bool PAPER>
 __global__ __launch_bounds__(kWave) void layered_rcq(GraphDev g, float *__restrict__ post,
                                                      const float *__restrict__ thresholds, int n_levels,
                                                      const int *__restrict__ q_of_iter, int T, int early_stop,
                                                      uint64_t *__restrict__ bitsT, uint64_t *__restrict__ done,
                                                      int *__restrict__ iters, int max_dc,
-                                                     uint8_t *__restrict__ codes)
+                                                     uint8_t *__restrict__ codes, const float *__restrict__ beta,
+                                                     const int *__restrict__ beta_slot, int n_beta)
 {
     constexpr int W = kWave * VEC;
     const int lane = threadIdx.x, tile = blockIdx.x;
@@ -2232,6 +2235,8 @@ __global__ __launch_bounds__(kWave) void layered_rcq(GraphDev g, float *__restri
         if (early_stop && __ballot(frozen != kAll) == 0ull) break;
         const float *thr = thresholds + (size_t)q_of_iter[it] * n_levels;
         const float *thr_prev = thresholds + (size_t)q_of_iter[it > 0 ? it - 1 : 0] * n_levels;
+        const float *beta_row = (PAPER && beta) ? beta + (size_t)it * n_beta : nullptr;
+        auto weigh = [&](int e, float raw) { return beta_row ? beta_row[beta_slot[e]] * raw : raw; };   // b * raw (flooding order)
         if constexpr (VEC == 1) {
             // The walk is ONE dependent chain per wave (a check reads what the previous one wrote), so what counts is
             // memory round trips per check.  With at most kHeld edges per check: the indices of check i+1 are fetched
@@ -2285,7 +2290,7 @@ __global__ __launch_bounds__(kWave) void layered_rcq(GraphDev g, float *__restri
                             if (t < dc) {
                                 const float a = __builtin_fabsf(x[t]);
                                 const float raw = (a == m1) ? m2 : m1;     // arg-min edge; ties make min2 == min1
-                                const float w = flip_sign<float>(raw, par ^ signbit_of<float>(x[t]));
+                                const float w = flip_sign<float>(weigh(e0 + t, raw), par ^ signbit_of<float>(x[t]));
                                 const float mag = __builtin_fabsf(w);
                                 float rec = thr[0];
                                 unsigned lvl = 0;
@@ -2340,7 +2345,7 @@ __global__ __launch_bounds__(kWave) void layered_rcq(GraphDev g, float *__restri
                 for (int c = 0; c < VEC; ++c) {
                     const float a = __builtin_fabsf(v.x[c]);
                     const float raw = (a == m1[c]) ? m2[c] : m1[c];       // arg-min edge; ties make min2 == min1
-                    const float w = flip_sign<float>(raw, par[c] ^ signbit_of<float>(v.x[c]));
+                    const float w = flip_sign<float>(weigh(e0 + t, raw), par[c] ^ signbit_of<float>(v.x[c]));
                     const float mag = __builtin_fabsf(w);
                     float rec = thr[0];
                     unsigned lvl = 0;

@@ -29,6 +29,9 @@
 // round trip, and the in-order form's LDS waits are what the fifth wave of a CU fills.
 //
 // Arithmetic is that of layered_rcq (same helpers): results are identical to the streaming kernel's.
+//
+// layered_paper_lds (below): the same walk for LDPC_SCHED_LAYERED, the paper's schedule (previous message subtracted, optional
+// beta), with each edge's message code kept in LDS beside the posteriors.
 #pragma once
 
 #include "ldpc_kernels.hip"
@@ -50,6 +53,10 @@ struct LayeredPlan {
                                    //          bit 29 (kLayDeg1Bit) on the entries of a degree-1 check ("min2 = min", :312-313);
                                    //          no-op rows up to m_pad (inf in, inf out), then 2 * kLayPf more that only the
                                    //          prefetch past the last check reads
+    // LDPC_SCHED_LAYERED (layered_paper_lds) only:
+    unsigned row_bytes;            // LDS bytes of one codeword: posteriors + the +inf word, then the codes
+    unsigned code_off;             // byte offset of the codes inside a codeword's region: code of plan entry (i, t) at + i * lw + t
+    const float *beta_lay;         // [T][m_pad + 2 * kLayPf][lw] beta_t of the edge in plan entry (i, t) (1 where none)
 };
 
 constexpr int kLayPf = 4;          // plan entries in flight ahead of the check being processed (= the unroll of the walk)
@@ -106,6 +113,14 @@ __device__ __forceinline__ float lay_lds_ld(unsigned byte_off)
 __device__ __forceinline__ void lay_lds_st(unsigned byte_off, float v)
 {
     *(__attribute__((address_space(3))) float *)(size_t)byte_off = v;
+}
+__device__ __forceinline__ unsigned lay_lds_ld8(unsigned byte_off)
+{
+    return *(__attribute__((address_space(3))) const uint8_t *)(size_t)byte_off;
+}
+__device__ __forceinline__ void lay_lds_st8(unsigned byte_off, unsigned v)
+{
+    *(__attribute__((address_space(3))) uint8_t *)(size_t)byte_off = (uint8_t)v;
 }
 
 // NL: compile-time level count (4 = bc 3), 0 = run-time (up to 8 in registers, more from global memory)
@@ -295,6 +310,193 @@ __global__ __launch_bounds__(kWave) void layered_lds(LayeredPlan pl, const float
             }
         }
     }
+}
+
+// ---- the paper's layered schedule (LDPC_SCHED_LAYERED): RCQMinSumDecoder(layered="paper") and
+// WeightedRCQDecoder(layered="paper").  Same walk, lanes and butterfly as layered_lds; what is added is each edge's
+// previous message, kept as its 1-byte code in LDS next to the codeword's posteriors (one byte per PLAN entry, i.e. per
+// lane of each check row: lanes without an edge own a byte nobody else reads).  Per check, lane (row, t) on edge e = (c, v):
+//   u      = P_v - Q_{t-1}^{-1}(R_e)                         (the code was written in the previous iteration; 0 before any)
+//   min1 / min2 / parity over the u of the check             (butterfly on the u bit patterns, as layered_lds)
+//   w      = +-(beta_t[slot(e)] * min_others)                (WB; the flooding W-RCQ product, sign = parity of the others)
+//   R_e    = Q_t(w),  P_v = u + Q_t^{-1}(R_e)
+// The codes in LDS carry level | sign << 7 (the reconstruction is sign-flipped tau[level]); 0 initially, which reconstructs
+// to +0 under the all-zero "previous" table of iteration 0: x - (+0) == x for every x, -0 included.
+// A frozen codeword (early stop) writes back what it read: posterior and code.  Arithmetic and conventions are those of
+// layered_rcq<VEC, true>: results are identical to the streaming kernel's.
+// NL: compile-time level count (4 = bc 3), 0 = run-time (up to 8 in registers, more from global memory); WB: weighted.
+template <int LW, int NL, bool ES, bool WB>
+__global__ __launch_bounds__(kWave) void layered_paper_lds(LayeredPlan pl, const float *__restrict__ llr, long long batch,
+                                                           const float *__restrict__ thresholds, int n_levels,
+                                                           const int *__restrict__ q_of_iter, int T,
+                                                           int *__restrict__ bits, float *__restrict__ posterior,
+                                                           int *__restrict__ iterations, uint8_t *__restrict__ success,
+                                                           uint8_t *__restrict__ packed)
+{
+    extern __shared__ __align__(16) unsigned char lay_smem[];       // the only LDS object: codeword regions start at offset 0
+    if (__builtin_amdgcn_groupstaticsize() != 0) __builtin_trap();
+    const int lane = threadIdx.x;
+    const int n = pl.n, m = pl.m_pad, cw = pl.cw;
+    const int row = lane / LW, t = lane % LW;
+    const long long b0 = (long long)blockIdx.x * cw;
+    const int row_eff = min(row, cw - 1);                           // shadow lanes: see layered_lds
+    const bool row_live = b0 + row_eff < batch;
+    const unsigned row_bytes = pl.row_bytes;
+    const unsigned row_base = (unsigned)row_eff * row_bytes;
+    const unsigned code_base = row_base + pl.code_off + (unsigned)t;
+
+    for (int r = 0; r < cw; ++r) {
+        const bool have = b0 + r < batch;
+        const float *src = llr + (size_t)(b0 + r) * n;
+        const unsigned rb = (unsigned)r * row_bytes;
+        for (int j = lane; j < n; j += kWave)
+            lay_lds_st(rb + (unsigned)j * 4u, have ? __builtin_nontemporal_load(src + j) : 1.0f);
+        if (lane == 0) lay_lds_st(rb + (unsigned)n * 4u, inf_of<float>());
+        for (unsigned k = pl.code_off + 4u * (unsigned)lane; k < row_bytes; k += 4u * kWave) lay_lds_st(rb + k, 0.0f);   // codes: none
+    }
+    asm volatile("" ::: "memory");
+
+    unsigned frozen = row_live ? 0u : 1u;
+    int my_iters = T;
+    const uint32_t *plan = pl.off + t;
+    const size_t plan_rows = (size_t)m + 2 * kLayPf;
+
+    auto syndrome = [&]() {
+        unsigned unsat = 0;
+#pragma unroll 4
+        for (int i = 0; i < m; ++i) {
+            const uint32_t o = plan[(size_t)i * LW];
+            unsigned s = lay_lds_ld(row_base + (o & kLayOffMask)) < 0.0f ? 1u : 0u;
+            lay_step_xor<1, LW>(s); lay_step_xor<2, LW>(s); lay_step_xor<4, LW>(s);
+            lay_step_xor<8, LW>(s); lay_step_xor<16, LW>(s); lay_step_xor<32, LW>(s);
+            unsat |= s;
+        }
+        return unsat & 1u;
+    };
+
+    for (int it = 0; it < T; ++it) {
+        if (ES && __ballot(frozen == 0u) == 0ull) break;
+        const float *thr = thresholds + (size_t)q_of_iter[it] * n_levels;
+        const float *thp = thresholds + (size_t)q_of_iter[it > 0 ? it - 1 : 0] * n_levels;
+        // thresholds of this iteration (c*) and of the previous one (p*, 0 at it 0) as SEPARATE registers, looked up by a select
+        // tree on the level bits: over an array, "lvl == q ? t[q] : ..." is folded into an indexed load, which puts the array in
+        // memory (promoted to static LDS -- the kernel must have none)
+        float c0, c1, c2, c3, c4, c5, c6, c7, p0, p1, p2, p3, p4, p5, p6, p7;
+        {
+            const int nl = NL > 0 ? NL : n_levels;
+            const float pad = NL > 0 ? 0.0f : __builtin_nanf("");  // never matched by a compare
+            auto ld = [&](const float *tb, int q, float none) { return q < nl && q < 8 ? tb[q] : none; };
+            c0 = ld(thr, 0, pad); c1 = ld(thr, 1, pad); c2 = ld(thr, 2, pad); c3 = ld(thr, 3, pad);
+            c4 = ld(thr, 4, pad); c5 = ld(thr, 5, pad); c6 = ld(thr, 6, pad); c7 = ld(thr, 7, pad);
+            auto lp = [&](int q) { return it > 0 ? ld(thp, q, 0.0f) : 0.0f; };
+            p0 = lp(0); p1 = lp(1); p2 = lp(2); p3 = lp(3); p4 = lp(4); p5 = lp(5); p6 = lp(6); p7 = lp(7);
+            asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5), "+v"(c6), "+v"(c7));
+            asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(p4), "+v"(p5), "+v"(p6), "+v"(p7));
+        }
+        auto sel4 = [](unsigned l, float a0, float a1, float a2, float a3) { return (l & 2u) ? ((l & 1u) ? a3 : a2) : ((l & 1u) ? a1 : a0); };
+        const float *bet = WB ? pl.beta_lay + (size_t)it * plan_rows * LW + t : nullptr;
+        auto step = [&](uint32_t o, float b, int i) {
+            const unsigned addr = row_base + (o & kLayOffMask), caddr = code_base + (unsigned)i * LW;
+            const float x = lay_lds_ld(addr);
+            const unsigned cold = lay_lds_ld8(caddr), lvo = cold & 0x7fu;
+            float ro;                                               // reconstruction of the previous code
+            if constexpr (NL > 0) {
+                static_assert(NL <= 4, "compile-time level counts: 4");
+                ro = sel4(lvo, p0, p1, p2, p3);
+            } else if (n_levels <= 8) {
+                ro = (lvo & 4u) ? sel4(lvo, p4, p5, p6, p7) : sel4(lvo, p0, p1, p2, p3);
+            } else {
+                ro = it > 0 ? thp[lvo] : 0.0f;                      // lvo < n_levels: written by this kernel
+            }
+            const float u = x - flip_sign<float>(ro, cold >> 7);    // "subtract previous C2V messages" (:300-302)
+            const unsigned ub = __float_as_uint(u), a = ub & 0x7fffffffu;
+            unsigned m1 = a, m2 = 0x7f800000u, par = ub;
+            lay_step<1, LW>(m1, m2, par); lay_step<2, LW>(m1, m2, par); lay_step<4, LW>(m1, m2, par);
+            lay_step<8, LW>(m1, m2, par); lay_step<16, LW>(m1, m2, par); lay_step<32, LW>(m1, m2, par);
+            if (o & kLayDeg1Bit) m2 = m1;                           // degree-1 check: min2 = min
+            const float raw = __uint_as_float((a == m1) ? m2 : m1); // arg-min edge; ties make min2 == min1
+            const float w = flip_sign<float>(WB ? b * raw : raw, (par ^ ub) >> 31);
+            const float mag = __builtin_fabsf(w);
+            float rec;
+            unsigned lvl = 0;
+            if constexpr (NL > 0) {
+                lvl = mag >= c1 ? 1u : lvl; lvl = mag >= c2 ? 2u : lvl; lvl = mag >= c3 ? 3u : lvl;
+                rec = sel4(lvl, c0, c1, c2, c3);
+            } else if (n_levels <= 8) {
+                lvl = mag >= c1 ? 1u : lvl; lvl = mag >= c2 ? 2u : lvl; lvl = mag >= c3 ? 3u : lvl; lvl = mag >= c4 ? 4u : lvl;
+                lvl = mag >= c5 ? 5u : lvl; lvl = mag >= c6 ? 6u : lvl; lvl = mag >= c7 ? 7u : lvl;
+                rec = (lvl & 4u) ? sel4(lvl, c4, c5, c6, c7) : sel4(lvl, c0, c1, c2, c3);
+            } else {
+                rec = thr[0];
+                for (int q = 1; q < n_levels; ++q) { const bool ge = mag >= thr[q]; rec = ge ? thr[q] : rec; lvl = ge ? (unsigned)q : lvl; }
+            }
+            const unsigned neg = w < 0.0f ? 1u : 0u;                // sign(w) < 0 (rcq_decoder.py:88)
+            float upd = u + flip_sign<float>(rec, neg);
+            unsigned cnew = lvl | (neg << 7);
+            if (ES && frozen) { upd = x; cnew = cold; }            // a stopped codeword keeps posterior and code
+            lay_lds_st(addr, upd);
+            lay_lds_st8(caddr, cnew);
+        };
+        // plan entries (and betas) a group ahead, as layered_lds: m is a multiple of kLayPf, 2 * kLayPf rows follow
+        uint32_t cur[kLayPf], nxt[kLayPf];
+        float bc[kLayPf], bn[kLayPf];
+#pragma unroll
+        for (int k = 0; k < kLayPf; ++k) {
+            cur[k] = plan[(size_t)k * LW];
+            bc[k] = WB ? bet[(size_t)k * LW] : 1.0f;
+        }
+        for (int i0 = 0; i0 < m; i0 += kLayPf) {
+#pragma unroll
+            for (int k = 0; k < kLayPf; ++k) {
+                nxt[k] = plan[(size_t)(i0 + kLayPf + k) * LW];
+                bn[k] = WB ? bet[(size_t)(i0 + kLayPf + k) * LW] : 1.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < kLayPf; ++k) step(cur[k], bc[k], i0 + k);
+#pragma unroll
+            for (int k = 0; k < kLayPf; ++k) { cur[k] = nxt[k]; bc[k] = bn[k]; }
+        }
+        if (ES) {
+            const unsigned unsat = syndrome();
+            if (frozen == 0u && unsat == 0u) { frozen = 1u; my_iters = it + 1; }
+        }
+    }
+    asm volatile("" ::: "memory");
+
+    unsigned ok;
+    if (ES) ok = (row_live && frozen != 0u) ? 1u : 0u;
+    else ok = syndrome() == 0u ? 1u : 0u;
+    if (row_live && row < cw && t == 0) {
+        if (iterations) iterations[b0 + row] = (ES && ok) ? my_iters : T;
+        if (success) success[b0 + row] = (uint8_t)ok;
+    }
+    const int nbytes = (n + 7) / 8;
+    for (int r = 0; r < cw; ++r) {
+        if (b0 + r >= batch) break;
+        const size_t ob = (size_t)(b0 + r) * n;
+        for (int j0 = 0; j0 < n; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool in = j < n;
+            const float v = in ? lay_lds_ld((unsigned)r * row_bytes + (unsigned)j * 4u) : 0.0f;
+            const bool neg = in && v < 0.0f;
+            if (in && posterior) __builtin_nontemporal_store(v, posterior + ob + j);
+            if (in && bits) __builtin_nontemporal_store(neg ? 1 : 0, bits + ob + j);
+            if (packed) {
+                const unsigned long long mk = __ballot(neg);
+                if (lane < 8 && j0 + 8 * lane < n) packed[(size_t)(b0 + r) * nbytes + (j0 >> 3) + lane] = (uint8_t)(mk >> (8 * lane));
+            }
+        }
+    }
+}
+
+// beta_lay[it][entry] = beta[it][slot[entry]] (1 where slot < 0): the paper kernel's beta, in plan order
+__global__ void lay_beta_gather(const float *__restrict__ beta, int n_beta, const int *__restrict__ slot, int entries, int T,
+                                float *__restrict__ out)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= (long long)entries * T) return;
+    const int it = (int)(k / entries), s = slot[k % entries];
+    out[k] = s >= 0 ? beta[(size_t)it * n_beta + s] : 1.0f;
 }
 
 }  // namespace ldpc

@@ -111,6 +111,7 @@ class DecodeEngine:
         self.np_dtype = np.float32 if dtype == torch.float32 else np.float64
         self.iters = int(iters)
         self.c2v_form = int(c2v_form)
+        self.schedule = int(schedule)
         lib = nat.load()
         self._lib = lib
         self._ng = _NativeGraph.get(graph, self.device)
@@ -189,7 +190,14 @@ class DecodeEngine:
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.int32)
         nat.check(self._lib.ldpc_decoder_info(self.handle, nat.ptr(out)), "ldpc_decoder_info")
-        return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])],
+        resident = int(out[0]) == nat.MODE_RESIDENT
+        if self.schedule == nat.SCHED_FLOODING:
+            kernel = "resident" if resident else {3: "sweeps", 4: "cn_gather", 5: "code_pair"}[int(out[0])]
+        else:   # the layered schedules: LDS-resident walk (ldpc_layered.hip) or the HBM-streaming one (layered_rcq)
+            paper = self.schedule == nat.SCHED_LAYERED
+            kernel = ("layered_paper_lds" if paper else "layered_lds") if resident else \
+                     ("layered_rcq<paper>" if paper else "layered_rcq<ref>")
+        return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel,
                 "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
                 "codewords_per_workgroup": int(out[1]),
                 "threads_per_workgroup": int(out[2]), "lds_bytes": int(out[3])}

@@ -13,7 +13,7 @@ Reference behaviour mirrored (file:line in /root/reference):
       reference; quantiser schedule by thirds                  rcq_decoder.py:123-279
   WeightedRCQDecoder(code, bc, bv, quantizer_params, weight_sharing_type=2,
       max_iterations=50, layered=False)(llr[n]) -> (int32[n], float32[n], int);
-      ``layered`` stored and ignored by forward as in the reference
+      ``layered`` stored and ignored by forward as in the reference (every value but "paper", see below)
                                                                rcq_decoder.py:352-597
 
 ``RCQMinSumDecoder(layered=True)`` runs the reference's layered schedule exactly as the
@@ -28,6 +28,18 @@ Extensions: batched ``[B, n]`` input and ``early_stop=False`` as in the other de
 subtracted before a check's update, new one added -- the one change is the message matrix living across checks).
 Nothing in the reference executes it, so its parity is UNPINNED: it is checked against an independent CPU
 restatement only.
+
+``WeightedRCQDecoder(layered="paper")`` is the weighted layered decoder of the RCQ paper, per codeword:
+P_v = llr_v; R_{c,v} = "no message" (reconstructs to 0).  Iteration t: checks in ascending order; for check c
+  u_v = P_v - Q_{t'}^{-1}(R_{c,v})          (t' = the iteration that wrote the code),
+  min1 / min2 / sign product over the u_v  (tie and sign(0) conventions of the flooding W-RCQ decode),
+  m = beta_t[beta_slot(c, v)] * sign_excl * (v == argmin ? min2 : min1)   (the flooding W-RCQ fp32 product),
+  R_{c,v} = Q_t(m),  P_v = u_v + Q_t^{-1}(R_{c,v});
+then hard decisions (P < 0) and the syndrome; with early_stop a codeword that satisfies every check stops with its
+posteriors, iterations t+1.  beta is indexed exactly as in the flooding forward (same slots and tables, all four sharing
+types).  alpha is NOT used: a layered update has no separate variable-node sum for it to scale.  Posteriors are fp32;
+``bv`` stays stored and unused.  With every beta 1.0 the result is bit-identical to RCQMinSumDecoder(layered="paper").
+Every other value of ``layered`` (True included) runs the flooding decode, as the reference does.  No backward pass.
 """
 
 from __future__ import annotations
@@ -182,7 +194,7 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
         super().__init__()
         self.bc = bc
         self.bv = bv
-        self.layered = layered            # stored; forward ignores it exactly like the reference's
+        self.layered = layered            # stored; forward ignores it like the reference's, except "paper" (module docstring)
         self.quantizers = [NonUniformQuantizer(bc, C, gamma) for C, gamma in quantizer_params]
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized Weighted RCQ decoder: bc={bc}, bv={bv}, "
@@ -191,12 +203,18 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
     def _get_quantizer(self, iteration: int) -> NonUniformQuantizer:
         return self.quantizers[_quantizer_index(len(self.quantizers), self.max_iterations, iteration)]
 
+    def _schedule(self) -> int:
+        """message schedule of the engine: the paper's layered one for layered="paper", else flooding (the reference
+        ignores ``layered`` here, rcq_decoder.py:377)"""
+        import _native as nat
+        return nat.SCHED_LAYERED if isinstance(self.layered, str) and self.layered == "paper" else nat.SCHED_FLOODING
+
     def _extra_key(self):
-        return _threshold_table(self.quantizers).tobytes()
+        return (_threshold_table(self.quantizers).tobytes(), self._schedule())
 
     def _engine_kwargs(self, layout, beta, alpha):
         import _native as nat
-        return dict(c2v_form=nat.C2V_RCQ, beta=beta, beta_slot=layout.beta_slot,
+        return dict(c2v_form=nat.C2V_RCQ, schedule=self._schedule(), beta=beta, beta_slot=layout.beta_slot,
                     alpha=alpha, alpha_slot=layout.alpha_slot,
                     thresholds=_threshold_table(self.quantizers),
                     q_of_iter=_quantizer_schedule(len(self.quantizers), self.max_iterations))

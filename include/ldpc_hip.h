@@ -66,7 +66,11 @@ enum {
  * 64 edges) and streaming (posteriors in HBM, a lane per codeword; LDPC_MODE_STREAM and every other case).
  * LAYERED is the schedule that code sets out to implement (and the RCQ paper defines): the check's previous
  * message IS subtracted before its update and the new one added -- an extension with no reference execution
- * to compare against (parity unpinned; checked against an independent CPU restatement only). */
+ * to compare against (parity unpinned; checked against an independent CPU restatement only).  LAYERED applies the decoder's beta
+ * table exactly as the flooding RCQ check update does (c2v = deq(quant(beta_t[beta_slot[e]] * s * min)); alpha is not used) --
+ * WeightedRCQDecoder(layered="paper"); a table of all 1.0 is the unweighted schedule.  Two kernels with identical results: LDS-resident
+ * (posteriors AND the per-edge message codes in LDS; LDPC_MODE_AUTO / RESIDENT when checks have <= 64 edges and at least four one-wave
+ * workgroups fit a CU's LDS) and streaming (every other case). */
 enum { LDPC_SCHED_FLOODING = 0, LDPC_SCHED_LAYERED_REF = 1, LDPC_SCHED_LAYERED = 2 };
 
 typedef struct ldpc_graph ldpc_graph;      /* Tanner graph, CSR + CSC, device resident */
