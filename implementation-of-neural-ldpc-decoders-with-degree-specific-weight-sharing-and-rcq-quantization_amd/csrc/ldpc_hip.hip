@@ -1045,35 +1045,45 @@ int allow_full_lds(const void *kfn, int device)
     return LDPC_OK;
 }
 
+// the variable state fits the lanes' registers (ResVarState): at most kResRegVars variables per lane, every degree > 4
+// variable in the first round, no split checks; other codes keep the streaming variable loop.  Fixed-T decodes only:
+// the early-stop kernels carry the syndrome/emit state as well and would spill the register state to scratch
+bool resident_reg_state(const ldpc_decoder *d)
+{
+    return !d->res.any_split && d->res.n <= kResRegVars * d->res_NT && d->res.n_hi <= d->res_NT;
+}
+
 template <int G>
 int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
 {
     const size_t lds = d->res_lds;
+    const bool reg = resident_reg_state(d) && !a.early_stop;
     if (d->dtype == LDPC_F64) {                       // one fp64 codeword per workgroup in the slots of a float pair
         if (G != 2 || !d->res.bslot_c) return fail(LDPC_ERR_ARG, "internal: fp64 resident geometry");
         const unsigned blocks64 = (unsigned)a.batch;
-#define LDPC_RES64(MS, SPLIT)                                                                             \
+#define LDPC_RES64(MS, SPLIT, REG)                                                                        \
     do {                                                                                                  \
-        auto kfn = a.early_stop ? resident_decode<1, FORM_NMS, true, 0, MS, 1, double, SPLIT>             \
-                                : resident_decode<1, FORM_NMS, true, 0, MS, 0, double, SPLIT>;            \
+        auto kfn = a.early_stop ? resident_decode<1, FORM_NMS, true, 0, MS, 1, double, SPLIT, false>      \
+                                : resident_decode<1, FORM_NMS, true, 0, MS, 0, double, SPLIT, REG>;       \
         if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                        \
         hipLaunchKernelGGL(kfn, dim3(blocks64), dim3(d->res_NT), lds, s, d->res, a);                      \
     } while (0)
         // codes with split (wide) checks run the generic-stride instantiation with the lane-group exchange compiled in
-        if (d->res.any_split) LDPC_RES64(0, true);
-        else if (d->res.mstride == 512) LDPC_RES64(512, false);
-        else LDPC_RES64(0, false);
+        if (d->res.any_split) LDPC_RES64(0, true, false);
+        else if (d->res.mstride == 512) { if (reg) LDPC_RES64(512, false, true); else LDPC_RES64(512, false, false); }
+        else if (reg) LDPC_RES64(0, false, true);
+        else LDPC_RES64(0, false, false);
 #undef LDPC_RES64
         HIP_TRY(hipGetLastError());
         return LDPC_OK;
     }
     const unsigned blocks = (unsigned)((a.batch + G - 1) / G);
-#define LDPC_RES_MS(FORM, NL, MS, SPLIT)                                                                 \
+#define LDPC_RES_MS(FORM, NL, MS, SPLIT, REG)                                                            \
     do {                                                                                                 \
-        auto kfn = d->res.bslot_c ? (a.early_stop ? resident_decode<G, FORM, true, NL, MS, 1, float, SPLIT>     \
-                                                  : resident_decode<G, FORM, true, NL, MS, 0, float, SPLIT>)    \
-                                  : (a.early_stop ? resident_decode<G, FORM, false, NL, MS, 1, float, SPLIT>    \
-                                                  : resident_decode<G, FORM, false, NL, MS, 0, float, SPLIT>);  \
+        auto kfn = d->res.bslot_c ? (a.early_stop ? resident_decode<G, FORM, true, NL, MS, 1, float, SPLIT, false>   \
+                                                  : resident_decode<G, FORM, true, NL, MS, 0, float, SPLIT, REG>)    \
+                                  : (a.early_stop ? resident_decode<G, FORM, false, NL, MS, 1, float, SPLIT, false>  \
+                                                  : resident_decode<G, FORM, false, NL, MS, 0, float, SPLIT, REG>);  \
         if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                       \
         hipLaunchKernelGGL(kfn, dim3(blocks), dim3(d->res_NT), lds, s, d->res, a);                       \
     } while (0)
@@ -1081,9 +1091,12 @@ int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
     // exchange compiled in -- the specialised ones stay exactly as lean as without the feature
 #define LDPC_RES(FORM, NL)                                                                               \
     do {                                                                                                 \
-        if (d->res.any_split) LDPC_RES_MS(FORM, 0, 0, true);                                             \
-        else if (d->res.mstride == 512) LDPC_RES_MS(FORM, NL, 512, false);                               \
-        else LDPC_RES_MS(FORM, NL, 0, false);                                                            \
+        if (d->res.any_split) LDPC_RES_MS(FORM, 0, 0, true, false);                                      \
+        else if (d->res.mstride == 512) {                                                                \
+            if (reg) LDPC_RES_MS(FORM, NL, 512, false, true);                                            \
+            else LDPC_RES_MS(FORM, NL, 512, false, false);                                               \
+        } else if (reg) LDPC_RES_MS(FORM, NL, 0, false, true);                                           \
+        else LDPC_RES_MS(FORM, NL, 0, false, false);                                                     \
     } while (0)
     if (d->form == LDPC_C2V_NMS) LDPC_RES(FORM_NMS, 0);
     else if (d->form == LDPC_C2V_OMS) LDPC_RES(FORM_OMS, 0);

@@ -542,10 +542,11 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
 //         (dead) LLR slot with the posterior so the output pass can read it in original order
 // MODE 4 / 6: MODE 0 / 2 plus the hard-decision byte from the same gathered values -- the early-stop
 //         iteration of callers that do not ask for the posterior (one gather pass instead of two)
+// `lreg`: the variable's LLR pair held in registers (ResVarState), or null to read it from llr_s
 template <int G, int DV, int MODE, typename T>
 __device__ __forceinline__ void res_var_body(unsigned char *smem, T *__restrict__ llr_s,
                                              uint8_t *__restrict__ bits_s, int q, const uint4 &slo, const uint4 &shi,
-                                             T a, unsigned emask, const ParScatter &ps)
+                                             T a, unsigned emask, const ParScatter &ps, const Pack<T, G> *lreg)
 {
     using P = Pack<T, G>;
     constexpr int ORD = std::is_same<T, float>::value ? 0 : 1;       // torch.sum fp32 order / np.sum fp64 order
@@ -554,7 +555,7 @@ __device__ __forceinline__ void res_var_body(unsigned char *smem, T *__restrict_
     P x[DV > 0 ? DV : 1];
 #pragma unroll
     for (int k = 0; k < DV; ++k) x[k] = lds_load<P>(off[k]);
-    P l = L[q];
+    P l = lreg ? *lreg : L[q];
     if constexpr (MODE == 0 || MODE == 2 || MODE == 4 || MODE == 6) {
         P out[DV > 0 ? DV : 1];
         auto v2c = [&](T llr, T sum) { return (MODE & 2) ? llr + sum : llr + a * sum; };
@@ -620,9 +621,10 @@ __device__ __forceinline__ uint4 plan_unpack(const uint2 &p)
 template <int G, int MODE, typename T>
 __device__ __forceinline__ void res_var_dispatch(unsigned char *smem, T *__restrict__ llr_s,
                                                  uint8_t *__restrict__ bits_s, int q, int dv, const uint4 &slo,
-                                                 const uint4 &shi, T a, unsigned emask, const ParScatter &ps)
+                                                 const uint4 &shi, T a, unsigned emask, const ParScatter &ps,
+                                                 const Pack<T, G> *lreg = nullptr)
 {
-#define LDPC_RV(D) case D: res_var_body<G, D, MODE, T>(smem, llr_s, bits_s, q, slo, shi, a, emask, ps); break;
+#define LDPC_RV(D) case D: res_var_body<G, D, MODE, T>(smem, llr_s, bits_s, q, slo, shi, a, emask, ps, lreg); break;
     switch (dv) {
         LDPC_RV(0) LDPC_RV(1) LDPC_RV(2) LDPC_RV(3) LDPC_RV(4) LDPC_RV(5) LDPC_RV(6) LDPC_RV(7) LDPC_RV(8)
     default: break;   // host admits only max_dv <= 8 to this engine
@@ -630,16 +632,64 @@ __device__ __forceinline__ void res_var_dispatch(unsigned char *smem, T *__restr
 #undef LDPC_RV
 }
 
+// Register-resident variable state (REG kernels, n <= kResRegVars * blockDim.x and n_hi <= blockDim.x): lane tid owns
+// the sorted variables q = tid + r * nt, r < kResRegVars; their plan entries (degree | alpha column, packed slot offsets)
+// and LLR pairs are loaded ONCE per launch and every variable phase runs from registers -- no plan loads and no llr_s
+// read per iteration.  The rounds are unrolled (the array indices must be compile-time to stay in registers); a wave
+// whose variables all lie past n leaves at a scalar branch.  Degree > 4 variables all sit in round 0, so only that
+// round carries the upper offset half.
+constexpr int kResRegVars = 4;
+template <typename T, int G>
+struct ResVarState {
+    unsigned meta[kResRegVars];   // vmeta of the variable, 0 past n
+    uint2 plo[kResRegVars];       // vslot_lo
+    uint2 phi0;                   // vslot_hi of the round-0 variable (degree > 4), else 0
+    Pack<T, G> l[kResRegVars];    // channel LLRs as the variable phase reads them (llr_s contents)
+};
+
+template <int G, int MODE, typename T>
+__device__ __forceinline__ void res_var_phase_reg(const ResidentPlan &pl, unsigned char *smem,
+                                                  T *__restrict__ llr_s, uint8_t *__restrict__ bits_s,
+                                                  const T *__restrict__ alpha_lds,
+                                                  const T *__restrict__ alpha_glb, unsigned emask,
+                                                  int tid, int nt, ResVarState<T, G> &st, const ParScatter &ps)
+{
+    // the packed entries are unpacked at the point of use, as in the streaming loop: an opaque redefinition per phase
+    // keeps the compiler from hoisting 8 unpacked offsets per variable out of the iteration loop (they would not fit
+    // the register budget of four waves per SIMD)
+#pragma unroll
+    for (int r = 0; r < kResRegVars; ++r) asm volatile("" : "+v"(st.meta[r]), "+v"(st.plo[r].x), "+v"(st.plo[r].y));
+    asm volatile("" : "+v"(st.phi0.x), "+v"(st.phi0.y));
+#pragma unroll
+    for (int r = 0; r < kResRegVars; ++r) {
+        const int q = tid + r * nt;
+        if (__builtin_amdgcn_readfirstlane(q - (tid & 63)) >= pl.n) break;   // the whole wave is past the end
+        if (q < pl.n) {
+            const unsigned meta = st.meta[r];
+            const uint4 slo = plan_unpack(st.plo[r]), shi = r == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
+            T a = (T)0;
+            if (MODE == 0 || MODE == 4) a = alpha_lds ? alpha_lds[meta >> 8] : alpha_glb[meta >> 8];
+            res_var_dispatch<G, MODE, T>(smem, llr_s, bits_s, q, (int)(meta & 0xffu), slo, shi, a, emask, ps, &st.l[r]);
+        }
+    }
+}
+
 // Index data (degree, alpha column, the slot offsets) of the NEXT variable of a lane is fetched from
 // global memory (L1/L2 resident, shared by every workgroup) while the current one is processed.
 // (A two-register-set ping-pong that avoids the hand-over copies doubled the code and measured no faster.)
-template <int G, int MODE, typename T>
+// REG: the register-resident form above instead.
+template <int G, int MODE, typename T, bool REG>
 __device__ __forceinline__ void res_var_phase(const ResidentPlan &pl, unsigned char *smem,
                                               T *__restrict__ llr_s, uint8_t *__restrict__ bits_s,
                                               const T *__restrict__ alpha_lds,
                                               const T *__restrict__ alpha_glb, unsigned emask,
-                                              int tid, int nt, const ParScatter ps = ParScatter{})
+                                              int tid, int nt, ResVarState<T, G> &st,
+                                              const ParScatter ps = ParScatter{})
 {
+    if constexpr (REG) {
+        res_var_phase_reg<G, MODE, T>(pl, smem, llr_s, bits_s, alpha_lds, alpha_glb, emask, tid, nt, st, ps);
+        return;
+    }
     const int n = pl.n, n_hi = pl.n_hi;
     // Plan loads are UNCONDITIONAL with clamped indices (a lane past the end re-reads the last entry, a variable of degree <= 4
     // reads the last `hi` entry: same cache lines, values unused): with a fixed number of loads per round the compiler waits for
@@ -857,7 +907,9 @@ __host__ __device__ inline size_t res_lds_total(int S, int n, int G, int n_alpha
 // the posterior/syndrome/emit code of the stop rule: the extra code cost the hot loop ~4 % when merged)
 constexpr int kResMaxThreads = 1024;   // launch bounds of resident_decode: threads per workgroup, waves per SIMD the
 constexpr int kResMinWaves = 4;        // register allocation must leave room for
-template <int G, int FORM, bool BPC, int NL, int MS, int ES, typename T = float, bool SPLIT = false>
+// REG: variable state in registers (ResVarState; the host takes it for fixed-T decodes of codes that qualify, see
+// resident_reg_state)
+template <int G, int FORM, bool BPC, int NL, int MS, int ES, typename T = float, bool SPLIT = false, bool REG = false>
 __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(ResidentPlan pl, ResidentArgs a)
 {
     extern __shared__ __align__(16) unsigned char res_smem[];     // the only LDS object: msg starts at offset 0
@@ -914,7 +966,41 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
     for (int k = tid; k < pl.par_words; k += nt) lds_store<unsigned>(psf.par_off + 4u * (unsigned)k, 0u);
     __syncthreads();
     // "initialise v2c with the channel LLRs" (T == 0: c2v = 0, the loop never runs)
-    {
+    ResVarState<T, G> st{};
+    if constexpr (REG) {
+        // the lane's variables q = tid + r*nt: plan entries and LLR pairs into registers, once per launch
+        const P *L = reinterpret_cast<const P *>(llr_s);
+#pragma unroll
+        for (int r = 0; r < kResRegVars; ++r) {
+            const int q = tid + r * nt;
+            if (q < n) {
+                st.meta[r] = pl.vmeta[q];
+                st.plo[r] = pl.vslot_lo[q];
+                if (r == 0 && q < pl.n_hi) st.phi0 = pl.vslot_hi[q];
+                st.l[r] = L[q];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kResRegVars; ++r) {
+            if (tid + r * nt < n) {
+                const uint4 slo = plan_unpack(st.plo[r]), shi = r == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
+                const unsigned off[8] = {slo.x, slo.y, slo.z, slo.w, shi.x, shi.y, shi.z, shi.w};
+                const int dv = (int)(st.meta[r] & 0xffu);
+                P l = st.l[r];
+                if constexpr (!std::is_same<T, float>::value) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) l.x[g] = __builtin_canonicalize(l.x[g]);   // quiet NaNs (see the fp64 check phase)
+                }
+                if (a.T == 0) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) l.x[g] = (T)0;
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (e < dv) lds_store<P>(off[e], l);
+            }
+        }
+    } else {
         const P *L = reinterpret_cast<const P *>(llr_s);
         for (int q0 = tid; q0 < n; q0 += kPro * nt) {
             int dvk[kPro];
@@ -978,9 +1064,9 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
             // reference stop rule without a second gather pass: the variable phase also yields this iteration's
             // hard decisions (the posterior shares the gathered C2V values); outputs are bits only
             const bool last = it == a.T - 1;
-            if (last) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, ps);
-            else if (a.unit_alpha) res_var_phase<G, 6, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, ps);
-            else res_var_phase<G, 4, T>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt, ps);
+            if (last) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, st, ps);
+            else if (a.unit_alpha) res_var_phase<G, 6, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, st, ps);
+            else res_var_phase<G, 4, T, REG>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt, st, ps);
             __syncthreads();
             // the flag word alternates between iterations: this one's is read after ONE barrier while thread 0 already clears
             // the other one for the next iteration (no third barrier)
@@ -1000,7 +1086,7 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
             continue;
         }
         if (ES) {
-            res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, ps);
+            res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, st, ps);
             __syncthreads();
             unsigned *su = sh_unsat + (it & 1);
             if (ps.par_off) res_parity_reduce<G, SPLIT>(pl, ps.par_off, su, tid, nt);
@@ -1011,7 +1097,7 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
             const unsigned newly = ~unsat & ~done & kAll;
             if (newly) {                                 // block-uniform
                 if (a.dbg_c2v) res_dump_c2v<G, T>(pl, a, b0, newly, tid, nt);      // slots still hold this iteration's C2V
-                res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, newly, tid, nt);
+                res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, newly, tid, nt, st);
                 __syncthreads();
                 res_emit<G, T>(pl, a, llr_s, b0, newly, it + 1, 0u, tid, nt);
                 done |= newly;
@@ -1020,8 +1106,8 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
             }
         }
         if (it != a.T - 1) {
-            if (a.unit_alpha) res_var_phase<G, 2, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt);
-            else res_var_phase<G, 0, T>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt);
+            if (a.unit_alpha) res_var_phase<G, 2, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, st);
+            else res_var_phase<G, 0, T, REG>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt, st);
             __syncthreads();
         }
     }
@@ -1045,9 +1131,9 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
     // decisions into them (one LDS atomic per edge, then m words are read); otherwise the decisions go into the dead message
     // slots and every check reads its row of them back (MODE 8 / res_syndrome_slots)
     const bool scatter = !ES && psf.par_off != 0;
-    if (ES) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt);
-    else if (scatter) res_var_phase<G, 1, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, psf);
-    else res_var_phase<G, 8, T>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt);
+    if (ES) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
+    else if (scatter) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st, psf);
+    else res_var_phase<G, 8, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     __syncthreads();
     unsigned unsat = kAll;
     if (!ES) {
