@@ -173,11 +173,11 @@ def load():
         lib.ldpc_debug_sweep.restype = C.c_int
         lib.ldpc_debug_sweep.argtypes = [vp, i64, i32, i32, vp, C.c_size_t, vp]
         lib.ldpc_debug_workspace_layout.restype = C.c_int
-        lib.ldpc_debug_workspace_layout.argtypes = [vp, i64, vp]
+        lib.ldpc_debug_workspace_layout.argtypes = [vp, i64, i32, vp]
         lib.ldpc_debug_key4.restype = C.c_int
         lib.ldpc_debug_key4.argtypes = [vp, i64, C.c_float, vp, vp, vp, vp]
         lib.ldpc_debug_resident_c2v.restype = C.c_int
-        lib.ldpc_debug_resident_c2v.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+        lib.ldpc_debug_resident_c2v.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp]
         lib.ldpc_train_saved_bytes.restype = C.c_size_t
         lib.ldpc_train_saved_bytes.argtypes = [vp, i64]
         lib.ldpc_train_workspace_bytes.restype = C.c_size_t

@@ -148,6 +148,10 @@ int pick_vec(const ldpc_decoder *d, int64_t batch)
 // entry points only enqueue work, so the cap lives exactly as long as the call that set it.
 thread_local int tl_iter_cap = INT_MAX;
 inline int capped_T(const ldpc_decoder *d) { return std::min(d->T, tl_iter_cap); }
+struct IterCap {
+    explicit IterCap(int c) { tl_iter_cap = c; }
+    ~IterCap() { tl_iter_cap = INT_MAX; }
+};
 
 struct Workspace {
     int vec = 0, tiles = 0;
@@ -1676,10 +1680,7 @@ int ldpc_decode_capped(const ldpc_decoder *d, const void *llr, int64_t batch, in
                        void *workspace, size_t workspace_bytes, void *stream)
 {
     if (max_iterations < 1) return fail(LDPC_ERR_ARG, "max_iterations must be >= 1");
-    struct Cap {
-        explicit Cap(int c) { tl_iter_cap = c; }
-        ~Cap() { tl_iter_cap = INT_MAX; }
-    } cap(max_iterations);
+    IterCap cap(max_iterations);
     return ldpc_decode(d, llr, batch, early_stop, bits, posterior, iterations, success, packed_bits, workspace, workspace_bytes,
                        stream);
 }
@@ -1875,26 +1876,28 @@ int ldpc_debug_key4(const float *values, int64_t count, float beta, const float 
     return LDPC_OK;
 }
 
-int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int64_t out8[8])
+int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int64_t out8[8])
 {
     if (!d || !out8 || batch <= 0) return fail(LDPC_ERR_ARG, "bad argument");
     if (use_resident(d) || use_layered_lds(d)) return fail(LDPC_ERR_ARG, "workspace layout exists only in LDPC_MODE_STREAM");
     char *base = reinterpret_cast<char *>(kAlign);   // any non-null base: only differences are used
     const Workspace w = carve(d, batch, base);
     out8[0] = w.vec; out8[1] = w.tiles;
-    // fused RCQ form: the codes ping-pong between the two buffers, iteration T-1 leaves them in buffer (T-1) & 1
-    const char *c2v_final = (use_gather(d) && d->T > 0 && ((d->T - 1) & 1)) ? w.v2c : w.c2v;
+    // fused RCQ form: the codes ping-pong between the two buffers, the last iteration it leaves them in buffer it & 1
+    const int T_run = max_iterations > 0 ? std::min(d->T, (int)max_iterations) : d->T;
+    const char *c2v_final = (use_gather(d) && T_run > 0 && ((T_run - 1) & 1)) ? w.v2c : w.c2v;
     out8[2] = w.llrT - base; out8[3] = w.v2c - base; out8[4] = c2v_final - base; out8[5] = w.postT - base;
     out8[6] = (char *)w.bitsT - base; out8[7] = (char *)w.done - base;
     return LDPC_OK;
 }
 
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,
-                            void *posterior, int32_t *iterations, void *c2v_out, void *stream)
+                            int32_t max_iterations, void *posterior, int32_t *iterations, void *c2v_out, void *stream)
 {
     if (!d || !llr || !posterior || !c2v_out || batch <= 0) return fail(LDPC_ERR_ARG, "bad argument");
     if (!use_resident(d)) return fail(LDPC_ERR_ARG, "the decoder is not on the LDS-resident engine");
     if (d->g->n == 0) return LDPC_OK;
+    IterCap cap(max_iterations > 0 ? max_iterations : INT_MAX);      // as ldpc_decode_capped; <= 0: the decoder's T
     return decode_resident(d, llr, batch, early_stop, nullptr, posterior, iterations, nullptr, nullptr, c2v_out, stream);
 }
 

@@ -437,10 +437,13 @@ class DecodeEngine:
                                                  C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)),
                       "ldpc_debug_sweep")
 
-    def debug_resident_c2v(self, llr: torch.Tensor, *, early_stop: bool = True):
+    def debug_resident_c2v(self, llr: torch.Tensor, *, early_stop: bool = True, max_iters: Optional[int] = None):
         """LDS-resident engine: decode `llr` and also return every codeword's C2V messages of its last executed
-        iteration -> (c2v [B, E] dtype values in CSR edge order, posterior [B, n], iterations [B]).  Test hook
-        (include/ldpc_hip_debug.h); RCQ decoders hold reconstructed values, see `rcq_codes_from_values`."""
+        iteration -> (c2v [B, E] dtype values in CSR edge order, posterior [B, n], iterations [B]).  max_iters: run at
+        most that many of the decoder's iterations, as decode(max_iters=...).  Test hook (include/ldpc_hip_debug.h);
+        RCQ decoders hold reconstructed values, see `codes_of` in tests/test_gpu_parity.py."""
+        if max_iters is not None and int(max_iters) < 1:
+            raise ValueError("max_iters must be >= 1")
         llr = self._check_llr(llr)
         B, n = llr.shape
         dev = self.device
@@ -450,15 +453,18 @@ class DecodeEngine:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             p = lambda t: C.c_void_p(t.data_ptr())
-            nat.check(self._lib.ldpc_debug_resident_c2v(self.handle, p(llr), B, int(bool(early_stop)), p(post), p(iters),
+            nat.check(self._lib.ldpc_debug_resident_c2v(self.handle, p(llr), B, int(bool(early_stop)),
+                                                        0 if max_iters is None else int(max_iters), p(post), p(iters),
                                                         p(c2v), C.c_void_p(stream)), "ldpc_debug_resident_c2v")
         return c2v, post, iters
 
-    def debug_c2v(self, batch: int) -> torch.Tensor:
+    def debug_c2v(self, batch: int, max_iters: Optional[int] = None) -> torch.Tensor:
         """Streaming engine: C2V state left by the last decode(batch): [B, E] uint8 quantiser codes (RCQ) or
-        dtype values, CSR edge order.  Test hook (per-edge code parity with the reference)."""
+        dtype values, CSR edge order.  max_iters: the cap that decode ran with (decode(max_iters=...)), None: uncapped.
+        Test hook (per-edge code parity with the reference)."""
         out8 = np.zeros(8, dtype=np.int64)
-        nat.check(self._lib.ldpc_debug_workspace_layout(self.handle, int(batch), nat.ptr(out8)),
+        cap = 0 if max_iters is None else int(max_iters)
+        nat.check(self._lib.ldpc_debug_workspace_layout(self.handle, int(batch), cap, nat.ptr(out8)),
                   "ldpc_debug_workspace_layout")
         vec, tiles, off = int(out8[0]), int(out8[1]), int(out8[4])
         W, E = 64 * vec, self.graph.E

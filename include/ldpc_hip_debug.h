@@ -24,15 +24,19 @@ int ldpc_debug_sweep(const ldpc_decoder *d, int64_t batch, int32_t which, int32_
 
 /* Byte offsets of the streaming engine's state arrays inside a workspace for `batch`
  * codewords: out8 = { VEC, tiles, llrT, v2c, c2v, postT, bitsT, done }.  Messages are laid out
- * [tile][edge][W] with W = 64*VEC codewords innermost. */
-int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int64_t out8[8]);
+ * [tile][edge][W] with W = 64*VEC codewords innermost.  c2v is where the last executed iteration
+ * left its messages in a decode capped at max_iterations (ldpc_decode_capped; <= 0: ldpc_decode). */
+int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int64_t out8[8]);
 
 /* LDS-resident engine: decode llr[batch][n] (posterior[batch][n] and iterations[batch] out, as
  * ldpc_decode) and ALSO copy every codeword's check-to-variable messages of its last executed
  * iteration out of LDS into c2v_out[batch][E] (decoder dtype, CSR edge order; RCQ decoders hold the
- * reconstructed values (1 - 2*sign) * tau[level], from which the test recovers the codes). */
+ * reconstructed values (1 - 2*sign) * tau[level], from which the test recovers the codes).
+ * max_iterations > 0 runs at most that many of the decoder's iterations, as ldpc_decode_capped;
+ * max_iterations <= 0 runs the decoder's T. */
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,
-                            void *posterior, int32_t *iterations, void *c2v_out, void *stream);
+                            int32_t max_iterations, void *posterior, int32_t *iterations, void *c2v_out,
+                            void *stream);
 
 /* The variable sweep of the RCQ code-pair form turns every outgoing value v into the key
  * [m > 0] + [m >= t1] + [m >= t2] + [m >= t3] of m = |beta * v| (thresholds4[0] is not used; device pointers, thresholds

@@ -256,6 +256,59 @@ def test_dvbs2_wrcq_32768_properties(gpu_device, oracle_mod):
     np.testing.assert_array_equal(res.posterior[rows].detach().cpu().numpy(), op)
 
 
+_dvbs2_expect = {}
+
+
+def test_dvbs2_wrcq_32768_rows_match_oracle_with_edge_codes(gpu_device, oracle_mod, engine_mode):
+    """config 5 as bench.py times it -- (16200,7200), W-RCQ type 2, T = 20, 32768 codewords, fixed T -- and with early stop:
+    112 sampled rows (both halves' ends, both edges of 256-codeword tiles) equal the oracle in bits, iterations, success, the
+    posterior (equal as values) and the 3-bit code of every edge in the last executed iteration.  Fixed T also at the caps
+    t = 1, 6, 7, 14: the quantiser switches at iterations 6 and 13 (0-based), the codes are the oracle trace's slice t - 1."""
+    import codes
+    from rcq_decoder import WeightedRCQDecoder
+    B, T = 32768, 20
+    code = codes.load_code("dvbs2_like_16200_7200", T)
+    g = code.tanner_graph()
+    dec = WeightedRCQDecoder(code, 3, 8, QP, weight_sharing_type=2, max_iterations=T)
+    rng = np.random.default_rng(4321)
+    with torch.no_grad():
+        for k in sorted(dec.beta_weights.keys()):
+            dec.beta_weights[k].fill_(float(np.float32(rng.uniform(0.5, 1.0))))
+        for k in sorted(dec.alpha_weights.keys()):
+            dec.alpha_weights[k].fill_(float(np.float32(rng.uniform(0.8, 1.2))))
+    beta = {k: float(v.item()) for k, v in dec.beta_weights.items()}
+    alpha = {k: float(v.item()) for k, v in dec.alpha_weights.items()}
+    eng = dec._get_engine(gpu_device)
+    assert eng.info()["engine"] == "stream"                    # the (16200,7200) code never takes the resident engine
+    llr = torch.cat([awgn_gpu(B // 2, g.n, 2.0, 7, gpu_device), awgn_gpu(B // 2, g.n, 5.0, 8, gpu_device)])
+    edges = [255, 256, 511, 512, B // 2 - 257, B // 2 - 256, B - 257, B - 256]
+    rows = np.unique(np.r_[0, B // 2 - 1, B // 2, B - 1, edges, np.random.default_rng(2).integers(0, B, 100)])
+    assert len(rows) >= 100
+    rows_t = torch.from_numpy(rows).to(gpu_device)
+    og = oracle_mod.OracleGraph(n=g.n, check_ptr=g.check_ptr, var_idx=g.var_idx)
+    for early in (False, True):
+        if early not in _dvbs2_expect:                        # the same for every engine form
+            _dvbs2_expect[early] = oracle_mod.weighted_rcq(og, llr[rows].cpu().numpy(), 3, QP, 2, T, beta, alpha,
+                                                           early_stop=early, trace_codes=True)
+        ob, op, oi, os_, oc = _dvbs2_expect[early]
+        res = eng.decode(llr, early_stop=early)
+        np.testing.assert_array_equal(res.bits[rows_t].cpu().numpy(), ob)
+        np.testing.assert_array_equal(res.iterations[rows_t].cpu().numpy(), oi)
+        np.testing.assert_array_equal(res.success[rows_t].cpu().numpy(), os_)
+        np.testing.assert_array_equal(res.posterior[rows_t].cpu().numpy(), op)
+        got = eng.debug_c2v(B)[rows_t].cpu().numpy()
+        np.testing.assert_array_equal(got, np.stack([oc[r, oi[r] - 1] for r in range(len(rows))]))
+        if early:
+            assert len(np.unique(oi)) >= 3 and os_.any() and not os_.all()   # stopped and unstopped rows in the sample
+            continue
+        assert os_.any() and not os_.all()
+        for t in (1, 6, 7, 14):
+            res = eng.decode(llr, early_stop=False, max_iters=t)
+            assert bool((res.iterations == t).all())
+            got = eng.debug_c2v(B, max_iters=t)[rows_t].cpu().numpy()
+            np.testing.assert_array_equal(got, oc[:, t - 1], err_msg=f"codes after {t} iterations")
+
+
 def run_bench(extra, env_extra=None, timeout=900):
     import json
     import os

@@ -37,17 +37,18 @@ def engine_mode(request, monkeypatch):
     return request.param
 
 
-def codes_of(dec, llr_gpu, early_stop=True):
+def codes_of(dec, llr_gpu, early_stop=True, max_iters=None):
     """per-edge quantiser codes [B, E] (CSR order) of every codeword's last executed iteration, on BOTH engines:
-    the streaming engine keeps the 1-byte codes in HBM (state of the last decode); the LDS-resident engine holds
-    reconstructed values (1 - 2*sign) * tau[level], dumped by ldpc_debug_resident_c2v and mapped back to codes here
-    (the sign bit of a reconstructed zero tells code L, "-0", from code 0)."""
+    the streaming engine keeps the 1-byte codes in HBM (state of the last decode, which must have run with this
+    max_iters); the LDS-resident engine holds reconstructed values (1 - 2*sign) * tau[level], dumped by
+    ldpc_debug_resident_c2v (its own decode, capped at max_iters) and mapped back to codes here (the sign bit of a
+    reconstructed zero tells code L, "-0", from code 0)."""
     eng = dec._engine
     B = llr_gpu.shape[0]
     if eng.info()["engine"] == "stream":
-        return eng.debug_c2v(B).detach().cpu().numpy()
+        return eng.debug_c2v(B, max_iters=max_iters).detach().cpu().numpy()
     from rcq_decoder import _quantizer_schedule, _threshold_table
-    vals, _, iters = eng.debug_resident_c2v(llr_gpu.to(torch.float32), early_stop=early_stop)
+    vals, _, iters = eng.debug_resident_c2v(llr_gpu.to(torch.float32), early_stop=early_stop, max_iters=max_iters)
     vals, iters = vals.cpu().numpy(), iters.cpu().numpy()
     thr = _threshold_table(dec.quantizers)                       # [Q, L] float32(tau)
     T = int(dec.max_iterations)
@@ -130,6 +131,40 @@ def check_neural(dec, sub, gpu):
 def final_codes(golden_codes, iters):
     """code trace [B,T,E] -> codes of the last executed iteration of every codeword"""
     return np.stack([golden_codes[r, iters[r] - 1] for r in range(len(iters))])
+
+
+def oracle_capped(oracle_mod, og, llr, kind, t, T, *, early_stop=True, trace_codes=False, factor=0.7, bc=3, qp=QP,
+                  wtype=None, beta=None, alpha=None):
+    """Expected outputs of a decode capped at t (ldpc_decode_capped, max_iters=t) by a decoder built for T iterations: the
+    oracle run for t iterations with the T-iteration decoder's tables -- beta / alpha rows 0..t-1 and the quantiser
+    schedule of T (oracle.quantizer_schedule, restated independently of rcq_decoder._quantizer_index).
+    kind: "basic" (fp32 or fp64 as llr), "neural2d", "offset" (Neural2DOffsetMinSumDecoder), "rcq", "wrcq".
+    -> (bits, posterior, iterations, success[, codes [B, t, E]])"""
+    assert 1 <= t <= T
+    o = oracle_mod
+    kw = dict(T=t, early_stop=early_stop, trace_codes=trace_codes)
+    no_beta = dict(beta=np.ones((T, 1), np.float32), beta_slot=np.zeros(og.E, np.int32))
+    no_alpha = dict(alpha=np.ones((T, 1), np.float32), alpha_slot=np.zeros(og.n, np.int32))
+    if kind == "basic":
+        dt = np.float64 if np.asarray(llr).dtype == np.float64 else np.float32
+        return o.decode(og, np.asarray(llr, dt), c2v_form=o.C2V_NMS, sum_order=o.SUM_NUMPY if dt == np.float64 else o.SUM_TORCH,
+                        beta=np.full((T, 1), factor, dt), beta_slot=np.zeros(og.E, np.int32),
+                        alpha=np.ones((T, 1), dt), alpha_slot=np.zeros(og.n, np.int32), **kw)
+    x = np.asarray(llr, np.float32)
+    if kind == "offset":
+        bt, bs, at, as_ = o.weight_tables(og, wtype, T, beta, alpha, beta_default=0.0, alpha_default=0.0)
+        return o.decode(og, x, c2v_form=o.C2V_OMS, beta=bt, beta_slot=bs, oms_alpha=at, oms_alpha_slot=as_[og.var_idx],
+                        **no_alpha, **kw)
+    if kind in ("neural2d", "wrcq"):
+        bt, bs, at, as_ = o.weight_tables(og, wtype, T, beta, alpha)
+        tables = dict(beta=bt, beta_slot=bs, alpha=at, alpha_slot=as_)
+    else:
+        assert kind == "rcq"
+        tables = dict(no_beta, **no_alpha)
+    if kind == "neural2d":
+        return o.decode(og, x, c2v_form=o.C2V_NMS, **tables, **kw)
+    thr = np.asarray([o.quantizer_thresholds(bc, c, gm) for c, gm in qp], dtype=np.float32)
+    return o.decode(og, x, c2v_form=o.C2V_RCQ, thresholds=thr, q_of_iter=o.quantizer_schedule(T, len(qp)), **tables, **kw)
 
 
 # --------------------------------------------------------------------------------- Basic
@@ -297,6 +332,70 @@ def test_wrcq_dvbs2_golden(gpu_device):
     check_wrcq(make_code(g, 20), g, gpu_device, int(g["wtype"]))
 
 
+# --------------------------------------------------------------------------------- RCQ, every iteration
+# every golden block with a per-iteration code trace: (file, prefix of the block or None)
+RCQ_TRACE_BLOCKS = [("toy_rcq", "rcq"), ("toy_rcq", "rcq4"), ("toy_rcq", "w1"), ("toy_rcq", "w2"), ("toy_rcq", "w3"),
+                    ("toy_rcq", "w4"), ("toy_rcq", "w2d"), ("small_rcq", "rcq"), ("small_rcq", "w1"), ("small_rcq", "w2"),
+                    ("ira_rcq", None), ("ira_wrcq", None), ("dvbs2_wrcq", None)]
+
+
+def rcq_trace_block(name, tag):
+    """-> (golden file dict, block dict, oracle_capped keyword arguments of the block's decoder)"""
+    g = load_golden(name)
+    sub = golden_sub(g, tag) if tag else g
+    kw = dict(kind="wrcq" if "wtype" in sub else "rcq", bc=int(sub["bc"]), qp=[tuple(x) for x in sub["qp"]])
+    if kw["kind"] == "wrcq":
+        kw.update(wtype=int(sub["wtype"]), beta=weights_dict(sub["beta_keys"], sub["beta_vals"]),
+                  alpha=weights_dict(sub["alpha_keys"], sub["alpha_vals"]))
+    return g, sub, kw
+
+
+@pytest.mark.parametrize("name,tag", RCQ_TRACE_BLOCKS, ids=[f"{n}-{t}" if t else n for n, t in RCQ_TRACE_BLOCKS])
+def test_rcq_golden_every_iteration(name, tag, gpu_device, oracle_mod, engine_mode):
+    """ldpc_decode_capped at every t in 1..T on every golden block with a code trace, both stop modes, every engine form:
+    the per-edge codes of the last executed iteration equal the reference's codes of iteration min(t, iters) (early stop)
+    and the oracle's (fixed T); bits, iterations, success and the posterior (equal as values) equal the oracle run for t
+    iterations with the T-iteration tables.  Pins the quantiser schedule and the beta / alpha row of EVERY iteration, not
+    only the last -- a schedule one iteration off can leave the final codes right when the codeword converges early."""
+    from rcq_decoder import RCQMinSumDecoder, WeightedRCQDecoder
+    g, sub, kw = rcq_trace_block(name, tag)
+    T, L = int(sub["T"]), 2 ** (int(sub["bc"]) - 1)
+    code = make_code(g, T)
+    og = oracle_mod.OracleGraph(n=code.n, check_ptr=code.tanner_graph().check_ptr, var_idx=code.tanner_graph().var_idx)
+    if kw["kind"] == "wrcq":
+        dec = WeightedRCQDecoder(code, kw["bc"], 8, kw["qp"], weight_sharing_type=kw["wtype"], max_iterations=T)
+        load_weights(dec, sub)
+    else:
+        dec = RCQMinSumDecoder(code, kw["bc"], 8, kw["qp"], max_iterations=T)
+    eng = dec._get_engine(gpu_device)
+    llr = sub["llr"]
+    x = torch.from_numpy(llr).to(gpu_device)
+    gi = sub["iters"].astype(np.int64)
+    full = eng.decode(x, early_stop=True)
+    np.testing.assert_array_equal(full.iterations.cpu().numpy(), gi)
+    for early in (True, False):
+        for t in range(1, T + 1):
+            res = eng.decode(x, early_stop=early, max_iters=t)
+            got = codes_of(dec, x, early, max_iters=t)
+            ob, op, oi, os_, oc = oracle_capped(oracle_mod, og, llr, t=t, T=T, early_stop=early, trace_codes=True, **kw)
+            what = f"t={t} early_stop={early}"
+            np.testing.assert_array_equal(res.iterations.cpu().numpy(), oi, err_msg=what)
+            np.testing.assert_array_equal(res.success.cpu().numpy(), os_, err_msg=what)
+            np.testing.assert_array_equal(res.bits.cpu().numpy(), ob, err_msg=what)
+            np.testing.assert_array_equal(res.posterior.cpu().numpy(), op, err_msg=what)
+            assert_codes(got, np.stack([oc[r, oi[r] - 1] for r in range(len(oi))]), L)
+            if early:
+                assert_codes(got, np.stack([sub["codes"][r, min(t, gi[r]) - 1] for r in range(len(gi))]), L)
+                done = gi <= t
+                it, sc = res.iterations.cpu().numpy(), res.success.cpu().numpy()
+                np.testing.assert_array_equal(it[done], gi[done], err_msg=what)
+                np.testing.assert_array_equal(res.bits.cpu().numpy()[done], sub["bits"][done].astype(np.int32), err_msg=what)
+                np.testing.assert_array_equal(sc[done], full.success.cpu().numpy()[done], err_msg=what)
+                assert np.all(it[~done] == t) and not sc[~done].any(), what
+            else:
+                assert bool((res.iterations == t).all()), what
+
+
 # --------------------------------------------------------------------------------- oracle, fresh inputs
 def awgn(rng, B, n, snr_db):
     s2 = 10.0 ** (-snr_db / 10.0)
@@ -377,6 +476,70 @@ def test_ira_batch_vs_oracle_all_decoders(early_stop, gpu_device, oracle_mod):
     np.testing.assert_array_equal(bits.detach().cpu().numpy(), ob)
     np.testing.assert_array_equal(post.detach().cpu().numpy(), op)
     assert_codes(codes_of(dec, x, early_stop), final_codes(oc, oi), 4)
+
+
+IRA_CAPS = (1, 2, 3, 5, 9)
+IRA_FLOAT_CASES = ["basic-f32", "basic-f64", "neural2d-1", "neural2d-2", "neural2d-3", "neural2d-4", "offset-2"]
+
+
+def ira_float_case(case):
+    """(1998,1512), T = 10: the decoder of `case` with seeded random weights, 300 codewords (a third each at 2.5, 5 and
+    7 dB: with this channel convention only the last two thirds converge within the caps, at 1 to 9 iterations)"""
+    import codes
+    from ldpc_decoder import BasicMinSumDecoder
+    from neural_2d_decoder import Neural2DMinSumDecoder, Neural2DOffsetMinSumDecoder
+    kind, arg = case.split("-")
+    code = codes.load_code("ira_1998_1512", 10)
+    rng = np.random.default_rng(sum(map(ord, case)))
+    llr = np.concatenate([awgn(rng, 100, code.n, 2.5), awgn(rng, 100, code.n, 5.0), awgn(rng, 100, code.n, 7.0)])
+    llr = llr[rng.permutation(len(llr))]
+    if kind == "basic":
+        return code, BasicMinSumDecoder(code, 0.7), (llr.astype(np.float64) if arg == "f64" else llr), {}
+    dec = (Neural2DOffsetMinSumDecoder if kind == "offset" else Neural2DMinSumDecoder)(code, weight_sharing_type=int(arg),
+                                                                                       max_iterations=10)
+    with torch.no_grad():
+        for p in dec.beta_weights.values():
+            p.fill_(float(np.float32(rng.uniform(0.0, 0.6) if kind == "offset" else rng.uniform(0.5, 1.0))))
+        for p in dec.alpha_weights.values():
+            p.fill_(float(np.float32(rng.uniform(0.0, 0.3) if kind == "offset" else rng.uniform(0.8, 1.2))))
+    beta = {k: float(v.item()) for k, v in dec.beta_weights.items()}
+    alpha = {k: float(v.item()) for k, v in dec.alpha_weights.items()}
+    return code, dec, llr, dict(wtype=int(arg), beta=beta, alpha=alpha)
+
+
+_ira_expect = {}
+
+
+@pytest.mark.parametrize("case", IRA_FLOAT_CASES)
+def test_float_decoders_every_cap_vs_oracle_ira(case, gpu_device, oracle_mod, engine_mode):
+    """Capped decodes (t = 1, 2, 3, 5, 9 of T = 10) of Basic fp32 / fp64, Neural-2D types 1-4 and Neural-2D offset on the
+    (1998,1512) code against the oracle run for t iterations with the T-iteration tables, both stop modes, every engine form:
+    bits, iterations, success exact, posterior within 1e-5.  Pins the beta / alpha row of every iteration; under auto the
+    fixed-T decodes run the register-state resident kernel with a loop count below the decoder's T."""
+    code, dec, llr, wkw = ira_float_case(case)
+    kind = case.split("-")[0]
+    tg = code.tanner_graph()
+    og = oracle_mod.OracleGraph(n=tg.n, check_ptr=tg.check_ptr, var_idx=tg.var_idx)
+    eng = dec._engine(torch.from_numpy(llr).dtype, gpu_device) if kind == "basic" else dec._get_engine(gpu_device)
+    if engine_mode == "auto":
+        assert eng.info()["engine"] == "resident"
+    x = torch.from_numpy(llr).to(gpu_device)
+    stopped = set()
+    for early in (True, False):
+        for t in IRA_CAPS:
+            key = (case, early, t)
+            if key not in _ira_expect:                        # the same for every engine form
+                _ira_expect[key] = oracle_capped(oracle_mod, og, llr, kind, t, 10, early_stop=early, **wkw)
+            ob, op, oi, os_ = _ira_expect[key]
+            res = eng.decode(x, early_stop=early, max_iters=t)
+            what = f"t={t} early_stop={early}"
+            np.testing.assert_array_equal(res.iterations.cpu().numpy(), oi, err_msg=what)
+            np.testing.assert_array_equal(res.success.cpu().numpy(), os_, err_msg=what)
+            np.testing.assert_array_equal(res.bits.cpu().numpy(), ob, err_msg=what)
+            assert_post(res.posterior.cpu().numpy(), op, what)
+            if early:
+                stopped |= set(np.unique(oi[os_]).tolist())
+    assert {1, 2, 3, 5} <= stopped                          # codewords stop inside the caps, at each of them
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64"])

@@ -255,6 +255,23 @@ def test_library_exports_every_declared_symbol():
     assert _native.load().ldpc_abi_version() == 1
 
 
+def test_ctypes_prototypes_match_the_headers():
+    """every function declared in include/ has a ctypes prototype in _native with as many arguments as the header gives it
+    (the debug hooks change with the tests that use them; a stale prototype would pass garbage to the library)"""
+    import _native
+    lib = _native.load()
+    seen = set()
+    for header in ("ldpc_hip.h", "ldpc_hip_debug.h"):
+        text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+        for name, params in re.findall(r"\b(ldpc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+            params = params.strip()
+            n_params = 0 if params in ("", "void") else params.count(",") + 1
+            argtypes = getattr(lib, name).argtypes
+            assert argtypes is not None and len(argtypes) == n_params, f"{name}: header {n_params} args, ctypes {argtypes}"
+            seen.add(name)
+    assert seen == set(_native.EXPORTS)
+
+
 def test_product_library_reads_no_environment():
     """no line of the native sources other than a comment mentions getenv, and the built library imports none"""
     for fn in os.listdir(os.path.join(PKG, "csrc")):

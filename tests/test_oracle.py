@@ -204,3 +204,81 @@ def test_basic_fp32_posterior_equals_neural2d_type3(oracle_mod):
     b1, p1, i1, _ = oracle_mod.basic_minsum(og, x, 0.7, 12, dtype=np.float32)
     b2, p2, i2, _ = oracle_mod.neural2d(og, x, 3, 12, beta, {})
     assert np.array_equal(b1, b2) and np.array_equal(i1, i2) and bitwise_equal(p1, p2)
+
+
+# ------------------------------------------------------------------ capped decodes (the GPU tests' per-iteration reference)
+@pytest.mark.parametrize("name,tag", [("toy_rcq", "rcq"), ("toy_rcq", "rcq4"), ("toy_rcq", "w2d"), ("small_rcq", "rcq"),
+                                      ("small_rcq", "w1"), ("ira_rcq", None), ("ira_wrcq", None), ("dvbs2_wrcq", None)])
+def test_oracle_capped_is_a_prefix_of_the_full_decode(name, tag, oracle_mod):
+    """oracle_capped (tests/test_gpu_parity.py) is what every capped GPU decode is held to: t iterations of the T-iteration
+    schedule.  Fixed T: its code trace is the first t slices of the full trace, every iteration count is t, success is the
+    syndrome of its bits.  Early stop: a codeword that stops within t has the full decode's outputs, any other one reports
+    t iterations and no success.  At t = T it gives the reference's golden bits, iterations, codes (and posterior)."""
+    from rcq_decoder import _quantizer_schedule
+    from test_gpu_parity import oracle_capped, rcq_trace_block
+    g, sub, kw = rcq_trace_block(name, tag)
+    og = graph_of(oracle_mod, g)
+    T, llr = int(sub["T"]), sub["llr"]
+    H = np.zeros((og.m, og.n), dtype=np.int64)
+    H[og.rows, og.var_idx] = 1
+    # the oracle's schedule is an independent restatement: it must be the one the decoders hand to the engine
+    np.testing.assert_array_equal(oracle_mod.quantizer_schedule(T, len(kw["qp"])), _quantizer_schedule(len(kw["qp"]), T))
+    fb, fp, fi, fs, fc = oracle_capped(oracle_mod, og, llr, t=T, T=T, early_stop=False, trace_codes=True, **kw)
+    eb, ep, ei, es, ec = oracle_capped(oracle_mod, og, llr, t=T, T=T, early_stop=True, trace_codes=True, **kw)
+    np.testing.assert_array_equal(eb, sub["bits"])
+    np.testing.assert_array_equal(ei, sub["iters"])
+    if "success" in sub:
+        np.testing.assert_array_equal(es, sub["success"])
+    assert bitwise_equal(ep, sub["posterior"] if "posterior" in sub else sub["oracle_posterior"])
+    for r, it in enumerate(sub["iters"]):
+        np.testing.assert_array_equal(ec[r, :it], sub["codes"][r, :it])
+    for t in range(1, T + 1):
+        b, p, i, s, c = oracle_capped(oracle_mod, og, llr, t=t, T=T, early_stop=False, trace_codes=True, **kw)
+        assert c.shape == (len(llr), t, og.E) and np.array_equal(c, fc[:, :t]), f"t={t}: code trace is not a prefix"
+        assert np.all(i == t)
+        np.testing.assert_array_equal(s, (H @ b.T % 2).sum(axis=0) == 0)
+        if t == T:
+            assert np.array_equal(b, fb) and bitwise_equal(p, fp) and np.array_equal(s, fs)
+        b, p, i, s, c = oracle_capped(oracle_mod, og, llr, t=t, T=T, early_stop=True, trace_codes=True, **kw)
+        done = ei <= t
+        assert np.array_equal(i[done], ei[done]) and np.array_equal(s[done], es[done]) and np.array_equal(b[done], eb[done])
+        assert bitwise_equal(p[done], ep[done])
+        assert np.all(i[~done] == t) and not s[~done].any()
+        for r in range(len(llr)):
+            np.testing.assert_array_equal(c[r, :i[r]], ec[r, :i[r]])
+        if len(kw["qp"]) == 1 and kw["kind"] == "rcq":
+            # one quantiser and no weights: nothing depends on T, the capped decode is the plain T = t decode
+            ob, op, oi, os_ = oracle_mod.rcq(og, llr, kw["bc"], kw["qp"], t, early_stop=True)
+            assert np.array_equal(b, ob) and bitwise_equal(p, op) and np.array_equal(i, oi) and np.array_equal(s, os_)
+
+
+def test_oracle_capped_float_decoders(oracle_mod):
+    """the helper's floating-point kinds at t = T are the oracle's own decoders; Basic has no per-iteration table, so at any
+    t it is the plain T = t decode"""
+    from test_gpu_parity import oracle_capped
+    g = load_golden("small_basic")
+    og = graph_of(oracle_mod, g)
+    rng = np.random.default_rng(3)
+    x32 = g["llr"].astype(np.float32)
+    T = 8
+    for early in (True, False):
+        for t in (1, 4, T):
+            for x in (g["llr"], x32):
+                got = oracle_capped(oracle_mod, og, x, "basic", t, T, early_stop=early)
+                want = oracle_mod.basic_minsum(og, x, 0.7, t, early_stop=early, dtype=x.dtype.type)
+                assert all(bitwise_equal(a, b) for a, b in zip(got, want))
+    keys = sorted({f"iter_{t}_dc{d}" for t in range(T) for d in og.dc.tolist()})
+    beta = {k: float(np.float32(rng.uniform(0.1, 1.0))) for k in keys}
+    alpha = {f"iter_{t}_dv{d}": float(np.float32(rng.uniform(0.1, 0.5))) for t in range(T) for d in og.dv.tolist()}
+    for early in (True, False):
+        got = oracle_capped(oracle_mod, og, x32, "neural2d", T, T, early_stop=early, wtype=2, beta=beta, alpha=alpha)
+        want = oracle_mod.neural2d(og, x32, 2, T, beta, alpha, early_stop=early)
+        assert all(bitwise_equal(a, b) for a, b in zip(got, want))
+        got = oracle_capped(oracle_mod, og, x32, "offset", T, T, early_stop=early, wtype=2, beta=beta, alpha=alpha)
+        want = oracle_mod.neural2d_offset(og, x32, 2, T, beta, alpha, early_stop=early)
+        assert all(bitwise_equal(a, b) for a, b in zip(got, want))
+        # t < T reads rows 0..t-1 of the T-row tables: the same as a t-iteration decoder given the same first t rows
+        t = 3
+        got = oracle_capped(oracle_mod, og, x32, "neural2d", t, T, early_stop=early, wtype=2, beta=beta, alpha=alpha)
+        want = oracle_mod.neural2d(og, x32, 2, t, beta, alpha, early_stop=early)
+        assert all(bitwise_equal(a, b) for a, b in zip(got, want))
