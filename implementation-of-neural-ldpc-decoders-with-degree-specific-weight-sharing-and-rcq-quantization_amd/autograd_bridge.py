@@ -80,3 +80,48 @@ def table_from_params(params, where, shape, default: float) -> torch.Tensor:
     rr = torch.tensor([w[0] for w in where], dtype=torch.long)
     cc = torch.tensor([w[1] for w in where], dtype=torch.long)
     return out.index_put((rr, cc), vals)
+
+
+def check_joint_args(n: int, T: int, llr, targets, iteration_weights):
+    """shape checks of joint_posterior_loss (before any device work): ValueError on a mismatch"""
+    shape = tuple(llr.shape)
+    if len(shape) not in (1, 2) or shape[-1] != n:
+        raise ValueError(f"llr must have shape [n] or [B, n] with n = {n}, got {shape}")
+    if targets is not None and tuple(targets.shape) != shape:
+        raise ValueError(f"targets must have the shape of llr {shape}, got {tuple(targets.shape)}")
+    if iteration_weights is not None and tuple(torch.as_tensor(iteration_weights).shape) != (T,):
+        raise ValueError(f"iteration_weights must have shape ({T},), got {tuple(torch.as_tensor(iteration_weights).shape)}")
+    if T < 1:
+        raise ValueError("the joint posterior loss needs max_iterations >= 1")
+
+
+def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets, iteration_weights,
+               alpha_is_oms: bool):
+    """posterior joint training through ``torch.ops.ldpc.minsum_joint_loss`` (torch_ops.py) -> (loss, loss_per_iteration,
+    bits, posterior): loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets) over the T iterations of the fixed-T
+    decode, differentiable in the tables (and in `llr` when it requires grad) with the posterior-local gradient of the
+    paper's training method.  No saved history: MAX_SAVED_BYTES does not apply."""
+    import torch_ops
+    from ldpc_decoder import _as_batch
+    T = int(engine.iters)
+    check_joint_args(engine.graph.n, T, llr, targets, iteration_weights)
+    _, x, single = _as_batch(llr, engine.graph.n)
+    xd = x.to(device=engine.device, dtype=torch.float32)
+    grad_on = torch.is_grad_enabled()
+    want_llr = grad_on and x.requires_grad
+    if not want_llr:
+        xd = xd.detach()
+    want_grads = grad_on and (beta_table.requires_grad or alpha_table.requires_grad)
+    y = None
+    if targets is not None:
+        y = torch.as_tensor(targets).detach().to(device=engine.device, dtype=torch.float32).reshape(xd.shape).contiguous()
+    w = (torch.full((T,), 1.0 / T, dtype=torch.float32) if iteration_weights is None
+         else torch.as_tensor(iteration_weights).detach().to(torch.float32))
+    w = w.to(engine.device).contiguous()
+    loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.minsum_joint_loss(
+        xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(alpha_is_oms),
+        bool(want_grads), bool(want_llr))
+    out_dev = llr.device
+    if single:
+        bits, post = bits[0], post[0]
+    return loss.to(out_dev), lpi.to(out_dev), bits.to(out_dev), post.to(out_dev)

@@ -318,9 +318,10 @@ struct RowsOut {
 
 int allow_full_lds(const void *kfn, int device);
 
+// keep_posterior: a non-last sweep also stores the posterior rows in w.postT (fp32 NMS / OMS only; ldpc_train_joint)
 template <typename T, int VEC>
 int launch_vn(const ldpc_decoder *d, const Workspace &w, int it, bool last, bool use_done, hipStream_t s,
-              bool store_posterior = true, const RowsOut *rows = nullptr)
+              bool store_posterior = true, const RowsOut *rows = nullptr, bool keep_posterior = false)
 {
     const GraphDev g = d->g->dev();
     if constexpr (sizeof(T) == 4 && VEC == 4) {
@@ -358,8 +359,8 @@ int launch_vn(const ldpc_decoder *d, const Workspace &w, int it, bool last, bool
     const int lut_cur = codes ? d->q_of_iter[row] * lut_stride : 0;
     const size_t shmem = (size_t)lut_total * sizeof(float);
     const uint64_t *done = use_done ? w.done : nullptr;
-#define LDPC_VN(CODES, LAST)                                                                           \
-    hipLaunchKernelGGL((vn_sweep<T, VEC, CODES, LAST>), grid, block, shmem, s, g, (const void *)w.c2v,  \
+#define LDPC_VN(CODES, LAST, ...)                                                                      \
+    hipLaunchKernelGGL((vn_sweep<T, VEC, CODES, LAST, ##__VA_ARGS__>), grid, block, shmem, s, g, (const void *)w.c2v,  \
                        (const T *)w.llrT, (T *)w.v2c, alpha_row, d->alpha_slot, (const float *)d->lut,  \
                        lut_total, lut_cur, lut_stride, (const int *)d->q_of_iter_dev,                   \
                        (const int *)w.iters, w.bitsT, store_posterior ? (T *)w.postT : (T *)nullptr, done, vb)
@@ -369,6 +370,9 @@ int launch_vn(const ldpc_decoder *d, const Workspace &w, int it, bool last, bool
         } else {
             return fail(LDPC_ERR_UNSUPPORTED, "RCQ messages are fp32 only");
         }
+    } else if (keep_posterior && !last) {
+        if constexpr (sizeof(T) == 4) LDPC_VN(false, false, true);
+        else return fail(LDPC_ERR_UNSUPPORTED, "internal: posterior-keeping sweeps are fp32 only");
     } else {
         if (last) LDPC_VN(false, true); else LDPC_VN(false, false);
     }
@@ -1780,17 +1784,155 @@ int backward_impl(const ldpc_decoder *d, const char *saved, const float *llr, in
                            (int *)nullptr, (long long)batch, g.n, vc);     // [tile][n][W] -> [batch][n], padding rows dropped
     // fixed-order reductions (one wave per slot and iteration): every table entry is written, no memset, no atomics
     if (grad_beta)
-        hipLaunchKernelGGL(reduce_table_grads, dim3((unsigned)d->n_beta, (unsigned)T), dim3(kWave), 0, s,
+        hipLaunchKernelGGL(reduce_table_grads<float>, dim3((unsigned)d->n_beta, (unsigned)T), dim3(kWave), 0, s,
                            (const float *)w.gbeta, w.tiles, g.E, (const int *)d->beta_inv_ptr,
                            (const int *)d->beta_inv_items, d->n_beta, grad_beta);
     if (grad_oms_alpha && d->form == LDPC_C2V_OMS && d->oms_alpha)
-        hipLaunchKernelGGL(reduce_table_grads, dim3((unsigned)d->n_oms_alpha, (unsigned)T), dim3(kWave), 0, s,
+        hipLaunchKernelGGL(reduce_table_grads<float>, dim3((unsigned)d->n_oms_alpha, (unsigned)T), dim3(kWave), 0, s,
                            (const float *)w.goa, w.tiles, g.E, (const int *)d->oms_inv_ptr,
                            (const int *)d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha);
     if (grad_alpha)
-        hipLaunchKernelGGL(reduce_table_grads, dim3((unsigned)d->n_alpha, (unsigned)T), dim3(kWave), 0, s,
+        hipLaunchKernelGGL(reduce_table_grads<float>, dim3((unsigned)d->n_alpha, (unsigned)T), dim3(kWave), 0, s,
                            (const float *)w.galpha, w.tiles, g.n, (const int *)d->alpha_inv_ptr,
                            (const int *)d->alpha_inv_items, d->n_alpha, grad_alpha);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+// ---- posterior joint training (ldpc_train_joint) ------------------------------------------------------------
+// The fixed-T decode with the loss of every iteration's posterior and its posterior-local gradient formed while that
+// iteration is decoded: nothing of earlier iterations is kept but c2v_t-1 (the alpha_t-1 partial reads its
+// leave-one-out sums), so the scratch is a constant number of rows per codeword whatever T is --
+// E rows: v2c_t / v2c_t+1 and c2v_t-1 / c2v_t (ping-pong), d J/d v2c_t;  n rows: llr, posterior (then g_l in place),
+// targets, d J/d llr;  plus per-tile partials of the table gradients and of the loss.
+struct JointWs {
+    Workspace fw;                            // forward view: llrT, postT, bitsT (v2c / c2v chosen per iteration)
+    char *v2c[2] = {nullptr, nullptr}, *c2v[2] = {nullptr, nullptr};
+    float *yT = nullptr, *gv2c = nullptr, *gllrT = nullptr, *gbeta = nullptr, *goa = nullptr, *galpha = nullptr;
+    double *loss_part = nullptr, *item_sum = nullptr;
+    size_t total = 0;
+};
+JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base)
+{
+    JointWs w;
+    w.fw.vec = pick_vec(d, batch);
+    const int W = 64 * w.fw.vec;
+    const int tiles = (int)std::max<int64_t>((batch + W - 1) / W, 1);
+    w.fw.tiles = tiles;
+    const size_t n = d->g->n, E = std::max(d->g->E, 1), tw = (size_t)tiles * W;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
+    const size_t o_llr = take(tw * n * 4), o_post = take(tw * n * 4), o_y = take(tw * n * 4), o_gl = take(tw * n * 4);
+    const size_t o_v0 = take(tw * E * 4), o_v1 = take(tw * E * 4), o_c0 = take(tw * E * 4), o_c1 = take(tw * E * 4);
+    const size_t o_gv = take(tw * E * 4);
+    const size_t o_bits = take((size_t)tiles * n * w.fw.vec * sizeof(uint64_t));
+    const size_t o_gb = take((size_t)tiles * E * 4), o_goa = take(d->form == LDPC_C2V_OMS ? (size_t)tiles * E * 4 : 0);
+    const size_t vb = (n + kWavesPerBlock - 1) / kWavesPerBlock;
+    const size_t o_ga = take((size_t)tiles * n * 4), o_lp = take((size_t)tiles * vb * sizeof(double));
+    const size_t o_is = take(std::max(n, E) * sizeof(double));
+    w.total = off;
+    if (base) {
+        char *b = (char *)base;
+        w.fw.llrT = b + o_llr; w.fw.postT = b + o_post; w.fw.bitsT = (uint64_t *)(b + o_bits);
+        w.v2c[0] = b + o_v0; w.v2c[1] = b + o_v1; w.c2v[0] = b + o_c0; w.c2v[1] = b + o_c1;
+        w.yT = (float *)(b + o_y); w.gllrT = (float *)(b + o_gl); w.gv2c = (float *)(b + o_gv);
+        w.gbeta = (float *)(b + o_gb); w.goa = (float *)(b + o_goa); w.galpha = (float *)(b + o_ga);
+        w.loss_part = (double *)(b + o_lp); w.item_sum = (double *)(b + o_is);
+    }
+    return w;
+}
+
+template <int VEC>
+int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, int64_t batch, const float *weights,
+               float *loss_per_iter, int32_t *bits, float *posterior, float *grad_beta, float *grad_alpha,
+               float *grad_oms_alpha, float *grad_llr, const JointWs &w, hipStream_t s)
+{
+    constexpr int W = 64 * VEC;
+    constexpr int JT = transpose_vars<float>();
+    const GraphDev g = d->g->dev();
+    const int T = d->T, tiles = w.fw.tiles, vc = (g.n + JT - 1) / JT;
+    const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
+    const bool oms = d->form == LDPC_C2V_OMS;
+    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
+    const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
+    hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, (float *)w.fw.llrT, (long long)batch, g.n, vc);
+    if (targets)
+        hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, targets, w.yT, (long long)batch, g.n, vc);
+    // rows no step writes: alpha_T-1 (and every alpha row of the offset forms, whose variable update has no parameter)
+    if (grad_alpha) {
+        const size_t row = (size_t)d->n_alpha * 4;
+        if (oms) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)T * row, s));
+        else HIP_TRY(hipMemsetAsync((char *)grad_alpha + (size_t)(T - 1) * row, 0, row, s));
+    }
+    if (grad_oms_alpha && !oa_grad && d->n_oms_alpha > 0)
+        HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)T * d->n_oms_alpha * 4, s));
+    if (grad_llr) HIP_TRY(hipMemsetAsync(w.gllrT, 0, (size_t)tiles * W * g.n * sizeof(float), s));
+    const int cb = (g.m + kWavesPerBlock - 1) / kWavesPerBlock, vb = (g.n + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int vbb = (g.n + kWavesPerBlock * kVnbVarsPerWave - 1) / (kWavesPerBlock * kVnbVarsPerWave);
+    const dim3 cgrid((unsigned)((size_t)tiles * cb)), vgrid((unsigned)((size_t)tiles * vb)), vbgrid((unsigned)((size_t)tiles * vbb));
+    const double inv_bn = 1.0 / ((double)batch * (double)g.n);
+    float *postT = (float *)w.fw.postT;
+    // one iteration's partials [tile][item] -> its row of a gradient table: per-item sums over the tiles, then per slot
+    auto reduce_step = [&](const float *part, int count, const int *slot_ptr, const int *slot_items, int n_slots, float *row) {
+        hipLaunchKernelGGL(reduce_tiles, dim3((unsigned)((count + kBlock - 1) / kBlock)), blk, 0, s, part, tiles, count, w.item_sum);
+        hipLaunchKernelGGL(reduce_table_grads<double>, dim3((unsigned)n_slots), dim3(kWave), 0, s, (const double *)w.item_sum, 1,
+                           count, slot_ptr, slot_items, n_slots, row);
+    };
+    for (int t = 0; t < T; ++t) {
+        const bool last = t == T - 1;
+        // forward iteration t: the decode's own sweeps (fixed T, no stop latch); the variable sweep keeps l_t in postT
+        Workspace wc = w.fw, wv = w.fw;
+        wc.v2c = w.v2c[t & 1]; wc.c2v = w.c2v[t & 1];
+        wv.c2v = w.c2v[t & 1]; wv.v2c = w.v2c[(t + 1) & 1];
+        int rc = launch_cn<float, VEC>(d, wc, t, /*use_done=*/false, s);
+        if (rc) return rc;
+        rc = launch_vn<float, VEC>(d, wv, t, last, /*use_done=*/false, s, /*store_posterior=*/true, nullptr, /*keep_posterior=*/true);
+        if (rc) return rc;
+        if (last && (bits || posterior))
+            hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)postT, (const uint64_t *)w.fw.bitsT,
+                               posterior, bits, (long long)batch, g.n, vc);
+        // J_t, and g_l over postT
+        if (want)
+            hipLaunchKernelGGL((joint_loss_grad<VEC, true>), vgrid, blk, 0, s, g.n, postT, (const float *)(targets ? w.yT : nullptr),
+                               weights, t, (long long)batch, (float)inv_bn, grad_llr ? w.gllrT : nullptr, w.loss_part, vb);
+        else
+            hipLaunchKernelGGL((joint_loss_grad<VEC, false>), vgrid, blk, 0, s, g.n, postT, (const float *)(targets ? w.yT : nullptr),
+                               weights, t, (long long)batch, (float)inv_bn, (float *)nullptr, w.loss_part, vb);
+        hipLaunchKernelGGL(joint_loss_reduce, dim3(1), blk, 0, s, (const double *)w.loss_part, (long long)tiles * vb, inv_bn,
+                           loss_per_iter + t);
+        HIP_TRY(hipGetLastError());
+        if (!want) continue;
+        // posterior-local backward of iteration t: check side (beta_t, offset alpha_t, d J/d v2c_t), then the alpha_t-1
+        // partial of the normalised forms and the LLR gradient
+        const bool need_gv = grad_llr || (!oms && t >= 1 && grad_alpha);
+        const float *src = t == 0 ? (const float *)w.fw.llrT : (const float *)w.v2c[t & 1];
+        const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
+        float *gv_out = need_gv ? w.gv2c : nullptr;
+        float *goa = oa_grad ? w.goa : nullptr;
+#define LDPC_CNJ(FIRST_, FORM_)                                                                                        \
+    hipLaunchKernelGGL((cn_backward<VEC, FIRST_, FORM_, true>), cgrid, blk, 0, s, g, src, (const float *)nullptr,     \
+                       (const float *)postT, (const int *)nullptr, (long long)batch, t, beta_row, (const int *)d->beta_slot, \
+                       gv_out, w.gbeta, goa, cb)
+        if (t == 0) { if (oms) LDPC_CNJ(true, FORM_OMS); else LDPC_CNJ(true, FORM_NMS); }
+        else { if (oms) LDPC_CNJ(false, FORM_OMS); else LDPC_CNJ(false, FORM_NMS); }
+#undef LDPC_CNJ
+        if (grad_beta) reduce_step(w.gbeta, g.E, d->beta_inv_ptr, d->beta_inv_items, d->n_beta, grad_beta + (size_t)t * d->n_beta);
+        if (oa_grad)
+            reduce_step(w.goa, g.E, d->oms_inv_ptr, d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha + (size_t)t * d->n_oms_alpha);
+        if (!oms && t >= 1 && grad_alpha) {
+            const float *alpha_row = (const float *)d->alpha + (size_t)(t - 1) * d->n_alpha;
+            hipLaunchKernelGGL((vn_backward<VEC, true>), vbgrid, blk, 0, s, g, (const float *)w.c2v[(t - 1) & 1],
+                               (const float *)w.gv2c, (const int *)nullptr, (long long)batch, t, alpha_row,
+                               (const int *)d->alpha_slot, (float *)nullptr, w.galpha, vbb);
+            reduce_step(w.galpha, g.n, d->alpha_inv_ptr, d->alpha_inv_items, d->n_alpha, grad_alpha + (size_t)(t - 1) * d->n_alpha);
+        }
+        if (grad_llr)
+            hipLaunchKernelGGL((llr_backward_accumulate<VEC>), vgrid, blk, 0, s, g, (const float *)w.gv2c, w.gllrT, vb);
+        HIP_TRY(hipGetLastError());
+    }
+    if (grad_llr)
+        hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.gllrT, (const uint64_t *)nullptr, grad_llr,
+                           (int *)nullptr, (long long)batch, g.n, vc);
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
@@ -1863,6 +2005,47 @@ int ldpc_backward(const ldpc_decoder *d, const void *saved, size_t saved_bytes, 
                                 (float *)grad_beta, (float *)grad_alpha, (float *)grad_oms_alpha, (float *)grad_llr, w, s);
     return backward_impl<4>(d, (const char *)saved, (const float *)llr, batch, iterations, (const float *)grad_posterior,
                             (float *)grad_beta, (float *)grad_alpha, (float *)grad_oms_alpha, (float *)grad_llr, w, s);
+}
+
+size_t ldpc_train_joint_workspace_bytes(const ldpc_decoder *d, int64_t batch)
+{
+    if (!d || batch < 0) return 0;
+    return carve_joint(d, batch, nullptr).total;
+}
+
+int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                     const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                     void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
+                     size_t workspace_bytes, void *stream)
+{
+    if (int rc = train_supported(d)) return rc;
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (d->T < 1) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs at least one iteration");
+    if (!loss_per_iter) return fail(LDPC_ERR_ARG, "NULL loss_per_iter");
+    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
+    if (want && !iteration_weights) return fail(LDPC_ERR_ARG, "NULL iteration_weights");
+    DeviceGuard guard(d->g->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (batch == 0) {                                 // an empty batch: every loss term and every gradient is 0
+        HIP_TRY(hipMemsetAsync(loss_per_iter, 0, (size_t)d->T * 4, s));
+        if (grad_beta) HIP_TRY(hipMemsetAsync(grad_beta, 0, (size_t)d->T * d->n_beta * 4, s));
+        if (grad_alpha) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)d->T * d->n_alpha * 4, s));
+        if (grad_oms_alpha && d->n_oms_alpha > 0) HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)d->T * d->n_oms_alpha * 4, s));
+        return LDPC_OK;
+    }
+    if (d->g->n == 0 || d->g->E == 0) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs a graph with edges");
+    if (!llr || !workspace) return fail(LDPC_ERR_ARG, "NULL llr/workspace");
+    if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
+    const JointWs w = carve_joint(d, batch, workspace);
+    if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
+    if ((size_t)w.fw.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+#define LDPC_JOINT(V_)                                                                                                 \
+    joint_impl<V_>(d, (const float *)llr, (const float *)targets, batch, (const float *)iteration_weights,             \
+                   (float *)loss_per_iter, bits, (float *)posterior, (float *)grad_beta, (float *)grad_alpha,          \
+                   (float *)grad_oms_alpha, (float *)grad_llr, w, s)
+    if (w.fw.vec == 1) return LDPC_JOINT(1);
+    return LDPC_JOINT(4);
+#undef LDPC_JOINT
 }
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

@@ -747,7 +747,7 @@ __device__ __forceinline__ Pack<T, VEC> load_c2v(const void *c2v, size_t elem_of
     }
 }
 
-template <typename T, int VEC, bool CODES, int ORDER, bool LAST, int DV>
+template <typename T, int VEC, bool CODES, int ORDER, bool LAST, int DV, bool POST = false>
 __device__ __forceinline__ void vn_body(const GraphDev &g, int tile, int j, int s0, int lane,
                                         const void *__restrict__ c2v, const T *__restrict__ llrT,
                                         T *__restrict__ v2c, T a, const Lut<VEC> &lut,
@@ -795,12 +795,12 @@ __device__ __forceinline__ void vn_body(const GraphDev &g, int tile, int j, int 
         uint64_t mask = __ballot(post.x[c] < (T)0);
         if (lane == 0) bitsT[((size_t)tile * g.n + j) * VEC + c] = mask;
     }
-    if constexpr (LAST) {
+    if constexpr (LAST || POST) {
         if (postT) st<T, VEC>(postT + ((size_t)tile * g.n + j) * W + lane_off, post);   // null: hard decisions only
     }
 }
 
-template <typename T, int VEC, bool CODES, int ORDER, bool LAST>
+template <typename T, int VEC, bool CODES, int ORDER, bool LAST, bool POST = false>
 __device__ __forceinline__ void vn_generic(const GraphDev &g, int tile, int j, int s0, int dv, int lane,
                                         const void *__restrict__ c2v, const T *__restrict__ llrT,
                                         T *__restrict__ v2c, T a, const Lut<VEC> &lut,
@@ -832,10 +832,12 @@ __device__ __forceinline__ void vn_generic(const GraphDev &g, int tile, int j, i
         uint64_t mask = __ballot(post.x[c] < (T)0);
         if (lane == 0) bitsT[((size_t)tile * g.n + j) * VEC + c] = mask;
     }
-    if (LAST && postT) st<T, VEC>(postT + ((size_t)tile * g.n + j) * W + lane_off, post);
+    if ((LAST || POST) && postT) st<T, VEC>(postT + ((size_t)tile * g.n + j) * W + lane_off, post);
 }
 
-template <typename T, int VEC, bool CODES, bool LAST>
+// POST: a non-LAST sweep also stores every codeword's posterior (the fixed-T joint loss of ldpc_train.hip reads the
+// posterior of every iteration); LAST sweeps store it regardless.
+template <typename T, int VEC, bool CODES, bool LAST, bool POST = false>
 __global__ __launch_bounds__(kBlock) void vn_sweep(GraphDev g, const void *__restrict__ c2v,
                                                    const T *__restrict__ llrT, T *__restrict__ v2c,
                                                    const T *__restrict__ alpha_row,
@@ -877,12 +879,12 @@ __global__ __launch_bounds__(kBlock) void vn_sweep(GraphDev g, const void *__res
     }
 
 #define LDPC_VN_CASE(D) \
-    case D: vn_body<T, VEC, CODES, ORDER, LAST, D>(g, tile, j, s0, lane, c2v, llrT, v2c, a, lut, bitsT, postT, fz); break;
+    case D: vn_body<T, VEC, CODES, ORDER, LAST, D, POST>(g, tile, j, s0, lane, c2v, llrT, v2c, a, lut, bitsT, postT, fz); break;
     switch (dv) {
         LDPC_VN_CASE(0) LDPC_VN_CASE(1) LDPC_VN_CASE(2) LDPC_VN_CASE(3) LDPC_VN_CASE(4)
         LDPC_VN_CASE(5) LDPC_VN_CASE(6) LDPC_VN_CASE(7) LDPC_VN_CASE(8)
     default:
-        vn_generic<T, VEC, CODES, ORDER, LAST>(g, tile, j, s0, dv, lane, c2v, llrT, v2c, a, lut, bitsT, postT, fz);
+        vn_generic<T, VEC, CODES, ORDER, LAST, POST>(g, tile, j, s0, dv, lane, c2v, llrT, v2c, a, lut, bitsT, postT, fz);
     }
 #undef LDPC_VN_CASE
 }

@@ -53,6 +53,21 @@ __device__ __forceinline__ void load_states(const int *__restrict__ iterations, 
     }
 }
 
+// LOCAL (posterior joint training, ldpc_train_joint): every real codeword takes part at every step, and its gradient
+// comes from that iteration's own posterior only (state 2; `iterations` is unused), padding codewords take no part
+template <int VEC, bool LOCAL>
+__device__ __forceinline__ void load_states_of(const int *__restrict__ iterations, long long batch, int tile, int lane,
+                                               int t, int (&state)[VEC])
+{
+    if constexpr (LOCAL) {
+        constexpr int W = kWave * VEC;
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) state[c] = ((long long)tile * W + (long long)lane * VEC + c < batch) ? 2 : 0;
+    } else {
+        load_states<VEC>(iterations, batch, tile, lane, t, state);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Check-node backward of iteration t.  in: v2c_t rows (llr rows when FIRST), d loss/d c2v_t.
 // out: d loss/d v2c_t rows (not when FIRST: v2c_0 = llr has no parameters upstream),
@@ -62,7 +77,9 @@ __device__ __forceinline__ void load_states(const int *__restrict__ iterations, 
 // FORM_NMS: c2v = beta * minval * prod(signs).   FORM_OMS: c2v = prod(signs) * (relu(minval - beta) - alpha_c)
 // (neural_2d_decoder.py:389-401, neural_minsum_decoder.py:245-253): d/d beta = -g*ps*[minval > beta],
 // d/d alpha_c = -g*ps (second per-edge partial, goa_part), d/d minval = g*ps*[minval > beta]; relu'(0) = 0.
-template <int VEC, bool FIRST, int FORM>
+// LOCAL: the posterior-local backward of ldpc_train_joint -- seeded from gpostT = d J_t/d l_t for every real codeword,
+// nothing chained in (gc2v and iterations unused).
+template <int VEC, bool FIRST, int FORM, bool LOCAL = false>
 __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *__restrict__ src,
                                                       const float *__restrict__ gc2v,
                                                       const float *__restrict__ gpostT,
@@ -83,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *_
     if (dc == 0) return;
 
     int state[VEC];
-    load_states<VEC>(iterations, batch, tile, lane, t, state);
+    load_states_of<VEC, LOCAL>(iterations, batch, tile, lane, t, state);
     bool mine = false, from_vn = false, from_post = false;
 #pragma unroll
     for (int c = 0; c < VEC; ++c) { mine |= state[c] != 0; from_vn |= state[c] == 1; from_post |= state[c] == 2; }
@@ -215,10 +232,12 @@ __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *_
 // Variable-node backward of the update that produced v2c_t (t >= 1) from c2v_t-1 with alpha_t-1.
 // in: c2v_t-1 rows, d loss/d v2c_t rows.  out: d loss/d c2v_t-1 rows, per-variable partial of
 // d loss/d alpha_t-1.  Leave-one-out sums are formed as (total - own) with the totals in fp64.
+// LOCAL (ldpc_train_joint): the leave-one-out sums are constants (stop-gradient), so only the alpha_t-1 partial
+// sum_e g_v2c_t[e] * S_t-1[e] is formed, for every real codeword, and no d loss/d c2v_t-1 is written (gc2v_out unused).
 // ------------------------------------------------------------------------------------------
 constexpr int kVnbVarsPerWave = 4;
 
-template <int VEC>
+template <int VEC, bool LOCAL = false>
 __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *__restrict__ c2v_prev,
                                                       const float *__restrict__ gv2c,
                                                       const int *__restrict__ iterations, long long batch, int t,
@@ -233,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
     const int jbase = uni(((blockIdx.x % var_blocks) * kWavesPerBlock + (threadIdx.x >> 6)) * kVnbVarsPerWave);
     if (jbase >= g.n) return;
     int state[VEC];
-    load_states<VEC>(iterations, batch, tile, lane, t, state);     // v2c_t exists for codewords with state != 0
+    load_states_of<VEC, LOCAL>(iterations, batch, tile, lane, t, state);     // v2c_t exists for codewords with state != 0
     bool mine = false;
 #pragma unroll
     for (int c = 0; c < VEC; ++c) mine |= state[c] != 0;
@@ -252,7 +271,8 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
         Pack<float, VEC> z;
 #pragma unroll
         for (int c = 0; c < VEC; ++c) z.x[c] = 0.0f;
-        for (int k = 0; k < dv; ++k) st<float, VEC>(gc2v_out + base + (size_t)g.csc_edge[k0 + k] * W, z);
+        if (!LOCAL)
+            for (int k = 0; k < dv; ++k) st<float, VEC>(gc2v_out + base + (size_t)g.csc_edge[k0 + k] * W, z);
         if (lane == 0) galpha_part[(size_t)tile * g.n + j] = 0.0f;
         continue;
     }
@@ -293,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
                         o.x[c] = alpha * (float)(totg[c] - (double)gv[k].x[c]);
                     }
                 }
-                st<float, VEC>(gc2v_out + row[k], o);
+                if (!LOCAL) st<float, VEC>(gc2v_out + row[k], o);
             }
         }
         ga = wave_sum(ga);
@@ -323,7 +343,7 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
                 o.x[c] = alpha * (float)(totg[c] - (double)gv.x[c]);         // c2v[e] feeds every OTHER edge of j
             }
         }
-        st<float, VEC>(gc2v_out + row, o);
+        if (!LOCAL) st<float, VEC>(gc2v_out + row, o);
     }
     ga = wave_sum(ga);
     if (lane == 0) galpha_part[(size_t)tile * g.n + j] = ga;
@@ -358,22 +378,107 @@ __global__ __launch_bounds__(kBlock) void llr_backward_accumulate(GraphDev g, co
     st<float, VEC>(acc_row, acc);
 }
 
+// ------------------------------------------------------------------------------------------
+// Posterior joint training (ldpc_train_joint): the loss term of iteration t, J_t = mean over the real codewords b and
+// the variables j of BCEWithLogits(-l_t[b][j], y[b][j]) (training_framework.py compute_loss), and its seed
+// g_l = w_t * (y - sigmoid(-l_t)) / (B n) = w_t * d J_t / d l_t.  One wave = one variable x W codewords, grid as the
+// variable sweep.  in: postT = l_t rows [tile][n][W], yT the target rows (nullptr: all zero).  out: loss_part[block]
+// = the block's sum of the per-element losses (each in fp32, summed in fp64: lanes by a fixed butterfly, the block's 4
+// waves in order -- bit-identical run to run);
+// with WANT_GRAD, g_l written over postT in place (the posterior rows are dead once the loss is formed) and, when
+// gllrT is given, added to it -- l_t enters d J/d llr directly.  Padding codewords contribute 0 to both.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+
+template <int VEC, bool WANT_GRAD>
+__global__ __launch_bounds__(kBlock) void joint_loss_grad(int n, float *__restrict__ postT, const float *__restrict__ yT,
+                                                          const float *__restrict__ weights, int t, long long batch,
+                                                          float inv_bn, float *__restrict__ gllrT,
+                                                          double *__restrict__ loss_part, int var_blocks)
+{
+    constexpr int W = kWave * VEC;
+    __shared__ double wsum[kWavesPerBlock];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int tile = uni(blockIdx.x / var_blocks);
+    const int j = uni((blockIdx.x % var_blocks) * kWavesPerBlock + wave);
+    const bool active = j < n;                     // waves past the last variable still meet the barrier below
+    const size_t off = ((size_t)tile * n + (active ? j : 0)) * W + (size_t)lane * VEC;
+    Pack<float, VEC> l, y;
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) { l.x[c] = 0.0f; y.x[c] = 0.0f; }
+    if (active) l = ld<float, VEC>(postT + off);
+    if (active && yT) y = ld<float, VEC>(yT + off);
+    const float wt = WANT_GRAD ? weights[t] : 0.0f;
+    double acc = 0.0;
+    Pack<float, VEC> gl;
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) {
+        const bool real = active && (long long)tile * W + (long long)lane * VEC + c < batch;
+        const float lc = l.x[c];
+        const float e = expf(-__builtin_fabsf(lc));                               // e^-|l|, shared by both terms
+        // BCEWithLogits(z = -l, y) = max(z, 0) - z y + log(1 + e^-|z|)
+        const float bce = (lc < 0.0f ? -lc : 0.0f) + lc * y.x[c] + log1pf(e);
+        if (real) acc += (double)bce;
+        const float sig = lc >= 0.0f ? e / (1.0f + e) : 1.0f / (1.0f + e);      // sigmoid(-l)
+        gl.x[c] = real ? wt * (y.x[c] - sig) * inv_bn : 0.0f;
+    }
+    acc = wave_sum_d(acc);
+    if (lane == 0) wsum[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) loss_part[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if constexpr (WANT_GRAD) {
+        if (!active) return;
+        st<float, VEC>(postT + off, gl);
+        if (gllrT) {
+            Pack<float, VEC> a = ld<float, VEC>(gllrT + off);
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) a.x[c] += gl.x[c];
+            st<float, VEC>(gllrT + off, a);
+        }
+    }
+}
+
+// loss_per_iter[t] = (sum of the count partials) * inv_bn: one block, thread k sums the partials k, k + kBlock, ... in
+// that order (8 loads in flight), then a fixed LDS tree -- bit-identical run to run.
+__global__ __launch_bounds__(kBlock) void joint_loss_reduce(const double *__restrict__ part, long long count, double inv_bn,
+                                                            float *__restrict__ out)
+{
+    __shared__ double s[kBlock];
+    double a = 0.0;
+#pragma unroll 8
+    for (long long i = threadIdx.x; i < count; i += kBlock) a += part[i];
+    s[threadIdx.x] = a;
+    __syncthreads();
+#pragma unroll
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)(s[0] * inv_bn);
+}
+
 // grad_table[t][s] = sum over the items x of slot s (x = edge for beta, variable for alpha) and over the tiles of
 // part[t][tile][x].  One wave per (slot, iteration), grid = (n_slots, T): lane l takes the items l, l+64, ... of the
 // slot's list (built by the host: slot_ptr / slot_items, the inverse of the slot map) in that order, sums in double,
 // and the 64 lane sums are combined by a fixed butterfly -- no atomics, so the result is bit-identical from run to
 // run.  Slots without items (and slots whose partials are all zero) come out as exactly 0.
-__global__ __launch_bounds__(kWave) void reduce_table_grads(const float *__restrict__ part, int tiles, int count,
+template <typename P>
+__global__ __launch_bounds__(kWave) void reduce_table_grads(const P *__restrict__ part, int tiles, int count,
                                                             const int *__restrict__ slot_ptr,
                                                             const int *__restrict__ slot_items, int n_slots,
                                                             float *__restrict__ grad)
 {
     const int s = blockIdx.x, t = blockIdx.y;
     const int i0 = slot_ptr[s], i1 = slot_ptr[s + 1];
-    const float *p = part + ((size_t)t * tiles) * count;
+    const P *p = part + ((size_t)t * tiles) * count;
     double acc = 0.0;
     for (int i = i0 + (int)threadIdx.x; i < i1; i += kWave) {
-        const float *q = p + slot_items[i];
+        const P *q = p + slot_items[i];
         double a = 0.0;
         for (int k = 0; k < tiles; ++k) a += (double)q[(size_t)k * count];
         acc += a;
@@ -381,6 +486,20 @@ __global__ __launch_bounds__(kWave) void reduce_table_grads(const float *__restr
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
     if (threadIdx.x == 0) grad[(size_t)t * n_slots + s] = (float)acc;
+}
+
+// First stage of the per-iteration table reduction of ldpc_train_joint: item_sum[x] = sum over the tiles of part[tile][x]
+// in fp64, tile order -- the same per-item sums reduce_table_grads forms, but one thread per item instead of one wave per
+// slot, so a step's reduction is not serialised over the few waves of a small table; reduce_table_grads<double> with
+// tiles = 1 then sums them per slot.
+__global__ __launch_bounds__(kBlock) void reduce_tiles(const float *__restrict__ part, int tiles, int count,
+                                                       double *__restrict__ item_sum)
+{
+    const int x = blockIdx.x * kBlock + threadIdx.x;
+    if (x >= count) return;
+    double a = 0.0;
+    for (int k = 0; k < tiles; ++k) a += (double)part[(size_t)k * count + x];
+    item_sum[x] = a;
 }
 
 }  // namespace ldpc

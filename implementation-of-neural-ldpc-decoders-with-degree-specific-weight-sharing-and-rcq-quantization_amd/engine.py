@@ -427,6 +427,58 @@ class DecodeEngine:
             return gb, ga, goa, gl
         return gb, ga, goa
 
+    # ------------------------------------------------------------------ posterior joint training
+    def train_joint_workspace_bytes(self, batch: int) -> int:
+        return int(self._lib.ldpc_train_joint_workspace_bytes(self.handle, int(batch)))
+
+    def train_joint(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                    iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
+                    want_grad_llr: bool = False) -> dict:
+        """Fixed-T decode with the loss on every iteration's posterior (ldpc_train_joint):
+        J_t = mean BCEWithLogits(-posterior_t, targets), J = sum_t w_t J_t, and -- want_grads -- the posterior-local
+        gradients of J (include/ldpc_hip.h).  targets [B, n] in [0, 1] (None: all zero), iteration_weights [T]
+        (None: 1/T each).  fp32 normalised / offset min-sum decoders only (NotImplementedError otherwise).
+        -> {"loss": 0-d, "loss_per_iter": [T], "bits": int32 [B, n], "posterior": [B, n] (of the last iteration),
+            "grad_beta", "grad_alpha": [T, slots] | None, "grad_oms_alpha": [T, slots] | None, "grad_llr": [B, n] | None}
+        Everything on this engine's device, fp32."""
+        llr = self._check_llr(llr)
+        B, n = llr.shape
+        dev = self.device
+        T = self.iters
+        if targets is not None:
+            targets = targets.to(device=dev, dtype=torch.float32).contiguous()
+            if targets.shape != llr.shape:
+                raise ValueError(f"targets must have shape {tuple(llr.shape)}, got {tuple(targets.shape)}")
+        if iteration_weights is None:
+            w = torch.full((max(T, 1),), 1.0 / max(T, 1), dtype=torch.float32, device=dev)
+        else:
+            w = torch.as_tensor(iteration_weights).to(device=dev, dtype=torch.float32).contiguous()
+            if w.shape != (T,):
+                raise ValueError(f"iteration_weights must have shape ({T},), got {tuple(w.shape)}")
+        lpi = torch.empty((T,), dtype=torch.float32, device=dev)
+        bits = torch.empty((B, n), dtype=torch.int32, device=dev)
+        post = torch.empty((B, n), dtype=torch.float32, device=dev)
+        gb = torch.empty(self._table_shapes[0], dtype=torch.float32, device=dev) if want_grads else None
+        ga = torch.empty(self._table_shapes[1], dtype=torch.float32, device=dev) if want_grads else None
+        goa = (torch.empty(self._table_shapes[2], dtype=torch.float32, device=dev)
+               if want_grads and self._table_shapes[2] is not None else None)
+        gl = torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr else None
+        ws = None
+        if B > 0:
+            need = self.train_joint_workspace_bytes(B)
+            ws = getattr(self, "_joint_ws", None)
+            if ws is None or ws.numel() < need:
+                self._joint_ws = None
+                self._joint_ws = ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            nat.check(self._lib.ldpc_train_joint(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
+                                                 p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),
+                                                 C.c_void_p(stream)), "ldpc_train_joint")
+        return {"loss": (w[:T] * lpi).sum(), "loss_per_iter": lpi, "bits": bits, "posterior": post,
+                "grad_beta": gb, "grad_alpha": ga, "grad_oms_alpha": goa, "grad_llr": gl}
+
     def debug_sweep(self, batch: int, which: int, it: int):
         """Launch one CN (which=0) or VN (which=1) sweep on the state a previous
         decode(batch) left in the workspace -- bench.py's per-kernel timing hook."""

@@ -152,6 +152,25 @@ class _DegreeSharedDecoder(nn.Module):
             return bits[0].to(out_dev), post[0].to(out_dev), int(iters[0].item())
         return bits.to(out_dev), post.to(out_dev), iters.to(out_dev)
 
+    def joint_posterior_loss(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                             iteration_weights: Optional[torch.Tensor] = None, device=None):
+        """Posterior joint training (the paper's training loss): decode ``llr`` ``[n]`` / ``[B, n]`` for exactly
+        ``max_iterations`` iterations and take the loss on every iteration's posterior,
+        ``loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets)`` (targets in [0, 1], default all zero = the
+        all-zero codeword; w = ``iteration_weights`` [T], default 1/T each, not trained).  ``loss.backward()`` gives each
+        parameter the posterior-local gradient: iteration t's loss reaches beta_t (offset form: alpha_t), alpha_t-1 and
+        the LLRs, nothing earlier (include/ldpc_hip.h ldpc_train_joint).  Keeps no per-iteration history, so the
+        memory does not grow with T.
+        -> (loss 0-d, loss_per_iteration [T], bits int32, posterior of the last iteration)"""
+        import autograd_bridge as ab
+        if not isinstance(llr, torch.Tensor):
+            raise TypeError("llr must be a torch.Tensor")
+        ab.check_joint_args(self.code.n, int(self.max_iterations), llr, targets, iteration_weights)
+        eng = self._get_engine(llr.device if llr.is_cuda else device)
+        bt, at = self._sharing_layout().tables_torch(self.beta_weights, self.alpha_weights, int(self.max_iterations),
+                                                     self._beta_default, self._alpha_default)
+        return ab.joint_loss(bt, at, eng, llr, targets, iteration_weights, self._alpha_is_oms)
+
 
 class Neural2DMinSumDecoder(_DegreeSharedDecoder):
     """

@@ -120,6 +120,24 @@ class _EdgeWeightDecoder(nn.Module):
             return res.bits[0].to(out_dev), res.posterior[0].to(out_dev), int(res.iterations[0].item())
         return res.bits.to(out_dev), res.posterior.to(out_dev), res.iterations.to(out_dev)
 
+    def joint_posterior_loss(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                             iteration_weights: Optional[torch.Tensor] = None, device=None):
+        """Posterior joint training with the per-edge weights: the fixed-T decode with
+        ``loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets)`` and its posterior-local gradient, as
+        ``Neural2DMinSumDecoder.joint_posterior_loss`` -> (loss, loss_per_iteration [T], bits, posterior)"""
+        import autograd_bridge as ab
+        if not isinstance(llr, torch.Tensor):
+            raise TypeError("llr must be a torch.Tensor")
+        g, T = self.code.tanner_graph(), int(self.max_iterations)
+        ab.check_joint_args(self.code.n, T, llr, targets, iteration_weights)
+        eng = self._get_engine(llr.device if llr.is_cuda else device)
+        rows, cols = g.check_of_edge.tolist(), g.var_idx.tolist()
+        params = [self.beta_weights[f"iter_{t}_c{i}_v{j}"] for t in range(T) for i, j in zip(rows, cols)]
+        where = [(t, e) for t in range(T) for e in range(g.E)]
+        bt = ab.table_from_params(params, where, (max(T, 1), max(g.E, 1)), 0.0)
+        at = torch.ones((max(T, 1), 1), dtype=torch.float32)
+        return ab.joint_loss(bt, at, eng, llr, targets, iteration_weights, False)
+
 
 class NeuralMinSumDecoder(_EdgeWeightDecoder):
     """Neural MinSum (N-NMS) decoder with edge-specific weights"""

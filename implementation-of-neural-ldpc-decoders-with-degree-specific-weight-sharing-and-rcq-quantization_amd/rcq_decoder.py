@@ -219,6 +219,10 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
                     thresholds=_threshold_table(self.quantizers),
                     q_of_iter=_quantizer_schedule(len(self.quantizers), self.max_iterations))
 
+    def joint_posterior_loss(self, llr, targets=None, iteration_weights=None, device=None):
+        """not available: the RCQ quantiser passes no gradient, so there is nothing to train through"""
+        raise NotImplementedError("WeightedRCQDecoder has no gradient path: the RCQ quantiser passes no gradient")
+
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):
         """
         Returns:

@@ -22,6 +22,13 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
   ldpc::minsum_backward(Tensor saved, Tensor llr, Tensor iterations, Tensor grad_posterior, Tensor beta,
                         Tensor alpha, int engine, bool alpha_is_oms, bool want_grad_llr)
         -> (Tensor grad_beta, Tensor grad_alpha, Tensor grad_llr)
+  ldpc::minsum_joint_loss(Tensor llr, Tensor? targets, Tensor beta, Tensor alpha, Tensor iteration_weights, int engine,
+                          bool alpha_is_oms, bool want_grads=True, bool want_grad_llr=False)
+        -> (Tensor loss, Tensor loss_per_iter, Tensor posterior, Tensor bits, Tensor grad_beta, Tensor grad_alpha,
+            Tensor grad_llr)
+     posterior joint training (ldpc_train_joint): the fixed-T decode with loss = sum_t w_t * BCE of iteration t's
+     posterior, whose gradients the forward already formed (no saved history); differentiable in `loss` only, the
+     backward scales the last three outputs (and d loss/d w_t = loss_per_iter[t]).
 
 ``engine`` is an integer handle of a live ``engine.DecodeEngine`` (``engine_handle(eng)``): operator schemas
 carry tensors and scalars, and the native decoder handle is neither.  There is no CPU implementation: the
@@ -32,7 +39,7 @@ from __future__ import annotations
 
 import threading
 import weakref
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -195,3 +202,69 @@ def _train_backward(ctx, g_post, _g_bits, _g_iters, _g_saved):
 
 
 minsum_decode_train.register_autograd(_train_backward, setup_context=_train_setup)
+
+
+# ------------------------------------------------------------------------------------------ posterior joint training
+@torch.library.custom_op("ldpc::minsum_joint_loss", mutates_args=())
+def minsum_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, iteration_weights: Tensor,
+                      engine: int, alpha_is_oms: bool, want_grads: bool = True,
+                      want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """fixed-T decode with the loss on every iteration's posterior (ldpc_train_joint):
+    loss = sum_t w_t J_t, loss_per_iter = J_t, posterior / bits of the last iteration, and the gradients of `loss`
+    the autograd formula scales: d loss/d beta [T, Sb], d loss/d alpha [T, Sa] (alpha_is_oms: the check-side offset)
+    -- empty when not want_grads -- and d loss/d llr [B, n] (empty when not want_grad_llr)"""
+    eng = _engine(engine)
+    restore = _with_tables(eng, _np_table(beta), _np_table(alpha), alpha_is_oms)
+    try:
+        r = eng.train_joint(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
+                            want_grads=want_grads, want_grad_llr=want_grad_llr)
+    finally:
+        restore()
+    dev = llr.device
+    if want_grads:
+        gb = r["grad_beta"].to(device=beta.device, dtype=beta.dtype)
+        ga = r["grad_oms_alpha"] if alpha_is_oms else r["grad_alpha"]
+        ga = (torch.zeros(tuple(alpha.shape), dtype=alpha.dtype, device=alpha.device) if ga is None
+              else ga.to(device=alpha.device, dtype=alpha.dtype))
+    else:
+        gb, ga = torch.empty((0,), dtype=beta.dtype, device=beta.device), torch.empty((0,), dtype=alpha.dtype, device=alpha.device)
+    gl = r["grad_llr"] if want_grad_llr else torch.empty((0,), dtype=torch.float32, device=dev)
+    return r["loss"], r["loss_per_iter"], r["posterior"], r["bits"], gb, ga, gl
+
+
+@minsum_joint_loss.register_fake
+def _(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads=True, want_grad_llr=False):
+    B, n = llr.shape
+    dev = llr.device
+    T = iteration_weights.shape[0]
+    return (torch.empty((), dtype=torch.float32, device=dev), torch.empty((T,), dtype=torch.float32, device=dev),
+            torch.empty((B, n), dtype=torch.float32, device=dev), torch.empty((B, n), dtype=torch.int32, device=dev),
+            torch.empty_like(beta) if want_grads else torch.empty((0,), dtype=beta.dtype, device=beta.device),
+            torch.empty_like(alpha) if want_grads else torch.empty((0,), dtype=alpha.dtype, device=alpha.device),
+            torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr
+            else torch.empty((0,), dtype=torch.float32, device=dev))
+
+
+def _joint_setup(ctx, inputs, output):
+    _llr, _targets, _beta, _alpha, _w, _engine_h, _oms, want_grads, want_grad_llr = inputs
+    _loss, lpi, post, bits, gb, ga, gl = output
+    ctx.want_grads, ctx.want_grad_llr = want_grads, want_grad_llr
+    ctx.save_for_backward(lpi, gb, ga, gl)
+    # only the scalar loss is differentiable: the gradients above are d loss / d input
+    ctx.mark_non_differentiable(lpi, post, bits, gb, ga, gl)
+    ctx.set_materialize_grads(False)
+
+
+def _joint_backward(ctx, g_loss, *_unused):
+    lpi, gb, ga, gl = ctx.saved_tensors
+    if g_loss is None:
+        return None, None, None, None, None, None, None, None, None
+    # J is linear in its seed: the saved gradients of `loss` scale by the incoming gradient
+    g_beta = gb * g_loss.to(gb.device) if ctx.want_grads and ctx.needs_input_grad[2] else None
+    g_alpha = ga * g_loss.to(ga.device) if ctx.want_grads and ctx.needs_input_grad[3] else None
+    g_llr = gl * g_loss if ctx.want_grad_llr and ctx.needs_input_grad[0] else None
+    g_w = lpi * g_loss if ctx.needs_input_grad[4] else None          # d loss / d w_t = J_t
+    return g_llr, None, g_beta, g_alpha, g_w, None, None, None, None
+
+
+minsum_joint_loss.register_autograd(_joint_backward, setup_context=_joint_setup)

@@ -19,6 +19,13 @@ default.  The reference calls simulate_awgn_channel, whose opposite convention m
 undecodable; `TrainingConfig.llr_convention = "reference"` reproduces that literally.
 `train_epoch` returns (loss, accuracy, gradient norm) -- the three values the reference's own caller unpacks
 (:208), although its annotation says two.
+
+By default the loss is the reference's: BCE of the posterior the decoder returns, differentiated through every
+iteration (full backpropagation through time).  `TrainingConfig.joint_posterior_loss = True` trains the way the paper
+does instead: the fixed-T decode with the BCE of EVERY iteration's posterior, each iteration's C2V messages receiving
+the gradient of that iteration's posterior only (``model.joint_posterior_loss``, include/ldpc_hip.h ldpc_train_joint);
+no per-iteration history is kept, so the memory does not grow with T.  `use_posterior_training` is the reference's
+field and changes nothing.
 """
 
 from __future__ import annotations
@@ -49,13 +56,14 @@ class TrainingConfig:
     snr_range: Tuple[float, float] = (0.0, 6.0)
     snr_step: float = 0.5
     max_grad_norm: float = 1.0
-    use_posterior_training: bool = True
+    use_posterior_training: bool = True      # the reference's field; no effect (see joint_posterior_loss)
     use_gradient_clipping: bool = False
     clip_threshold: float = 1e-3
     device: str = "cuda"
     llr_convention: str = "decoder"          # "reference": simulate_awgn_channel literally (see module docstring)
     data_parallel: bool = False              # one process per GPU: average the gradients over the ranks every step
     seed: Optional[int] = None               # training-data noise seed (decoder convention only)
+    joint_posterior_loss: bool = False       # True: the per-iteration posterior loss of the paper (model.joint_posterior_loss)
 
 
 def _grad_norm(model: nn.Module) -> float:
@@ -88,7 +96,9 @@ def _plot_series(panels, figsize, save_path):
 
 
 class PosteriorJointTrainer:
-    """Posterior joint training: Adam on the BCE of the posterior the decoder returns (no per-iteration losses)."""
+    """Adam on the BCE of the posterior the decoder returns (default), or -- config.joint_posterior_loss -- on the
+    weighted sum of every iteration's posterior BCE with the paper's posterior-local gradient; then the history also
+    holds each epoch's per-iteration training losses (`train_iteration_losses`, one [T] list per epoch)."""
 
     def __init__(self, model: nn.Module, config: TrainingConfig):
         self.model, self.config = model, config
@@ -98,6 +108,8 @@ class PosteriorJointTrainer:
         self.train_losses: List[float] = []
         self.train_accuracies: List[float] = []
         self.gradient_norms: List[float] = []
+        self.train_iteration_losses: List[List[float]] = []
+        self._pass_iteration_losses: Optional[List[float]] = None
         logger.info("trainer ready: %d trainable scalars", sum(p.numel() for p in model.parameters()))
 
     # ---- data ------------------------------------------------------------------------------------------
@@ -129,11 +141,18 @@ class PosteriorJointTrainer:
     def _pass(self, loader: DataLoader, train: bool) -> Tuple[float, float, float]:
         self.model.train(train)
         loss_sum, right, seen, norms = 0.0, 0, 0, []
+        joint = self.config.joint_posterior_loss
+        iter_sum = None
         for step, (llrs, targets) in enumerate(loader):
             llrs, targets = llrs.to(self.device), targets.to(self.device)
             with torch.set_grad_enabled(train):
-                decoded, posteriors, _ = self.model(llrs)
-                loss = self.compute_loss(decoded, targets, posteriors)
+                if joint:       # loss on every iteration's posterior, bits of the last one
+                    loss, per_iter, decoded, _ = self.model.joint_posterior_loss(llrs, targets)
+                    per_iter = per_iter.detach().double().cpu()
+                    iter_sum = per_iter if iter_sum is None else iter_sum + per_iter
+                else:
+                    decoded, posteriors, _ = self.model(llrs)
+                    loss = self.compute_loss(decoded, targets, posteriors)
             if train:
                 self.optimizer.zero_grad()
                 loss.backward()                                 # HIP backward sweeps (autograd_bridge.py)
@@ -150,6 +169,7 @@ class PosteriorJointTrainer:
             right += _frames_right(decoded, targets)
             seen += llrs.shape[0]
         batches = max(len(loader), 1)
+        self._pass_iteration_losses = None if iter_sum is None else (iter_sum / batches).tolist()
         return loss_sum / batches, right / max(seen, 1), (float(np.mean(norms)) if norms else 0.0)
 
     def train_epoch(self, train_loader: DataLoader) -> Tuple[float, float, float]:
@@ -167,6 +187,8 @@ class PosteriorJointTrainer:
         for epoch in range(self.config.num_epochs):
             t0 = time.time()
             loss, acc, gnorm = self.train_epoch(train_loader)
+            if self.config.joint_posterior_loss:
+                self.train_iteration_losses.append(self._pass_iteration_losses or [])
             vloss, vacc, _ = self.validate(val_loader)
             self.train_losses.append(loss)
             self.train_accuracies.append(acc)
@@ -175,8 +197,11 @@ class PosteriorJointTrainer:
                         epoch + 1, self.config.num_epochs, loss, acc, vloss, vacc, gnorm, time.time() - t0)
             if acc > 0.99:                                       # the reference's stop rule (:222-224)
                 break
-        return {"train_losses": self.train_losses, "train_accuracies": self.train_accuracies,
-                "gradient_norms": self.gradient_norms}
+        history = {"train_losses": self.train_losses, "train_accuracies": self.train_accuracies,
+                   "gradient_norms": self.gradient_norms}
+        if self.config.joint_posterior_loss:
+            history["train_iteration_losses"] = self.train_iteration_losses
+        return history
 
     def plot_training_history(self, save_path: Optional[str] = None):
         _plot_series([("line", self.train_losses, "Training Loss", "Epoch", "Loss"),

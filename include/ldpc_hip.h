@@ -198,6 +198,29 @@ int ldpc_backward(const ldpc_decoder *d, const void *saved, size_t saved_bytes, 
                   void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr,
                   void *workspace, size_t workspace_bytes, void *stream);
 
+
+/* ---- posterior joint training (the paper's training method) -------------------------------
+ * The fixed-T decode (no early stop) of the same fp32 LDPC_C2V_NMS / LDPC_C2V_OMS flooding decoders
+ * (LDPC_ERR_UNSUPPORTED otherwise, as ldpc_decode_saving) with the loss taken on the posterior
+ * l_t of EVERY iteration t = 0..T-1:
+ *   J_t = mean over b, j of BCEWithLogits(-l_t[b][j], targets[b][j])      J = sum_t w_t * J_t
+ * and the gradient of J with the previous iteration's leave-one-out C2V sum in the variable update
+ * treated as a constant, so iteration t's loss reaches beta_t, the offset alpha_t, alpha_t-1 (through
+ * v2c_t) and the LLRs, nothing earlier.  The gradients are formed while iteration t is decoded: the
+ * scratch (ldpc_train_joint_workspace_bytes, 256-byte aligned) does not depend on T and nothing is saved.
+ *   llr[batch][n], targets[batch][n] (NULL: all zero), iteration_weights[T] fp32 (device; read only when
+ *   a gradient is asked for) -> loss_per_iter[T] = J_t fp32, bits[batch][n] int32 and posterior[batch][n]
+ *   fp32 of the last iteration (identical to ldpc_decode with early_stop = 0), grad_beta[T][n_beta_slots],
+ *   grad_alpha[T][n_alpha_slots], grad_oms_alpha[T][n_oms_alpha_slots], grad_llr[batch][n] fp32 (device,
+ *   overwritten; bits, posterior and every gradient may be NULL -- with no gradient only the loss is
+ *   formed).  Parameters the loss cannot reach (alpha_T-1, the alpha table of the offset forms) get 0;
+ *   batch == 0 gives zero losses and gradients.  Deterministic: no atomics. */
+size_t ldpc_train_joint_workspace_bytes(const ldpc_decoder *d, int64_t batch);
+int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                     const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                     void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
 /* sha256 (hex) over the sources and the compile recipe this library was built from, embedded at build time

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Time one posterior-joint-training step (joint_posterior_loss: fixed-T decode with the per-iteration loss and its
+posterior-local HIP gradients, backward scaling, Adam) next to the existing full-backpropagation step (forward with saved
+messages, HIP backward sweeps, Adam) at the same size.
+
+    python tools/time_train_joint.py [--steps 10]
+Prints one JSON line with a result per workload: (1998,1512) Neural-2D type 2 at T = 10 with B = 4096 and 32768, and
+(16200,7200) at T = 20 with B = 1024.  Device events around each step.  Algorithmic HBM bytes of a PJT step, per codeword
+and iteration: forward sweeps 16E + 8n (check: read v2c, write c2v; variable: read c2v + llr, write v2c + posterior), loss
+8n (read posterior, write g_l), local backward 20E (check: read v2c, gathered g_l and write d/dv2c; variable: read c2v_t-1
+and d/dv2c)."""
+import argparse, json, os, sys
+os.environ.setdefault("LDPC_TRAIN_MAX_SAVED_BYTES", str(64 << 30))     # let the BPTT step run where the HBM holds it
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402  (puts the package on sys.path)
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+WORKLOADS = (("ira_1998_1512", 10, 4096), ("ira_1998_1512", 10, 32768), ("dvbs2_like_16200_7200", 20, 1024))
+
+
+def time_steps(step, steps):
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    for _ in range(2):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = ev(), ev()
+    e0.record()
+    for _ in range(steps):
+        loss = step()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / steps, float(loss.item())
+
+
+def run(name, T, B, steps, snr_db, dev):
+    import autograd_bridge as ab
+    import codes
+    from neural_2d_decoder import Neural2DMinSumDecoder
+    code = codes.load_code(name, max_iterations=T)
+    model = Neural2DMinSumDecoder(code, 2, T)
+    with torch.no_grad():
+        for p in model.beta_weights.values():
+            p.fill_(0.7)
+        for p in model.alpha_weights.values():
+            p.fill_(1.0)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    llr = bench.make_llr(B, code.n, snr_db, 1234, dev)
+    tgt = torch.zeros_like(llr)
+    g = code.tanner_graph()
+
+    def pjt():
+        opt.zero_grad()
+        loss = model.joint_posterior_loss(llr)[0]
+        loss.backward()
+        opt.step()
+        return loss
+
+    def bptt():
+        opt.zero_grad()
+        _, post, _ = model(llr, early_stop=False)
+        loss = F.binary_cross_entropy_with_logits(-post, tgt)
+        loss.backward()
+        opt.step()
+        return loss
+
+    eng = model._get_engine(dev)
+    ms, loss = time_steps(pjt, steps)
+    alg = B * T * (36 * g.E + 16 * g.n)
+    out = {"workload": f"{name} Neural2D type 2, T={T}, batch {B}", "pjt_ms_per_step": ms,
+           "pjt_codewords_per_s": B / ms * 1e3, "pjt_algorithmic_GBps": alg / (ms * 1e-3) / 1e9,
+           "pjt_workspace_bytes_per_codeword": eng.train_joint_workspace_bytes(B) / B, "pjt_loss": loss}
+    saved = eng.train_saved_bytes(B)
+    out["bptt_saved_bytes_per_codeword"] = saved / B
+    if saved <= ab.MAX_SAVED_BYTES:
+        torch.cuda.empty_cache()
+        ms_b, loss_b = time_steps(bptt, steps)
+        out.update({"bptt_ms_per_step": ms_b, "bptt_codewords_per_s": B / ms_b * 1e3, "bptt_loss": loss_b,
+                    "pjt_over_bptt_time": ms / ms_b})
+    else:
+        out["bptt_ms_per_step"] = None                     # the saved history does not fit the cap
+    del model, opt, eng
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--snr-db", type=float, default=3.0)
+    ap.add_argument("--workload", type=int, default=None, help="run only WORKLOADS[i]")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    todo = WORKLOADS if a.workload is None else WORKLOADS[a.workload:a.workload + 1]
+    res = [run(name, T, B, a.steps, a.snr_db, dev) for name, T, B in todo]
+    print(json.dumps({"tool": "time_train_joint", "steps": a.steps, "results": res}))
+
+
+if __name__ == "__main__":
+    main()
