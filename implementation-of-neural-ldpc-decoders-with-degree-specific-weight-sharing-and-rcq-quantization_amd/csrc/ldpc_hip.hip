@@ -103,6 +103,11 @@ struct ldpc_decoder {
     bool beta_per_check = false;                  // every edge of a check uses the same beta slot
     size_t res_lds = 0;
     ResidentPlan res{};
+    // compact fixed-T geometry (resident_decode<..., CPT>): a second slot layout at row stride kResCptStride, taken by
+    // fixed-T fp32 decodes when three workgroups fit a CU; early-stop and fp64 decodes keep `res`
+    bool resc_ok = false;
+    size_t resc_lds = 0;
+    ResidentPlan resc{};
     std::vector<void *> res_bufs;  // device allocations owned by the plan
     // inverse slot maps of the gradient path (reduce_table_grads): items of slot s = inv_items[inv_ptr[s] .. inv_ptr[s+1])
     int *beta_inv_ptr = nullptr, *beta_inv_items = nullptr;
@@ -896,6 +901,11 @@ void optimise_lane_order(std::vector<int> &order, const std::vector<std::vector<
     }
 }
 
+// a lane position of the check phase: (sub-)check `check`, its edges e0 .. e0+dc-1, lane-group size gs
+struct ResVCheck { int check, e0, dc, gs; };
+int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
+                    long long S, int G, ResidentPlan &pl);
+
 // Sort checks and variables by degree (stable, descending), lay the edges out ELL-transposed.
 int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
 {
@@ -913,8 +923,7 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     // one is split into 2^k sub-checks of contiguous edges (balanced, at most kResSubDegree each) that sit on ADJACENT lanes
     // and are combined by wavefront exchanges (ldpc_resident.hip: group_combine).  Groups come first, by descending size --
     // every group then starts at a multiple of its size, so it never straddles a wave -- then the whole checks.
-    struct VCheck { int check, e0, dc, gs; };
-    std::vector<VCheck> vc;
+    std::vector<ResVCheck> vc;
     {
         auto dc_real = [&](int i) { return g->h_check_ptr[i + 1] - g->h_check_ptr[i]; };
         std::vector<int> wide_ids, plain_ids;
@@ -938,7 +947,7 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     const int m = (int)vc.size();
     const bool any_split = m != g->m;
     int max_sub = 0;
-    for (const VCheck &v : vc) max_sub = std::max(max_sub, v.dc);
+    for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
     if (m > 65535 || max_sub > 255) return LDPC_OK;
 
     // geometry: G codewords per workgroup, NT threads, and the row stride of the slot layout.
@@ -965,7 +974,43 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     }
     const long long S = (long long)max_sub * mstride;
     const int NT = blocks >= 2 ? 512 : 1024;
+    if (int rc = resident_layout(d, desc, vc, mstride, S, G, d->res)) return rc;
+    d->res_G = G; d->res_NT = NT;
+    d->res_lds = res_lds_total((int)S, n, G, resident_alpha_floats(d), d->res.par_words);
+    d->res_ok = true;
 
+    // compact fixed-T geometry: row stride kResCptStride, S truncated after the last slot in use (checks are sorted by
+    // descending degree, so the last row holds only the checks of the largest degree), no llr_s / bits_s / parity words /
+    // alpha table in LDS.  Taken when it gives kResCptBlocks workgroups of 512 threads per CU and the variable state fits
+    // the registers (resident_reg_state)
+    d->resc_ok = false;
+    if (!f64 && G == 2 && NT == kResCptThreads && !any_split && m <= kResCptStride && n <= kResRegVars * kResCptThreads) {
+        int n_top = 0;
+        while (n_top < m && vc[n_top].dc == max_sub) ++n_top;
+        const long long Sc = (long long)(max_sub - 1) * kResCptStride + n_top;
+        const size_t lds_c = res_cpt_lds_total((int)Sc, 2);
+        int n_hi = 0;
+        for (int j = 0; j < n; ++j) n_hi += (g->h_var_ptr[j + 1] - g->h_var_ptr[j]) > 4 ? 1 : 0;
+        if (Sc * 2 * 4 <= 65535 && (long long)n * 2 * 4 <= Sc * 2 * 4 && n_hi <= kResCptThreads &&
+            kResCptBlocks * lds_c <= kLdsBytes) {
+            if (int rc = resident_layout(d, desc, vc, kResCptStride, Sc, 2, d->resc)) return rc;
+            d->resc_lds = lds_c;
+            d->resc_ok = true;
+        }
+    }
+    return LDPC_OK;
+}
+
+// slot layout of one geometry: row stride `mstride`, S slots, G codewords per slot; variables ordered inside their degree
+// classes for LDS banking; the plan arrays go to the device (owned by d->res_bufs)
+int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
+                    long long S, int G, ResidentPlan &pl)
+{
+    const ldpc_graph *g = d->g;
+    const int n = g->n, m = (int)vc.size();
+    const bool any_split = m != g->m;
+    int max_sub = 0;
+    for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
     std::vector<int> perm_v(n), pos_v(n);
     for (int j = 0; j < n; ++j) perm_v[j] = j;
     auto dv_of = [&](int j) { return g->h_var_ptr[j + 1] - g->h_var_ptr[j]; };
@@ -989,7 +1034,7 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     std::vector<uint32_t> edge_of_slot((size_t)S, 0xffffffffu);
     bool per_check = true;
     for (int p = 0; p < m; ++p) {
-        const VCheck &v = vc[p];
+        const ResVCheck &v = vc[p];
         const int first = g->h_check_ptr[v.check];                  // the WHOLE check's first edge decides "one beta per check"
         dc_s[p] = (uint8_t)v.dc;
         gsz[p] = (uint8_t)v.gs;
@@ -1013,7 +1058,6 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
         vslot_hi[q] = make_uint2(off[4] | (off[5] << 16), off[6] | (off[7] << 16));
         if (dv > 4) n_hi = q + 1;                                                     // degree-sorted: they come first
     }
-    ResidentPlan &pl = d->res;
     pl = ResidentPlan{};
     pl.n = n; pl.m = m; pl.S = (int)S; pl.max_dc = max_sub; pl.max_dv = g->max_dv; pl.mstride = mstride; pl.E = g->E;
     pl.any_split = any_split ? 1 : 0;
@@ -1032,11 +1076,7 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     if (!rc) rc = plan_upload(d, &pl.vslot_hi, vslot_hi);
     if (!rc) rc = plan_upload(d, &pl.inv_perm_v, inv);
     if (!rc) rc = plan_upload(d, &pl.edge_of_slot, edge_of_slot);
-    if (rc) return rc;
-    d->res_G = G; d->res_NT = NT;
-    d->res_lds = res_lds_total((int)S, n, G, resident_alpha_floats(d), pl.par_words);
-    d->res_ok = true;
-    return LDPC_OK;
+    return rc;
 }
 
 // A kernel's dynamic-LDS ceiling is process-wide state of that kernel on a device: it is raised ONCE per
@@ -1086,6 +1126,26 @@ int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
         return LDPC_OK;
     }
     const unsigned blocks = (unsigned)((a.batch + G - 1) / G);
+    if constexpr (G == 2) {
+        if (d->resc_ok && !a.early_stop) {            // compact fixed-T geometry: three workgroups per CU
+            ResidentArgs ac = a;
+            ac.alpha_in_lds = 0;                      // no alpha table in the compact carve: read from global memory
+#define LDPC_RES_CPT(FORM, NL)                                                                                         \
+    do {                                                                                                               \
+        auto kfn = d->resc.bslot_c ? resident_decode<2, FORM, true, NL, kResCptStride, 0, float, false, true, true>    \
+                                   : resident_decode<2, FORM, false, NL, kResCptStride, 0, float, false, true, true>;  \
+        if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                                     \
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kResCptThreads), d->resc_lds, s, d->resc, ac);                      \
+    } while (0)
+            if (d->form == LDPC_C2V_NMS) LDPC_RES_CPT(FORM_NMS, 0);
+            else if (d->form == LDPC_C2V_OMS) LDPC_RES_CPT(FORM_OMS, 0);
+            else if (d->n_levels == 4) LDPC_RES_CPT(FORM_RCQ, 4);
+            else LDPC_RES_CPT(FORM_RCQ, 0);
+#undef LDPC_RES_CPT
+            HIP_TRY(hipGetLastError());
+            return LDPC_OK;
+        }
+    }
 #define LDPC_RES_MS(FORM, NL, MS, SPLIT, REG)                                                            \
     do {                                                                                                 \
         auto kfn = d->res.bslot_c ? (a.early_stop ? resident_decode<G, FORM, true, NL, MS, 1, float, SPLIT, false>   \
@@ -1605,6 +1665,7 @@ int ldpc_decoder_info(const ldpc_decoder *d, int32_t out4[4])
     out4[1] = d->res_ok ? (d->dtype == LDPC_F64 ? 1 : d->res_G) : 0;      // fp64: one codeword in a float pair's slots
     out4[2] = d->res_ok ? d->res_NT : 0;
     out4[3] = d->res_ok ? (int32_t)d->res_lds : 0;
+    if (d->resc_ok) { out4[2] = kResCptThreads; out4[3] = (int32_t)d->resc_lds; }   // the fixed-T decode's compact geometry
     if (d->lay_ok) { out4[1] = d->lay.cw; out4[2] = kWave; out4[3] = (int32_t)d->lay_lds; }   // layered: codewords per (one-wave) workgroup
     return LDPC_OK;
 }

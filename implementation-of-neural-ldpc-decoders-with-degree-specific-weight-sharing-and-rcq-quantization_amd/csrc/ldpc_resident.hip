@@ -542,11 +542,13 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
 //         (dead) LLR slot with the posterior so the output pass can read it in original order
 // MODE 4 / 6: MODE 0 / 2 plus the hard-decision byte from the same gathered values -- the early-stop
 //         iteration of callers that do not ask for the posterior (one gather pass instead of two)
+// MODE 9: MODE 8 with the posterior of the `emask` components kept in *lreg (compact kernels: no llr_s, the slots are
+//         still being read by other lanes)
 // `lreg`: the variable's LLR pair held in registers (ResVarState), or null to read it from llr_s
 template <int G, int DV, int MODE, typename T>
 __device__ __forceinline__ void res_var_body(unsigned char *smem, T *__restrict__ llr_s,
                                              uint8_t *__restrict__ bits_s, int q, const uint4 &slo, const uint4 &shi,
-                                             T a, unsigned emask, const ParScatter &ps, const Pack<T, G> *lreg)
+                                             T a, unsigned emask, const ParScatter &ps, Pack<T, G> *lreg)
 {
     using P = Pack<T, G>;
     constexpr int ORD = std::is_same<T, float>::value ? 0 : 1;       // torch.sum fp32 order / np.sum fp64 order
@@ -596,7 +598,7 @@ __device__ __forceinline__ void res_var_body(unsigned char *smem, T *__restrict_
             byte |= (post < (T)0 ? 1u : 0u) << g;
             if ((emask >> g) & 1u) { l.x[g] = post; store = true; }
         }
-        if constexpr (MODE == 8) {
+        if constexpr (MODE == 8 || MODE == 9) {
             // last pass of a fixed-T decode: the c2v values in this variable's slots are dead once read above, so the
             // hard decisions go there (bit g = codeword g) and the final syndrome reads them back with consecutive
             // addresses per check (res_syndrome_slots) instead of gathering bytes through global index loads
@@ -609,7 +611,10 @@ __device__ __forceinline__ void res_var_body(unsigned char *smem, T *__restrict_
                 for (int k = 0; k < DV; ++k) lds_atomic_xor(ps.par_off + (((off[k] >> ps.shift) & ps.mask) << 2), byte);
             }
         }
-        if (store) L[q] = l;
+        if (store) {
+            if constexpr (MODE == 9) *lreg = l;
+            else L[q] = l;
+        }
     }
 }
 
@@ -622,7 +627,7 @@ template <int G, int MODE, typename T>
 __device__ __forceinline__ void res_var_dispatch(unsigned char *smem, T *__restrict__ llr_s,
                                                  uint8_t *__restrict__ bits_s, int q, int dv, const uint4 &slo,
                                                  const uint4 &shi, T a, unsigned emask, const ParScatter &ps,
-                                                 const Pack<T, G> *lreg = nullptr)
+                                                 Pack<T, G> *lreg = nullptr)
 {
 #define LDPC_RV(D) case D: res_var_body<G, D, MODE, T>(smem, llr_s, bits_s, q, slo, shi, a, emask, ps, lreg); break;
     switch (dv) {
@@ -903,15 +908,30 @@ __host__ __device__ inline size_t res_off_par(int S, int n, int G, int n_alpha_l
 // `m_par` parity words follow (early-stop syndrome by scatter); 0 when the stride is not a power of two
 __host__ __device__ inline size_t res_lds_total(int S, int n, int G, int n_alpha_lds, int m_par) { return res_off_par(S, n, G, n_alpha_lds) + 4 * (size_t)m_par; }
 
+// compact kernels (CPT): only the message slots and the flag words -- the LLR rows are staged in the not-yet-initialised
+// message area and the posteriors in the dead one, the alpha table is read from global memory, no bits_s / parity words
+__host__ __device__ inline size_t res_cpt_off_flag(int S, int G) { return ((size_t)S * G * 4 + 15) / 16 * 16; }
+__host__ __device__ inline size_t res_cpt_lds_total(int S, int G) { return res_cpt_off_flag(S, G) + 16; }
+
 // ES: 0 = fixed-iteration kernel, 1 = early-stop kernel (kept apart so that the fixed-T kernel does not carry
 // the posterior/syndrome/emit code of the stop rule: the extra code cost the hot loop ~4 % when merged)
 constexpr int kResMaxThreads = 1024;   // launch bounds of resident_decode: threads per workgroup, waves per SIMD the
 constexpr int kResMinWaves = 4;        // register allocation must leave room for
+// compact geometry (CPT): three 512-thread workgroups per CU -> six waves per SIMD, at most 80 VGPRs
+constexpr int kResCptThreads = 512;
+constexpr int kResCptWaves = 6;
+constexpr int kResCptBlocks = 3;       // workgroups per CU the compact LDS carve must allow
+constexpr int kResCptStride = 496;     // compile-time row stride of the compact slot layout (m <= 496)
 // REG: variable state in registers (ResVarState; the host takes it for fixed-T decodes of codes that qualify, see
 // resident_reg_state)
-template <int G, int FORM, bool BPC, int NL, int MS, int ES, typename T = float, bool SPLIT = false, bool REG = false>
-__global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(ResidentPlan pl, ResidentArgs a)
+// CPT: compact fixed-T kernel (REG, fp32, no split checks): res_cpt_lds_total bytes of LDS, so that kResCptBlocks
+// workgroups share a CU (build_resident_plan)
+template <int G, int FORM, bool BPC, int NL, int MS, int ES, typename T = float, bool SPLIT = false, bool REG = false,
+          bool CPT = false>
+__global__ __launch_bounds__(CPT ? kResCptThreads : kResMaxThreads, CPT ? kResCptWaves : kResMinWaves)
+void resident_decode(ResidentPlan pl, ResidentArgs a)
 {
+    static_assert(!CPT || (REG && !ES && !SPLIT && std::is_same<T, float>::value), "compact: fixed-T fp32 REG kernels only");
     extern __shared__ __align__(16) unsigned char res_smem[];     // the only LDS object: msg starts at offset 0
     if (__builtin_amdgcn_groupstaticsize() != 0) __builtin_trap();  // lds_load/lds_store rely on that (folds away)
     // T = float: G codewords per workgroup; T = double (fp64 Basic): the same 8-byte slots hold ONE codeword, so the
@@ -919,10 +939,12 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
     // typed float for the common case and re-read as T here.
     constexpr int GE = G * (int)(sizeof(T) / 4);
     const int n_alpha_lds = a.alpha_in_lds ? a.T * a.n_alpha * (int)(sizeof(T) / 4) : 0;
-    T *llr_s = reinterpret_cast<T *>(res_smem + res_off_llr(pl.S, GE));
+    // CPT: the LLR rows are staged at offset 0, in the message area the init scatter writes only after they are read
+    T *llr_s = reinterpret_cast<T *>(res_smem + (CPT ? 0 : res_off_llr(pl.S, GE)));
     T *alpha_s = reinterpret_cast<T *>(res_smem + res_off_alpha(pl.S, pl.n, GE));
     uint8_t *bits_s = res_smem + res_off_bits(pl.S, pl.n, GE, n_alpha_lds);
-    unsigned *sh_unsat = reinterpret_cast<unsigned *>(res_smem + res_off_flag(pl.S, pl.n, GE, n_alpha_lds));
+    unsigned *sh_unsat = reinterpret_cast<unsigned *>(res_smem + (CPT ? res_cpt_off_flag(pl.S, GE)
+                                                                        : res_off_flag(pl.S, pl.n, GE, n_alpha_lds)));
     ParScatter ps, psf;                                  // per-iteration syndrome (early stop) / final syndrome (fixed T)
     if (pl.par_words) {
         psf.par_off = (unsigned)res_off_par(pl.S, pl.n, GE, n_alpha_lds);
@@ -980,6 +1002,7 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
                 st.l[r] = L[q];
             }
         }
+        if constexpr (CPT) __syncthreads();                // the init scatter below overwrites the staged LLR rows
 #pragma unroll
         for (int r = 0; r < kResRegVars; ++r) {
             if (tid + r * nt < n) {
@@ -1133,7 +1156,7 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
     const bool scatter = !ES && psf.par_off != 0;
     if (ES) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     else if (scatter) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st, psf);
-    else res_var_phase<G, 8, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
+    else res_var_phase<G, CPT ? 9 : 8, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     __syncthreads();
     unsigned unsat = kAll;
     if (!ES) {
@@ -1141,6 +1164,13 @@ __global__ __launch_bounds__(kResMaxThreads, kResMinWaves) void resident_decode(
         else res_syndrome_slots<G, T, SPLIT>(pl, sh_unsat, tid, nt);
         __syncthreads();
         unsat = *sh_unsat;
+    }
+    if constexpr (CPT) {
+        // the slots are dead now: the posteriors the last pass kept in registers go to the staging rows (sorted order)
+#pragma unroll
+        for (int r = 0; r < kResRegVars; ++r)
+            if (tid + r * nt < n) reinterpret_cast<P *>(llr_s)[tid + r * nt] = st.l[r];
+        __syncthreads();
     }
     res_emit<G, T>(pl, a, llr_s, b0, open, a.T, unsat, tid, nt);
 }

@@ -197,10 +197,13 @@ class DecodeEngine:
             paper = self.schedule == nat.SCHED_LAYERED
             kernel = ("layered_paper_lds" if paper else "layered_lds") if resident else \
                      ("layered_rcq<paper>" if paper else "layered_rcq<ref>")
+        # workgroups per CU as LDS (160 KiB) and the wave slots (32 per CU) allow; 0 on the streaming engine
+        threads, lds = int(out[2]), int(out[3])
+        per_cu = min((160 * 1024) // lds, (32 * 64) // threads) if resident and threads and lds else 0
         return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel,
                 "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
                 "codewords_per_workgroup": int(out[1]),
-                "threads_per_workgroup": int(out[2]), "lds_bytes": int(out[3])}
+                "threads_per_workgroup": threads, "lds_bytes": lds, "workgroups_per_cu": per_cu}
 
     # ------------------------------------------------------------------ weights
     def set_weights(self, beta: Optional[np.ndarray], alpha: Optional[np.ndarray],

@@ -135,7 +135,8 @@ enum { LDPC_MODE_AUTO = 0, LDPC_MODE_STREAM = 1, LDPC_MODE_RESIDENT = 2, LDPC_MO
 int ldpc_decoder_set_mode(ldpc_decoder *d, int32_t mode);
 /* out4 = { engine and form a decode would use now (LDPC_MODE_RESIDENT, or the streaming form LDPC_MODE_PAIR /
  * LDPC_MODE_GATHER / LDPC_MODE_SWEEPS), codewords per workgroup, threads per
- * workgroup, LDS bytes per workgroup } -- the last three 0 when the code does not qualify */
+ * workgroup, LDS bytes per workgroup } -- the last three 0 when the code does not qualify; the geometry of a
+ * fixed-iteration decode where it has one of its own (the compact resident kernel) */
 int ldpc_decoder_info(const ldpc_decoder *d, int32_t out4[4]);
 /* re-upload beta/alpha(/oms_alpha) tables of an existing decoder (same shapes);
  * enqueued on `stream`, host arrays must stay valid until it has run. */
