@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """
-bench.py -- decoded codewords/s at fixed iterations + roofline of the dominant kernel.
+bench.py -- decoded codewords/s at fixed iterations; with --full also the roofline of the dominant kernel and more.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload basic|neural2d|rcq|wrcq_dvbs2|basic_f64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload basic|neural2d|rcq|wrcq_dvbs2|basic_f64] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,10 @@ fp32, 10 iterations, batch 65536 per GPU, SNR 2.0 dB, fixed iterations (early_st
 `--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy: the inputs
 are seeded, so two builds run with the same arguments can be compared output for output.
 
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the steps,
+checks that every iteration ran, writes the outputs if asked and prints the line.  Everything measured
+beside the headline runs only with `--full`, after the timed steps, and leaves them unchanged.
+
 N > 1: one process per GPU.  Started bare (`python bench.py --gpus N`, no WORLD_SIZE in the
 environment) the script spawns its N ranks itself as child processes BEFORE anything touches the
 GPU, relays rank 0's JSON line and exits non-zero if a rank fails; started under
@@ -20,11 +24,11 @@ torch.distributed.run it is one of the ranks.  Weak scaling by default (every ra
 batch; `--strong` splits --batch over the ranks); every step ends with the RCCL all-gather of
 the bit-packed hard decisions; value = all ranks' codewords / max-rank time.  A multi-rank line also
 carries `distributed` (world size / backend as the process group reports them, every rank's device,
-the all-gather timed alone, a content check of the gathered array on every rank) and
-`sharded_workloads`: BASELINE config 5 -- (16200,7200) W-RCQ, T=20 -- weak (32768 per GPU) and strong
-(262144 in total) with the same all-gather per step; rank 0 adds roofline and cpu_baseline as at N=1.
+a content check of the gathered array on every rank; with --full the all-gather timed alone) and, with
+--full, `sharded_workloads`: BASELINE config 5 -- (16200,7200) W-RCQ, T=20 -- weak (32768 per GPU) and
+strong (262144 in total) with the same all-gather per step; rank 0 adds the --full fields as at N=1.
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+Prints ONE JSON line (rank 0) with the driver's fields; --full adds
   roofline     : the dominant kernel of the timed step, timed live with HIP events on its stream.
                  LDS-resident engine: bound "lds" (conflict-free LDS time of its iteration phases / measured
                  time), its real HBM rate under "hbm" and the SURVEY 8d byte model under "hbm_formulation_equiv";
@@ -32,6 +36,7 @@ Prints ONE JSON line (rank 0) with the driver's fields plus
   stream_engine: the HBM-streaming engine on the same workload with the CN->VN sweep's HBM roofline (north_star)
   workloads    : bounded legs for the other BASELINE configs (Neural-2D, RCQ, (16200,7200) W-RCQ, fp64 Basic)
   cpu_baseline : the CPU oracle (C port of the reference loops) on a bounded sample
+  measured_ceilings : the box's 1 GiB device copy and fill rates
 """
 import argparse
 import json
@@ -73,18 +78,22 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=0, help="codewords per GPU (default: the workload's)")
     ap.add_argument("--snr-db", type=float, default=2.0)
     ap.add_argument("--early-stop", action="store_true", help="reference early-exit semantics instead of fixed T")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sweep-reps", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: rooflines, the streaming-engine leg, the copy / "
+                         "fill ceilings, the CPU baseline, legs for the other BASELINE configs, and with several ranks config 5 "
+                         "sharded and the all-gather timed alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--sweep-reps", type=int, default=20, help="--full: launches per roofline timing")
     ap.add_argument("--no-overlap", action="store_true", help="join every step's all-gather before the next decode")
-    ap.add_argument("--no-stream-leg", action="store_true", help="skip the secondary streaming-engine measurement")
-    ap.add_argument("--no-legs", action="store_true", help="skip the legs for the other BASELINE configs")
-    ap.add_argument("--leg-steps", type=int, default=5)
+    ap.add_argument("--no-stream-leg", action="store_true", help="--full without the secondary streaming-engine measurement")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the legs for the other BASELINE configs")
+    ap.add_argument("--leg-steps", type=int, default=5, help="--full: timed steps per leg")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group and run the all-gather path even with one rank (checks the RCCL plumbing on a single GPU)")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --batch (default: the workload's) is the TOTAL over all GPUs, split evenly")
     ap.add_argument("--config5-total", type=int, default=262144,
-                    help="total codewords of the strong-scaling config-5 leg of a multi-rank run (BASELINE.json: 262144)")
+                    help="total codewords of the strong-scaling config-5 leg of a multi-rank --full run (BASELINE.json: 262144)")
     ap.add_argument("--config5-max-per-gpu", type=int, default=262144,
                     help="skip that leg when total / N exceeds this many codewords per GPU (memory: ~0.42 MB per codeword)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -806,7 +815,6 @@ def main():
     ver = main_run.verify()                                       # nothing skipped; gathered == the ranks' shards
     dumped = dump_outputs(args.dump_outputs, main_run.res, main_run.gathered) if args.dump_outputs and rank == 0 else None
     inventory = rank_inventory(ctx)
-    allgather = main_run.gather_alone()
 
     out = {
         "metric": METRIC,
@@ -822,20 +830,22 @@ def main():
                    "converged_fraction": ver["converged_fraction"],
                    "dtype_note": "the reference's BasicMinSumDecoder computes in float64 (numpy default); the benchmark "
                                  "config is defined on fp32 (BASELINE.json north_star, SURVEY 8d) -- the float64 kernels "
-                                 "run as the `basic_f64` leg; fp32-vs-fp64 decision mismatch rates are in BASELINE.md"},
+                                 "run as the `basic_f64` leg of --full; fp32-vs-fp64 decision mismatch rates are in BASELINE.md"},
     }
     if dumped:
         out["dump_outputs"] = dumped
     if use_dist:
-        out["distributed"] = {**inventory, "allgather": allgather, "gather_check": ver.get("gather_check"),
+        out["distributed"] = {**inventory, "gather_check": ver.get("gather_check"),
                               "step": "decode of this rank's shard, then all_gather_into_tensor of uint8[B, ceil(n/8)]; "
                                       + ("the gather of step k overlaps the decode of step k+1 (joined one step later)"
                                          if not args.no_overlap else "joined before the next decode (--no-overlap)")}
+        if args.full:
+            out["distributed"]["allgather"] = main_run.gather_alone()       # collective: every rank runs this line
 
     # BASELINE config 5 as written, inside the multi-rank line (every rank takes part): weak 32768/GPU and strong 262144 total
     sharded = {}
     default_line = args.workload == "basic" and not args.batch and not early and not args.strong
-    if use_dist and not args.no_legs and default_line:
+    if use_dist and args.full and not args.no_legs and default_line:
         main_run.fence()
         llr = None
         main_run.res = main_run.gathered = None
@@ -857,44 +867,45 @@ def main():
         if sharded:
             out["sharded_workloads"] = sharded
         out["config"]["engine"] = eng.info()
-        reps = max(args.sweep_reps, 1)
         bm = byte_model(args.workload, g, T, B)
-        copy_gbs = copy_ceiling(device, torch)
-        out["measured_ceilings"] = {"copy_GBps": copy_gbs, "fill_GBps": fill_ceiling(device, torch),
-                                    "note": "1 GiB device copy (read + write bytes) and 1 GiB device fill (write only), best of 6"}
-        run = lambda: eng.decode(llr, early_stop=early, want_bits=True, want_posterior=want_post)
-        if args.workload == "rcq_layered":
-            out["roofline"] = layered_roofline(eng, g, T, B, event_ms(run, max(reps // 4, 2), torch))
-        elif eng.info()["engine"] == "resident":
-            # dominant kernel = ldpc::resident_decode (the whole decode is this one launch), timed with HIP events
-            ms = event_ms(run, reps, torch)
-            out["roofline"] = resident_roofline(eng, args.workload, g, T, B, ms, copy_gbs)
-            if not args.no_stream_leg:
-                # the HBM-bound engine (used for codes that do not fit LDS), same workload: the north_star's CN->VN sweep
-                os.environ["LDPC_ENGINE_MODE"] = "stream"
-                try:
-                    eng_s, dec_s, _ = build_decoder(args.workload, device)
-                finally:
-                    os.environ.pop("LDPC_ENGINE_MODE", None)
-                run_s = lambda: eng_s.decode(llr, early_stop=early, want_bits=True, want_posterior=want_post)
-                run_s()
-                ms_s = event_ms(run_s, 3, torch)
-                out["stream_engine"] = {"ms_per_step": ms_s, "value": B / (ms_s * 1e-3), "engine": eng_s.info(),
-                                        "roofline": stream_roofline(eng_s, args.workload, g, T, B, llr, reps, copy_gbs, torch)}
-                del eng_s, dec_s
-        else:
-            out["roofline"] = stream_roofline(eng, args.workload, g, T, B, llr, reps, copy_gbs, torch)
         out["decode_algorithmic_GBps"] = bm["decode"] / (ms_per_step * 1e-3) / 1e9
-        if not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.workload, dec, code, args.snr_db)     # rank 0's host cores, any N
-        if not use_dist and not args.no_legs and default_line:
-            # the other BASELINE configs, bounded (a few steps each), so that one driver run carries every config
-            del llr
-            main_run.release()
-            out["workloads"] = {}
-            for w in LEGS:
-                out["workloads"][w] = measure_leg(w, device, args.snr_db, max(args.leg_steps, 1), reps, copy_gbs,
-                                                  not args.no_cpu_baseline, torch)
+        if args.full:
+            reps = max(args.sweep_reps, 1)
+            copy_gbs = copy_ceiling(device, torch)
+            out["measured_ceilings"] = {"copy_GBps": copy_gbs, "fill_GBps": fill_ceiling(device, torch),
+                                        "note": "1 GiB device copy (read + write bytes) and 1 GiB device fill (write only), best of 6"}
+            run = lambda: eng.decode(llr, early_stop=early, want_bits=True, want_posterior=want_post)
+            if args.workload == "rcq_layered":
+                out["roofline"] = layered_roofline(eng, g, T, B, event_ms(run, max(reps // 4, 2), torch))
+            elif eng.info()["engine"] == "resident":
+                # dominant kernel = ldpc::resident_decode (the whole decode is this one launch), timed with HIP events
+                ms = event_ms(run, reps, torch)
+                out["roofline"] = resident_roofline(eng, args.workload, g, T, B, ms, copy_gbs)
+                if not args.no_stream_leg:
+                    # the HBM-bound engine (used for codes that do not fit LDS), same workload: the north_star's CN->VN sweep
+                    os.environ["LDPC_ENGINE_MODE"] = "stream"
+                    try:
+                        eng_s, dec_s, _ = build_decoder(args.workload, device)
+                    finally:
+                        os.environ.pop("LDPC_ENGINE_MODE", None)
+                    run_s = lambda: eng_s.decode(llr, early_stop=early, want_bits=True, want_posterior=want_post)
+                    run_s()
+                    ms_s = event_ms(run_s, 3, torch)
+                    out["stream_engine"] = {"ms_per_step": ms_s, "value": B / (ms_s * 1e-3), "engine": eng_s.info(),
+                                            "roofline": stream_roofline(eng_s, args.workload, g, T, B, llr, reps, copy_gbs, torch)}
+                    del eng_s, dec_s
+            else:
+                out["roofline"] = stream_roofline(eng, args.workload, g, T, B, llr, reps, copy_gbs, torch)
+            if not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.workload, dec, code, args.snr_db)     # rank 0's host cores, any N
+            if not use_dist and not args.no_legs and default_line:
+                # the other BASELINE configs, bounded (a few steps each), so that one driver run carries every config
+                del llr
+                main_run.release()
+                out["workloads"] = {}
+                for w in LEGS:
+                    out["workloads"][w] = measure_leg(w, device, args.snr_db, max(args.leg_steps, 1), reps, copy_gbs,
+                                                      not args.no_cpu_baseline, torch)
         sys.stdout.flush()
         os.dup2(result_fd, 1)
         print(json.dumps(out), flush=True)

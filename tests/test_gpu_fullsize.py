@@ -328,11 +328,24 @@ def run_bench(extra, env_extra=None, timeout=900):
 
 
 @pytest.mark.parametrize("engine_mode", ["auto"], indirect=True)
-def test_bench_contract_line(gpu_device):
-    """bench.py prints ONE JSON line with the driver's keys plus the roofline and cpu_baseline objects"""
-    d = run_bench(["--steps", "2", "--warmup", "1", "--batch", "4096", "--sweep-reps", "2"])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "stream_engine"):
+def test_bench_contract_line(gpu_device, tmp_path):
+    """bench.py prints ONE JSON line with the driver's keys; a plain run carries nothing measured beside the headline,
+    --full adds the roofline and cpu_baseline objects and leaves what the timed steps return unchanged"""
+    import numpy as np
+    head = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "config")
+    extras = ("roofline", "cpu_baseline", "stream_engine", "measured_ceilings", "workloads", "sharded_workloads")
+    p = run_bench(["--steps", "2", "--warmup", "1", "--batch", "4096", "--dump-outputs", str(tmp_path / "plain")])
+    for k in head:
+        assert k in p, k
+    assert not any(k in p for k in extras), sorted(p)
+    assert p["n_gpus"] == 1 and p["steps"] == 2 and p["unit"] == "codewords/s" and p["higher_is_better"] is True
+    d = run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "4096", "--sweep-reps", "2",
+                   "--dump-outputs", str(tmp_path / "full")])
+    assert p["dump_outputs"]["files"] == d["dump_outputs"]["files"]
+    for f in p["dump_outputs"]["files"]:
+        np.testing.assert_array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f), err_msg=f)
+    for k in head + ("roofline", "cpu_baseline", "stream_engine"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "codewords/s"
     assert d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None and "workload" in d["config"]
@@ -353,8 +366,8 @@ def test_bench_contract_line(gpu_device):
 
 @pytest.mark.parametrize("engine_mode", ["auto"], indirect=True)
 def test_bench_default_run_carries_every_baseline_config(gpu_device):
-    """the default invocation (what the driver runs) reports configs 3, 4, 5 and the float64 Basic decoder as legs"""
-    d = run_bench(["--steps", "3", "--warmup", "1", "--leg-steps", "2", "--sweep-reps", "4", "--no-cpu-baseline"])
+    """the default invocation with --full reports configs 3, 4, 5 and the float64 Basic decoder as legs"""
+    d = run_bench(["--full", "--steps", "3", "--warmup", "1", "--leg-steps", "2", "--sweep-reps", "4", "--no-cpu-baseline"])
     assert d["config"]["batch_per_gpu"] == 65536 and "workloads" in d
     for w in ("neural2d", "rcq", "wrcq_dvbs2", "basic_f64", "rcq_layered"):
         leg = d["workloads"][w]
@@ -372,7 +385,7 @@ def test_bench_bare_multi_rank_launch(gpu_device):
     gloo rehearsal on this one GPU and a 1-rank RCCL run each give exactly one JSON line that carries everything the
     north_star asks of a multi-GPU run: the rank count the process group reports, every rank's device, the all-gather
     timed alone, the content check of the gathered array, config 5 sharded weak and strong, and the CPU baseline."""
-    d = run_bench(["--gpus", "2", "--batch", "8192", "--steps", "2", "--warmup", "1", "--no-stream-leg", "--no-legs"],
+    d = run_bench(["--full", "--gpus", "2", "--batch", "8192", "--steps", "2", "--warmup", "1", "--no-stream-leg", "--no-legs"],
                   {"LDPC_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 16384 and d["scaling"] == "weak"
     assert "all_gather" in d["config"]["collective"]
@@ -386,8 +399,8 @@ def test_bench_bare_multi_rank_launch(gpu_device):
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] == "port"     # rank 0's host cores, also at N > 1
     assert d["roofline"]["bound"] == "lds"
     # the DEFAULT multi-rank line (no --batch / --workload): config 2 weak + config 5 sharded weak and strong in the same line
-    d = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--leg-steps", "1", "--no-stream-leg", "--no-cpu-baseline",
-                   "--config5-total", "4096", "--sweep-reps", "2"], {"LDPC_BENCH_BACKEND": "gloo"}, timeout=1500)
+    d = run_bench(["--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--leg-steps", "1", "--no-stream-leg",
+                   "--no-cpu-baseline", "--config5-total", "4096", "--sweep-reps", "2"], {"LDPC_BENCH_BACKEND": "gloo"}, timeout=1500)
     assert d["n_gpus"] == 2 and d["config"]["batch_per_gpu"] == 65536
     sw = d["sharded_workloads"]
     weak, strong = sw["wrcq_dvbs2_weak"], sw["wrcq_dvbs2_strong"]
@@ -402,12 +415,12 @@ def test_bench_bare_multi_rank_launch(gpu_device):
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["batch_per_gpu"] == 1024
     assert d["distributed"]["gather_check"]["ok"]
     # one rank over RCCL (backend "nccl"): the collective really is RCCL's, overlapped and un-overlapped
-    d = run_bench(["--gpus", "1", "--force-dist", "--batch", "8192", "--steps", "2", "--warmup", "1", "--no-stream-leg",
+    d = run_bench(["--full", "--gpus", "1", "--force-dist", "--batch", "8192", "--steps", "2", "--warmup", "1", "--no-stream-leg",
                    "--no-cpu-baseline", "--no-legs"])
     assert d["n_gpus"] == 1 and "nccl" in d["config"]["collective"] and d["distributed"]["backend"] == "nccl"
     assert d["distributed"]["world_size"] == 1 and d["distributed"]["gather_check"]["ok"]
     assert d["distributed"]["allgather"]["ms"] > 0 and d["config"]["overlap"] is True
-    d = run_bench(["--gpus", "1", "--force-dist", "--no-overlap", "--steps", "1", "--warmup", "1", "--leg-steps", "1",
+    d = run_bench(["--full", "--gpus", "1", "--force-dist", "--no-overlap", "--steps", "1", "--warmup", "1", "--leg-steps", "1",
                    "--no-stream-leg", "--no-cpu-baseline", "--config5-total", "2048", "--sweep-reps", "2"])
     assert d["config"]["overlap"] is False and d["sharded_workloads"]["wrcq_dvbs2_strong"]["batch_per_gpu"] == 2048
     assert d["sharded_workloads"]["wrcq_dvbs2_weak"]["gather_check"]["ok"]
