@@ -83,6 +83,25 @@ struct ldpc_graph {
     GraphDev dev() const { return GraphDev{n, m, E, check_ptr, var_idx, var_ptr, csc_edge}; }
 };
 
+// Compact plan: variables on a (round, wave, lane) grid.
+// The compact kernel (kResCptThreads = 512 lanes, kResRegVars = 4 rounds) runs the variable at position
+// q = r*512 + w*64 + lane in round r of wave w.  Every variable phase ends at a workgroup barrier, so the phase costs
+// what its busiest wave costs; a cell (w, r) whose 64 lanes share one degree runs one body behind a scalar branch
+// (ResidentPlan::vcell), a mixed cell runs the body of every degree it holds.  Cost of one body, in VALU-equivalents,
+// from the instruction model (not from ISA counts): dv leave-one-out sums of dv-1 terms each, formed separately in the
+// reference's association order (<= dv*(dv-1) adds), 2*dv LDS operations and ~4 for the offset unpacking.
+constexpr int kCptWaves = kResCptThreads / 64;
+constexpr int kCptCells = kCptWaves * kResRegVars;
+constexpr int kCptMaxDv = 8;
+inline int cpt_body_cost(int dv) { return dv * (dv - 1) + 2 * dv + 4; }
+
+struct CptLayout {
+    std::vector<int> var_at;       // [n_pos] variable at grid position q, -1 = empty
+    unsigned cell[kCptWaves] = {}; // ResidentPlan::vcell
+    int worst = 0, total = 0;      // largest and summed per-wave cost of one variable phase (cpt_body_cost model)
+    int mixed = 0;                 // cells of kind kCellMixed
+};
+
 struct ldpc_decoder {
     const ldpc_graph *g = nullptr;
     int dtype = LDPC_F32, form = LDPC_C2V_NMS, T = 0;
@@ -108,6 +127,7 @@ struct ldpc_decoder {
     bool resc_ok = false;
     size_t resc_lds = 0;
     ResidentPlan resc{};
+    CptLayout resc_layout;         // its variable grid and cell table (host copy, ldpc_debug_compact_layout)
     std::vector<void *> res_bufs;  // device allocations owned by the plan
     // inverse slot maps of the gradient path (reduce_table_grads): items of slot s = inv_items[inv_ptr[s] .. inv_ptr[s+1])
     int *beta_inv_ptr = nullptr, *beta_inv_items = nullptr;
@@ -901,10 +921,251 @@ void optimise_lane_order(std::vector<int> &order, const std::vector<std::vector<
     }
 }
 
+// ---- compact plan: variables on a (round, wave, lane) grid (CptLayout) --------------------------
+// cell bytes and model costs of a grid (any placement: the balanced one or the degree-sorted fallback)
+void cpt_cells(const std::vector<int> &dv, CptLayout &L)
+{
+    const int n_pos = (int)L.var_at.size();
+    L.worst = L.total = L.mixed = 0;
+    for (int w = 0; w < kCptWaves; ++w) {
+        L.cell[w] = 0;
+        int wave = 0;
+        for (int r = 0; r < kResRegVars; ++r) {
+            bool has[kCptMaxDv + 1] = {};
+            int used = 0, kinds = 0, deg = 0, cost = 0;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int q = r * kResCptThreads + w * 64 + lane;
+                const int j = q < n_pos ? L.var_at[q] : -1;
+                if (j < 0) continue;
+                ++used;
+                if (!has[dv[j]]) { has[dv[j]] = true; ++kinds; deg = dv[j]; cost += cpt_body_cost(dv[j]); }
+            }
+            unsigned byte = kCellEmpty;
+            if (used) byte = (kinds == 1 && deg > 0) ? (unsigned)deg | (used < 64 ? kCellHoles : 0u) : kCellMixed;
+            L.mixed += byte == kCellMixed ? 1 : 0;
+            L.cell[w] |= byte << (8 * r);
+            wave += cost;
+        }
+        L.worst = std::max(L.worst, wave);
+        L.total += wave;
+    }
+}
+
+// Balanced placement.  Cells are formed per degree (full cells of 64, one partial cell per degree); partial cells are
+// merged -- the pair whose merged cell costs least -- or, when no pair fits 64 lanes, the smallest one is poured into
+// the others' free lanes, until there are at most kCptCells cells and at most kCptWaves of them hold a degree > 4
+// (those need the upper offset half, which only round 0 carries).  Degree > 4 cells go to round 0 of distinct waves,
+// the others largest first to the cheapest wave with a free round; pairwise moves then lower the largest wave cost,
+// and the waves are ordered so that w and w + 4 (assumed to share a SIMD) carry equal totals.  Deterministic.
+bool cpt_assign(const std::vector<int> &dv, CptLayout &L)
+{
+    struct Cell { int cnt[kCptMaxDv + 1] = {}; int size = 0; };
+    auto hi = [](const Cell &c) { for (int d = 5; d <= kCptMaxDv; ++d) if (c.cnt[d]) return true; return false; };
+    auto cost = [](const Cell &c) { int k = 0; for (int d = 0; d <= kCptMaxDv; ++d) if (c.cnt[d]) k += cpt_body_cost(d); return k; };
+    const int n = (int)dv.size();
+    int cnt[kCptMaxDv + 1] = {};
+    for (int j = 0; j < n; ++j) {
+        if (dv[j] < 0 || dv[j] > kCptMaxDv) return false;
+        ++cnt[dv[j]];
+    }
+    std::vector<Cell> cells;
+    std::vector<char> partial;
+    for (int d = kCptMaxDv; d >= 0; --d) {
+        for (int k = cnt[d]; k > 0; k -= 64) {
+            Cell c; c.cnt[d] = c.size = std::min(k, 64);
+            cells.push_back(c);
+            partial.push_back(c.size < 64);
+        }
+    }
+    for (;;) {
+        int nhi = 0;
+        for (const Cell &c : cells) nhi += hi(c) ? 1 : 0;
+        const bool need_hi = nhi > kCptWaves;
+        if (!need_hi && (int)cells.size() <= kCptCells) break;
+        int a = -1, b = -1, best = INT_MAX;
+        for (int i = 0; i < (int)cells.size(); ++i)
+            for (int k = i + 1; k < (int)cells.size(); ++k) {
+                if (cells[i].size + cells[k].size > 64 || (need_hi && !(hi(cells[i]) && hi(cells[k])))) continue;
+                Cell m = cells[i];
+                for (int d = 0; d <= kCptMaxDv; ++d) m.cnt[d] += cells[k].cnt[d];
+                if (cost(m) < best) { best = cost(m); a = i; b = k; }
+            }
+        if (a < 0) {                                     // pour the smallest suitable cell into the others' free lanes
+            int src = -1;
+            for (int pass = 0; pass < 2 && src < 0; ++pass)
+                for (int i = 0; i < (int)cells.size(); ++i) {
+                    if (cells[i].size == 64 || hi(cells[i]) != (need_hi || pass == 1)) continue;
+                    if (src < 0 || cells[i].size < cells[src].size) src = i;
+                }
+            if (src < 0) return false;
+            const bool src_hi = hi(cells[src]);
+            for (int d = kCptMaxDv; d >= 0; --d)
+                while (cells[src].cnt[d] > 0) {
+                    int t = -1;
+                    for (int i = 0; i < (int)cells.size(); ++i) {
+                        if (i == src || cells[i].size == 64 || (src_hi && !hi(cells[i]))) continue;
+                        if (t < 0 || cells[i].size < cells[t].size) t = i;
+                    }
+                    if (t < 0) return false;
+                    const int k = std::min(cells[src].cnt[d], 64 - cells[t].size);
+                    cells[t].cnt[d] += k; cells[t].size += k;
+                    cells[src].cnt[d] -= k; cells[src].size -= k;
+                }
+            cells.erase(cells.begin() + src);
+            continue;
+        }
+        for (int d = 0; d <= kCptMaxDv; ++d) cells[a].cnt[d] += cells[b].cnt[d];
+        cells[a].size += cells[b].size;
+        cells.erase(cells.begin() + b);
+    }
+
+    // placement: slot[w][r] = cell index or -1
+    int slot[kCptWaves][kResRegVars];
+    for (auto &w : slot) for (int &x : w) x = -1;
+    int load[kCptWaves] = {};
+    std::vector<int> order((size_t)cells.size());
+    for (int i = 0; i < (int)cells.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+        if (hi(cells[x]) != hi(cells[y])) return hi(cells[x]);
+        return cost(cells[x]) > cost(cells[y]);
+    });
+    int next_hi = 0;
+    for (int i : order) {
+        if (hi(cells[i])) { slot[next_hi][0] = i; load[next_hi++] += cost(cells[i]); continue; }
+        int bw = -1;
+        for (int w = 0; w < kCptWaves; ++w) {
+            bool free_ = false;
+            for (int r = 0; r < kResRegVars; ++r) free_ = free_ || slot[w][r] < 0;
+            if (free_ && (bw < 0 || load[w] < load[bw])) bw = w;
+        }
+        if (bw < 0) return false;
+        for (int r = 0; r < kResRegVars; ++r)
+            if (slot[bw][r] < 0) { slot[bw][r] = i; break; }
+        load[bw] += cost(cells[i]);
+    }
+    // pairwise exchanges (a cell with an empty slot included): largest wave cost first, then the sum of squares
+    auto objective = [&](long long &mx, long long &sq) {
+        mx = 0; sq = 0;
+        for (int w = 0; w < kCptWaves; ++w) { mx = std::max<long long>(mx, load[w]); sq += (long long)load[w] * load[w]; }
+    };
+    for (bool improved = true; improved;) {
+        improved = false;
+        for (int x = 0; x < kCptCells; ++x)
+            for (int y = x + 1; y < kCptCells; ++y) {
+                const int wx = x / kResRegVars, rx = x % kResRegVars, wy = y / kResRegVars, ry = y % kResRegVars;
+                const int cx = slot[wx][rx], cy = slot[wy][ry];
+                if (wx == wy || (cx < 0 && cy < 0)) continue;
+                if ((cx >= 0 && hi(cells[cx]) && ry != 0) || (cy >= 0 && hi(cells[cy]) && rx != 0)) continue;
+                long long m0, s0, m1, s1;
+                objective(m0, s0);
+                const int kx = cx >= 0 ? cost(cells[cx]) : 0, ky = cy >= 0 ? cost(cells[cy]) : 0;
+                load[wx] += ky - kx; load[wy] += kx - ky;
+                objective(m1, s1);
+                if (m1 < m0 || (m1 == m0 && s1 < s0)) { std::swap(slot[wx][rx], slot[wy][ry]); improved = true; }
+                else { load[wx] -= ky - kx; load[wy] -= kx - ky; }
+            }
+    }
+    // waves w and w + 4: the heaviest with the lightest, and so on
+    int by_load[kCptWaves];
+    for (int w = 0; w < kCptWaves; ++w) by_load[w] = w;
+    std::stable_sort(by_load, by_load + kCptWaves, [&](int x, int y) { return load[x] > load[y]; });
+    int wave_of[kCptWaves];                              // new wave index -> old one
+    for (int k = 0; k < kCptWaves / 2; ++k) {
+        wave_of[k] = by_load[k];
+        wave_of[k + kCptWaves / 2] = by_load[kCptWaves - 1 - k];
+    }
+    // inside a wave: the degree > 4 cell in round 0, then by falling cost, empty rounds last
+    std::vector<std::vector<int>> of_deg(kCptMaxDv + 1);
+    for (int j = 0; j < n; ++j) of_deg[dv[j]].push_back(j);
+    size_t taken[kCptMaxDv + 1] = {};
+    L.var_at.assign((size_t)kCptCells * 64, -1);
+    for (int w = 0; w < kCptWaves; ++w) {
+        int cs[kResRegVars];
+        for (int r = 0; r < kResRegVars; ++r) cs[r] = slot[wave_of[w]][r];
+        std::stable_sort(cs, cs + kResRegVars, [&](int x, int y) {
+            if (x < 0 || y < 0) return x >= 0 && y < 0;
+            if (hi(cells[x]) != hi(cells[y])) return hi(cells[x]);
+            return cost(cells[x]) > cost(cells[y]);
+        });
+        for (int r = 0; r < kResRegVars; ++r) {
+            if (cs[r] < 0) continue;
+            int lane = 0;
+            for (int d = kCptMaxDv; d >= 0; --d)
+                for (int k = 0; k < cells[cs[r]].cnt[d]; ++k)
+                    L.var_at[(size_t)r * kResCptThreads + w * 64 + lane++] = of_deg[d][taken[d]++];
+        }
+    }
+    int n_pos = 0;
+    for (int q = 0; q < (int)L.var_at.size(); ++q)
+        if (L.var_at[q] >= 0) n_pos = q + 1;
+    L.var_at.resize((size_t)n_pos);
+    cpt_cells(dv, L);
+    return true;
+}
+
+// optimise_lane_order for a grid: variables change places only with variables of the same degree (the cells keep their
+// degrees); `vs[n]` is the empty entry of the holes
+void cpt_lane_order(std::vector<int> &var_at, const std::vector<std::vector<int>> &vs, int G)
+{
+    const int n = (int)vs.size() - 1;
+    std::vector<int> order(var_at.size());
+    for (size_t q = 0; q < var_at.size(); ++q) order[q] = var_at[q] >= 0 ? var_at[q] : n;
+    LaneCost lc{vs, order, 32, 32, G == 2 ? 16 : 32, G == 2 ? 16 : 32};
+    std::vector<std::vector<int>> classes(kCptMaxDv + 1);
+    for (int q = 0; q < (int)order.size(); ++q) {
+        const int d = (int)vs[order[q]].size();
+        if (order[q] != n && d > 0 && d <= kCptMaxDv) classes[d].push_back(q);
+    }
+    classes.erase(std::remove_if(classes.begin(), classes.end(), [](const std::vector<int> &c) { return c.size() < 2; }),
+                  classes.end());
+    if (classes.empty()) return;
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+    const long trials = std::min<long>(400000, 150L * n);
+    for (long it = 0; it < trials; ++it) {
+        const auto &c = classes[next() % classes.size()];
+        const int x = c[next() % c.size()], y = c[next() % c.size()];
+        if (x / lc.wg == y / lc.wg) continue;
+        const int before = lc.around(x, y);
+        std::swap(order[x], order[y]);
+        if (lc.around(x, y) > before) std::swap(order[x], order[y]);
+    }
+    for (size_t q = 0; q < var_at.size(); ++q) var_at[q] = order[q] == n ? -1 : order[q];
+}
+
 // a lane position of the check phase: (sub-)check `check`, its edges e0 .. e0+dc-1, lane-group size gs
 struct ResVCheck { int check, e0, dc, gs; };
 int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
-                    long long S, int G, ResidentPlan &pl);
+                    long long S, int G, ResidentPlan &pl, const CptLayout *cl = nullptr);
+void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L);
+bool cpt_geometry(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long &Sc);
+
+// Lane positions of the check phase are VIRTUAL checks.  A check of degree <= kResSubDegreeCap is one of them; a wider
+// one is split into 2^k sub-checks of contiguous edges (balanced, at most kResSubDegree each) that sit on ADJACENT lanes
+// and are combined by wavefront exchanges (ldpc_resident.hip: group_combine).  Groups come first, by descending size --
+// every group then starts at a multiple of its size, so it never straddles a wave -- then the whole checks.
+bool resident_checks(const ldpc_graph *g, std::vector<ResVCheck> &vc)
+{
+    auto dc_real = [&](int i) { return g->h_check_ptr[i + 1] - g->h_check_ptr[i]; };
+    std::vector<int> wide_ids, plain_ids;
+    for (int i = 0; i < g->m; ++i) (dc_real(i) > kResSubDegreeCap ? wide_ids : plain_ids).push_back(i);
+    auto group_of = [&](int i) { int k = 1; while (k * kResSubDegree < dc_real(i)) k <<= 1; return k; };
+    for (int i : wide_ids)
+        if (group_of(i) > 64) return false;                 // wider than a wavefront of sub-checks
+    std::stable_sort(wide_ids.begin(), wide_ids.end(), [&](int a, int b) { return group_of(a) > group_of(b); });
+    for (int i : wide_ids) {
+        const int k = group_of(i), dc = dc_real(i), base = dc / k, rem = dc % k;
+        int e = g->h_check_ptr[i];
+        for (int j = 0; j < k; ++j) {
+            const int len = base + (j < rem ? 1 : 0);
+            vc.push_back({i, e, len, k});
+            e += len;
+        }
+    }
+    std::stable_sort(plain_ids.begin(), plain_ids.end(), [&](int a, int b) { return dc_real(a) > dc_real(b); });
+    for (int i : plain_ids) vc.push_back({i, g->h_check_ptr[i], dc_real(i), 1});
+    return true;
+}
 
 // Sort checks and variables by degree (stable, descending), lay the edges out ELL-transposed.
 int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
@@ -919,33 +1180,9 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     const int n = g->n;
     if (n > 65535 || d->n_beta > 65535 || d->n_alpha >= (1 << 24) || d->n_oms_alpha > 65535) return LDPC_OK;
 
-    // Lane positions of the check phase are VIRTUAL checks.  A check of degree <= kResSubDegreeCap is one of them; a wider
-    // one is split into 2^k sub-checks of contiguous edges (balanced, at most kResSubDegree each) that sit on ADJACENT lanes
-    // and are combined by wavefront exchanges (ldpc_resident.hip: group_combine).  Groups come first, by descending size --
-    // every group then starts at a multiple of its size, so it never straddles a wave -- then the whole checks.
     std::vector<ResVCheck> vc;
-    {
-        auto dc_real = [&](int i) { return g->h_check_ptr[i + 1] - g->h_check_ptr[i]; };
-        std::vector<int> wide_ids, plain_ids;
-        for (int i = 0; i < g->m; ++i) (dc_real(i) > kResSubDegreeCap ? wide_ids : plain_ids).push_back(i);
-        auto group_of = [&](int i) { int k = 1; while (k * kResSubDegree < dc_real(i)) k <<= 1; return k; };
-        for (int i : wide_ids)
-            if (group_of(i) > 64) return LDPC_OK;                 // wider than a wavefront of sub-checks
-        std::stable_sort(wide_ids.begin(), wide_ids.end(), [&](int a, int b) { return group_of(a) > group_of(b); });
-        for (int i : wide_ids) {
-            const int k = group_of(i), dc = dc_real(i), base = dc / k, rem = dc % k;
-            int e = g->h_check_ptr[i];
-            for (int j = 0; j < k; ++j) {
-                const int len = base + (j < rem ? 1 : 0);
-                vc.push_back({i, e, len, k});
-                e += len;
-            }
-        }
-        std::stable_sort(plain_ids.begin(), plain_ids.end(), [&](int a, int b) { return dc_real(a) > dc_real(b); });
-        for (int i : plain_ids) vc.push_back({i, g->h_check_ptr[i], dc_real(i), 1});
-    }
+    if (!resident_checks(g, vc)) return LDPC_OK;
     const int m = (int)vc.size();
-    const bool any_split = m != g->m;
     int max_sub = 0;
     for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
     if (m > 65535 || max_sub > 255) return LDPC_OK;
@@ -984,27 +1221,62 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     // alpha table in LDS.  Taken when it gives kResCptBlocks workgroups of 512 threads per CU and the variable state fits
     // the registers (resident_reg_state)
     d->resc_ok = false;
-    if (!f64 && G == 2 && NT == kResCptThreads && !any_split && m <= kResCptStride && n <= kResRegVars * kResCptThreads) {
-        int n_top = 0;
-        while (n_top < m && vc[n_top].dc == max_sub) ++n_top;
-        const long long Sc = (long long)(max_sub - 1) * kResCptStride + n_top;
-        const size_t lds_c = res_cpt_lds_total((int)Sc, 2);
-        int n_hi = 0;
-        for (int j = 0; j < n; ++j) n_hi += (g->h_var_ptr[j + 1] - g->h_var_ptr[j]) > 4 ? 1 : 0;
-        if (Sc * 2 * 4 <= 65535 && (long long)n * 2 * 4 <= Sc * 2 * 4 && n_hi <= kResCptThreads &&
-            kResCptBlocks * lds_c <= kLdsBytes) {
-            if (int rc = resident_layout(d, desc, vc, kResCptStride, Sc, 2, d->resc)) return rc;
-            d->resc_lds = lds_c;
-            d->resc_ok = true;
-        }
+    long long Sc = 0;
+    if (!f64 && G == 2 && NT == kResCptThreads && cpt_geometry(g, vc, Sc)) {
+        cpt_layout(g, vc, Sc, d->resc_layout);
+        if (int rc = resident_layout(d, desc, vc, kResCptStride, Sc, 2, d->resc, &d->resc_layout)) return rc;
+        d->resc_lds = res_cpt_lds_total((int)Sc, 2);
+        d->resc_ok = true;
     }
     return LDPC_OK;
 }
 
+// the compact geometry's slot count Sc when the graph qualifies: no split checks, m <= kResCptStride, the variables within
+// kResRegVars rounds of 512 lanes with every degree > 4 one in round 0, 16-bit slot offsets, the LLR rows stageable in the
+// slot area (cpt_layout keeps its positions below Sc) and kResCptBlocks workgroups per CU
+bool cpt_geometry(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long &Sc)
+{
+    const int n = g->n, m = (int)vc.size();
+    int max_sub = 0;
+    for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
+    if (m != g->m || m > kResCptStride || n > kResRegVars * kResCptThreads || g->max_dv > kCptMaxDv || max_sub < 1)
+        return false;
+    int n_top = 0;
+    while (n_top < m && vc[n_top].dc == max_sub) ++n_top;
+    Sc = (long long)(max_sub - 1) * kResCptStride + n_top;
+    int n_hi = 0;
+    for (int j = 0; j < n; ++j) n_hi += (g->h_var_ptr[j + 1] - g->h_var_ptr[j]) > 4 ? 1 : 0;
+    return Sc * 2 * 4 <= 65535 && (long long)n <= Sc && n_hi <= kResCptThreads &&
+           kResCptBlocks * res_cpt_lds_total((int)Sc, 2) <= kLdsBytes;
+}
+
+// the compact plan's grid for a graph and its check order: the balanced placement, else (a staging area too small for its
+// positions) the degree-sorted order of the general plan; variables then ordered inside their degrees for LDS banking
+void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L)
+{
+    const int n = g->n, m = (int)vc.size();
+    std::vector<int> dv(n);
+    for (int j = 0; j < n; ++j) dv[j] = g->h_var_ptr[j + 1] - g->h_var_ptr[j];
+    std::vector<int> slot_of_edge(g->E);
+    for (int p = 0; p < m; ++p)
+        for (int t = 0; t < vc[p].dc; ++t) slot_of_edge[vc[p].e0 + t] = t * kResCptStride + p;
+    std::vector<std::vector<int>> vs(n + 1);
+    for (int j = 0; j < n; ++j)
+        for (int k = 0; k < dv[j]; ++k) vs[j].push_back(slot_of_edge[g->h_csc[g->h_var_ptr[j] + k]]);
+    if (!cpt_assign(dv, L) || (long long)L.var_at.size() > S) {
+        L.var_at.resize(n);
+        for (int j = 0; j < n; ++j) L.var_at[j] = j;
+        std::stable_sort(L.var_at.begin(), L.var_at.end(), [&](int a, int b) { return dv[a] > dv[b]; });
+    }
+    cpt_lane_order(L.var_at, vs, 2);
+    cpt_cells(dv, L);
+}
+
 // slot layout of one geometry: row stride `mstride`, S slots, G codewords per slot; variables ordered inside their degree
-// classes for LDS banking; the plan arrays go to the device (owned by d->res_bufs)
+// classes for LDS banking (general plan) or at the positions of the compact grid `cl`; the plan arrays go to the device
+// (owned by d->res_bufs)
 int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
-                    long long S, int G, ResidentPlan &pl)
+                    long long S, int G, ResidentPlan &pl, const CptLayout *cl)
 {
     const ldpc_graph *g = d->g;
     const int n = g->n, m = (int)vc.size();
@@ -1018,18 +1290,24 @@ int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::v
     std::vector<int> slot_of_edge(g->E);
     for (int p = 0; p < m; ++p)
         for (int t = 0; t < vc[p].dc; ++t) slot_of_edge[vc[p].e0 + t] = t * mstride + p;
-    {   // slots are fixed by the check order alone; choose the variable order inside each degree class
+    if (cl) {
+        perm_v = cl->var_at;                                     // position -> variable, -1 = empty
+    } else {   // slots are fixed by the check order alone; choose the variable order inside each degree class
         std::vector<std::vector<int>> vs(n);
         for (int j = 0; j < n; ++j)
             for (int k = 0; k < dv_of(j); ++k) vs[j].push_back(slot_of_edge[g->h_csc[g->h_var_ptr[j] + k]]);
         optimise_lane_order(perm_v, vs, G);
     }
-    for (int q = 0; q < n; ++q) pos_v[perm_v[q]] = q;
+    const int n_pos = (int)perm_v.size();
+    // the compact kernels load the plan entries of whole cells: padded to a multiple of 64 positions
+    const int n_ent = cl ? (n_pos + 63) / 64 * 64 : n;
+    for (int q = 0; q < n_pos; ++q)
+        if (perm_v[q] >= 0) pos_v[perm_v[q]] = q;
 
     std::vector<uint8_t> dc_s(m), gsz(m);
     std::vector<uint16_t> cvar((size_t)S, 0), bslot((size_t)S, 0), oaslot((size_t)S, 0), bslot_c(m, 0), inv(n);
-    std::vector<uint32_t> vmeta(n);
-    std::vector<uint2> vslot_lo(n), vslot_hi(std::max(n, 1));
+    std::vector<uint32_t> vmeta(n_ent, 0u);
+    std::vector<uint2> vslot_lo(n_ent, make_uint2(0, kResHole)), vslot_hi(std::max(n_ent, 1), make_uint2(0, 0));
     int n_hi = 0;
     std::vector<uint32_t> edge_of_slot((size_t)S, 0xffffffffu);
     bool per_check = true;
@@ -1048,7 +1326,8 @@ int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::v
         }
         bslot_c[p] = v.dc ? (uint16_t)desc->beta_slot[first] : 0;
     }
-    for (int q = 0; q < n; ++q) {
+    for (int q = 0; q < n_pos; ++q) {
+        if (perm_v[q] < 0) continue;                                                   // empty: vmeta 0, kResHole
         const int j = perm_v[q], s0 = g->h_var_ptr[j], dv = dv_of(j);
         vmeta[q] = (uint32_t)dv | ((uint32_t)desc->alpha_slot[j] << 8);
         inv[j] = (uint16_t)q;
@@ -1056,12 +1335,14 @@ int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::v
         for (int k = 0; k < dv; ++k) off[k] = (uint32_t)slot_of_edge[g->h_csc[s0 + k]] * G * 4;
         vslot_lo[q] = make_uint2(off[0] | (off[1] << 16), off[2] | (off[3] << 16));      // offsets <= 65535 (resident_fits)
         vslot_hi[q] = make_uint2(off[4] | (off[5] << 16), off[6] | (off[7] << 16));
-        if (dv > 4) n_hi = q + 1;                                                     // degree-sorted: they come first
+        if (dv > 4) n_hi = q + 1;            // general plan: they come first; compact: all in round 0 (q < 512)
     }
     pl = ResidentPlan{};
     pl.n = n; pl.m = m; pl.S = (int)S; pl.max_dc = max_sub; pl.max_dv = g->max_dv; pl.mstride = mstride; pl.E = g->E;
     pl.any_split = any_split ? 1 : 0;
     pl.n_hi = n_hi;
+    pl.n_pos = n_pos;
+    if (cl) std::copy(cl->cell, cl->cell + kCptWaves, pl.vcell);
     pl.par_words = is_pow2(mstride) ? m : 0;
     pl.par_shift = G == 2 ? 3 : 2;                     // slot byte offset = slot * G * 4
     int rc = plan_upload(d, &pl.dc_s, dc_s);
@@ -1399,11 +1680,9 @@ const char *ldpc_source_hash(void) { return LDPC_STR(LDPC_SRC_HASH); }
         return fail(LDPC_ERR_HIP, "internal error");                                           \
     }
 
-static int graph_create_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
-                             const int32_t *var_idx)
+// validated CSR -> the host copies of a graph (CSC by scanning CSR edges in order: every variable's checks ascend)
+static int graph_host_build(ldpc_graph *g, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr, const int32_t *var_idx)
 {
-    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
-    *out = nullptr;
     if (n < 0 || m < 0 || E < 0 || !check_ptr || (E > 0 && !var_idx)) return fail(LDPC_ERR_ARG, "bad graph sizes");
     if (check_ptr[0] != 0 || check_ptr[m] != E) return fail(LDPC_ERR_ARG, "check_ptr must span [0, E]");
     std::vector<int> dv(n, 0);
@@ -1425,13 +1704,10 @@ static int graph_create_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, 
         var_ptr[j + 1] = var_ptr[j] + dv[j];
         max_dv = std::max(max_dv, dv[j]);
     }
-    // scanning CSR edges in order visits the checks of every variable in ascending order
     for (int e = 0; e < E; ++e) {
         const int j = var_idx[e];
         csc[var_ptr[j] + fill[j]++] = e;
     }
-    ldpc_graph *g = new (std::nothrow) ldpc_graph();
-    if (!g) return fail(LDPC_ERR_ARG, "out of host memory");
     g->n = n; g->m = m; g->E = E; g->max_dc = max_dc; g->max_dv = max_dv;
     g->h_check_ptr.assign(check_ptr, check_ptr + m + 1);
     g->h_var_idx.assign(var_idx, var_idx + E);
@@ -1440,6 +1716,21 @@ static int graph_create_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, 
     g->h_check_of_edge.resize(E);
     for (int i = 0; i < m; ++i)
         for (int e = check_ptr[i]; e < check_ptr[i + 1]; ++e) g->h_check_of_edge[e] = i;
+    return LDPC_OK;
+}
+
+static int graph_create_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                             const int32_t *var_idx)
+{
+    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    ldpc_graph *g = new (std::nothrow) ldpc_graph();
+    if (!g) return fail(LDPC_ERR_ARG, "out of host memory");
+    if (int rc = graph_host_build(g, n, m, E, check_ptr, var_idx)) {
+        delete g;
+        return rc;
+    }
+    const std::vector<int> &var_ptr = g->h_var_ptr, &csc = g->h_csc;
     if (hipGetDevice(&g->device) != hipSuccess) {
         delete g;
         return fail(LDPC_ERR_HIP, "no HIP device available");
@@ -1447,7 +1738,7 @@ static int graph_create_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, 
     int rc = upload(&g->check_ptr, check_ptr, (size_t)m + 1);
     if (!rc) rc = upload(&g->var_idx, var_idx, (size_t)E);
     if (!rc) rc = upload(&g->var_ptr, var_ptr.data(), (size_t)n + 1);
-    if (!rc) rc = upload(&g->csc_edge, csc.data(), (size_t)E);
+    if (!rc) rc = upload(&g->csc_edge, E > 0 ? csc.data() : nullptr, (size_t)E);
     std::vector<int> wide;
     for (int i = 0; i < m; ++i)
         if (check_ptr[i + 1] - check_ptr[i] > kWideCheck) wide.push_back(i);
@@ -2133,6 +2424,43 @@ int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t ma
     out8[2] = w.llrT - base; out8[3] = w.v2c - base; out8[4] = c2v_final - base; out8[5] = w.postT - base;
     out8[6] = (char *)w.bitsT - base; out8[7] = (char *)w.done - base;
     return LDPC_OK;
+}
+
+static int compact_layout_impl(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                               const int32_t *var_idx, int32_t *pos_of_var, uint8_t *cells, int32_t *stats)
+{
+    CptLayout own;
+    const CptLayout *L = &own;
+    if (d) {
+        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
+        L = &d->resc_layout;
+        n = d->g->n;
+    } else {
+        ldpc_graph g;                                    // host copies only: no device is touched
+        if (int rc = graph_host_build(&g, n, m, E, check_ptr, var_idx)) return rc;
+        std::vector<ResVCheck> vc;
+        long long Sc = 0;
+        if (!resident_checks(&g, vc) || !cpt_geometry(&g, vc, Sc))
+            return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
+        cpt_layout(&g, vc, Sc, own);
+    }
+    if (pos_of_var) {
+        for (int j = 0; j < n; ++j) pos_of_var[j] = -1;
+        for (int q = 0; q < (int)L->var_at.size(); ++q)
+            if (L->var_at[q] >= 0) pos_of_var[L->var_at[q]] = q;
+    }
+    if (cells)
+        for (int c = 0; c < kCptCells; ++c) cells[c] = (uint8_t)(L->cell[c / kResRegVars] >> (8 * (c % kResRegVars)));
+    if (stats) {
+        stats[0] = (int32_t)L->var_at.size(); stats[1] = L->worst; stats[2] = L->total; stats[3] = L->mixed;
+    }
+    return LDPC_OK;
+}
+
+int ldpc_debug_compact_layout(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                              const int32_t *var_idx, int32_t *pos_of_var, uint8_t cells[32], int32_t stats[4])
+{
+    LDPC_NOTHROW(compact_layout_impl(d, n, m, E, check_ptr, var_idx, pos_of_var, cells, stats))
 }
 
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,

@@ -57,6 +57,8 @@ struct ResidentPlan {
                                   // the CU's 32 KiB L1 across iterations (with 32-bit offsets and the hi half read for every
                                   // variable it was 72 KB per workgroup and iteration from L2)
     const uint16_t *inv_perm_v;   // [n]          sorted position of original variable j
+    int n_pos;                    //              positions in use: n, or (compact plan) the highest occupied one + 1
+    unsigned vcell[8];            // compact plan: byte r of word w = the cell (wave w, round r) -- kCell* below
     int E;                        // edges of the graph
     const uint32_t *edge_of_slot; // [S]          CSR edge id held by a slot, 0xffffffff for padding slots (test hook
                                   //              ldpc_debug_resident_c2v: dumps the C2V state in CSR order)
@@ -623,13 +625,15 @@ __device__ __forceinline__ uint4 plan_unpack(const uint2 &p)
     return make_uint4(p.x & 0xffffu, p.x >> 16, p.y & 0xffffu, p.y >> 16);
 }
 
-template <int G, int MODE, typename T>
+// DMAX: the largest degree the caller can meet (the compact plan's rounds 1-3 hold degree <= 4 only)
+template <int G, int MODE, typename T, int DMAX = 8>
 __device__ __forceinline__ void res_var_dispatch(unsigned char *smem, T *__restrict__ llr_s,
                                                  uint8_t *__restrict__ bits_s, int q, int dv, const uint4 &slo,
                                                  const uint4 &shi, T a, unsigned emask, const ParScatter &ps,
                                                  Pack<T, G> *lreg = nullptr)
 {
-#define LDPC_RV(D) case D: res_var_body<G, D, MODE, T>(smem, llr_s, bits_s, q, slo, shi, a, emask, ps, lreg); break;
+#define LDPC_RV(D) \
+    case D: if constexpr (D <= DMAX) res_var_body<G, D, MODE, T>(smem, llr_s, bits_s, q, slo, shi, a, emask, ps, lreg); break;
     switch (dv) {
         LDPC_RV(0) LDPC_RV(1) LDPC_RV(2) LDPC_RV(3) LDPC_RV(4) LDPC_RV(5) LDPC_RV(6) LDPC_RV(7) LDPC_RV(8)
     default: break;   // host admits only max_dv <= 8 to this engine
@@ -646,11 +650,64 @@ __device__ __forceinline__ void res_var_dispatch(unsigned char *smem, T *__restr
 constexpr int kResRegVars = 4;
 template <typename T, int G>
 struct ResVarState {
-    unsigned meta[kResRegVars];   // vmeta of the variable, 0 past n
+    unsigned meta[kResRegVars];   // vmeta of the variable, 0 past n (not kept by the compact kernels)
     uint2 plo[kResRegVars];       // vslot_lo
     uint2 phi0;                   // vslot_hi of the round-0 variable (degree > 4), else 0
     Pack<T, G> l[kResRegVars];    // channel LLRs as the variable phase reads them (llr_s contents)
+    unsigned cells;               // compact kernels: this wave's word of ResidentPlan::vcell (wave-uniform, SGPR)
 };
+
+// Compact plan (CPT): the host places variables on a grid q = r*512 + w*64 + lane (round r, wave w) so that most
+// (wave, round) cells hold ONE degree, and the cell table ResidentPlan::vcell tells every wave what its rounds hold:
+constexpr unsigned kCellEmpty = 0x00;   // no variable: the round is skipped
+constexpr unsigned kCellHoles = 0x40;   // | degree: one degree, some lanes empty (their vslot_lo.y is kResHole)
+constexpr unsigned kCellMixed = 0xff;   // several degrees (or degree 0): the per-lane switch, degree from vmeta
+                                        // otherwise the byte is the degree 1..8 of all 64 lanes
+constexpr unsigned kResHole = 0xffffffffu;   // vslot_lo.y of an empty position (no variable's: offsets are multiples of 8)
+
+// one round of the compact variable phase: a uniform cell branches on its scalar degree straight into the body
+// (rounds 1-3 hold degree <= 4 only); the alpha column and a mixed cell's degrees come from vmeta, which the rare
+// users load instead of keeping four registers of it per lane
+template <int G, int MODE, typename T, int R>
+__device__ __forceinline__ void res_var_round_cpt(const ResidentPlan &pl, unsigned char *smem, const T *__restrict__ alpha_glb,
+                                                  unsigned emask, int tid, int nt, ResVarState<T, G> &st)
+{
+    constexpr int DMAX = R == 0 ? 8 : 4;
+    const unsigned cd = (st.cells >> (8 * R)) & 0xffu;
+    if (cd == kCellEmpty) return;
+    const int q = tid + R * nt;
+    const uint4 slo = plan_unpack(st.plo[R]), shi = R == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
+    T a = (T)0;
+    if (MODE == 0) a = alpha_glb[pl.vmeta[q] >> 8];
+    const ParScatter ps{};
+    if (cd == kCellMixed) {
+        res_var_dispatch<G, MODE, T, DMAX>(smem, nullptr, nullptr, q, (int)(pl.vmeta[q] & 0xffu), slo, shi, a, emask, ps,
+                                           &st.l[R]);
+        return;
+    }
+    if ((cd & kCellHoles) && st.plo[R].y == kResHole) return;       // the empty lanes of the cell
+#define LDPC_RVU(D) \
+    case D: if constexpr (D <= DMAX) res_var_body<G, D, MODE, T>(smem, nullptr, nullptr, q, slo, shi, a, emask, ps, &st.l[R]); break;
+    switch (cd & 0xfu) {                                           // wave-uniform: scalar compares and branches
+        LDPC_RVU(1) LDPC_RVU(2) LDPC_RVU(3) LDPC_RVU(4) LDPC_RVU(5) LDPC_RVU(6) LDPC_RVU(7) LDPC_RVU(8)
+    default: break;
+    }
+#undef LDPC_RVU
+}
+
+template <int G, int MODE, typename T>
+__device__ __forceinline__ void res_var_phase_cpt(const ResidentPlan &pl, unsigned char *smem, const T *__restrict__ alpha_glb,
+                                                  unsigned emask, int tid, int nt, ResVarState<T, G> &st)
+{
+#pragma unroll
+    for (int r = 0; r < kResRegVars; ++r) asm volatile("" : "+v"(st.plo[r].x), "+v"(st.plo[r].y));
+    asm volatile("" : "+v"(st.phi0.x), "+v"(st.phi0.y));
+    static_assert(kResRegVars == 4, "four rounds");
+    res_var_round_cpt<G, MODE, T, 0>(pl, smem, alpha_glb, emask, tid, nt, st);
+    res_var_round_cpt<G, MODE, T, 1>(pl, smem, alpha_glb, emask, tid, nt, st);
+    res_var_round_cpt<G, MODE, T, 2>(pl, smem, alpha_glb, emask, tid, nt, st);
+    res_var_round_cpt<G, MODE, T, 3>(pl, smem, alpha_glb, emask, tid, nt, st);
+}
 
 template <int G, int MODE, typename T>
 __device__ __forceinline__ void res_var_phase_reg(const ResidentPlan &pl, unsigned char *smem,
@@ -683,7 +740,7 @@ __device__ __forceinline__ void res_var_phase_reg(const ResidentPlan &pl, unsign
 // global memory (L1/L2 resident, shared by every workgroup) while the current one is processed.
 // (A two-register-set ping-pong that avoids the hand-over copies doubled the code and measured no faster.)
 // REG: the register-resident form above instead.
-template <int G, int MODE, typename T, bool REG>
+template <int G, int MODE, typename T, bool REG, bool CPT = false>
 __device__ __forceinline__ void res_var_phase(const ResidentPlan &pl, unsigned char *smem,
                                               T *__restrict__ llr_s, uint8_t *__restrict__ bits_s,
                                               const T *__restrict__ alpha_lds,
@@ -691,7 +748,11 @@ __device__ __forceinline__ void res_var_phase(const ResidentPlan &pl, unsigned c
                                               int tid, int nt, ResVarState<T, G> &st,
                                               const ParScatter ps = ParScatter{})
 {
-    if constexpr (REG) {
+    if constexpr (CPT) {
+        static_assert(REG && (MODE == 0 || MODE == 2 || MODE == 9), "compact: fixed-T register-state modes");
+        res_var_phase_cpt<G, MODE, T>(pl, smem, alpha_glb, emask, tid, nt, st);
+        return;
+    } else if constexpr (REG) {
         res_var_phase_reg<G, MODE, T>(pl, smem, llr_s, bits_s, alpha_lds, alpha_glb, emask, tid, nt, st, ps);
         return;
     }
@@ -989,7 +1050,41 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
     __syncthreads();
     // "initialise v2c with the channel LLRs" (T == 0: c2v = 0, the loop never runs)
     ResVarState<T, G> st{};
-    if constexpr (REG) {
+    if constexpr (CPT) {
+        // the lane's positions q = tid + r*nt of the host's grid: plan entries and LLR pairs into registers once per
+        // launch, the wave's cell word into an SGPR; empty cells load nothing, empty lanes of a cell keep kResHole
+        st.cells = pl.vcell[__builtin_amdgcn_readfirstlane(tid) >> 6];
+        const P *L = reinterpret_cast<const P *>(llr_s);
+#pragma unroll
+        for (int r = 0; r < kResRegVars; ++r) {
+            const int q = tid + r * nt;
+            if (q < pl.n_pos) st.l[r] = L[q];                     // the staging rows hold positions < n_pos
+            if ((st.cells >> (8 * r)) & 0xffu) {
+                st.plo[r] = pl.vslot_lo[q];                       // padded to whole cells
+                if (r == 0 && q < pl.n_hi) st.phi0 = pl.vslot_hi[q];
+            }
+        }
+        __syncthreads();                                   // the init scatter below overwrites the staged LLR rows
+#pragma unroll
+        for (int r = 0; r < kResRegVars; ++r) {
+            const unsigned cd = (st.cells >> (8 * r)) & 0xffu;
+            if (cd == kCellEmpty) continue;
+            const int q = tid + r * nt;
+            int dv = (int)(cd & 0xfu);
+            if (cd == kCellMixed) dv = (int)(pl.vmeta[q] & 0xffu);
+            else if ((cd & kCellHoles) && st.plo[r].y == kResHole) dv = 0;
+            const uint4 slo = plan_unpack(st.plo[r]), shi = r == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
+            const unsigned off[8] = {slo.x, slo.y, slo.z, slo.w, shi.x, shi.y, shi.z, shi.w};
+            P l = st.l[r];
+            if (a.T == 0) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) l.x[g] = (T)0;
+            }
+#pragma unroll
+            for (int e = 0; e < (r == 0 ? 8 : 4); ++e)
+                if (e < dv) lds_store<P>(off[e], l);
+        }
+    } else if constexpr (REG) {
         // the lane's variables q = tid + r*nt: plan entries and LLR pairs into registers, once per launch
         const P *L = reinterpret_cast<const P *>(llr_s);
 #pragma unroll
@@ -1002,7 +1097,6 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
                 st.l[r] = L[q];
             }
         }
-        if constexpr (CPT) __syncthreads();                // the init scatter below overwrites the staged LLR rows
 #pragma unroll
         for (int r = 0; r < kResRegVars; ++r) {
             if (tid + r * nt < n) {
@@ -1129,8 +1223,8 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
             }
         }
         if (it != a.T - 1) {
-            if (a.unit_alpha) res_var_phase<G, 2, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, st);
-            else res_var_phase<G, 0, T, REG>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt, st);
+            if (a.unit_alpha) res_var_phase<G, 2, T, REG, CPT>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, 0u, tid, nt, st);
+            else res_var_phase<G, 0, T, REG, CPT>(pl, res_smem, llr_s, bits_s, alpha_lds, alpha_glb, 0u, tid, nt, st);
             __syncthreads();
         }
     }
@@ -1153,10 +1247,10 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
     // fixed-T mode: success = final syndrome is zero.  With parity words (power-of-two stride) the posterior pass scatters the
     // decisions into them (one LDS atomic per edge, then m words are read); otherwise the decisions go into the dead message
     // slots and every check reads its row of them back (MODE 8 / res_syndrome_slots)
-    const bool scatter = !ES && psf.par_off != 0;
+    const bool scatter = !ES && !CPT && psf.par_off != 0;   // compact plans: row stride 496, no parity words
     if (ES) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     else if (scatter) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st, psf);
-    else res_var_phase<G, CPT ? 9 : 8, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
+    else res_var_phase<G, CPT ? 9 : 8, T, REG, CPT>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     __syncthreads();
     unsigned unsat = kAll;
     if (!ES) {
@@ -1169,7 +1263,7 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
         // the slots are dead now: the posteriors the last pass kept in registers go to the staging rows (sorted order)
 #pragma unroll
         for (int r = 0; r < kResRegVars; ++r)
-            if (tid + r * nt < n) reinterpret_cast<P *>(llr_s)[tid + r * nt] = st.l[r];
+            if (tid + r * nt < pl.n_pos) reinterpret_cast<P *>(llr_s)[tid + r * nt] = st.l[r];
         __syncthreads();
     }
     res_emit<G, T>(pl, a, llr_s, b0, open, a.T, unsat, tid, nt);

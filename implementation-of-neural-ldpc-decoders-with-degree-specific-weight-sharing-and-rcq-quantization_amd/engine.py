@@ -200,10 +200,17 @@ class DecodeEngine:
         # workgroups per CU as LDS (160 KiB) and the wave slots (32 per CU) allow; 0 on the streaming engine
         threads, lds = int(out[2]), int(out[3])
         per_cu = min((160 * 1024) // lds, (32 * 64) // threads) if resident and threads and lds else 0
+        # the compact fixed-T plan's variable grid, costed by the body-cost model of its variable phase (per wave and phase)
+        stats = np.zeros(4, dtype=np.int32)
+        plan = None
+        if self._lib.ldpc_debug_compact_layout(self.handle, 0, 0, 0, None, None, None, None, nat.ptr(stats)) == 0:
+            plan = {"positions": int(stats[0]), "worst_wave_cost": int(stats[1]), "mean_wave_cost": float(stats[2]) / 8,
+                    "mixed_cells": int(stats[3])}
         return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel,
                 "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
                 "codewords_per_workgroup": int(out[1]),
-                "threads_per_workgroup": threads, "lds_bytes": lds, "workgroups_per_cu": per_cu}
+                "threads_per_workgroup": threads, "lds_bytes": lds, "workgroups_per_cu": per_cu,
+                "compact_plan": plan}
 
     # ------------------------------------------------------------------ weights
     def set_weights(self, beta: Optional[np.ndarray], alpha: Optional[np.ndarray],

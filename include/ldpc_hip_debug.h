@@ -38,6 +38,17 @@ int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batc
                             int32_t max_iterations, void *posterior, int32_t *iterations, void *c2v_out,
                             void *stream);
 
+/* Compact fixed-T plan of the LDS-resident engine (host only, no device is touched).  The kernel runs the variable at
+ * position q = r*512 + w*64 + lane in round r (< 4) of wave w (< 8); cells[w*4 + r] describes cell (w, r): 0 empty,
+ * 1..8 the one degree of all 64 lanes, 0x40 | degree one degree with some lanes empty, 0xff mixed (or degree 0).
+ * d != NULL: the plan decoder d builds for its fixed-T decodes (the graph arguments are ignored; LDPC_ERR_UNSUPPORTED
+ * when it has none).  d == NULL: the plan of the graph (n, m, E, check_ptr, var_idx as ldpc_graph_create), whether or
+ * not a decoder's tables would let it take the compact geometry.  pos_of_var[n] receives every variable's position;
+ * stats = { positions in use (highest + 1), largest per-wave cost, summed per-wave cost, mixed cells } under the body-cost
+ * model of the variable phase (csrc/ldpc_hip.hip, cpt_body_cost).  Output pointers may be NULL. */
+int ldpc_debug_compact_layout(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                              const int32_t *var_idx, int32_t *pos_of_var, uint8_t cells[32], int32_t stats[4]);
+
 /* The variable sweep of the RCQ code-pair form turns every outgoing value v into the key
  * [m > 0] + [m >= t1] + [m >= t2] + [m >= t3] of m = |beta * v| (thresholds4[0] is not used; device pointers, thresholds
  * within [2^-50, 2^50]).  Runs BOTH device forms of that key on `count` arbitrary values: the float form the 4-level
