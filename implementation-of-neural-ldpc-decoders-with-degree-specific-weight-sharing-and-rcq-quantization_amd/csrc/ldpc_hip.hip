@@ -1138,6 +1138,7 @@ struct ResVCheck { int check, e0, dc, gs; };
 int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
                     long long S, int G, ResidentPlan &pl, const CptLayout *cl = nullptr);
 void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L);
+void cpt_check_words(const std::vector<ResVCheck> &vc, bool select_form, unsigned (&words)[kCptWaves]);
 bool cpt_geometry(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long &Sc);
 
 // Lane positions of the check phase are VIRTUAL checks.  A check of degree <= kResSubDegreeCap is one of them; a wider
@@ -1250,6 +1251,19 @@ bool cpt_geometry(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long lo
            kResCptBlocks * res_cpt_lds_total((int)Sc, 2) <= kLdsBytes;
 }
 
+// the compact plan's check table (ResidentPlan::ccell): wave w holds the checks at positions 64w .. 64w+63.  `select_form`:
+// the decoder's check phase is the one-beta-per-check select form, the only one with a scalar-counted body
+void cpt_check_words(const std::vector<ResVCheck> &vc, bool select_form, unsigned (&words)[kCptWaves])
+{
+    const int m = (int)vc.size();
+    for (int w = 0; w < kCptWaves; ++w) {
+        const int p0 = std::min(64 * w, m), p1 = std::min(p0 + 64, m);
+        int lo = p0 < p1 ? 255 : 0, hi = 0;
+        for (int p = p0; p < p1; ++p) { lo = std::min(lo, vc[p].dc); hi = std::max(hi, vc[p].dc); }
+        words[w] = p0 < p1 ? chk_word(lo, hi, p1 - p0) | (select_form ? 0u : kChkPerLane) : 0u;
+    }
+}
+
 // the compact plan's grid for a graph and its check order: the balanced placement, else (a staging area too small for its
 // positions) the degree-sorted order of the general plan; variables then ordered inside their degrees for LDS banking
 void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L)
@@ -1342,7 +1356,11 @@ int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::v
     pl.any_split = any_split ? 1 : 0;
     pl.n_hi = n_hi;
     pl.n_pos = n_pos;
-    if (cl) std::copy(cl->cell, cl->cell + kCptWaves, pl.vcell);
+    if (cl) {
+        std::copy(cl->cell, cl->cell + kCptWaves, pl.vcell);
+        cpt_check_words(vc, per_check && (d->form == LDPC_C2V_NMS || (d->form == LDPC_C2V_RCQ && d->rcq_zero0)),
+                        pl.ccell);
+    }
     pl.par_words = is_pow2(mstride) ? m : 0;
     pl.par_shift = G == 2 ? 3 : 2;                     // slot byte offset = slot * G * 4
     int rc = plan_upload(d, &pl.dc_s, dc_s);
@@ -2461,6 +2479,33 @@ int ldpc_debug_compact_layout(const ldpc_decoder *d, int32_t n, int32_t m, int32
                               const int32_t *var_idx, int32_t *pos_of_var, uint8_t cells[32], int32_t stats[4])
 {
     LDPC_NOTHROW(compact_layout_impl(d, n, m, E, check_ptr, var_idx, pos_of_var, cells, stats))
+}
+
+static int compact_checks_impl(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                               const int32_t *var_idx, uint32_t *words)
+{
+    if (!words) return fail(LDPC_ERR_ARG, "NULL argument");
+    if (d) {
+        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
+        std::copy(d->resc.ccell, d->resc.ccell + kCptWaves, words);
+        return LDPC_OK;
+    }
+    ldpc_graph g;                                        // host copies only: no device is touched
+    if (int rc = graph_host_build(&g, n, m, E, check_ptr, var_idx)) return rc;
+    std::vector<ResVCheck> vc;
+    long long Sc = 0;
+    if (!resident_checks(&g, vc) || !cpt_geometry(&g, vc, Sc))
+        return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
+    unsigned own[kCptWaves];
+    cpt_check_words(vc, true, own);
+    std::copy(own, own + kCptWaves, words);
+    return LDPC_OK;
+}
+
+int ldpc_debug_compact_checks(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                              const int32_t *var_idx, uint32_t words[8])
+{
+    LDPC_NOTHROW(compact_checks_impl(d, n, m, E, check_ptr, var_idx, words))
 }
 
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,

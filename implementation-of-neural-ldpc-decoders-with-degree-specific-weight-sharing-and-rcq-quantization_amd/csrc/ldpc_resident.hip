@@ -59,6 +59,7 @@ struct ResidentPlan {
     const uint16_t *inv_perm_v;   // [n]          sorted position of original variable j
     int n_pos;                    //              positions in use: n, or (compact plan) the highest occupied one + 1
     unsigned vcell[8];            // compact plan: byte r of word w = the cell (wave w, round r) -- kCell* below
+    unsigned ccell[8];            // compact plan: word w = the checks of wave w (positions 64w .. 64w+63) -- kChk* below
     int E;                        // edges of the graph
     const uint32_t *edge_of_slot; // [S]          CSR edge id held by a slot, 0xffffffff for padding slots (test hook
                                   //              ldpc_debug_resident_c2v: dumps the C2V state in CSR order)
@@ -247,6 +248,30 @@ __device__ __forceinline__ void res_select4(float &x0, float &x1, float &x2, flo
         : "vcc");
 }
 
+// res_select4 with the results in registers of their own.  An asm statement's in/out ("+v") operands are tied pairs, and
+// the compiler copies a tied operand past the sixteenth into a scratch register and back (v_mov, s_nop, v_mov per
+// call); with plain inputs and early-clobber outputs, which double as the selects' temporaries, nothing is copied.
+__device__ __forceinline__ void res_select4_out(float (&y)[4], float x0, float x1, float x2, float x3, float m1a, float m1b,
+                                                uint32_t o1a, uint32_t o2a, uint32_t o1b, uint32_t o2b, uint32_t sign_v)
+{
+    unsigned long long c0, c1, c2;
+    asm("v_cmp_eq_f32_e64 %4, |%7|, %11\n\t"
+        "v_cmp_eq_f32_e64 %5, |%8|, %12\n\t"
+        "v_cmp_eq_f32_e64 %6, |%9|, %11\n\t"
+        "v_cmp_eq_f32_e64 vcc, |%10|, %12\n\t"
+        "v_cndmask_b32_e64 %0, %13, %14, %4\n\t"
+        "v_cndmask_b32_e64 %1, %15, %16, %5\n\t"
+        "v_cndmask_b32_e64 %2, %13, %14, %6\n\t"
+        "v_cndmask_b32_e32 %3, %15, %16, vcc\n\t"
+        "v_bitop3_b32 %0, %0, %7, %17 bitop3:0x78\n\t"
+        "v_bitop3_b32 %1, %1, %8, %17 bitop3:0x78\n\t"
+        "v_bitop3_b32 %2, %2, %9, %17 bitop3:0x78\n\t"
+        "v_bitop3_b32 %3, %3, %10, %17 bitop3:0x78"
+        : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "=&s"(c0), "=&s"(c1), "=&s"(c2)
+        : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(m1a), "v"(m1b), "v"(o1a), "v"(o2a), "v"(o1b), "v"(o2b), "v"(sign_v)
+        : "vcc");
+}
+
 // the same for FOUR edges of one float64 codeword: compares on the 64-bit values, selects and sign on the 32-bit halves
 __device__ __forceinline__ void res_select4_f64(double (&x)[4], double m1, double o1, double o2, uint32_t sign_v)
 {
@@ -279,6 +304,120 @@ __device__ __forceinline__ void res_select4_f64(double (&x)[4], double m1, doubl
         : "vcc");
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = __longlong_as_double((long long)(((unsigned long long)rh[i] << 32) | rl[i]));
+}
+
+// Compact plan: the checks of wave w, one word of ResidentPlan::ccell (checks are sorted by degree, so nearly every wave
+// holds one degree or two adjacent ones): d_lo = smallest degree in the wave | (largest - d_lo) << 8 | lanes in use << 16,
+// kChkPerLane set for a wave the scalar-counted form does not take: d_lo < 4 (which also keeps the degree-1 rule
+// "min2 = min1" in the per-lane form alone), and every wave of a decoder whose check phase is not the one-beta-per-check
+// select form (per-edge beta, OMS, RCQ with tau_0 != 0).
+constexpr unsigned kChkPerLane = 0x80000000u;
+__host__ __device__ constexpr unsigned chk_word(int d_lo, int d_hi, int lanes)
+{
+    return (unsigned)d_lo | (unsigned)(d_hi - d_lo) << 8 | (unsigned)lanes << 16 | (d_lo < 4 ? kChkPerLane : 0u);
+}
+__host__ __device__ constexpr int chk_lo(unsigned w) { return (int)(w & 0xffu); }
+__host__ __device__ constexpr int chk_spread(unsigned w) { return (int)(w >> 8 & 0xffu); }
+__host__ __device__ constexpr int chk_lanes(unsigned w) { return (int)(w >> 16 & 0xffu); }
+
+// Edges 0 .. dc-1 of a lane's check in ascending order with the loop control on the scalar unit: d_lo (wave-uniform) edges
+// as groups of four plus a tail of two and of one on scalar branches, f(address of the group's first slot, edges in the
+// group as a compile-time constant) -- the slots of a group sit at immediate offsets k*stride from one address register
+// -- and then, only in a wave that holds several degrees, the lanes with dc > d_lo take their remaining edges one at a
+// time under the exec mask.  A wave of one degree executes no exec-mask instruction and no per-trip vector compare.
+template <typename F>
+__device__ __forceinline__ void res_walk_edges(unsigned base, unsigned stride, int d_lo, int spread, int dc, F &&f)
+{
+    unsigned addr = base;
+#pragma unroll 1
+    for (int t = 0; t + 4 <= d_lo; t += 4) {
+        f(addr, std::integral_constant<int, 4>{});
+        addr += 4 * stride;
+    }
+    if (d_lo & 2) {
+        f(addr, std::integral_constant<int, 2>{});
+        addr += 2 * stride;
+    }
+    if (d_lo & 1) f(addr, std::integral_constant<int, 1>{});
+#pragma unroll 1
+    for (int e = d_lo; e < d_lo + spread; ++e)
+        if (e < dc) f(base + (unsigned)e * stride, std::integral_constant<int, 1>{});
+}
+
+// The check phase of the compact kernels (fp32 codeword pairs, no split checks) for a wave with d_lo >= 4, in the
+// one-beta-per-check form (normalised min-sum, RCQ with tau_0 == 0): the two passes of res_check_body below -- the same
+// arithmetic on the same edges in the same order, so every output is the same bits -- walked by res_walk_edges.  The
+// host marks every wave of a decoder with per-edge tables or other forms kChkPerLane.
+template <int FORM, int NL, int MS>
+__device__ __forceinline__ void res_check_body_uniform(int p, int dc, unsigned cw, float b_check, const float (&th)[8],
+                                                       const float *__restrict__ thr, int n_levels)
+{
+    static_assert(FORM == FORM_NMS || FORM == FORM_RCQ, "forms with two outgoing magnitudes per check");
+    static_assert(MS > 0, "compile-time row stride: the slots of a group are immediate offsets");
+    constexpr int G = 2;
+    using P = Pack<float, G>;
+    constexpr unsigned stride = (unsigned)MS * G * (unsigned)sizeof(float);
+    const unsigned base = (unsigned)p * G * (unsigned)sizeof(float);
+    const int d_lo = chk_lo(cw), spread = chk_spread(cw);
+    float m1[G], m2[G];
+    uint32_t sacc[G];
+    float ninf = -inf_of<float>();
+    asm volatile("" : "+v"(ninf));                    // see res_check_body
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        m1[g] = inf_of<float>(); m2[g] = inf_of<float>(); sacc[g] = 0;
+    }
+    res_walk_edges(base, stride, d_lo, spread, dc, [&](unsigned addr, auto kc) {
+        constexpr int K = decltype(kc)::value;
+        P v[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = lds_load<P>(addr + k * stride);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float a = __builtin_fabsf(v[k].x[g]);
+                sacc[g] ^= __float_as_uint(v[k].x[g]);
+                m2[g] = __builtin_amdgcn_fmed3f(a, m1[g], m2[g]);
+                m1[g] = __builtin_amdgcn_fmed3f(a, m1[g], ninf);
+            }
+        }
+    });
+
+    uint32_t o1[G], o2[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float w1 = b_check * m1[g], w2 = b_check * m2[g];
+        if (FORM == FORM_RCQ) {
+            const float r1 = res_quant_rec<NL>(__builtin_fabsf(w1), th, thr, n_levels);
+            const float r2 = res_quant_rec<NL>(__builtin_fabsf(w2), th, thr, n_levels);
+            w1 = flip_sign<float>(r1, (w1 < 0.0f) ? 1u : 0u);
+            w2 = flip_sign<float>(r2, (w2 < 0.0f) ? 1u : 0u);
+        }
+        const uint32_t par = sacc[g] & 0x80000000u;
+        o1[g] = __float_as_uint(w1) ^ par;
+        o2[g] = __float_as_uint(w2) ^ par;
+        asm volatile("" : "+v"(o1[g]), "+v"(o2[g]));
+    }
+    uint32_t sign_v = 0x80000000u;
+    asm volatile("" : "+v"(sign_v));
+    // every edge goes through res_select4_out (the constant in a VGPR); an odd edge is paired with a dummy pair whose
+    // result is dropped
+    res_walk_edges(base, stride, d_lo, spread, dc, [&](unsigned addr, auto kc) {
+        constexpr int K = decltype(kc)::value;
+        P v[4];
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = lds_load<P>(addr + k * stride);
+        if constexpr (K & 1) asm volatile("" : "=v"(v[K].x[0]), "=v"(v[K].x[1]));    // any two registers
+#pragma unroll
+        for (int k = 0; k < K; k += 2) {
+            float y[4];
+            res_select4_out(y, v[k].x[0], v[k].x[1], v[k + 1].x[0], v[k + 1].x[1], m1[0], m1[1], o1[0], o2[0], o1[1], o2[1],
+                            sign_v);
+            lds_store<P>(addr + k * stride, P{{y[0], y[1]}});
+            if (k + 1 < K) lds_store<P>(addr + (k + 1) * stride, P{{y[2], y[3]}});
+        }
+    });
 }
 
 template <int G, int FORM, bool BPC, int NL, int MS, typename T, bool SPLIT = false>
@@ -502,17 +641,39 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
 
 // `dc_pre` / `b_pre` are the first round's degree and per-check beta, fetched by the caller ahead of
 // the barrier so their global-memory latency is off the critical path.
-template <int G, int FORM, bool BPC, int NL, int MS, typename T, bool SPLIT>
+// CPT (compact kernels): `cw` is the wave's word of ResidentPlan::ccell, in an SGPR; the kernels of the one-beta-per-check
+// select form run the scalar-counted body on it, everything else the per-lane form below.
+template <int G, int FORM, bool BPC, int NL, int MS, typename T, bool SPLIT, bool CPT = false>
 __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned char *smem,
                                                 const T *__restrict__ beta_row,
                                                 const T *__restrict__ oa_row,
                                                 const float *__restrict__ thr, int n_levels, bool rcq_zero0,
-                                                int dc_pre, T b_pre, int tid, int nt)
+                                                int dc_pre, T b_pre, int tid, int nt, unsigned cw = 0)
 {
     float th[8];
     if (FORM == FORM_RCQ) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) th[q] = (q < n_levels) ? thr[q] : __builtin_nanf("");
+    }
+    if constexpr (CPT && BPC && (FORM == FORM_NMS || FORM == FORM_RCQ)) {
+        static_assert(G == 2 && !SPLIT && std::is_same<T, float>::value, "compact: fp32 codeword pairs, whole checks");
+        // opaque per phase: the conditions derived from the word and the lane masks derived from the degree are
+        // recomputed where they are used instead of being held in SGPR pairs across the iteration loop
+        asm volatile("" : "+s"(cw));
+        asm volatile("" : "+v"(dc_pre), "+v"(b_pre));
+        if (!(cw & kChkPerLane)) {
+            // position tid is the lane's only check (m <= kResCptStride < the thread count) and the prefetched degree and
+            // beta are all it needs.  A full wave runs with no lane mask at all, the last one is masked once for the whole
+            // phase, a wave without checks leaves.
+            const int lanes = chk_lanes(cw);
+            if (lanes == 64) res_check_body_uniform<FORM, NL, MS>(tid, dc_pre, cw, b_pre, th, thr, n_levels);
+            else if ((tid & 63) < lanes) res_check_body_uniform<FORM, NL, MS>(tid, dc_pre, cw, b_pre, th, thr, n_levels);
+            return;
+        }
+        // per-lane waves of these kernels: the form below on the lane's one check
+        if (tid < pl.m)
+            res_check_body<G, FORM, BPC, NL, MS, T>(pl, smem, tid, dc_pre, b_pre, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
+        return;
     }
     int dc = dc_pre;
     T b_check = b_pre;
@@ -531,8 +692,9 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
             }
         }
         // every lane runs the edge loops with ITS degree as trip count (exec-masked vector loops): one pass per wave
-        // whatever the mix of degrees.  Measured fastest against scalar per-degree forms: the phase is bound
-        // by VALU issue -- six instructions per edge and codeword, which the scalar forms do not reduce -- not by loop control.
+        // whatever the mix of degrees.  At two workgroups per CU it measured fastest against scalar per-degree forms
+        // (DESIGN.md 3c table); at six waves per SIMD the loop control it spends in the vector unit counts, and the compact
+        // kernels of the select form take res_check_body_uniform above instead.
         res_check_body<G, FORM, BPC, NL, MS, T>(pl, smem, p, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
     }
 }
@@ -1156,6 +1318,8 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
             }
         }
     }
+    unsigned chk_cells = 0;                              // compact kernels: this wave's check word, in an SGPR
+    if constexpr (CPT) chk_cells = pl.ccell[__builtin_amdgcn_readfirstlane(tid) >> 6];
     // first-round check degree (iteration-invariant) and per-check beta of iteration 0, in registers
     const int dc_pre = tid < pl.m ? pl.dc_s[tid] : 0;
     T b_pre = (BPC && tid < pl.m && a.T > 0) ? g_beta[pl.bslot_c[tid]] : (T)0;
@@ -1172,8 +1336,8 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
         const float *thr = FORM == FORM_RCQ ? a.thr + (size_t)a.q_of_iter[it] * a.n_levels : nullptr;
         const T *alpha_lds = a.alpha_in_lds ? alpha_s + it * a.n_alpha : nullptr;
         const T *alpha_glb = g_alpha + (size_t)it * a.n_alpha;
-        res_check_phase<G, FORM, BPC, NL, MS, T, SPLIT>(pl, res_smem, beta_row, oa_row, thr, a.n_levels, a.rcq_zero0 != 0,
-                                              dc_pre, b_pre, tid, nt);
+        res_check_phase<G, FORM, BPC, NL, MS, T, SPLIT, CPT>(pl, res_smem, beta_row, oa_row, thr, a.n_levels,
+                                                             a.rcq_zero0 != 0, dc_pre, b_pre, tid, nt, chk_cells);
         if (BPC && tid < pl.m && it + 1 < a.T)           // next iteration's beta: in flight across the phases below
             b_pre = g_beta[(size_t)(it + 1) * a.n_beta + pl.bslot_c[tid]];
         __syncthreads();

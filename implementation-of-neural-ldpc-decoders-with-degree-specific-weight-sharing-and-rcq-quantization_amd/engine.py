@@ -206,6 +206,11 @@ class DecodeEngine:
         if self._lib.ldpc_debug_compact_layout(self.handle, 0, 0, 0, None, None, None, None, nat.ptr(stats)) == 0:
             plan = {"positions": int(stats[0]), "worst_wave_cost": int(stats[1]), "mean_wave_cost": float(stats[2]) / 8,
                     "mixed_cells": int(stats[3])}
+            # waves whose check phase runs on a scalar trip count (bit 31 of a check word: the per-lane form)
+            words = np.zeros(8, dtype=np.uint32)
+            nat.check(self._lib.ldpc_debug_compact_checks(self.handle, 0, 0, 0, None, None, nat.ptr(words)),
+                      "ldpc_debug_compact_checks")
+            plan["scalar_check_waves"] = int(np.count_nonzero((words != 0) & (words >> 31 == 0)))
         return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel,
                 "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
                 "codewords_per_workgroup": int(out[1]),

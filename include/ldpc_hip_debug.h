@@ -49,6 +49,16 @@ int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batc
 int ldpc_debug_compact_layout(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
                               const int32_t *var_idx, int32_t *pos_of_var, uint8_t cells[32], int32_t stats[4]);
 
+/* Check table of the compact fixed-T plan (host only, arguments as ldpc_debug_compact_layout).  Checks are sorted by
+ * descending degree and wave w runs positions 64w .. 64w+63; words[w] = d_lo | (d_hi - d_lo) << 8 | lanes << 16 with d_lo /
+ * d_hi the smallest / largest degree among the wave's checks and `lanes` how many it holds (0: the whole word is 0).
+ * Bit 31 marks a wave that runs the per-lane form of the check phase; every other wave runs d_lo edges on a scalar trip
+ * count and only the d_hi - d_lo remaining ones under a lane mask.  d == NULL: the graph's table, bit 31 where d_lo < 4.
+ * d != NULL: the table the decoder runs with -- every wave marked unless its check phase is the one-beta-per-check
+ * select form (normalised min-sum or RCQ with tau_0 == 0, one beta slot per check). */
+int ldpc_debug_compact_checks(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                              const int32_t *var_idx, uint32_t words[8]);
+
 /* The variable sweep of the RCQ code-pair form turns every outgoing value v into the key
  * [m > 0] + [m >= t1] + [m >= t2] + [m >= t3] of m = |beta * v| (thresholds4[0] is not used; device pointers, thresholds
  * within [2^-50, 2^50]).  Runs BOTH device forms of that key on `count` arbitrary values: the float form the 4-level
