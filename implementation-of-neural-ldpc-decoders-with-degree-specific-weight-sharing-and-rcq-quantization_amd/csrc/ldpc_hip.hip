@@ -93,6 +93,7 @@ struct ldpc_graph {
 constexpr int kCptWaves = kResCptThreads / 64;
 constexpr int kCptCells = kCptWaves * kResRegVars;
 constexpr int kCptMaxDv = 8;
+constexpr long kCptJointTrials = 3000000;    // budget of the joint bank-aware placement search (cpt_place_banks)
 inline int cpt_body_cost(int dv) { return dv * (dv - 1) + 2 * dv + 4; }
 
 struct CptLayout {
@@ -100,6 +101,12 @@ struct CptLayout {
     unsigned cell[kCptWaves] = {}; // ResidentPlan::vcell
     int worst = 0, total = 0;      // largest and summed per-wave cost of one variable phase (cpt_body_cost model)
     int mixed = 0;                 // cells of kind kCellMixed
+    // slot placement (cpt_place_banks): check position p runs the check vc[check_at[p]] of the degree-sorted list, edge e
+    // sits in slot slot_of_edge[e] = row * kResCptStride + p.  banks = { gather cost, gather groups, scatter cost,
+    // scatter groups } of one variable phase under the LDS model (BankModel); base_* is the same for the placement of
+    // the stable check order with rows in CSR order and the variables-only search, the starting point of the joint one
+    std::vector<int> check_at, slot_of_edge, base_check_at, base_slot_of_edge;
+    int banks[4] = {}, base_banks[4] = {};
 };
 
 struct ldpc_decoder {
@@ -1103,38 +1110,202 @@ bool cpt_assign(const std::vector<int> &dv, CptLayout &L)
     return true;
 }
 
-// optimise_lane_order for a grid: variables change places only with variables of the same degree (the cells keep their
-// degrees); `vs[n]` is the empty entry of the holes
-void cpt_lane_order(std::vector<int> &var_at, const std::vector<std::vector<int>> &vs, int G)
-{
-    const int n = (int)vs.size() - 1;
-    std::vector<int> order(var_at.size());
-    for (size_t q = 0; q < var_at.size(); ++q) order[q] = var_at[q] >= 0 ? var_at[q] : n;
-    LaneCost lc{vs, order, 32, 32, G == 2 ? 16 : 32, G == 2 ? 16 : 32};
-    std::vector<std::vector<int>> classes(kCptMaxDv + 1);
-    for (int q = 0; q < (int)order.size(); ++q) {
-        const int d = (int)vs[order[q]].size();
-        if (order[q] != n && d > 0 && d <= kCptMaxDv) classes[d].push_back(q);
-    }
-    classes.erase(std::remove_if(classes.begin(), classes.end(), [](const std::vector<int> &c) { return c.size() < 2; }),
-                  classes.end());
-    if (classes.empty()) return;
-    uint64_t rng = 0x9E3779B97F4A7C15ull;
-    auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
-    const long trials = std::min<long>(400000, 150L * n);
-    for (long it = 0; it < trials; ++it) {
-        const auto &c = classes[next() % classes.size()];
-        const int x = c[next() % c.size()], y = c[next() % c.size()];
-        if (x / lc.wg == y / lc.wg) continue;
-        const int before = lc.around(x, y);
-        std::swap(order[x], order[y]);
-        if (lc.around(x, y) > before) std::swap(order[x], order[y]);
-    }
-    for (size_t q = 0; q < var_at.size(); ++q) var_at[q] = order[q] == n ? -1 : order[q];
-}
-
 // a lane position of the check phase: (sub-)check `check`, its edges e0 .. e0+dc-1, lane-group size gs
 struct ResVCheck { int check, e0, dc, gs; };
+
+// ---- compact plan: joint bank-aware slot placement ------------------------------------------------
+// The LDS model of one variable phase of the compact kernels (codeword pairs: 8-byte slots).  The lane at grid position q
+// gathers and scatters the slot of its variable's k-th edge (CSC order) with the k-th ds_read_b64 / ds_write_b64 of its
+// round; a read resolves 32 lanes per LDS cycle on slot mod 32, a write 16 lanes on slot mod 16, and a group takes as
+// many cycles as its fullest bank holds lanes.  Three things are free and change no result: which variables of one
+// degree share a lane group, which position a check takes among the checks of its degree (the per-wave degrees, so
+// ccell and Sc, stay), and which row each edge of a check takes (min1, min2 and the sign parity do not depend on the
+// order of the edges; every per-slot table is filled from the same map).  BankModel keeps one bank histogram per
+// (group, k) and evaluates a move from the entries it changes; every move is its own inverse.
+struct BankModel {
+    static constexpr int kRG = 32, kRM = 32, kWG = 16, kWM = 16;
+    const ldpc_graph *g;
+    const std::vector<ResVCheck> &vc;
+    std::vector<int> &var_at, &check_at, &slot_of_edge;
+    std::vector<int> pos_of_var, k_of_edge, edge_at;     // edge_at[vc[c].e0 + t] = the edge in row t of check c
+    std::vector<unsigned char> hist[2], mx[2];           // [0] gathers, [1] scatters: [cell][bank], [cell]
+    std::vector<int> dirty;                              // cells whose fullest bank lost a lane: kind | cell << 1
+    long long cost = 0, sq = 0;                          // sum of the cells' maxima; sum of the squared bank counts
+
+    BankModel(const ldpc_graph *g_, const std::vector<ResVCheck> &vc_, std::vector<int> &var_at_,
+              std::vector<int> &check_at_, std::vector<int> &slot_of_edge_)
+        : g(g_), vc(vc_), var_at(var_at_), check_at(check_at_), slot_of_edge(slot_of_edge_)
+    {
+        const int n_pos = (int)var_at.size();
+        pos_of_var.assign(g->n, -1);
+        for (int q = 0; q < n_pos; ++q)
+            if (var_at[q] >= 0) pos_of_var[var_at[q]] = q;
+        k_of_edge.assign(g->E, 0);
+        for (int j = 0; j < g->n; ++j)
+            for (int s = g->h_var_ptr[j]; s < g->h_var_ptr[j + 1]; ++s) k_of_edge[g->h_csc[s]] = s - g->h_var_ptr[j];
+        edge_at.assign(g->E, 0);
+        for (const ResVCheck &v : vc)
+            for (int t = 0; t < v.dc; ++t) edge_at[v.e0 + t] = v.e0 + t;
+        const int rcells = (n_pos + kRG - 1) / kRG * kCptMaxDv, wcells = (n_pos + kWG - 1) / kWG * kCptMaxDv;
+        hist[0].assign((size_t)rcells * kRM, 0); mx[0].assign(rcells, 0);
+        hist[1].assign((size_t)wcells * kWM, 0); mx[1].assign(wcells, 0);
+        for (int e = 0; e < g->E; ++e) entry(e, +1);
+        settle();
+    }
+    void bump(int kind, int cell, int banks, int bank, int sign)
+    {
+        unsigned char &c = hist[kind][(size_t)cell * banks + bank];
+        if (sign > 0) {
+            sq += 2 * c + 1;
+            if (++c > mx[kind][cell]) { mx[kind][cell] = c; ++cost; }
+        } else {
+            sq -= 2 * c - 1;
+            if (c-- == mx[kind][cell]) dirty.push_back(kind | cell << 1);
+        }
+    }
+    void entry(int e, int sign)                          // edge e's accesses enter (+1) or leave (-1) the histograms
+    {
+        const int q = pos_of_var[g->h_var_idx[e]], k = k_of_edge[e], s = slot_of_edge[e];
+        bump(0, q / kRG * kCptMaxDv + k, kRM, s % kRM, sign);
+        bump(1, q / kWG * kCptMaxDv + k, kWM, s % kWM, sign);
+    }
+    void settle()                                        // exact maxima of the dirty cells
+    {
+        for (int dc : dirty) {
+            const int kind = dc & 1, cell = dc >> 1, banks = kind ? kWM : kRM;
+            const unsigned char *h = &hist[kind][(size_t)cell * banks];
+            unsigned char m = 0;
+            for (int b = 0; b < banks; ++b) m = std::max(m, h[b]);
+            cost += (int)m - (int)mx[kind][cell];
+            mx[kind][cell] = m;
+        }
+        dirty.clear();
+    }
+    void swap_vars(int x, int y)                         // grid positions of two variables
+    {
+        const int jx = var_at[x], jy = var_at[y];
+        for (int j : {jx, jy})
+            for (int s = g->h_var_ptr[j]; s < g->h_var_ptr[j + 1]; ++s) entry(g->h_csc[s], -1);
+        std::swap(var_at[x], var_at[y]);
+        pos_of_var[jx] = y; pos_of_var[jy] = x;
+        for (int j : {jx, jy})
+            for (int s = g->h_var_ptr[j]; s < g->h_var_ptr[j + 1]; ++s) entry(g->h_csc[s], +1);
+        settle();
+    }
+    void swap_checks(int p, int r)                       // two positions that hold checks of one degree
+    {
+        const ResVCheck &a = vc[check_at[p]], &b = vc[check_at[r]];
+        for (int t = 0; t < a.dc; ++t) { entry(a.e0 + t, -1); entry(b.e0 + t, -1); }
+        for (int t = 0; t < a.dc; ++t) { slot_of_edge[a.e0 + t] += r - p; slot_of_edge[b.e0 + t] += p - r; }
+        for (int t = 0; t < a.dc; ++t) { entry(a.e0 + t, +1); entry(b.e0 + t, +1); }
+        std::swap(check_at[p], check_at[r]);
+        settle();
+    }
+    void swap_rows(int p, int t, int u)                  // two rows of the check at position p
+    {
+        const ResVCheck &a = vc[check_at[p]];
+        const int e = edge_at[a.e0 + t], f = edge_at[a.e0 + u];
+        entry(e, -1); entry(f, -1);
+        std::swap(slot_of_edge[e], slot_of_edge[f]);
+        std::swap(edge_at[a.e0 + t], edge_at[a.e0 + u]);
+        entry(e, +1); entry(f, +1);
+        settle();
+    }
+    void report(int (&out)[4]) const                     // { gather cost, gather groups, scatter cost, scatter groups }
+    {
+        for (int kind = 0; kind < 2; ++kind) {
+            int c = 0, groups = 0;
+            for (unsigned char m : mx[kind]) { c += m; groups += m ? 1 : 0; }
+            out[2 * kind] = c; out[2 * kind + 1] = groups;
+        }
+    }
+};
+
+// Seeded local search over L.var_at, L.check_at and L.slot_of_edge, budgeted by trial counts alone (deterministic).
+// First the variables-only climb on the summed maxima that this planner has always run (same moves, same acceptance, same
+// random sequence); its result is recorded as the baseline.  Then the joint climb: swaps of two variables of one degree,
+// of two checks of one degree, of two rows of one check, accepted when the summed maxima fall, or stay while the summed
+// squared bank counts do not rise -- the second term keeps a gradient once every group sits at two lanes per bank.
+void cpt_place_banks(const ldpc_graph *g, const std::vector<ResVCheck> &vc, CptLayout &L)
+{
+    const int n = g->n, m = (int)vc.size();
+    L.check_at.resize(m);
+    L.slot_of_edge.assign(g->E, 0);
+    for (int p = 0; p < m; ++p) {
+        L.check_at[p] = p;
+        for (int t = 0; t < vc[p].dc; ++t) L.slot_of_edge[vc[p].e0 + t] = t * kResCptStride + p;
+    }
+    BankModel bm(g, vc, L.var_at, L.check_at, L.slot_of_edge);
+    std::vector<std::vector<int>> vclass(kCptMaxDv + 1);                // grid positions by variable degree
+    for (int q = 0; q < (int)L.var_at.size(); ++q) {
+        if (L.var_at[q] < 0) continue;
+        const int d = g->h_var_ptr[L.var_at[q] + 1] - g->h_var_ptr[L.var_at[q]];
+        if (d > 0 && d <= kCptMaxDv) vclass[d].push_back(q);
+    }
+    vclass.erase(std::remove_if(vclass.begin(), vclass.end(), [](const std::vector<int> &c) { return c.size() < 2; }),
+                 vclass.end());
+    std::vector<std::pair<int, int>> cclass;                            // [first, last) positions of one check degree
+    std::vector<int> rowable;                                           // positions whose check has two rows or more
+    for (int p = 0; p < m;) {
+        int r = p;
+        while (r < m && vc[r].dc == vc[p].dc) ++r;
+        if (r - p >= 2 && vc[p].dc > 0) cclass.push_back({p, r});
+        p = r;
+    }
+    for (int p = 0; p < m; ++p)
+        if (vc[p].dc >= 2) rowable.push_back(p);
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+    if (!vclass.empty()) {
+        const long trials = std::min<long>(400000, 150L * n);
+        for (long it = 0; it < trials; ++it) {
+            const auto &c = vclass[next() % vclass.size()];
+            const int x = c[next() % c.size()], y = c[next() % c.size()];
+            if (x / BankModel::kWG == y / BankModel::kWG) continue;
+            const long long before = bm.cost;
+            bm.swap_vars(x, y);
+            if (bm.cost > before) bm.swap_vars(x, y);
+        }
+    }
+    bm.report(L.base_banks);
+    L.base_check_at = L.check_at;
+    L.base_slot_of_edge = L.slot_of_edge;
+
+    // rows are the cheapest move and the most productive: 29 trials in 32; 2 move variables, 1 moves checks
+    const long joint = std::min<long>(kCptJointTrials, 500L * g->E);
+    for (long it = 0; it < joint; ++it) {
+        const long long cost0 = bm.cost, sq0 = bm.sq;
+        const unsigned kind = (unsigned)(next() % 32);
+        int a = 0, b = 0, c = 0;
+        if (kind < 2) {
+            if (vclass.empty()) continue;
+            const auto &cl = vclass[next() % vclass.size()];
+            a = cl[next() % cl.size()]; b = cl[next() % cl.size()];
+            if (a / BankModel::kWG == b / BankModel::kWG) continue;
+            bm.swap_vars(a, b);
+        } else if (kind < 3) {
+            if (cclass.empty()) continue;
+            const auto &cl = cclass[next() % cclass.size()];
+            a = cl.first + (int)(next() % (uint64_t)(cl.second - cl.first));
+            b = cl.first + (int)(next() % (uint64_t)(cl.second - cl.first));
+            if (a == b) continue;
+            bm.swap_checks(a, b);
+        } else {
+            if (rowable.empty()) continue;
+            a = rowable[next() % rowable.size()];
+            const int dc = vc[L.check_at[a]].dc;
+            b = (int)(next() % (uint64_t)dc); c = (int)(next() % (uint64_t)dc);
+            if (b == c) continue;
+            bm.swap_rows(a, b, c);
+        }
+        if (bm.cost < cost0 || (bm.cost == cost0 && bm.sq <= sq0)) continue;
+        if (kind < 2) bm.swap_vars(a, b);
+        else if (kind < 3) bm.swap_checks(a, b);
+        else bm.swap_rows(a, b, c);
+    }
+    bm.report(L.banks);
+}
+
 int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
                     long long S, int G, ResidentPlan &pl, const CptLayout *cl = nullptr);
 void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L);
@@ -1265,34 +1436,33 @@ void cpt_check_words(const std::vector<ResVCheck> &vc, bool select_form, unsigne
 }
 
 // the compact plan's grid for a graph and its check order: the balanced placement, else (a staging area too small for its
-// positions) the degree-sorted order of the general plan; variables then ordered inside their degrees for LDS banking
+// positions) the degree-sorted order of the general plan; then variables, check positions and edge rows are placed for LDS
+// banking (cpt_place_banks)
 void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L)
 {
-    const int n = g->n, m = (int)vc.size();
+    const int n = g->n;
     std::vector<int> dv(n);
     for (int j = 0; j < n; ++j) dv[j] = g->h_var_ptr[j + 1] - g->h_var_ptr[j];
-    std::vector<int> slot_of_edge(g->E);
-    for (int p = 0; p < m; ++p)
-        for (int t = 0; t < vc[p].dc; ++t) slot_of_edge[vc[p].e0 + t] = t * kResCptStride + p;
-    std::vector<std::vector<int>> vs(n + 1);
-    for (int j = 0; j < n; ++j)
-        for (int k = 0; k < dv[j]; ++k) vs[j].push_back(slot_of_edge[g->h_csc[g->h_var_ptr[j] + k]]);
     if (!cpt_assign(dv, L) || (long long)L.var_at.size() > S) {
         L.var_at.resize(n);
         for (int j = 0; j < n; ++j) L.var_at[j] = j;
         std::stable_sort(L.var_at.begin(), L.var_at.end(), [&](int a, int b) { return dv[a] > dv[b]; });
     }
-    cpt_lane_order(L.var_at, vs, 2);
+    cpt_place_banks(g, vc, L);
     cpt_cells(dv, L);
 }
 
 // slot layout of one geometry: row stride `mstride`, S slots, G codewords per slot; variables ordered inside their degree
 // classes for LDS banking (general plan) or at the positions of the compact grid `cl`; the plan arrays go to the device
 // (owned by d->res_bufs)
-int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
+int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &sorted, int mstride,
                     long long S, int G, ResidentPlan &pl, const CptLayout *cl)
 {
     const ldpc_graph *g = d->g;
+    std::vector<ResVCheck> placed;                               // compact plan: the checks in position order
+    if (cl)
+        for (int c : cl->check_at) placed.push_back(sorted[c]);
+    const std::vector<ResVCheck> &vc = cl ? placed : sorted;
     const int n = g->n, m = (int)vc.size();
     const bool any_split = m != g->m;
     int max_sub = 0;
@@ -1306,6 +1476,7 @@ int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::v
         for (int t = 0; t < vc[p].dc; ++t) slot_of_edge[vc[p].e0 + t] = t * mstride + p;
     if (cl) {
         perm_v = cl->var_at;                                     // position -> variable, -1 = empty
+        slot_of_edge = cl->slot_of_edge;                         // rows of a check in the placement's order
     } else {   // slots are fixed by the check order alone; choose the variable order inside each degree class
         std::vector<std::vector<int>> vs(n);
         for (int j = 0; j < n; ++j)
@@ -1331,7 +1502,7 @@ int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::v
         dc_s[p] = (uint8_t)v.dc;
         gsz[p] = (uint8_t)v.gs;
         for (int t = 0; t < v.dc; ++t) {
-            const int e = v.e0 + t, slot = t * mstride + p;
+            const int e = v.e0 + t, slot = slot_of_edge[e];
             edge_of_slot[slot] = (uint32_t)e;
             cvar[slot] = (uint16_t)pos_v[g->h_var_idx[e]];
             bslot[slot] = (uint16_t)desc->beta_slot[e];
@@ -2506,6 +2677,51 @@ int ldpc_debug_compact_checks(const ldpc_decoder *d, int32_t n, int32_t m, int32
                               const int32_t *var_idx, uint32_t words[8])
 {
     LDPC_NOTHROW(compact_checks_impl(d, n, m, E, check_ptr, var_idx, words))
+}
+
+static int compact_banks_impl(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                              const int32_t *var_idx, int32_t *slot_of_edge, int32_t *pos_of_check, int32_t *model,
+                              int32_t *base_slot_of_edge, int32_t *base_pos_of_check, int32_t *base_model,
+                              int32_t *geometry)
+{
+    CptLayout own;
+    ldpc_graph own_g;                                    // host copies only: no device is touched
+    const CptLayout *L = &own;
+    const ldpc_graph *g = &own_g;
+    std::vector<ResVCheck> vc;
+    long long Sc = 0;
+    if (d) {
+        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
+        L = &d->resc_layout;
+        g = d->g;
+        Sc = d->resc.S;
+        if (!resident_checks(g, vc)) return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
+    } else {
+        if (int rc = graph_host_build(&own_g, n, m, E, check_ptr, var_idx)) return rc;
+        if (!resident_checks(g, vc) || !cpt_geometry(g, vc, Sc))
+            return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
+        cpt_layout(g, vc, Sc, own);
+    }
+    auto emit = [&](const std::vector<int> &slots, const std::vector<int> &check_at, const int (&banks)[4],
+                    int32_t *slots_out, int32_t *pos_out, int32_t *model_out) {
+        if (slots_out) std::copy(slots.begin(), slots.end(), slots_out);
+        if (pos_out)
+            for (int p = 0; p < (int)check_at.size(); ++p) pos_out[vc[check_at[p]].check] = p;
+        if (model_out) std::copy(banks, banks + 4, model_out);
+    };
+    emit(L->slot_of_edge, L->check_at, L->banks, slot_of_edge, pos_of_check, model);
+    emit(L->base_slot_of_edge, L->base_check_at, L->base_banks, base_slot_of_edge, base_pos_of_check, base_model);
+    if (geometry) { geometry[0] = kResCptStride; geometry[1] = (int32_t)Sc; }
+    return LDPC_OK;
+}
+
+int ldpc_debug_compact_banks(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                             const int32_t *var_idx, int32_t *slot_of_edge, int32_t *pos_of_check, int32_t model[4],
+                             int32_t *base_slot_of_edge, int32_t *base_pos_of_check, int32_t base_model[4],
+                             int32_t geometry[2])
+{
+    LDPC_NOTHROW(compact_banks_impl(d, n, m, E, check_ptr, var_idx, slot_of_edge, pos_of_check, model, base_slot_of_edge,
+                                    base_pos_of_check, base_model, geometry))
 }
 
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,

@@ -1144,7 +1144,14 @@ constexpr int kResMinWaves = 4;        // register allocation must leave room fo
 constexpr int kResCptThreads = 512;
 constexpr int kResCptWaves = 6;
 constexpr int kResCptBlocks = 3;       // workgroups per CU the compact LDS carve must allow
-constexpr int kResCptStride = 496;     // compile-time row stride of the compact slot layout (m <= 496)
+// compile-time row stride of the compact slot layout (m <= 495).  Odd: with an even stride the bank of slot(p,t) =
+// t*stride + p depends on p alone (496 = 0 mod 16 for the scatters) or on p and the parity of t (16 mod 32 for the
+// gathers), so the rows give the host's placement search (cpt_place_banks) nothing to choose from.  495 and not 497: the
+// (1998,1512) code at stride 496 takes 53,760 bytes of LDS, exactly a third of the CU's 128 allocation granules of 1,280
+// bytes, and at 497 (53,856 bytes, under 160 KiB / 3 all the same) only two workgroups were resident per CU and the launch
+// took 2.46 ms instead of 2.08 (profiles/README.md, r09).  The check phase is unaffected: consecutive p are consecutive
+// 8-byte slots at any row base
+constexpr int kResCptStride = 495;
 // REG: variable state in registers (ResVarState; the host takes it for fixed-T decodes of codes that qualify, see
 // resident_reg_state)
 // CPT: compact fixed-T kernel (REG, fp32, no split checks): res_cpt_lds_total bytes of LDS, so that kResCptBlocks
@@ -1411,7 +1418,7 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
     // fixed-T mode: success = final syndrome is zero.  With parity words (power-of-two stride) the posterior pass scatters the
     // decisions into them (one LDS atomic per edge, then m words are read); otherwise the decisions go into the dead message
     // slots and every check reads its row of them back (MODE 8 / res_syndrome_slots)
-    const bool scatter = !ES && !CPT && psf.par_off != 0;   // compact plans: row stride 496, no parity words
+    const bool scatter = !ES && !CPT && psf.par_off != 0;   // compact plans: odd row stride, no parity words
     if (ES) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     else if (scatter) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st, psf);
     else res_var_phase<G, CPT ? 9 : 8, T, REG, CPT>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);

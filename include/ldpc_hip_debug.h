@@ -59,6 +59,19 @@ int ldpc_debug_compact_layout(const ldpc_decoder *d, int32_t n, int32_t m, int32
 int ldpc_debug_compact_checks(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
                               const int32_t *var_idx, uint32_t words[8]);
 
+/* Slot placement of the compact fixed-T plan and its LDS bank model (host only, arguments as ldpc_debug_compact_layout).
+ * Check position p (< m) runs one check; its dc edges sit in the slots row * geometry[0] + p, rows 0 .. dc-1 in an order
+ * the planner chooses.  slot_of_edge[E] (CSR edge order) and pos_of_check[m] describe the placement the plan ships;
+ * model = { gather cost, gather groups, scatter cost, scatter groups } of one variable phase in LDS-array cycles: a group
+ * is the 32 lanes of one ds_read_b64 (16 of one ds_write_b64) that hold at least one edge, its cost the largest number of
+ * its lanes on one bank, slot mod 32 (slot mod 16).  base_* is the same for the placement the planner starts from: checks
+ * in stable degree order, rows in CSR order, variables placed by the variables-only search.  geometry = { row stride,
+ * slots Sc }.  Output pointers may be NULL. */
+int ldpc_debug_compact_banks(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                             const int32_t *var_idx, int32_t *slot_of_edge, int32_t *pos_of_check, int32_t model[4],
+                             int32_t *base_slot_of_edge, int32_t *base_pos_of_check, int32_t base_model[4],
+                             int32_t geometry[2]);
+
 /* The variable sweep of the RCQ code-pair form turns every outgoing value v into the key
  * [m > 0] + [m >= t1] + [m >= t2] + [m >= t3] of m = |beta * v| (thresholds4[0] is not used; device pointers, thresholds
  * within [2^-50, 2^50]).  Runs BOTH device forms of that key on `count` arbitrary values: the float form the 4-level
