@@ -1571,13 +1571,57 @@ bool resident_reg_state(const ldpc_decoder *d)
     return !d->res.any_split && d->res.n <= kResRegVars * d->res_NT && d->res.n_hi <= d->res_NT;
 }
 
+// What a decode of d launches on the LDS-resident engine in stop mode `early_stop`: the plan and the template arguments
+// of resident_decode.  The ONE place that holds these predicates: launch_resident switches on the fields, and
+// ldpc_debug_resident_kernel reports them.
+enum { kResPlanGeneral = 0, kResPlanReg = 1, kResPlanCompact = 2 };
+struct ResidentKernel {
+    int plan;            // kResPlanGeneral: streaming variable loop; kResPlanReg: register-held variable state (d->res);
+                         // kResPlanCompact: the compact fixed-T geometry (d->resc)
+    int G, form, nl, ms; // template arguments of the KERNEL: codewords per workgroup, FORM_*, NL and MS (0: the run-time value).
+                         // G is 1 for fp64 although the host dispatch is launch_resident<2> (the plan's geometry is a float
+                         // pair's); the launcher does not read it, only the hook reports it
+    bool bpc, split, f64;
+    bool alpha_in_lds;   // ResidentArgs::alpha_in_lds of the launch
+};
+
+ResidentKernel resident_kernel(const ldpc_decoder *d, bool early_stop)
+{
+    ResidentKernel k{};
+    const bool reg = resident_reg_state(d) && !early_stop;
+    k.form = d->form == LDPC_C2V_NMS ? FORM_NMS : d->form == LDPC_C2V_OMS ? FORM_OMS : FORM_RCQ;
+    k.f64 = d->dtype == LDPC_F64;
+    k.alpha_in_lds = resident_alpha_floats(d) > 0;
+    if (d->resc_ok && !early_stop) {   // compact fixed-T geometry, three workgroups per CU (resc_ok implies fp32 and G = 2)
+        k.plan = kResPlanCompact;
+        k.G = 2;
+        k.bpc = d->resc.bslot_c != nullptr;
+        k.nl = (k.form == FORM_RCQ && d->n_levels == 4) ? 4 : 0;
+        k.ms = kResCptStride;
+        k.alpha_in_lds = false;                       // no alpha table in the compact carve: read from global memory
+        return k;
+    }
+    // codes with split (wide) checks run the generic instantiation (run-time stride and level count) with the lane-group
+    // exchange compiled in -- the specialised ones stay exactly as lean as without the feature
+    k.G = k.f64 ? 1 : d->res_G;                       // one fp64 codeword per workgroup in the slots of a float pair
+    k.bpc = d->res.bslot_c != nullptr;
+    k.split = d->res.any_split != 0;
+    k.ms = (!k.split && d->res.mstride == 512) ? 512 : 0;
+    k.nl = (!k.split && k.form == FORM_RCQ && d->n_levels == 4) ? 4 : 0;   // bc = 3, the paper's and the benchmark's quantiser
+    k.plan = (!k.split && reg) ? kResPlanReg : kResPlanGeneral;
+    return k;
+}
+
 template <int G>
-int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
+int launch_resident(const ldpc_decoder *d, const ResidentArgs &args, hipStream_t s)
 {
     const size_t lds = d->res_lds;
-    const bool reg = resident_reg_state(d) && !a.early_stop;
-    if (d->dtype == LDPC_F64) {                       // one fp64 codeword per workgroup in the slots of a float pair
-        if (G != 2 || !d->res.bslot_c) return fail(LDPC_ERR_ARG, "internal: fp64 resident geometry");
+    const ResidentKernel k = resident_kernel(d, args.early_stop);
+    const bool reg = k.plan == kResPlanReg;
+    ResidentArgs a = args;
+    a.alpha_in_lds = k.alpha_in_lds;
+    if (k.f64) {
+        if (G != 2 || !k.bpc) return fail(LDPC_ERR_ARG, "internal: fp64 resident geometry");
         const unsigned blocks64 = (unsigned)a.batch;
 #define LDPC_RES64(MS, SPLIT, REG)                                                                        \
     do {                                                                                                  \
@@ -1586,9 +1630,8 @@ int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
         if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                        \
         hipLaunchKernelGGL(kfn, dim3(blocks64), dim3(d->res_NT), lds, s, d->res, a);                      \
     } while (0)
-        // codes with split (wide) checks run the generic-stride instantiation with the lane-group exchange compiled in
-        if (d->res.any_split) LDPC_RES64(0, true, false);
-        else if (d->res.mstride == 512) { if (reg) LDPC_RES64(512, false, true); else LDPC_RES64(512, false, false); }
+        if (k.split) LDPC_RES64(0, true, false);
+        else if (k.ms == 512) { if (reg) LDPC_RES64(512, false, true); else LDPC_RES64(512, false, false); }
         else if (reg) LDPC_RES64(0, false, true);
         else LDPC_RES64(0, false, false);
 #undef LDPC_RES64
@@ -1597,19 +1640,17 @@ int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
     }
     const unsigned blocks = (unsigned)((a.batch + G - 1) / G);
     if constexpr (G == 2) {
-        if (d->resc_ok && !a.early_stop) {            // compact fixed-T geometry: three workgroups per CU
-            ResidentArgs ac = a;
-            ac.alpha_in_lds = 0;                      // no alpha table in the compact carve: read from global memory
+        if (k.plan == kResPlanCompact) {
 #define LDPC_RES_CPT(FORM, NL)                                                                                         \
     do {                                                                                                               \
-        auto kfn = d->resc.bslot_c ? resident_decode<2, FORM, true, NL, kResCptStride, 0, float, false, true, true>    \
-                                   : resident_decode<2, FORM, false, NL, kResCptStride, 0, float, false, true, true>;  \
+        auto kfn = k.bpc ? resident_decode<2, FORM, true, NL, kResCptStride, 0, float, false, true, true>              \
+                         : resident_decode<2, FORM, false, NL, kResCptStride, 0, float, false, true, true>;            \
         if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                                     \
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kResCptThreads), d->resc_lds, s, d->resc, ac);                      \
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kResCptThreads), d->resc_lds, s, d->resc, a);                       \
     } while (0)
-            if (d->form == LDPC_C2V_NMS) LDPC_RES_CPT(FORM_NMS, 0);
-            else if (d->form == LDPC_C2V_OMS) LDPC_RES_CPT(FORM_OMS, 0);
-            else if (d->n_levels == 4) LDPC_RES_CPT(FORM_RCQ, 4);
+            if (k.form == FORM_NMS) LDPC_RES_CPT(FORM_NMS, 0);
+            else if (k.form == FORM_OMS) LDPC_RES_CPT(FORM_OMS, 0);
+            else if (k.nl == 4) LDPC_RES_CPT(FORM_RCQ, 4);
             else LDPC_RES_CPT(FORM_RCQ, 0);
 #undef LDPC_RES_CPT
             HIP_TRY(hipGetLastError());
@@ -1618,27 +1659,25 @@ int launch_resident(const ldpc_decoder *d, const ResidentArgs &a, hipStream_t s)
     }
 #define LDPC_RES_MS(FORM, NL, MS, SPLIT, REG)                                                            \
     do {                                                                                                 \
-        auto kfn = d->res.bslot_c ? (a.early_stop ? resident_decode<G, FORM, true, NL, MS, 1, float, SPLIT, false>   \
-                                                  : resident_decode<G, FORM, true, NL, MS, 0, float, SPLIT, REG>)    \
-                                  : (a.early_stop ? resident_decode<G, FORM, false, NL, MS, 1, float, SPLIT, false>  \
-                                                  : resident_decode<G, FORM, false, NL, MS, 0, float, SPLIT, REG>);  \
+        auto kfn = k.bpc ? (a.early_stop ? resident_decode<G, FORM, true, NL, MS, 1, float, SPLIT, false>            \
+                                         : resident_decode<G, FORM, true, NL, MS, 0, float, SPLIT, REG>)             \
+                         : (a.early_stop ? resident_decode<G, FORM, false, NL, MS, 1, float, SPLIT, false>           \
+                                         : resident_decode<G, FORM, false, NL, MS, 0, float, SPLIT, REG>);           \
         if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                       \
         hipLaunchKernelGGL(kfn, dim3(blocks), dim3(d->res_NT), lds, s, d->res, a);                       \
     } while (0)
-    // codes with split (wide) checks: the generic instantiation (run-time stride and level count) with the lane-group
-    // exchange compiled in -- the specialised ones stay exactly as lean as without the feature
 #define LDPC_RES(FORM, NL)                                                                               \
     do {                                                                                                 \
-        if (d->res.any_split) LDPC_RES_MS(FORM, 0, 0, true, false);                                      \
-        else if (d->res.mstride == 512) {                                                                \
+        if (k.split) LDPC_RES_MS(FORM, 0, 0, true, false);                                               \
+        else if (k.ms == 512) {                                                                          \
             if (reg) LDPC_RES_MS(FORM, NL, 512, false, true);                                            \
             else LDPC_RES_MS(FORM, NL, 512, false, false);                                               \
         } else if (reg) LDPC_RES_MS(FORM, NL, 0, false, true);                                           \
         else LDPC_RES_MS(FORM, NL, 0, false, false);                                                     \
     } while (0)
-    if (d->form == LDPC_C2V_NMS) LDPC_RES(FORM_NMS, 0);
-    else if (d->form == LDPC_C2V_OMS) LDPC_RES(FORM_OMS, 0);
-    else if (d->n_levels == 4) LDPC_RES(FORM_RCQ, 4);       // bc = 3, the paper's and the benchmark's quantiser
+    if (k.form == FORM_NMS) LDPC_RES(FORM_NMS, 0);
+    else if (k.form == FORM_OMS) LDPC_RES(FORM_OMS, 0);
+    else if (k.nl == 4) LDPC_RES(FORM_RCQ, 4);
     else LDPC_RES(FORM_RCQ, 0);
 #undef LDPC_RES_MS
 #undef LDPC_RES
@@ -1660,7 +1699,6 @@ int decode_resident(const ldpc_decoder *d, const void *llr, int64_t batch, int32
     a.bits = bits; a.posterior = (float *)posterior; a.iterations = iterations; a.success = success;
     a.packed = packed_bits;
     a.dbg_c2v = dbg_c2v;
-    a.alpha_in_lds = resident_alpha_floats(d) > 0;
     a.unit_alpha = d->unit_alpha; a.rcq_zero0 = d->rcq_zero0;
     hipStream_t rs = (hipStream_t)stream;
     switch (d->res_G) {
@@ -2722,6 +2760,20 @@ int ldpc_debug_compact_banks(const ldpc_decoder *d, int32_t n, int32_t m, int32_
 {
     LDPC_NOTHROW(compact_banks_impl(d, n, m, E, check_ptr, var_idx, slot_of_edge, pos_of_check, model, base_slot_of_edge,
                                     base_pos_of_check, base_model, geometry))
+}
+
+int ldpc_debug_resident_kernel(const ldpc_decoder *d, int32_t early_stop, int32_t out12[12])
+{
+    if (!d || !out12) return fail(LDPC_ERR_ARG, "NULL argument");
+    if (d->schedule != LDPC_SCHED_FLOODING || !use_resident(d))       // the layered schedules never launch resident_decode
+        return fail(LDPC_ERR_UNSUPPORTED, "the decoder does not decode with resident_decode (flooding schedule on the LDS-resident engine)");
+    const ResidentKernel k = resident_kernel(d, early_stop != 0);
+    const ResidentPlan &pl = k.plan == kResPlanCompact ? d->resc : d->res;
+    const int32_t out[12] = {k.plan, k.G, k.form == FORM_NMS ? LDPC_C2V_NMS : k.form == FORM_OMS ? LDPC_C2V_OMS : LDPC_C2V_RCQ,
+                             k.bpc, k.nl, k.ms, pl.mstride, k.split, d->unit_alpha, d->rcq_zero0,
+                             d->form == LDPC_C2V_OMS && d->oms_alpha != nullptr, k.alpha_in_lds};
+    std::copy(out, out + 12, out12);
+    return LDPC_OK;
 }
 
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,

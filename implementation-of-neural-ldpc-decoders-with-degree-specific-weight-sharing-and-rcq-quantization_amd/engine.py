@@ -211,11 +211,26 @@ class DecodeEngine:
             nat.check(self._lib.ldpc_debug_compact_checks(self.handle, 0, 0, 0, None, None, nat.ptr(words)),
                       "ldpc_debug_compact_checks")
             plan["scalar_check_waves"] = int(np.count_nonzero((words != 0) & (words >> 31 == 0)))
+        # what a flooding decode launches on the resident engine, per stop mode (None on the streaming engine)
+        kernels = None
+        if resident and self.schedule == nat.SCHED_FLOODING:
+            kernels = {"fixed_T": self._resident_kernel(False), "early_stop": self._resident_kernel(True)}
         return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel,
                 "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
                 "codewords_per_workgroup": int(out[1]),
                 "threads_per_workgroup": threads, "lds_bytes": lds, "workgroups_per_cu": per_cu,
-                "compact_plan": plan}
+                "compact_plan": plan, "resident_kernel": kernels}
+
+    def _resident_kernel(self, early_stop: bool) -> dict:
+        """the resident_decode instantiation and table flags of a decode in this stop mode (ldpc_debug_resident_kernel)"""
+        o = np.zeros(12, dtype=np.int32)
+        nat.check(self._lib.ldpc_debug_resident_kernel(self.handle, int(early_stop), nat.ptr(o)),
+                  "ldpc_debug_resident_kernel")
+        return {"plan": ("general", "register-state", "compact")[int(o[0])], "G": int(o[1]),
+                "form": {nat.C2V_NMS: "NMS", nat.C2V_RCQ: "RCQ", nat.C2V_OMS: "OMS"}[int(o[2])], "bpc": bool(o[3]),
+                "nl": int(o[4]), "ms": int(o[5]), "row_stride": int(o[6]), "split": bool(o[7]),
+                "unit_alpha": bool(o[8]), "rcq_zero0": bool(o[9]), "oms_alpha": bool(o[10]),
+                "alpha_in_lds": bool(o[11])}
 
     # ------------------------------------------------------------------ weights
     def set_weights(self, beta: Optional[np.ndarray], alpha: Optional[np.ndarray],

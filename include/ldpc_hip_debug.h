@@ -5,7 +5,7 @@
  * reference interface corresponds to it.  bench.py uses ldpc_debug_sweep to time one sweep kernel
  * with HIP events; the parity tests use the two state dumps to compare per-edge check-to-variable
  * messages (for RCQ: the 3-bit quantiser codes the reference emits, rcq_decoder.py:244-246) on BOTH
- * engines.
+ * engines; ldpc_debug_resident_kernel lets a test assert WHICH resident kernel and table flags a decode runs.
  */
 #ifndef LDPC_HIP_DEBUG_H
 #define LDPC_HIP_DEBUG_H
@@ -37,6 +37,17 @@ int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t ma
 int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,
                             int32_t max_iterations, void *posterior, int32_t *iterations, void *c2v_out,
                             void *stream);
+
+/* The kernel a decode of d runs on the LDS-resident engine (host only, no device is touched), for early_stop != 0 or the
+ * fixed-T decode: out12 = { plan, G, FORM, BPC, NL, MS, row stride, SPLIT, unit_alpha, rcq_zero0, oms_alpha, alpha_in_lds }.
+ * plan: 0 general (streaming variable loop), 1 register-held variable state, 2 the compact fixed-T plan.  G, FORM
+ * (LDPC_C2V_*), BPC (one beta slot per check), NL (compile-time level count, 0: run time), MS (compile-time row stride, 0:
+ * run time) and SPLIT are the template arguments of resident_decode; row stride is the plan's own.  The last four are the
+ * table properties the kernel branches on: every alpha exactly 1, every quantiser's tau_0 == 0, a check-side alpha table
+ * of the offset form, the alpha table staged in LDS.  The launcher and this hook read one selection (csrc/ldpc_hip.hip,
+ * resident_kernel).  G is the kernel's (1 for fp64: one codeword in the slots of a float pair).  LDPC_ERR_UNSUPPORTED when the
+ * decoder's mode does not put it on the resident engine or its schedule is layered (those never launch resident_decode). */
+int ldpc_debug_resident_kernel(const ldpc_decoder *d, int32_t early_stop, int32_t out12[12]);
 
 /* Compact fixed-T plan of the LDS-resident engine (host only, no device is touched).  The kernel runs the variable at
  * position q = r*512 + w*64 + lane in round r (< 4) of wave w (< 8); cells[w*4 + r] describes cell (w, r): 0 empty,
