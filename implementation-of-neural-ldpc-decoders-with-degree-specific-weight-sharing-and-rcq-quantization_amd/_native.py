@@ -38,7 +38,9 @@ class NativeEngineError(RuntimeError):
     pass
 
 
-SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip")
+# the one compiled unit first, then everything it includes
+SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
+           "ldpc_resident_geom.h", "ldpc_plan.h")
 
 
 def _source_files():

@@ -7,6 +7,7 @@
 #include "ldpc_resident.hip"
 #include "ldpc_train.hip"
 #include "ldpc_layered.hip"
+#include "ldpc_plan.h"
 
 #include <algorithm>
 #include <climits>
@@ -73,40 +74,12 @@ struct DeviceGuard {
 
 }  // namespace
 
-struct ldpc_graph {
+struct ldpc_graph : HostGraph {   // the host copies (ldpc_plan.h) and their device images
     int device = 0;
-    int n = 0, m = 0, E = 0, max_dc = 0, max_dv = 0;
     int *check_ptr = nullptr, *var_idx = nullptr, *var_ptr = nullptr, *csc_edge = nullptr;
     int *wide_checks = nullptr;    // checks of degree > kWideCheck (cn_sweep_wide splits each over a block)
     int n_wide = 0;
-    std::vector<int> h_check_ptr, h_var_idx, h_var_ptr, h_csc, h_check_of_edge;   // host copies (resident-plan builder)
     GraphDev dev() const { return GraphDev{n, m, E, check_ptr, var_idx, var_ptr, csc_edge}; }
-};
-
-// Compact plan: variables on a (round, wave, lane) grid.
-// The compact kernel (kResCptThreads = 512 lanes, kResRegVars = 4 rounds) runs the variable at position
-// q = r*512 + w*64 + lane in round r of wave w.  Every variable phase ends at a workgroup barrier, so the phase costs
-// what its busiest wave costs; a cell (w, r) whose 64 lanes share one degree runs one body behind a scalar branch
-// (ResidentPlan::vcell), a mixed cell runs the body of every degree it holds.  Cost of one body, in VALU-equivalents,
-// from the instruction model (not from ISA counts): dv leave-one-out sums of dv-1 terms each, formed separately in the
-// reference's association order (<= dv*(dv-1) adds), 2*dv LDS operations and ~4 for the offset unpacking.
-constexpr int kCptWaves = kResCptThreads / 64;
-constexpr int kCptCells = kCptWaves * kResRegVars;
-constexpr int kCptMaxDv = 8;
-constexpr long kCptJointTrials = 3000000;    // budget of the joint bank-aware placement search (cpt_place_banks)
-inline int cpt_body_cost(int dv) { return dv * (dv - 1) + 2 * dv + 4; }
-
-struct CptLayout {
-    std::vector<int> var_at;       // [n_pos] variable at grid position q, -1 = empty
-    unsigned cell[kCptWaves] = {}; // ResidentPlan::vcell
-    int worst = 0, total = 0;      // largest and summed per-wave cost of one variable phase (cpt_body_cost model)
-    int mixed = 0;                 // cells of kind kCellMixed
-    // slot placement (cpt_place_banks): check position p runs the check vc[check_at[p]] of the degree-sorted list, edge e
-    // sits in slot slot_of_edge[e] = row * kResCptStride + p.  banks = { gather cost, gather groups, scatter cost,
-    // scatter groups } of one variable phase under the LDS model (BankModel); base_* is the same for the placement of
-    // the stable check order with rows in CSR order and the variables-only search, the starting point of the joint one
-    std::vector<int> check_at, slot_of_edge, base_check_at, base_slot_of_edge;
-    int banks[4] = {}, base_banks[4] = {};
 };
 
 struct ldpc_decoder {
@@ -829,724 +802,72 @@ void beta_table_flags(ldpc_decoder *d, const void *beta_host)
     d->beta_unit = unit;
 }
 
-// ---- LDS-resident engine: plan (host) ---------------------------------------------------------
-constexpr size_t kLdsBytes = 160 * 1024;          // LDS per CU; one workgroup may take all of it
-constexpr int kResSubDegreeCap = 32;              // checks up to this degree stay whole in the resident engine ...
-constexpr int kResSubDegree = 16;                 // ... wider ones are split into lane groups of sub-checks this long
+// ---- LDS-resident engine: plan upload (the planner is ldpc_plan.h) ------------------------------
+static_assert(kPlanF32 == LDPC_F32 && kPlanF64 == LDPC_F64 && kPlanNMS == LDPC_C2V_NMS && kPlanRCQ == LDPC_C2V_RCQ &&
+              kPlanOMS == LDPC_C2V_OMS, "the planner's dtype and form values are the C ABI's");
+static_assert(sizeof(Word2) == sizeof(uint2) && alignof(Word2) <= alignof(uint2) && offsetof(Word2, x) == offsetof(uint2, x) &&
+              offsetof(Word2, y) == offsetof(uint2, y), "Word2 tables are uploaded as uint2");
 
-template <typename X>
-int plan_upload(ldpc_decoder *d, const X **dst, const std::vector<X> &src)
+template <typename X, typename H>
+int plan_upload(ldpc_decoder *d, const X **dst, const std::vector<H> &src)
 {
+    static_assert(sizeof(X) == sizeof(H), "host and device element");
     X *p = nullptr;
-    int rc = upload(&p, src.data(), src.size());
+    int rc = upload(&p, reinterpret_cast<const X *>(src.data()), src.size());
     if (rc) return rc;
     d->res_bufs.push_back((void *)p);
     *dst = p;
     return LDPC_OK;
 }
 
-int resident_alpha_floats(const ldpc_decoder *d)
+// one planned geometry to the device: the scalars into pl, the tables into allocations owned by d->res_bufs
+int upload_plan(ldpc_decoder *d, const PlanTables &t, ResidentPlan &pl)
 {
-    if (d->dtype != LDPC_F32) return 0;                 // the fp64 kernel reads alpha from global memory
-    const long long cnt = (long long)d->T * d->n_alpha;
-    return cnt <= kResAlphaMax ? (int)cnt : 0;
+    pl = ResidentPlan{};
+    pl.n = t.n; pl.m = t.m; pl.S = t.S; pl.max_dc = t.max_dc; pl.max_dv = t.max_dv; pl.mstride = t.mstride; pl.E = t.E;
+    pl.any_split = t.any_split; pl.par_words = t.par_words; pl.par_shift = t.par_shift;
+    pl.n_hi = t.n_hi; pl.n_pos = t.n_pos;
+    std::copy(t.vcell, t.vcell + 8, pl.vcell);
+    std::copy(t.ccell, t.ccell + 8, pl.ccell);
+    int rc = plan_upload(d, &pl.dc_s, t.dc_s);
+    if (!rc && t.any_split) rc = plan_upload(d, &pl.gsz, t.gsz);
+    if (!rc) rc = plan_upload(d, &pl.cvar, t.cvar);
+    if (!rc) rc = plan_upload(d, &pl.bslot, t.bslot);
+    if (!rc && t.per_check) rc = plan_upload(d, &pl.bslot_c, t.bslot_c);
+    if (!rc && t.has_oaslot) rc = plan_upload(d, &pl.oaslot, t.oaslot);
+    if (!rc) rc = plan_upload(d, &pl.vmeta, t.vmeta);
+    if (!rc) rc = plan_upload(d, &pl.vslot_lo, t.vslot_lo);
+    if (!rc) rc = plan_upload(d, &pl.vslot_hi, t.vslot_hi);
+    if (!rc) rc = plan_upload(d, &pl.inv_perm_v, t.inv_perm_v);
+    if (!rc) rc = plan_upload(d, &pl.edge_of_slot, t.edge_of_slot);
+    return rc;
 }
 
-// G codewords per workgroup fit when the state is within LDS and slot byte offsets fit 16 bits
-bool resident_fits(const ldpc_decoder *d, long long S, int G, int blocks, int m_par)
+PlanInputs plan_inputs(const ldpc_decoder *d, const ldpc_decoder_desc *desc)
 {
-    if (S * G * 4 > 65535) return false;
-    return blocks * res_lds_total((int)S, d->g->n, G, resident_alpha_floats(d), m_par) <= kLdsBytes;
-}
-bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-
-// ---- LDS bank-conflict-aware lane assignment -------------------------------------------------
-// The check phase touches consecutive slots (conflict-free by construction); the variable phase
-// gathers/scatters the slots of a variable's edges, so which variables share a wave decides how
-// many LDS passes those accesses take.  Any order of the variables INSIDE a degree class is valid,
-// so a seeded hill climb swaps variables between lane groups whenever that lowers
-//     sum over read groups  (32 lanes) of  max multiplicity of (slot mod RM)
-//   + sum over write groups (WG lanes) of  max multiplicity of (slot mod WM)
-// (RM/WG/WM follow the instruction's banking: ds_read_b64 64 banks, ds_write_b64 32 banks in
-// 16-lane groups; MI355X_MICROARCH.md "LDS").  On the (1998,1512) code the gathers go from 3.3 to
-// ~2.1 passes per instruction, the scatters from 2.9 to ~2.0.  Purely a performance choice.
-struct LaneCost {
-    const std::vector<std::vector<int>> &vs;   // slots of each variable, CSC order
-    const std::vector<int> &order;
-    int rg, rm, wg, wm;
-    int group(int first, int count, int mod) const
-    {
-        const int last = std::min<int>(first + count, (int)order.size());
-        int kmax = 0;
-        for (int i = first; i < last; ++i) kmax = std::max<int>(kmax, (int)vs[order[i]].size());
-        int cost = 0;
-        unsigned char cnt[64];
-        for (int k = 0; k < kmax; ++k) {
-            std::memset(cnt, 0, sizeof(cnt));
-            int mx = 0;
-            for (int i = first; i < last; ++i) {
-                const auto &v = vs[order[i]];
-                if ((int)v.size() > k) mx = std::max<int>(mx, ++cnt[v[k] % mod]);
-            }
-            cost += mx;
-        }
-        return cost;
-    }
-    int around(int x, int y) const            // cost of every group containing position x or y
-    {
-        int c = group(x / rg * rg, rg, rm) + group(x / wg * wg, wg, wm);
-        if (y / rg != x / rg) c += group(y / rg * rg, rg, rm);
-        if (y / wg != x / wg) c += group(y / wg * wg, wg, wm);
-        return c;
-    }
-};
-
-void optimise_lane_order(std::vector<int> &order, const std::vector<std::vector<int>> &vs, int G)
-{
-    if (G != 1 && G != 2) return;
-    LaneCost lc{vs, order, 32, 32, G == 2 ? 16 : 32, G == 2 ? 16 : 32};
-    const int n = (int)order.size();
-    std::vector<std::pair<int, int>> classes;
-    for (int i = 0; i < n;) {
-        int j = i;
-        while (j < n && vs[order[j]].size() == vs[order[i]].size()) ++j;
-        if (j - i >= 2 && !vs[order[i]].empty()) classes.push_back({i, j});
-        i = j;
-    }
-    if (classes.empty()) return;
-    uint64_t rng = 0x9E3779B97F4A7C15ull;
-    auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
-    const long trials = std::min<long>(400000, 150L * n);
-    for (long it = 0; it < trials; ++it) {
-        const auto &c = classes[next() % classes.size()];
-        const int x = c.first + (int)(next() % (uint64_t)(c.second - c.first));
-        const int y = c.first + (int)(next() % (uint64_t)(c.second - c.first));
-        if (x / lc.wg == y / lc.wg) continue;
-        const int before = lc.around(x, y);
-        std::swap(order[x], order[y]);
-        if (lc.around(x, y) > before) std::swap(order[x], order[y]);
-    }
+    PlanInputs in;
+    in.dtype = d->dtype; in.form = d->form; in.T = d->T;
+    in.n_beta = d->n_beta; in.n_alpha = d->n_alpha; in.n_oms_alpha = d->n_oms_alpha;
+    in.beta_per_check = d->beta_per_check; in.rcq_zero0 = d->rcq_zero0;
+    in.has_oms_alpha = desc->oms_alpha != nullptr;
+    in.beta_slot = desc->beta_slot; in.alpha_slot = desc->alpha_slot; in.oms_alpha_slot = desc->oms_alpha_slot;
+    return in;
 }
 
-// ---- compact plan: variables on a (round, wave, lane) grid (CptLayout) --------------------------
-// cell bytes and model costs of a grid (any placement: the balanced one or the degree-sorted fallback)
-void cpt_cells(const std::vector<int> &dv, CptLayout &L)
-{
-    const int n_pos = (int)L.var_at.size();
-    L.worst = L.total = L.mixed = 0;
-    for (int w = 0; w < kCptWaves; ++w) {
-        L.cell[w] = 0;
-        int wave = 0;
-        for (int r = 0; r < kResRegVars; ++r) {
-            bool has[kCptMaxDv + 1] = {};
-            int used = 0, kinds = 0, deg = 0, cost = 0;
-            for (int lane = 0; lane < 64; ++lane) {
-                const int q = r * kResCptThreads + w * 64 + lane;
-                const int j = q < n_pos ? L.var_at[q] : -1;
-                if (j < 0) continue;
-                ++used;
-                if (!has[dv[j]]) { has[dv[j]] = true; ++kinds; deg = dv[j]; cost += cpt_body_cost(dv[j]); }
-            }
-            unsigned byte = kCellEmpty;
-            if (used) byte = (kinds == 1 && deg > 0) ? (unsigned)deg | (used < 64 ? kCellHoles : 0u) : kCellMixed;
-            L.mixed += byte == kCellMixed ? 1 : 0;
-            L.cell[w] |= byte << (8 * r);
-            wave += cost;
-        }
-        L.worst = std::max(L.worst, wave);
-        L.total += wave;
-    }
-}
-
-// Balanced placement.  Cells are formed per degree (full cells of 64, one partial cell per degree); partial cells are
-// merged -- the pair whose merged cell costs least -- or, when no pair fits 64 lanes, the smallest one is poured into
-// the others' free lanes, until there are at most kCptCells cells and at most kCptWaves of them hold a degree > 4
-// (those need the upper offset half, which only round 0 carries).  Degree > 4 cells go to round 0 of distinct waves,
-// the others largest first to the cheapest wave with a free round; pairwise moves then lower the largest wave cost,
-// and the waves are ordered so that w and w + 4 (assumed to share a SIMD) carry equal totals.  Deterministic.
-bool cpt_assign(const std::vector<int> &dv, CptLayout &L)
-{
-    struct Cell { int cnt[kCptMaxDv + 1] = {}; int size = 0; };
-    auto hi = [](const Cell &c) { for (int d = 5; d <= kCptMaxDv; ++d) if (c.cnt[d]) return true; return false; };
-    auto cost = [](const Cell &c) { int k = 0; for (int d = 0; d <= kCptMaxDv; ++d) if (c.cnt[d]) k += cpt_body_cost(d); return k; };
-    const int n = (int)dv.size();
-    int cnt[kCptMaxDv + 1] = {};
-    for (int j = 0; j < n; ++j) {
-        if (dv[j] < 0 || dv[j] > kCptMaxDv) return false;
-        ++cnt[dv[j]];
-    }
-    std::vector<Cell> cells;
-    std::vector<char> partial;
-    for (int d = kCptMaxDv; d >= 0; --d) {
-        for (int k = cnt[d]; k > 0; k -= 64) {
-            Cell c; c.cnt[d] = c.size = std::min(k, 64);
-            cells.push_back(c);
-            partial.push_back(c.size < 64);
-        }
-    }
-    for (;;) {
-        int nhi = 0;
-        for (const Cell &c : cells) nhi += hi(c) ? 1 : 0;
-        const bool need_hi = nhi > kCptWaves;
-        if (!need_hi && (int)cells.size() <= kCptCells) break;
-        int a = -1, b = -1, best = INT_MAX;
-        for (int i = 0; i < (int)cells.size(); ++i)
-            for (int k = i + 1; k < (int)cells.size(); ++k) {
-                if (cells[i].size + cells[k].size > 64 || (need_hi && !(hi(cells[i]) && hi(cells[k])))) continue;
-                Cell m = cells[i];
-                for (int d = 0; d <= kCptMaxDv; ++d) m.cnt[d] += cells[k].cnt[d];
-                if (cost(m) < best) { best = cost(m); a = i; b = k; }
-            }
-        if (a < 0) {                                     // pour the smallest suitable cell into the others' free lanes
-            int src = -1;
-            for (int pass = 0; pass < 2 && src < 0; ++pass)
-                for (int i = 0; i < (int)cells.size(); ++i) {
-                    if (cells[i].size == 64 || hi(cells[i]) != (need_hi || pass == 1)) continue;
-                    if (src < 0 || cells[i].size < cells[src].size) src = i;
-                }
-            if (src < 0) return false;
-            const bool src_hi = hi(cells[src]);
-            for (int d = kCptMaxDv; d >= 0; --d)
-                while (cells[src].cnt[d] > 0) {
-                    int t = -1;
-                    for (int i = 0; i < (int)cells.size(); ++i) {
-                        if (i == src || cells[i].size == 64 || (src_hi && !hi(cells[i]))) continue;
-                        if (t < 0 || cells[i].size < cells[t].size) t = i;
-                    }
-                    if (t < 0) return false;
-                    const int k = std::min(cells[src].cnt[d], 64 - cells[t].size);
-                    cells[t].cnt[d] += k; cells[t].size += k;
-                    cells[src].cnt[d] -= k; cells[src].size -= k;
-                }
-            cells.erase(cells.begin() + src);
-            continue;
-        }
-        for (int d = 0; d <= kCptMaxDv; ++d) cells[a].cnt[d] += cells[b].cnt[d];
-        cells[a].size += cells[b].size;
-        cells.erase(cells.begin() + b);
-    }
-
-    // placement: slot[w][r] = cell index or -1
-    int slot[kCptWaves][kResRegVars];
-    for (auto &w : slot) for (int &x : w) x = -1;
-    int load[kCptWaves] = {};
-    std::vector<int> order((size_t)cells.size());
-    for (int i = 0; i < (int)cells.size(); ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-        if (hi(cells[x]) != hi(cells[y])) return hi(cells[x]);
-        return cost(cells[x]) > cost(cells[y]);
-    });
-    int next_hi = 0;
-    for (int i : order) {
-        if (hi(cells[i])) { slot[next_hi][0] = i; load[next_hi++] += cost(cells[i]); continue; }
-        int bw = -1;
-        for (int w = 0; w < kCptWaves; ++w) {
-            bool free_ = false;
-            for (int r = 0; r < kResRegVars; ++r) free_ = free_ || slot[w][r] < 0;
-            if (free_ && (bw < 0 || load[w] < load[bw])) bw = w;
-        }
-        if (bw < 0) return false;
-        for (int r = 0; r < kResRegVars; ++r)
-            if (slot[bw][r] < 0) { slot[bw][r] = i; break; }
-        load[bw] += cost(cells[i]);
-    }
-    // pairwise exchanges (a cell with an empty slot included): largest wave cost first, then the sum of squares
-    auto objective = [&](long long &mx, long long &sq) {
-        mx = 0; sq = 0;
-        for (int w = 0; w < kCptWaves; ++w) { mx = std::max<long long>(mx, load[w]); sq += (long long)load[w] * load[w]; }
-    };
-    for (bool improved = true; improved;) {
-        improved = false;
-        for (int x = 0; x < kCptCells; ++x)
-            for (int y = x + 1; y < kCptCells; ++y) {
-                const int wx = x / kResRegVars, rx = x % kResRegVars, wy = y / kResRegVars, ry = y % kResRegVars;
-                const int cx = slot[wx][rx], cy = slot[wy][ry];
-                if (wx == wy || (cx < 0 && cy < 0)) continue;
-                if ((cx >= 0 && hi(cells[cx]) && ry != 0) || (cy >= 0 && hi(cells[cy]) && rx != 0)) continue;
-                long long m0, s0, m1, s1;
-                objective(m0, s0);
-                const int kx = cx >= 0 ? cost(cells[cx]) : 0, ky = cy >= 0 ? cost(cells[cy]) : 0;
-                load[wx] += ky - kx; load[wy] += kx - ky;
-                objective(m1, s1);
-                if (m1 < m0 || (m1 == m0 && s1 < s0)) { std::swap(slot[wx][rx], slot[wy][ry]); improved = true; }
-                else { load[wx] -= ky - kx; load[wy] -= kx - ky; }
-            }
-    }
-    // waves w and w + 4: the heaviest with the lightest, and so on
-    int by_load[kCptWaves];
-    for (int w = 0; w < kCptWaves; ++w) by_load[w] = w;
-    std::stable_sort(by_load, by_load + kCptWaves, [&](int x, int y) { return load[x] > load[y]; });
-    int wave_of[kCptWaves];                              // new wave index -> old one
-    for (int k = 0; k < kCptWaves / 2; ++k) {
-        wave_of[k] = by_load[k];
-        wave_of[k + kCptWaves / 2] = by_load[kCptWaves - 1 - k];
-    }
-    // inside a wave: the degree > 4 cell in round 0, then by falling cost, empty rounds last
-    std::vector<std::vector<int>> of_deg(kCptMaxDv + 1);
-    for (int j = 0; j < n; ++j) of_deg[dv[j]].push_back(j);
-    size_t taken[kCptMaxDv + 1] = {};
-    L.var_at.assign((size_t)kCptCells * 64, -1);
-    for (int w = 0; w < kCptWaves; ++w) {
-        int cs[kResRegVars];
-        for (int r = 0; r < kResRegVars; ++r) cs[r] = slot[wave_of[w]][r];
-        std::stable_sort(cs, cs + kResRegVars, [&](int x, int y) {
-            if (x < 0 || y < 0) return x >= 0 && y < 0;
-            if (hi(cells[x]) != hi(cells[y])) return hi(cells[x]);
-            return cost(cells[x]) > cost(cells[y]);
-        });
-        for (int r = 0; r < kResRegVars; ++r) {
-            if (cs[r] < 0) continue;
-            int lane = 0;
-            for (int d = kCptMaxDv; d >= 0; --d)
-                for (int k = 0; k < cells[cs[r]].cnt[d]; ++k)
-                    L.var_at[(size_t)r * kResCptThreads + w * 64 + lane++] = of_deg[d][taken[d]++];
-        }
-    }
-    int n_pos = 0;
-    for (int q = 0; q < (int)L.var_at.size(); ++q)
-        if (L.var_at[q] >= 0) n_pos = q + 1;
-    L.var_at.resize((size_t)n_pos);
-    cpt_cells(dv, L);
-    return true;
-}
-
-// a lane position of the check phase: (sub-)check `check`, its edges e0 .. e0+dc-1, lane-group size gs
-struct ResVCheck { int check, e0, dc, gs; };
-
-// ---- compact plan: joint bank-aware slot placement ------------------------------------------------
-// The LDS model of one variable phase of the compact kernels (codeword pairs: 8-byte slots).  The lane at grid position q
-// gathers and scatters the slot of its variable's k-th edge (CSC order) with the k-th ds_read_b64 / ds_write_b64 of its
-// round; a read resolves 32 lanes per LDS cycle on slot mod 32, a write 16 lanes on slot mod 16, and a group takes as
-// many cycles as its fullest bank holds lanes.  Three things are free and change no result: which variables of one
-// degree share a lane group, which position a check takes among the checks of its degree (the per-wave degrees, so
-// ccell and Sc, stay), and which row each edge of a check takes (min1, min2 and the sign parity do not depend on the
-// order of the edges; every per-slot table is filled from the same map).  BankModel keeps one bank histogram per
-// (group, k) and evaluates a move from the entries it changes; every move is its own inverse.
-struct BankModel {
-    static constexpr int kRG = 32, kRM = 32, kWG = 16, kWM = 16;
-    const ldpc_graph *g;
-    const std::vector<ResVCheck> &vc;
-    std::vector<int> &var_at, &check_at, &slot_of_edge;
-    std::vector<int> pos_of_var, k_of_edge, edge_at;     // edge_at[vc[c].e0 + t] = the edge in row t of check c
-    std::vector<unsigned char> hist[2], mx[2];           // [0] gathers, [1] scatters: [cell][bank], [cell]
-    std::vector<int> dirty;                              // cells whose fullest bank lost a lane: kind | cell << 1
-    long long cost = 0, sq = 0;                          // sum of the cells' maxima; sum of the squared bank counts
-
-    BankModel(const ldpc_graph *g_, const std::vector<ResVCheck> &vc_, std::vector<int> &var_at_,
-              std::vector<int> &check_at_, std::vector<int> &slot_of_edge_)
-        : g(g_), vc(vc_), var_at(var_at_), check_at(check_at_), slot_of_edge(slot_of_edge_)
-    {
-        const int n_pos = (int)var_at.size();
-        pos_of_var.assign(g->n, -1);
-        for (int q = 0; q < n_pos; ++q)
-            if (var_at[q] >= 0) pos_of_var[var_at[q]] = q;
-        k_of_edge.assign(g->E, 0);
-        for (int j = 0; j < g->n; ++j)
-            for (int s = g->h_var_ptr[j]; s < g->h_var_ptr[j + 1]; ++s) k_of_edge[g->h_csc[s]] = s - g->h_var_ptr[j];
-        edge_at.assign(g->E, 0);
-        for (const ResVCheck &v : vc)
-            for (int t = 0; t < v.dc; ++t) edge_at[v.e0 + t] = v.e0 + t;
-        const int rcells = (n_pos + kRG - 1) / kRG * kCptMaxDv, wcells = (n_pos + kWG - 1) / kWG * kCptMaxDv;
-        hist[0].assign((size_t)rcells * kRM, 0); mx[0].assign(rcells, 0);
-        hist[1].assign((size_t)wcells * kWM, 0); mx[1].assign(wcells, 0);
-        for (int e = 0; e < g->E; ++e) entry(e, +1);
-        settle();
-    }
-    void bump(int kind, int cell, int banks, int bank, int sign)
-    {
-        unsigned char &c = hist[kind][(size_t)cell * banks + bank];
-        if (sign > 0) {
-            sq += 2 * c + 1;
-            if (++c > mx[kind][cell]) { mx[kind][cell] = c; ++cost; }
-        } else {
-            sq -= 2 * c - 1;
-            if (c-- == mx[kind][cell]) dirty.push_back(kind | cell << 1);
-        }
-    }
-    void entry(int e, int sign)                          // edge e's accesses enter (+1) or leave (-1) the histograms
-    {
-        const int q = pos_of_var[g->h_var_idx[e]], k = k_of_edge[e], s = slot_of_edge[e];
-        bump(0, q / kRG * kCptMaxDv + k, kRM, s % kRM, sign);
-        bump(1, q / kWG * kCptMaxDv + k, kWM, s % kWM, sign);
-    }
-    void settle()                                        // exact maxima of the dirty cells
-    {
-        for (int dc : dirty) {
-            const int kind = dc & 1, cell = dc >> 1, banks = kind ? kWM : kRM;
-            const unsigned char *h = &hist[kind][(size_t)cell * banks];
-            unsigned char m = 0;
-            for (int b = 0; b < banks; ++b) m = std::max(m, h[b]);
-            cost += (int)m - (int)mx[kind][cell];
-            mx[kind][cell] = m;
-        }
-        dirty.clear();
-    }
-    void swap_vars(int x, int y)                         // grid positions of two variables
-    {
-        const int jx = var_at[x], jy = var_at[y];
-        for (int j : {jx, jy})
-            for (int s = g->h_var_ptr[j]; s < g->h_var_ptr[j + 1]; ++s) entry(g->h_csc[s], -1);
-        std::swap(var_at[x], var_at[y]);
-        pos_of_var[jx] = y; pos_of_var[jy] = x;
-        for (int j : {jx, jy})
-            for (int s = g->h_var_ptr[j]; s < g->h_var_ptr[j + 1]; ++s) entry(g->h_csc[s], +1);
-        settle();
-    }
-    void swap_checks(int p, int r)                       // two positions that hold checks of one degree
-    {
-        const ResVCheck &a = vc[check_at[p]], &b = vc[check_at[r]];
-        for (int t = 0; t < a.dc; ++t) { entry(a.e0 + t, -1); entry(b.e0 + t, -1); }
-        for (int t = 0; t < a.dc; ++t) { slot_of_edge[a.e0 + t] += r - p; slot_of_edge[b.e0 + t] += p - r; }
-        for (int t = 0; t < a.dc; ++t) { entry(a.e0 + t, +1); entry(b.e0 + t, +1); }
-        std::swap(check_at[p], check_at[r]);
-        settle();
-    }
-    void swap_rows(int p, int t, int u)                  // two rows of the check at position p
-    {
-        const ResVCheck &a = vc[check_at[p]];
-        const int e = edge_at[a.e0 + t], f = edge_at[a.e0 + u];
-        entry(e, -1); entry(f, -1);
-        std::swap(slot_of_edge[e], slot_of_edge[f]);
-        std::swap(edge_at[a.e0 + t], edge_at[a.e0 + u]);
-        entry(e, +1); entry(f, +1);
-        settle();
-    }
-    void report(int (&out)[4]) const                     // { gather cost, gather groups, scatter cost, scatter groups }
-    {
-        for (int kind = 0; kind < 2; ++kind) {
-            int c = 0, groups = 0;
-            for (unsigned char m : mx[kind]) { c += m; groups += m ? 1 : 0; }
-            out[2 * kind] = c; out[2 * kind + 1] = groups;
-        }
-    }
-};
-
-// Seeded local search over L.var_at, L.check_at and L.slot_of_edge, budgeted by trial counts alone (deterministic).
-// First the variables-only climb on the summed maxima that this planner has always run (same moves, same acceptance, same
-// random sequence); its result is recorded as the baseline.  Then the joint climb: swaps of two variables of one degree,
-// of two checks of one degree, of two rows of one check, accepted when the summed maxima fall, or stay while the summed
-// squared bank counts do not rise -- the second term keeps a gradient once every group sits at two lanes per bank.
-void cpt_place_banks(const ldpc_graph *g, const std::vector<ResVCheck> &vc, CptLayout &L)
-{
-    const int n = g->n, m = (int)vc.size();
-    L.check_at.resize(m);
-    L.slot_of_edge.assign(g->E, 0);
-    for (int p = 0; p < m; ++p) {
-        L.check_at[p] = p;
-        for (int t = 0; t < vc[p].dc; ++t) L.slot_of_edge[vc[p].e0 + t] = t * kResCptStride + p;
-    }
-    BankModel bm(g, vc, L.var_at, L.check_at, L.slot_of_edge);
-    std::vector<std::vector<int>> vclass(kCptMaxDv + 1);                // grid positions by variable degree
-    for (int q = 0; q < (int)L.var_at.size(); ++q) {
-        if (L.var_at[q] < 0) continue;
-        const int d = g->h_var_ptr[L.var_at[q] + 1] - g->h_var_ptr[L.var_at[q]];
-        if (d > 0 && d <= kCptMaxDv) vclass[d].push_back(q);
-    }
-    vclass.erase(std::remove_if(vclass.begin(), vclass.end(), [](const std::vector<int> &c) { return c.size() < 2; }),
-                 vclass.end());
-    std::vector<std::pair<int, int>> cclass;                            // [first, last) positions of one check degree
-    std::vector<int> rowable;                                           // positions whose check has two rows or more
-    for (int p = 0; p < m;) {
-        int r = p;
-        while (r < m && vc[r].dc == vc[p].dc) ++r;
-        if (r - p >= 2 && vc[p].dc > 0) cclass.push_back({p, r});
-        p = r;
-    }
-    for (int p = 0; p < m; ++p)
-        if (vc[p].dc >= 2) rowable.push_back(p);
-    uint64_t rng = 0x9E3779B97F4A7C15ull;
-    auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
-    if (!vclass.empty()) {
-        const long trials = std::min<long>(400000, 150L * n);
-        for (long it = 0; it < trials; ++it) {
-            const auto &c = vclass[next() % vclass.size()];
-            const int x = c[next() % c.size()], y = c[next() % c.size()];
-            if (x / BankModel::kWG == y / BankModel::kWG) continue;
-            const long long before = bm.cost;
-            bm.swap_vars(x, y);
-            if (bm.cost > before) bm.swap_vars(x, y);
-        }
-    }
-    bm.report(L.base_banks);
-    L.base_check_at = L.check_at;
-    L.base_slot_of_edge = L.slot_of_edge;
-
-    // rows are the cheapest move and the most productive: 29 trials in 32; 2 move variables, 1 moves checks
-    const long joint = std::min<long>(kCptJointTrials, 500L * g->E);
-    for (long it = 0; it < joint; ++it) {
-        const long long cost0 = bm.cost, sq0 = bm.sq;
-        const unsigned kind = (unsigned)(next() % 32);
-        int a = 0, b = 0, c = 0;
-        if (kind < 2) {
-            if (vclass.empty()) continue;
-            const auto &cl = vclass[next() % vclass.size()];
-            a = cl[next() % cl.size()]; b = cl[next() % cl.size()];
-            if (a / BankModel::kWG == b / BankModel::kWG) continue;
-            bm.swap_vars(a, b);
-        } else if (kind < 3) {
-            if (cclass.empty()) continue;
-            const auto &cl = cclass[next() % cclass.size()];
-            a = cl.first + (int)(next() % (uint64_t)(cl.second - cl.first));
-            b = cl.first + (int)(next() % (uint64_t)(cl.second - cl.first));
-            if (a == b) continue;
-            bm.swap_checks(a, b);
-        } else {
-            if (rowable.empty()) continue;
-            a = rowable[next() % rowable.size()];
-            const int dc = vc[L.check_at[a]].dc;
-            b = (int)(next() % (uint64_t)dc); c = (int)(next() % (uint64_t)dc);
-            if (b == c) continue;
-            bm.swap_rows(a, b, c);
-        }
-        if (bm.cost < cost0 || (bm.cost == cost0 && bm.sq <= sq0)) continue;
-        if (kind < 2) bm.swap_vars(a, b);
-        else if (kind < 3) bm.swap_checks(a, b);
-        else bm.swap_rows(a, b, c);
-    }
-    bm.report(L.banks);
-}
-
-int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &vc, int mstride,
-                    long long S, int G, ResidentPlan &pl, const CptLayout *cl = nullptr);
-void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L);
-void cpt_check_words(const std::vector<ResVCheck> &vc, bool select_form, unsigned (&words)[kCptWaves]);
-bool cpt_geometry(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long &Sc);
-
-// Lane positions of the check phase are VIRTUAL checks.  A check of degree <= kResSubDegreeCap is one of them; a wider
-// one is split into 2^k sub-checks of contiguous edges (balanced, at most kResSubDegree each) that sit on ADJACENT lanes
-// and are combined by wavefront exchanges (ldpc_resident.hip: group_combine).  Groups come first, by descending size --
-// every group then starts at a multiple of its size, so it never straddles a wave -- then the whole checks.
-bool resident_checks(const ldpc_graph *g, std::vector<ResVCheck> &vc)
-{
-    auto dc_real = [&](int i) { return g->h_check_ptr[i + 1] - g->h_check_ptr[i]; };
-    std::vector<int> wide_ids, plain_ids;
-    for (int i = 0; i < g->m; ++i) (dc_real(i) > kResSubDegreeCap ? wide_ids : plain_ids).push_back(i);
-    auto group_of = [&](int i) { int k = 1; while (k * kResSubDegree < dc_real(i)) k <<= 1; return k; };
-    for (int i : wide_ids)
-        if (group_of(i) > 64) return false;                 // wider than a wavefront of sub-checks
-    std::stable_sort(wide_ids.begin(), wide_ids.end(), [&](int a, int b) { return group_of(a) > group_of(b); });
-    for (int i : wide_ids) {
-        const int k = group_of(i), dc = dc_real(i), base = dc / k, rem = dc % k;
-        int e = g->h_check_ptr[i];
-        for (int j = 0; j < k; ++j) {
-            const int len = base + (j < rem ? 1 : 0);
-            vc.push_back({i, e, len, k});
-            e += len;
-        }
-    }
-    std::stable_sort(plain_ids.begin(), plain_ids.end(), [&](int a, int b) { return dc_real(a) > dc_real(b); });
-    for (int i : plain_ids) vc.push_back({i, g->h_check_ptr[i], dc_real(i), 1});
-    return true;
-}
-
-// Sort checks and variables by degree (stable, descending), lay the edges out ELL-transposed.
 int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
 {
-    const ldpc_graph *g = d->g;
-    d->res_ok = false;
-    if (g->E == 0 || g->max_dv > 8) return LDPC_OK;
-    // fp64 (the reference's BasicMinSumDecoder dtype): the normalised form with one factor per check; a codeword's
-    // 8-byte slots take the place of a float codeword PAIR, so the geometry below must come out at G = 2
-    const bool f64 = d->dtype == LDPC_F64;
-    if (f64 && (d->form != LDPC_C2V_NMS || !d->beta_per_check)) return LDPC_OK;
-    const int n = g->n;
-    if (n > 65535 || d->n_beta > 65535 || d->n_alpha >= (1 << 24) || d->n_oms_alpha > 65535) return LDPC_OK;
-
-    std::vector<ResVCheck> vc;
-    if (!resident_checks(g, vc)) return LDPC_OK;
-    const int m = (int)vc.size();
-    int max_sub = 0;
-    for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
-    if (m > 65535 || max_sub > 255) return LDPC_OK;
-
-    // geometry: G codewords per workgroup, NT threads, and the row stride of the slot layout.
-    // Two 512-thread workgroups per CU (G = 2, ds_read/write_b64) let one workgroup's barrier wait overlap
-    // the other's phase -- measured best on the (1998,1512) code; larger codes fall back to one workgroup
-    // per CU or G = 1.  A row stride of 512 slots (instead of m) lets LDS instructions carry t*stride as an
-    // immediate offset; it is taken when it costs neither G nor workgroups per CU.
-    auto geometry = [&](int stride, int &G_out, int &blocks_out) {
-        const long long S_ = (long long)max_sub * stride;
-        const int mp = is_pow2(stride) ? m : 0;           // parity words of the early-stop syndrome (power-of-two strides)
-        if (S_ > 65535 || !resident_fits(d, S_, 1, 1, mp)) return false;
-        const int G_ = resident_fits(d, S_, 2, 1, mp) ? 2 : 1;
-        int b_ = 1;
-        while (b_ < 8 && resident_fits(d, S_, G_, b_ + 1, mp)) ++b_;
-        G_out = G_; blocks_out = b_;
-        return true;
-    };
-    int G = 0, blocks = 0, mstride = m;
-    if (!geometry(m, G, blocks)) return LDPC_OK;
-    if (f64 && G != 2) return LDPC_OK;
-    if (m <= 512) {
-        int G5 = 0, b5 = 0;
-        if (geometry(512, G5, b5) && G5 == G && std::min(b5, 2) == std::min(blocks, 2)) { mstride = 512; blocks = b5; }
-    }
-    const long long S = (long long)max_sub * mstride;
-    const int NT = blocks >= 2 ? 512 : 1024;
-    if (int rc = resident_layout(d, desc, vc, mstride, S, G, d->res)) return rc;
-    d->res_G = G; d->res_NT = NT;
-    d->res_lds = res_lds_total((int)S, n, G, resident_alpha_floats(d), d->res.par_words);
+    ResidentChoice c = choose_resident_plan(d->g, plan_inputs(d, desc));
+    d->res_ok = d->resc_ok = false;
+    if (!c.res_ok) return LDPC_OK;
+    if (int rc = upload_plan(d, c.res, d->res)) return rc;
+    d->res_G = c.G; d->res_NT = c.NT; d->res_lds = c.res_lds;
     d->res_ok = true;
-
-    // compact fixed-T geometry: row stride kResCptStride, S truncated after the last slot in use (checks are sorted by
-    // descending degree, so the last row holds only the checks of the largest degree), no llr_s / bits_s / parity words /
-    // alpha table in LDS.  Taken when it gives kResCptBlocks workgroups of 512 threads per CU and the variable state fits
-    // the registers (resident_reg_state)
-    d->resc_ok = false;
-    long long Sc = 0;
-    if (!f64 && G == 2 && NT == kResCptThreads && cpt_geometry(g, vc, Sc)) {
-        cpt_layout(g, vc, Sc, d->resc_layout);
-        if (int rc = resident_layout(d, desc, vc, kResCptStride, Sc, 2, d->resc, &d->resc_layout)) return rc;
-        d->resc_lds = res_cpt_lds_total((int)Sc, 2);
-        d->resc_ok = true;
-    }
+    if (!c.resc_ok) return LDPC_OK;
+    if (int rc = upload_plan(d, c.resc, d->resc)) return rc;
+    d->resc_layout = std::move(c.resc_layout);
+    d->resc_lds = c.resc_lds;
+    d->resc_ok = true;
     return LDPC_OK;
-}
-
-// the compact geometry's slot count Sc when the graph qualifies: no split checks, m <= kResCptStride, the variables within
-// kResRegVars rounds of 512 lanes with every degree > 4 one in round 0, 16-bit slot offsets, the LLR rows stageable in the
-// slot area (cpt_layout keeps its positions below Sc) and kResCptBlocks workgroups per CU
-bool cpt_geometry(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long &Sc)
-{
-    const int n = g->n, m = (int)vc.size();
-    int max_sub = 0;
-    for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
-    if (m != g->m || m > kResCptStride || n > kResRegVars * kResCptThreads || g->max_dv > kCptMaxDv || max_sub < 1)
-        return false;
-    int n_top = 0;
-    while (n_top < m && vc[n_top].dc == max_sub) ++n_top;
-    Sc = (long long)(max_sub - 1) * kResCptStride + n_top;
-    int n_hi = 0;
-    for (int j = 0; j < n; ++j) n_hi += (g->h_var_ptr[j + 1] - g->h_var_ptr[j]) > 4 ? 1 : 0;
-    return Sc * 2 * 4 <= 65535 && (long long)n <= Sc && n_hi <= kResCptThreads &&
-           kResCptBlocks * res_cpt_lds_total((int)Sc, 2) <= kLdsBytes;
-}
-
-// the compact plan's check table (ResidentPlan::ccell): wave w holds the checks at positions 64w .. 64w+63.  `select_form`:
-// the decoder's check phase is the one-beta-per-check select form, the only one with a scalar-counted body
-void cpt_check_words(const std::vector<ResVCheck> &vc, bool select_form, unsigned (&words)[kCptWaves])
-{
-    const int m = (int)vc.size();
-    for (int w = 0; w < kCptWaves; ++w) {
-        const int p0 = std::min(64 * w, m), p1 = std::min(p0 + 64, m);
-        int lo = p0 < p1 ? 255 : 0, hi = 0;
-        for (int p = p0; p < p1; ++p) { lo = std::min(lo, vc[p].dc); hi = std::max(hi, vc[p].dc); }
-        words[w] = p0 < p1 ? chk_word(lo, hi, p1 - p0) | (select_form ? 0u : kChkPerLane) : 0u;
-    }
-}
-
-// the compact plan's grid for a graph and its check order: the balanced placement, else (a staging area too small for its
-// positions) the degree-sorted order of the general plan; then variables, check positions and edge rows are placed for LDS
-// banking (cpt_place_banks)
-void cpt_layout(const ldpc_graph *g, const std::vector<ResVCheck> &vc, long long S, CptLayout &L)
-{
-    const int n = g->n;
-    std::vector<int> dv(n);
-    for (int j = 0; j < n; ++j) dv[j] = g->h_var_ptr[j + 1] - g->h_var_ptr[j];
-    if (!cpt_assign(dv, L) || (long long)L.var_at.size() > S) {
-        L.var_at.resize(n);
-        for (int j = 0; j < n; ++j) L.var_at[j] = j;
-        std::stable_sort(L.var_at.begin(), L.var_at.end(), [&](int a, int b) { return dv[a] > dv[b]; });
-    }
-    cpt_place_banks(g, vc, L);
-    cpt_cells(dv, L);
-}
-
-// slot layout of one geometry: row stride `mstride`, S slots, G codewords per slot; variables ordered inside their degree
-// classes for LDS banking (general plan) or at the positions of the compact grid `cl`; the plan arrays go to the device
-// (owned by d->res_bufs)
-int resident_layout(ldpc_decoder *d, const ldpc_decoder_desc *desc, const std::vector<ResVCheck> &sorted, int mstride,
-                    long long S, int G, ResidentPlan &pl, const CptLayout *cl)
-{
-    const ldpc_graph *g = d->g;
-    std::vector<ResVCheck> placed;                               // compact plan: the checks in position order
-    if (cl)
-        for (int c : cl->check_at) placed.push_back(sorted[c]);
-    const std::vector<ResVCheck> &vc = cl ? placed : sorted;
-    const int n = g->n, m = (int)vc.size();
-    const bool any_split = m != g->m;
-    int max_sub = 0;
-    for (const ResVCheck &v : vc) max_sub = std::max(max_sub, v.dc);
-    std::vector<int> perm_v(n), pos_v(n);
-    for (int j = 0; j < n; ++j) perm_v[j] = j;
-    auto dv_of = [&](int j) { return g->h_var_ptr[j + 1] - g->h_var_ptr[j]; };
-    std::stable_sort(perm_v.begin(), perm_v.end(), [&](int a, int b) { return dv_of(a) > dv_of(b); });
-    std::vector<int> slot_of_edge(g->E);
-    for (int p = 0; p < m; ++p)
-        for (int t = 0; t < vc[p].dc; ++t) slot_of_edge[vc[p].e0 + t] = t * mstride + p;
-    if (cl) {
-        perm_v = cl->var_at;                                     // position -> variable, -1 = empty
-        slot_of_edge = cl->slot_of_edge;                         // rows of a check in the placement's order
-    } else {   // slots are fixed by the check order alone; choose the variable order inside each degree class
-        std::vector<std::vector<int>> vs(n);
-        for (int j = 0; j < n; ++j)
-            for (int k = 0; k < dv_of(j); ++k) vs[j].push_back(slot_of_edge[g->h_csc[g->h_var_ptr[j] + k]]);
-        optimise_lane_order(perm_v, vs, G);
-    }
-    const int n_pos = (int)perm_v.size();
-    // the compact kernels load the plan entries of whole cells: padded to a multiple of 64 positions
-    const int n_ent = cl ? (n_pos + 63) / 64 * 64 : n;
-    for (int q = 0; q < n_pos; ++q)
-        if (perm_v[q] >= 0) pos_v[perm_v[q]] = q;
-
-    std::vector<uint8_t> dc_s(m), gsz(m);
-    std::vector<uint16_t> cvar((size_t)S, 0), bslot((size_t)S, 0), oaslot((size_t)S, 0), bslot_c(m, 0), inv(n);
-    std::vector<uint32_t> vmeta(n_ent, 0u);
-    std::vector<uint2> vslot_lo(n_ent, make_uint2(0, kResHole)), vslot_hi(std::max(n_ent, 1), make_uint2(0, 0));
-    int n_hi = 0;
-    std::vector<uint32_t> edge_of_slot((size_t)S, 0xffffffffu);
-    bool per_check = true;
-    for (int p = 0; p < m; ++p) {
-        const ResVCheck &v = vc[p];
-        const int first = g->h_check_ptr[v.check];                  // the WHOLE check's first edge decides "one beta per check"
-        dc_s[p] = (uint8_t)v.dc;
-        gsz[p] = (uint8_t)v.gs;
-        for (int t = 0; t < v.dc; ++t) {
-            const int e = v.e0 + t, slot = slot_of_edge[e];
-            edge_of_slot[slot] = (uint32_t)e;
-            cvar[slot] = (uint16_t)pos_v[g->h_var_idx[e]];
-            bslot[slot] = (uint16_t)desc->beta_slot[e];
-            if (desc->beta_slot[e] != desc->beta_slot[first]) per_check = false;
-            if (d->form == LDPC_C2V_OMS && desc->oms_alpha) oaslot[slot] = (uint16_t)desc->oms_alpha_slot[e];
-        }
-        bslot_c[p] = v.dc ? (uint16_t)desc->beta_slot[first] : 0;
-    }
-    for (int q = 0; q < n_pos; ++q) {
-        if (perm_v[q] < 0) continue;                                                   // empty: vmeta 0, kResHole
-        const int j = perm_v[q], s0 = g->h_var_ptr[j], dv = dv_of(j);
-        vmeta[q] = (uint32_t)dv | ((uint32_t)desc->alpha_slot[j] << 8);
-        inv[j] = (uint16_t)q;
-        uint32_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = 0; k < dv; ++k) off[k] = (uint32_t)slot_of_edge[g->h_csc[s0 + k]] * G * 4;
-        vslot_lo[q] = make_uint2(off[0] | (off[1] << 16), off[2] | (off[3] << 16));      // offsets <= 65535 (resident_fits)
-        vslot_hi[q] = make_uint2(off[4] | (off[5] << 16), off[6] | (off[7] << 16));
-        if (dv > 4) n_hi = q + 1;            // general plan: they come first; compact: all in round 0 (q < 512)
-    }
-    pl = ResidentPlan{};
-    pl.n = n; pl.m = m; pl.S = (int)S; pl.max_dc = max_sub; pl.max_dv = g->max_dv; pl.mstride = mstride; pl.E = g->E;
-    pl.any_split = any_split ? 1 : 0;
-    pl.n_hi = n_hi;
-    pl.n_pos = n_pos;
-    if (cl) {
-        std::copy(cl->cell, cl->cell + kCptWaves, pl.vcell);
-        cpt_check_words(vc, per_check && (d->form == LDPC_C2V_NMS || (d->form == LDPC_C2V_RCQ && d->rcq_zero0)),
-                        pl.ccell);
-    }
-    pl.par_words = is_pow2(mstride) ? m : 0;
-    pl.par_shift = G == 2 ? 3 : 2;                     // slot byte offset = slot * G * 4
-    int rc = plan_upload(d, &pl.dc_s, dc_s);
-    if (!rc && any_split) rc = plan_upload(d, &pl.gsz, gsz);
-    if (!rc) rc = plan_upload(d, &pl.cvar, cvar);
-    if (!rc) rc = plan_upload(d, &pl.bslot, bslot);
-    if (!rc && per_check) rc = plan_upload(d, &pl.bslot_c, bslot_c);
-    if (!rc && d->form == LDPC_C2V_OMS && desc->oms_alpha) rc = plan_upload(d, &pl.oaslot, oaslot);
-    if (!rc) rc = plan_upload(d, &pl.vmeta, vmeta);
-    if (!rc) rc = plan_upload(d, &pl.vslot_lo, vslot_lo);
-    vslot_hi.resize((size_t)std::max(n_hi, 1));
-    if (!rc) rc = plan_upload(d, &pl.vslot_hi, vslot_hi);
-    if (!rc) rc = plan_upload(d, &pl.inv_perm_v, inv);
-    if (!rc) rc = plan_upload(d, &pl.edge_of_slot, edge_of_slot);
-    return rc;
 }
 
 // A kernel's dynamic-LDS ceiling is process-wide state of that kernel on a device: it is raised ONCE per
@@ -1591,7 +912,7 @@ ResidentKernel resident_kernel(const ldpc_decoder *d, bool early_stop)
     const bool reg = resident_reg_state(d) && !early_stop;
     k.form = d->form == LDPC_C2V_NMS ? FORM_NMS : d->form == LDPC_C2V_OMS ? FORM_OMS : FORM_RCQ;
     k.f64 = d->dtype == LDPC_F64;
-    k.alpha_in_lds = resident_alpha_floats(d) > 0;
+    k.alpha_in_lds = resident_alpha_floats(d->dtype, d->T, d->n_alpha) > 0;
     if (d->resc_ok && !early_stop) {   // compact fixed-T geometry, three workgroups per CU (resc_ok implies fp32 and G = 2)
         k.plan = kResPlanCompact;
         k.G = 2;
@@ -1907,42 +1228,21 @@ const char *ldpc_source_hash(void) { return LDPC_STR(LDPC_SRC_HASH); }
         return fail(LDPC_ERR_HIP, "internal error");                                           \
     }
 
-// validated CSR -> the host copies of a graph (CSC by scanning CSR edges in order: every variable's checks ascend)
-static int graph_host_build(ldpc_graph *g, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr, const int32_t *var_idx)
+// validates a CSR and fills the host copies of a graph
+static int graph_host_build(HostGraph *g, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr, const int32_t *var_idx)
 {
     if (n < 0 || m < 0 || E < 0 || !check_ptr || (E > 0 && !var_idx)) return fail(LDPC_ERR_ARG, "bad graph sizes");
     if (check_ptr[0] != 0 || check_ptr[m] != E) return fail(LDPC_ERR_ARG, "check_ptr must span [0, E]");
-    std::vector<int> dv(n, 0);
-    int max_dc = 0;
     for (int i = 0; i < m; ++i) {
         const int a = check_ptr[i], b = check_ptr[i + 1];
         if (b < a || b > E) return fail(LDPC_ERR_ARG, "check_ptr not monotone at check %d", i);
-        max_dc = std::max(max_dc, b - a);
         for (int e = a; e < b; ++e) {
             const int j = var_idx[e];
             if (j < 0 || j >= n) return fail(LDPC_ERR_ARG, "var_idx[%d]=%d out of range", e, j);
             if (e > a && var_idx[e - 1] >= j) return fail(LDPC_ERR_ARG, "edges of check %d not strictly ascending", i);
-            dv[j]++;
         }
     }
-    std::vector<int> var_ptr(n + 1, 0), csc(std::max(E, 1), 0), fill(n, 0);
-    int max_dv = 0;
-    for (int j = 0; j < n; ++j) {
-        var_ptr[j + 1] = var_ptr[j] + dv[j];
-        max_dv = std::max(max_dv, dv[j]);
-    }
-    for (int e = 0; e < E; ++e) {
-        const int j = var_idx[e];
-        csc[var_ptr[j] + fill[j]++] = e;
-    }
-    g->n = n; g->m = m; g->E = E; g->max_dc = max_dc; g->max_dv = max_dv;
-    g->h_check_ptr.assign(check_ptr, check_ptr + m + 1);
-    g->h_var_idx.assign(var_idx, var_idx + E);
-    g->h_var_ptr = var_ptr;
-    g->h_csc.assign(csc.begin(), csc.begin() + E);
-    g->h_check_of_edge.resize(E);
-    for (int i = 0; i < m; ++i)
-        for (int e = check_ptr[i]; e < check_ptr[i + 1]; ++e) g->h_check_of_edge[e] = i;
+    host_graph_fill(g, n, m, E, check_ptr, var_idx);
     return LDPC_OK;
 }
 
@@ -2653,26 +1953,41 @@ int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t ma
     return LDPC_OK;
 }
 
+// The compact plan a debug hook reports: a decoder's stored layout, or (d == NULL) a layout planned from these arrays on
+// host copies only -- no device is touched.  `place` = false stops before the placement search (cpt_layout), for a
+// hook that needs the check order alone.
+struct CompactView {
+    HostGraph own_g;
+    CptLayout own;
+    const HostGraph *g = &own_g;
+    const CptLayout *L = &own;
+    std::vector<ResVCheck> vc;                           // the degree-sorted checks (resident_checks)
+    long long Sc = 0;
+};
+
+static int compact_view(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                        const int32_t *var_idx, bool place, CompactView &v)
+{
+    if (d) {
+        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
+        v.L = &d->resc_layout; v.g = d->g; v.Sc = d->resc.S;
+    } else if (int rc = graph_host_build(&v.own_g, n, m, E, check_ptr, var_idx)) {
+        return rc;
+    }
+    if (!resident_checks(v.g, v.vc) || (!d && !cpt_geometry(v.g, v.vc, v.Sc)))
+        return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
+    if (!d && place) cpt_layout(v.g, v.vc, v.Sc, v.own);
+    return LDPC_OK;
+}
+
 static int compact_layout_impl(const ldpc_decoder *d, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
                                const int32_t *var_idx, int32_t *pos_of_var, uint8_t *cells, int32_t *stats)
 {
-    CptLayout own;
-    const CptLayout *L = &own;
-    if (d) {
-        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
-        L = &d->resc_layout;
-        n = d->g->n;
-    } else {
-        ldpc_graph g;                                    // host copies only: no device is touched
-        if (int rc = graph_host_build(&g, n, m, E, check_ptr, var_idx)) return rc;
-        std::vector<ResVCheck> vc;
-        long long Sc = 0;
-        if (!resident_checks(&g, vc) || !cpt_geometry(&g, vc, Sc))
-            return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
-        cpt_layout(&g, vc, Sc, own);
-    }
+    CompactView v;
+    if (int rc = compact_view(d, n, m, E, check_ptr, var_idx, true, v)) return rc;
+    const CptLayout *L = v.L;
     if (pos_of_var) {
-        for (int j = 0; j < n; ++j) pos_of_var[j] = -1;
+        for (int j = 0; j < v.g->n; ++j) pos_of_var[j] = -1;
         for (int q = 0; q < (int)L->var_at.size(); ++q)
             if (L->var_at[q] >= 0) pos_of_var[L->var_at[q]] = q;
     }
@@ -2694,20 +2009,12 @@ static int compact_checks_impl(const ldpc_decoder *d, int32_t n, int32_t m, int3
                                const int32_t *var_idx, uint32_t *words)
 {
     if (!words) return fail(LDPC_ERR_ARG, "NULL argument");
-    if (d) {
-        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
-        std::copy(d->resc.ccell, d->resc.ccell + kCptWaves, words);
-        return LDPC_OK;
-    }
-    ldpc_graph g;                                        // host copies only: no device is touched
-    if (int rc = graph_host_build(&g, n, m, E, check_ptr, var_idx)) return rc;
-    std::vector<ResVCheck> vc;
-    long long Sc = 0;
-    if (!resident_checks(&g, vc) || !cpt_geometry(&g, vc, Sc))
-        return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
+    CompactView v;
+    if (int rc = compact_view(d, n, m, E, check_ptr, var_idx, false, v)) return rc;
     unsigned own[kCptWaves];
-    cpt_check_words(vc, true, own);
-    std::copy(own, own + kCptWaves, words);
+    if (!d) cpt_check_words(v.vc, true, own);
+    const unsigned *src = d ? d->resc.ccell : own;
+    std::copy(src, src + kCptWaves, words);
     return LDPC_OK;
 }
 
@@ -2722,34 +2029,19 @@ static int compact_banks_impl(const ldpc_decoder *d, int32_t n, int32_t m, int32
                               int32_t *base_slot_of_edge, int32_t *base_pos_of_check, int32_t *base_model,
                               int32_t *geometry)
 {
-    CptLayout own;
-    ldpc_graph own_g;                                    // host copies only: no device is touched
-    const CptLayout *L = &own;
-    const ldpc_graph *g = &own_g;
-    std::vector<ResVCheck> vc;
-    long long Sc = 0;
-    if (d) {
-        if (!d->resc_ok) return fail(LDPC_ERR_UNSUPPORTED, "the decoder has no compact fixed-T plan");
-        L = &d->resc_layout;
-        g = d->g;
-        Sc = d->resc.S;
-        if (!resident_checks(g, vc)) return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
-    } else {
-        if (int rc = graph_host_build(&own_g, n, m, E, check_ptr, var_idx)) return rc;
-        if (!resident_checks(g, vc) || !cpt_geometry(g, vc, Sc))
-            return fail(LDPC_ERR_UNSUPPORTED, "the graph does not qualify for the compact plan");
-        cpt_layout(g, vc, Sc, own);
-    }
+    CompactView v;
+    if (int rc = compact_view(d, n, m, E, check_ptr, var_idx, true, v)) return rc;
+    const CptLayout *L = v.L;
     auto emit = [&](const std::vector<int> &slots, const std::vector<int> &check_at, const int (&banks)[4],
                     int32_t *slots_out, int32_t *pos_out, int32_t *model_out) {
         if (slots_out) std::copy(slots.begin(), slots.end(), slots_out);
         if (pos_out)
-            for (int p = 0; p < (int)check_at.size(); ++p) pos_out[vc[check_at[p]].check] = p;
+            for (int p = 0; p < (int)check_at.size(); ++p) pos_out[v.vc[check_at[p]].check] = p;
         if (model_out) std::copy(banks, banks + 4, model_out);
     };
     emit(L->slot_of_edge, L->check_at, L->banks, slot_of_edge, pos_of_check, model);
     emit(L->base_slot_of_edge, L->base_check_at, L->base_banks, base_slot_of_edge, base_pos_of_check, base_model);
-    if (geometry) { geometry[0] = kResCptStride; geometry[1] = (int32_t)Sc; }
+    if (geometry) { geometry[0] = kResCptStride; geometry[1] = (int32_t)v.Sc; }
     return LDPC_OK;
 }
 
@@ -2761,7 +2053,6 @@ int ldpc_debug_compact_banks(const ldpc_decoder *d, int32_t n, int32_t m, int32_
     LDPC_NOTHROW(compact_banks_impl(d, n, m, E, check_ptr, var_idx, slot_of_edge, pos_of_check, model, base_slot_of_edge,
                                     base_pos_of_check, base_model, geometry))
 }
-
 int ldpc_debug_resident_kernel(const ldpc_decoder *d, int32_t early_stop, int32_t out12[12])
 {
     if (!d || !out12) return fail(LDPC_ERR_ARG, "NULL argument");

@@ -29,6 +29,7 @@
 #pragma once
 
 #include "ldpc_kernels.hip"
+#include "ldpc_resident_geom.h"
 
 namespace ldpc {
 
@@ -80,8 +81,6 @@ struct ResidentArgs {
     void *dbg_c2v;                // [batch][E] or null: C2V values of every codeword's last executed iteration, CSR edge
                                   // order (include/ldpc_hip_debug.h; lets the tests compare per-edge RCQ codes on this engine)
 };
-
-constexpr int kResAlphaMax = 1024;   // floats of alpha table kept in LDS
 
 // LDS access by byte offset.  The dynamic LDS block is this kernel's only LDS object (no static
 // __shared__), so it starts at LDS address 0 and a message slot's byte offset IS its LDS address:
@@ -305,20 +304,6 @@ __device__ __forceinline__ void res_select4_f64(double (&x)[4], double m1, doubl
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = __longlong_as_double((long long)(((unsigned long long)rh[i] << 32) | rl[i]));
 }
-
-// Compact plan: the checks of wave w, one word of ResidentPlan::ccell (checks are sorted by degree, so nearly every wave
-// holds one degree or two adjacent ones): d_lo = smallest degree in the wave | (largest - d_lo) << 8 | lanes in use << 16,
-// kChkPerLane set for a wave the scalar-counted form does not take: d_lo < 4 (which also keeps the degree-1 rule
-// "min2 = min1" in the per-lane form alone), and every wave of a decoder whose check phase is not the one-beta-per-check
-// select form (per-edge beta, OMS, RCQ with tau_0 != 0).
-constexpr unsigned kChkPerLane = 0x80000000u;
-__host__ __device__ constexpr unsigned chk_word(int d_lo, int d_hi, int lanes)
-{
-    return (unsigned)d_lo | (unsigned)(d_hi - d_lo) << 8 | (unsigned)lanes << 16 | (d_lo < 4 ? kChkPerLane : 0u);
-}
-__host__ __device__ constexpr int chk_lo(unsigned w) { return (int)(w & 0xffu); }
-__host__ __device__ constexpr int chk_spread(unsigned w) { return (int)(w >> 8 & 0xffu); }
-__host__ __device__ constexpr int chk_lanes(unsigned w) { return (int)(w >> 16 & 0xffu); }
 
 // Edges 0 .. dc-1 of a lane's check in ascending order with the loop control on the scalar unit: d_lo (wave-uniform) edges
 // as groups of four plus a tail of two and of one on scalar branches, f(address of the group's first slot, edges in the
@@ -809,7 +794,6 @@ __device__ __forceinline__ void res_var_dispatch(unsigned char *smem, T *__restr
 // read per iteration.  The rounds are unrolled (the array indices must be compile-time to stay in registers); a wave
 // whose variables all lie past n leaves at a scalar branch.  Degree > 4 variables all sit in round 0, so only that
 // round carries the upper offset half.
-constexpr int kResRegVars = 4;
 template <typename T, int G>
 struct ResVarState {
     unsigned meta[kResRegVars];   // vmeta of the variable, 0 past n (not kept by the compact kernels)
@@ -818,14 +802,6 @@ struct ResVarState {
     Pack<T, G> l[kResRegVars];    // channel LLRs as the variable phase reads them (llr_s contents)
     unsigned cells;               // compact kernels: this wave's word of ResidentPlan::vcell (wave-uniform, SGPR)
 };
-
-// Compact plan (CPT): the host places variables on a grid q = r*512 + w*64 + lane (round r, wave w) so that most
-// (wave, round) cells hold ONE degree, and the cell table ResidentPlan::vcell tells every wave what its rounds hold:
-constexpr unsigned kCellEmpty = 0x00;   // no variable: the round is skipped
-constexpr unsigned kCellHoles = 0x40;   // | degree: one degree, some lanes empty (their vslot_lo.y is kResHole)
-constexpr unsigned kCellMixed = 0xff;   // several degrees (or degree 0): the per-lane switch, degree from vmeta
-                                        // otherwise the byte is the degree 1..8 of all 64 lanes
-constexpr unsigned kResHole = 0xffffffffu;   // vslot_lo.y of an empty position (no variable's: offsets are multiples of 8)
 
 // one round of the compact variable phase: a uniform cell branches on its scalar degree straight into the body
 // (rounds 1-3 hold degree <= 4 only); the alpha column and a mixed cell's degrees come from vmeta, which the rare
@@ -1122,36 +1098,10 @@ __device__ __forceinline__ void res_dump_c2v(const ResidentPlan &pl, const Resid
     }
 }
 
-// LDS carve (bytes): msg at 0, then llr_s, alpha_s, bits_s, the syndrome word
-__host__ __device__ inline size_t res_off_llr(int S, int G) { return (size_t)S * G * 4; }
-__host__ __device__ inline size_t res_off_alpha(int S, int n, int G) { return res_off_llr(S, G) + (size_t)n * G * 4; }
-__host__ __device__ inline size_t res_off_bits(int S, int n, int G, int n_alpha_lds) { return res_off_alpha(S, n, G) + (size_t)n_alpha_lds * 4; }
-__host__ __device__ inline size_t res_off_flag(int S, int n, int G, int n_alpha_lds) { return (res_off_bits(S, n, G, n_alpha_lds) + n + 3) / 4 * 4; }
-__host__ __device__ inline size_t res_off_par(int S, int n, int G, int n_alpha_lds) { return res_off_flag(S, n, G, n_alpha_lds) + 16; }
-// `m_par` parity words follow (early-stop syndrome by scatter); 0 when the stride is not a power of two
-__host__ __device__ inline size_t res_lds_total(int S, int n, int G, int n_alpha_lds, int m_par) { return res_off_par(S, n, G, n_alpha_lds) + 4 * (size_t)m_par; }
-
-// compact kernels (CPT): only the message slots and the flag words -- the LLR rows are staged in the not-yet-initialised
-// message area and the posteriors in the dead one, the alpha table is read from global memory, no bits_s / parity words
-__host__ __device__ inline size_t res_cpt_off_flag(int S, int G) { return ((size_t)S * G * 4 + 15) / 16 * 16; }
-__host__ __device__ inline size_t res_cpt_lds_total(int S, int G) { return res_cpt_off_flag(S, G) + 16; }
-
 // ES: 0 = fixed-iteration kernel, 1 = early-stop kernel (kept apart so that the fixed-T kernel does not carry
 // the posterior/syndrome/emit code of the stop rule: the extra code cost the hot loop ~4 % when merged)
 constexpr int kResMaxThreads = 1024;   // launch bounds of resident_decode: threads per workgroup, waves per SIMD the
 constexpr int kResMinWaves = 4;        // register allocation must leave room for
-// compact geometry (CPT): three 512-thread workgroups per CU -> six waves per SIMD, at most 80 VGPRs
-constexpr int kResCptThreads = 512;
-constexpr int kResCptWaves = 6;
-constexpr int kResCptBlocks = 3;       // workgroups per CU the compact LDS carve must allow
-// compile-time row stride of the compact slot layout (m <= 495).  Odd: with an even stride the bank of slot(p,t) =
-// t*stride + p depends on p alone (496 = 0 mod 16 for the scatters) or on p and the parity of t (16 mod 32 for the
-// gathers), so the rows give the host's placement search (cpt_place_banks) nothing to choose from.  495 and not 497: the
-// (1998,1512) code at stride 496 takes 53,760 bytes of LDS, exactly a third of the CU's 128 allocation granules of 1,280
-// bytes, and at 497 (53,856 bytes, under 160 KiB / 3 all the same) only two workgroups were resident per CU and the launch
-// took 2.46 ms instead of 2.08 (profiles/README.md, r09).  The check phase is unaffected: consecutive p are consecutive
-// 8-byte slots at any row base
-constexpr int kResCptStride = 495;
 // REG: variable state in registers (ResVarState; the host takes it for fixed-T decodes of codes that qualify, see
 // resident_reg_state)
 // CPT: compact fixed-T kernel (REG, fp32, no split checks): res_cpt_lds_total bytes of LDS, so that kResCptBlocks

@@ -1,5 +1,5 @@
 """
-Host-only tests of the compact fixed-T plan's slot placement (csrc/ldpc_hip.hip: cpt_place_banks) through
+Host-only tests of the compact fixed-T plan's slot placement (csrc/ldpc_plan.h: cpt_place_banks) through
 ldpc_debug_compact_banks (include/ldpc_hip_debug.h), which touches no device.  Check position p runs one check and its
 edges sit in the slots row * stride + p; the planner chooses the position of a check among the checks of its degree, the
 row of every edge and the variables' lanes so that the variable phase's gathers and scatters meet few LDS bank conflicts.

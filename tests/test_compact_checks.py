@@ -1,5 +1,5 @@
 """
-Host-only tests of the compact fixed-T plan's check table (csrc/ldpc_hip.hip: cpt_check_words) through
+Host-only tests of the compact fixed-T plan's check table (csrc/ldpc_plan.h: cpt_check_words) through
 ldpc_debug_compact_checks (include/ldpc_hip_debug.h), which touches no device.  The plan sorts checks by descending
 degree and wave w of the compact kernel runs the checks at positions 64w .. 64w+63; its word tells the wave the smallest
 degree d_lo among them (that many edges run on a scalar trip count), the spread d_hi - d_lo (edges left to a lane mask),

@@ -74,7 +74,7 @@ def test_capped_and_final_iterations_run_a_quantiser_with_distinct_levels():
 
 
 def _one_beta_slot_per_check(family, code):
-    """what the plan derives from the decoder's beta_slot table (csrc/ldpc_hip.hip, resident_layout: per_check)"""
+    """what the plan derives from the decoder's beta_slot table (csrc/ldpc_plan.h, resident_layout: per_check)"""
     from weight_sharing import SharingLayout
     g = code.tanner_graph()
     f = cf.FAMILIES[family]

@@ -1,5 +1,5 @@
 """
-Host-only tests of the compact fixed-T plan's variable grid (csrc/ldpc_hip.hip: cpt_assign / cpt_layout) through
+Host-only tests of the compact fixed-T plan's variable grid (csrc/ldpc_plan.h: cpt_assign / cpt_layout) through
 ldpc_debug_compact_layout (include/ldpc_hip_debug.h), which touches no device.  The compact kernel runs the variable at
 q = r*512 + w*64 + lane in round r of wave w; the cell table tells each wave what its four rounds hold.  Checked on the
 (1998,1512) code and on random codes: every variable at exactly one position, degree > 4 variables in round 0, the

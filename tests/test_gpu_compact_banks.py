@@ -1,6 +1,6 @@
 """
 GPU tests (-m gpu) of the compact fixed-T kernel (resident_decode<..., CPT>) on the jointly placed slot layout: odd row
-stride, check positions permuted inside their degrees, the rows of every check permuted (csrc/ldpc_hip.hip:
+stride, check positions permuted inside their degrees, the rows of every check permuted (csrc/ldpc_plan.h:
 cpt_place_banks).  Every per-slot table (cvar, bslot, oaslot, edge_of_slot, the variables' slot offsets) is filled from
 the permuted map, so the per-edge check-to-variable messages of the last iteration (ldpc_debug_resident_c2v, CSR order)
 and every decode output must equal the streaming engine's bit for bit: Basic, Neural-2D (both sharing types; one beta
