@@ -95,8 +95,27 @@ def check_joint_args(n: int, T: int, llr, targets, iteration_weights):
         raise ValueError("the joint posterior loss needs max_iterations >= 1")
 
 
+QUANTIZER_GRADIENTS = ("straight_through",)
+
+
+def check_quantizer_gradient(value):
+    """the estimators joint_posterior_loss of the quantised decoder knows: None (no gradient path) or one of
+    QUANTIZER_GRADIENTS; ValueError otherwise"""
+    if value is not None and value not in QUANTIZER_GRADIENTS:
+        raise ValueError(f"quantizer_gradient must be None or one of {QUANTIZER_GRADIENTS}, got {value!r}")
+    return value
+
+
+def joint_loss_ste(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets,
+                   iteration_weights):
+    """joint_loss() of the quantised WeightedRCQDecoder through ``torch.ops.ldpc.rcq_joint_loss``: the same loss on the
+    decoder's own fixed-T decode, differentiable with the straight-through rule of include/ldpc_hip.h
+    (ldpc_train_joint_ste) -> (loss, loss_per_iteration, bits, posterior)"""
+    return joint_loss(beta_table, alpha_table, engine, llr, targets, iteration_weights, False, quantised=True)
+
+
 def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets, iteration_weights,
-               alpha_is_oms: bool):
+               alpha_is_oms: bool, quantised: bool = False):
     """posterior joint training through ``torch.ops.ldpc.minsum_joint_loss`` (torch_ops.py) -> (loss, loss_per_iteration,
     bits, posterior): loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets) over the T iterations of the fixed-T
     decode, differentiable in the tables (and in `llr` when it requires grad) with the posterior-local gradient of the
@@ -118,9 +137,13 @@ def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr:
     w = (torch.full((T,), 1.0 / T, dtype=torch.float32) if iteration_weights is None
          else torch.as_tensor(iteration_weights).detach().to(torch.float32))
     w = w.to(engine.device).contiguous()
-    loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.minsum_joint_loss(
-        xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(alpha_is_oms),
-        bool(want_grads), bool(want_llr))
+    if quantised:
+        loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.rcq_joint_loss(
+            xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(want_grads), bool(want_llr))
+    else:
+        loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.minsum_joint_loss(
+            xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(alpha_is_oms),
+            bool(want_grads), bool(want_llr))
     out_dev = llr.device
     if single:
         bits, post = bits[0], post[0]

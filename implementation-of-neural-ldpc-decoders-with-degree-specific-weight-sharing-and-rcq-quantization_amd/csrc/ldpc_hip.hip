@@ -323,7 +323,8 @@ struct RowsOut {
 
 int allow_full_lds(const void *kfn, int device);
 
-// keep_posterior: a non-last sweep also stores the posterior rows in w.postT (fp32 NMS / OMS only; ldpc_train_joint)
+// keep_posterior: a non-last sweep also stores the posterior rows in w.postT (fp32 only; ldpc_train_joint and, on the
+// code rows of the two-sweep RCQ form, ldpc_train_joint_ste)
 template <typename T, int VEC>
 int launch_vn(const ldpc_decoder *d, const Workspace &w, int it, bool last, bool use_done, hipStream_t s,
               bool store_posterior = true, const RowsOut *rows = nullptr, bool keep_posterior = false)
@@ -371,7 +372,7 @@ int launch_vn(const ldpc_decoder *d, const Workspace &w, int it, bool last, bool
                        (const int *)w.iters, w.bitsT, store_posterior ? (T *)w.postT : (T *)nullptr, done, vb)
     if (codes) {
         if constexpr (sizeof(T) == 4) {
-            if (last) LDPC_VN(true, true); else LDPC_VN(true, false);
+            if (last) LDPC_VN(true, true); else if (keep_posterior) LDPC_VN(true, false, true); else LDPC_VN(true, false);
         } else {
             return fail(LDPC_ERR_UNSUPPORTED, "RCQ messages are fp32 only");
         }
@@ -1389,7 +1390,8 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
         rc = up_bytes(&d->oms_alpha, desc->oms_alpha, rows * d->n_oms_alpha * es);
         if (!rc) rc = upload(&d->oms_alpha_slot, desc->oms_alpha_slot, (size_t)g->E);
     }
-    if (!rc && d->dtype == LDPC_F32 && d->form != LDPC_C2V_RCQ && d->schedule == LDPC_SCHED_FLOODING) {
+    // inverse slot maps of the gradient paths: the min-sum forms (ldpc_backward, ldpc_train_joint) and RCQ (ldpc_train_joint_ste)
+    if (!rc && d->dtype == LDPC_F32 && d->schedule == LDPC_SCHED_FLOODING) {
         auto invert = [&](const int32_t *slot, int count, int n_slots, int **ptr_dev, int **items_dev) {
             std::vector<int> ptr((size_t)n_slots + 1, 0), items((size_t)std::max(count, 1), 0);
             for (int x = 0; x < count; ++x) ptr[slot[x] + 1]++;
@@ -1581,6 +1583,16 @@ int train_supported(const ldpc_decoder *d)
     return LDPC_OK;
 }
 
+// ldpc_train_joint_ste: the quantised decoder, differentiated with the straight-through rule
+int ste_supported(const ldpc_decoder *d)
+{
+    if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
+    if (d->dtype != LDPC_F32 || d->form != LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_FLOODING)
+        return fail(LDPC_ERR_UNSUPPORTED, "the straight-through joint loss exists for the fp32 RCQ flooding decoders "
+                                          "(ldpc_train_joint has the min-sum forms; the layered schedules have no gradient path)");
+    return LDPC_OK;
+}
+
 struct BackwardWs {
     int vec = 0, tiles = 0;
     float *llrT = nullptr, *gpostT = nullptr, *gv2c = nullptr, *gc2v = nullptr, *gbeta = nullptr, *galpha = nullptr;
@@ -1684,6 +1696,7 @@ int backward_impl(const ldpc_decoder *d, const char *saved, const float *llr, in
 // leave-one-out sums), so the scratch is a constant number of rows per codeword whatever T is --
 // E rows: v2c_t / v2c_t+1 and c2v_t-1 / c2v_t (ping-pong), d J/d v2c_t;  n rows: llr, posterior (then g_l in place),
 // targets, d J/d llr;  plus per-tile partials of the table gradients and of the loss.
+// ldpc_train_joint_ste (RCQ, `codes`): the same loop on the two-sweep RCQ form -- the two C2V buffers hold 1-byte codes.
 struct JointWs {
     Workspace fw;                            // forward view: llrT, postT, bitsT (v2c / c2v chosen per iteration)
     char *v2c[2] = {nullptr, nullptr}, *c2v[2] = {nullptr, nullptr};
@@ -1691,7 +1704,7 @@ struct JointWs {
     double *loss_part = nullptr, *item_sum = nullptr;
     size_t total = 0;
 };
-JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base)
+JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, bool codes = false)
 {
     JointWs w;
     w.fw.vec = pick_vec(d, batch);
@@ -1702,7 +1715,8 @@ JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base)
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
     const size_t o_llr = take(tw * n * 4), o_post = take(tw * n * 4), o_y = take(tw * n * 4), o_gl = take(tw * n * 4);
-    const size_t o_v0 = take(tw * E * 4), o_v1 = take(tw * E * 4), o_c0 = take(tw * E * 4), o_c1 = take(tw * E * 4);
+    const size_t cs = codes ? 1 : 4;
+    const size_t o_v0 = take(tw * E * 4), o_v1 = take(tw * E * 4), o_c0 = take(tw * E * cs), o_c1 = take(tw * E * cs);
     const size_t o_gv = take(tw * E * 4);
     const size_t o_bits = take((size_t)tiles * n * w.fw.vec * sizeof(uint64_t));
     const size_t o_gb = take((size_t)tiles * E * 4), o_goa = take(d->form == LDPC_C2V_OMS ? (size_t)tiles * E * 4 : 0);
@@ -1731,7 +1745,7 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
     const GraphDev g = d->g->dev();
     const int T = d->T, tiles = w.fw.tiles, vc = (g.n + JT - 1) / JT;
     const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
-    const bool oms = d->form == LDPC_C2V_OMS;
+    const bool oms = d->form == LDPC_C2V_OMS, rcq = d->form == LDPC_C2V_RCQ;
     const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
     const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
     hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, (float *)w.fw.llrT, (long long)batch, g.n, vc);
@@ -1791,18 +1805,26 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
 #define LDPC_CNJ(FIRST_, FORM_)                                                                                        \
     hipLaunchKernelGGL((cn_backward<VEC, FIRST_, FORM_, true>), cgrid, blk, 0, s, g, src, (const float *)nullptr,     \
                        (const float *)postT, (const int *)nullptr, (long long)batch, t, beta_row, (const int *)d->beta_slot, \
-                       gv_out, w.gbeta, goa, cb)
-        if (t == 0) { if (oms) LDPC_CNJ(true, FORM_OMS); else LDPC_CNJ(true, FORM_NMS); }
-        else { if (oms) LDPC_CNJ(false, FORM_OMS); else LDPC_CNJ(false, FORM_NMS); }
+                       gv_out, w.gbeta, goa, cb, (const uint8_t *)(rcq ? w.c2v[t & 1] : nullptr), d->n_levels)
+        if (t == 0) { if (oms) LDPC_CNJ(true, FORM_OMS); else if (rcq) LDPC_CNJ(true, FORM_RCQ); else LDPC_CNJ(true, FORM_NMS); }
+        else { if (oms) LDPC_CNJ(false, FORM_OMS); else if (rcq) LDPC_CNJ(false, FORM_RCQ); else LDPC_CNJ(false, FORM_NMS); }
 #undef LDPC_CNJ
         if (grad_beta) reduce_step(w.gbeta, g.E, d->beta_inv_ptr, d->beta_inv_items, d->n_beta, grad_beta + (size_t)t * d->n_beta);
         if (oa_grad)
             reduce_step(w.goa, g.E, d->oms_inv_ptr, d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha + (size_t)t * d->n_oms_alpha);
         if (!oms && t >= 1 && grad_alpha) {
             const float *alpha_row = (const float *)d->alpha + (size_t)(t - 1) * d->n_alpha;
-            hipLaunchKernelGGL((vn_backward<VEC, true>), vbgrid, blk, 0, s, g, (const float *)w.c2v[(t - 1) & 1],
-                               (const float *)w.gv2c, (const int *)nullptr, (long long)batch, t, alpha_row,
-                               (const int *)d->alpha_slot, (float *)nullptr, w.galpha, vbb);
+            if (rcq) {                                    // code rows of iteration t-1, reconstructed with ITS quantiser
+                const int lut_entries = 2 * d->n_levels;
+                hipLaunchKernelGGL((vn_backward<VEC, true, true>), vbgrid, blk, 0, s, g, (const void *)w.c2v[(t - 1) & 1],
+                                   (const float *)w.gv2c, (const int *)nullptr, (long long)batch, t, alpha_row,
+                                   (const int *)d->alpha_slot, (float *)nullptr, w.galpha, vbb,
+                                   (const float *)d->lut + (size_t)d->q_of_iter[t - 1] * lut_entries, lut_entries);
+            } else {
+                hipLaunchKernelGGL((vn_backward<VEC, true>), vbgrid, blk, 0, s, g, (const void *)w.c2v[(t - 1) & 1],
+                                   (const float *)w.gv2c, (const int *)nullptr, (long long)batch, t, alpha_row,
+                                   (const int *)d->alpha_slot, (float *)nullptr, w.galpha, vbb);
+            }
             reduce_step(w.galpha, g.n, d->alpha_inv_ptr, d->alpha_inv_items, d->n_alpha, grad_alpha + (size_t)(t - 1) * d->n_alpha);
         }
         if (grad_llr)
@@ -1892,14 +1914,17 @@ size_t ldpc_train_joint_workspace_bytes(const ldpc_decoder *d, int64_t batch)
     return carve_joint(d, batch, nullptr).total;
 }
 
-int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
-                     const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
-                     void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
-                     size_t workspace_bytes, void *stream)
+// ldpc_train_joint (ste = false) and ldpc_train_joint_ste (ste = true): the same argument rules, the same loop
+static int train_joint_entry(const ldpc_decoder *d, bool ste, const void *llr, const void *targets, int64_t batch,
+                             const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                             void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
+                             size_t workspace_bytes, void *stream)
 {
-    if (int rc = train_supported(d)) return rc;
+    if (int rc = ste ? ste_supported(d) : train_supported(d)) return rc;
     if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
     if (d->T < 1) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs at least one iteration");
+    if (!d->beta_inv_ptr || !d->alpha_inv_ptr) return fail(LDPC_ERR_UNSUPPORTED, "internal: the decoder has no inverse slot maps");
+    if (ste && d->n_levels > kVnbLutMax / 2) return fail(LDPC_ERR_UNSUPPORTED, "more than %d quantiser levels", kVnbLutMax / 2);
     if (!loss_per_iter) return fail(LDPC_ERR_ARG, "NULL loss_per_iter");
     const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
     if (want && !iteration_weights) return fail(LDPC_ERR_ARG, "NULL iteration_weights");
@@ -1915,7 +1940,7 @@ int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets
     if (d->g->n == 0 || d->g->E == 0) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs a graph with edges");
     if (!llr || !workspace) return fail(LDPC_ERR_ARG, "NULL llr/workspace");
     if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
-    const JointWs w = carve_joint(d, batch, workspace);
+    const JointWs w = carve_joint(d, batch, workspace, ste);
     if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
     if ((size_t)w.fw.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
 #define LDPC_JOINT(V_)                                                                                                 \
@@ -1925,6 +1950,30 @@ int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets
     if (w.fw.vec == 1) return LDPC_JOINT(1);
     return LDPC_JOINT(4);
 #undef LDPC_JOINT
+}
+
+int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                     const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                     void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
+                     size_t workspace_bytes, void *stream)
+{
+    return train_joint_entry(d, false, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
+                             grad_alpha, grad_oms_alpha, grad_llr, workspace, workspace_bytes, stream);
+}
+
+size_t ldpc_train_joint_ste_workspace_bytes(const ldpc_decoder *d, int64_t batch)
+{
+    if (!d || batch < 0) return 0;
+    return carve_joint(d, batch, nullptr, /*codes=*/true).total;
+}
+
+int ldpc_train_joint_ste(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                         const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                         void *grad_beta, void *grad_alpha, void *grad_llr, void *workspace, size_t workspace_bytes,
+                         void *stream)
+{
+    return train_joint_entry(d, true, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
+                             grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream);
 }
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

@@ -79,6 +79,11 @@ __device__ __forceinline__ void load_states_of(const int *__restrict__ iteration
 // d/d alpha_c = -g*ps (second per-edge partial, goa_part), d/d minval = g*ps*[minval > beta]; relu'(0) = 0.
 // LOCAL: the posterior-local backward of ldpc_train_joint -- seeded from gpostT = d J_t/d l_t for every real codeword,
 // nothing chained in (gc2v and iterations unused).
+// FORM_RCQ (LOCAL only, ldpc_train_joint_ste): c2v = deq(quant(m)), m = beta * minval * prod(signs), differentiated with the
+// straight-through rule d c2v/d m := 1 where the code the forward wrote (`codes`, the u8 rows of this iteration's check
+// sweep: one dword per lane at VEC = 4) lies below the top level, 0 where it saturated -- the FORM_NMS body with that
+// per-edge mask on both the beta partial and the gradient passed on to the magnitudes.  The mask is read, not recomputed:
+// no comparison is repeated, so it cannot disagree with the forward.
 template <int VEC, bool FIRST, int FORM, bool LOCAL = false>
 __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *__restrict__ src,
                                                       const float *__restrict__ gc2v,
@@ -88,8 +93,10 @@ __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *_
                                                       const int *__restrict__ beta_slot,
                                                       float *__restrict__ gv2c_out,
                                                       float *__restrict__ gbeta_part,
-                                                      float *__restrict__ goa_part, int check_blocks)
+                                                      float *__restrict__ goa_part, int check_blocks,
+                                                      const uint8_t *__restrict__ codes = nullptr, int n_levels = 0)
 {
+    static_assert(FORM != FORM_RCQ || LOCAL, "the quantised form has a posterior-local backward only");
     constexpr int W = kWave * VEC;
     const int lane = threadIdx.x & (kWave - 1);
     const int tile = uni(blockIdx.x / check_blocks);
@@ -177,6 +184,8 @@ __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *_
         if (any_vn) gv = ld<float, VEC>(gc2v + erow + (size_t)u * W);
         if (any_post) gp = ld<float, VEC>(gpostT + ((size_t)tile * g.n + g.var_idx[e0 + u]) * W + lane_off);
         if (wide) re = ld<float, VEC>(in_row(u));
+        Pack<uint8_t, VEC> cq;
+        if constexpr (FORM == FORM_RCQ) cq = ld<uint8_t, VEC>(codes + erow + (size_t)u * W);
         float gb = 0.0f, goa = 0.0f;
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
@@ -195,8 +204,14 @@ __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *_
                     goa -= gps;
                     gm = open;
                 } else {
-                    gb += gps * minval;
-                    gm = gps * b;
+                    float gk = gps;
+                    if constexpr (FORM == FORM_RCQ) {           // straight-through below the top level, 0 where saturated
+                        const int q = cq.x[c];
+                        const int lvl = q >= n_levels ? q - n_levels : q;
+                        gk = lvl < n_levels - 1 ? gps : 0.0f;
+                    }
+                    gb += gk * minval;
+                    gm = gk * b;
                 }
                 if (u == idx[c]) acc2[c] += gm; else acc1[c] += gm;
             }
@@ -234,19 +249,35 @@ __global__ __launch_bounds__(kBlock) void cn_backward(GraphDev g, const float *_
 // d loss/d alpha_t-1.  Leave-one-out sums are formed as (total - own) with the totals in fp64.
 // LOCAL (ldpc_train_joint): the leave-one-out sums are constants (stop-gradient), so only the alpha_t-1 partial
 // sum_e g_v2c_t[e] * S_t-1[e] is formed, for every real codeword, and no d loss/d c2v_t-1 is written (gc2v_out unused).
+// CODES (LOCAL only, ldpc_train_joint_ste): c2v_t-1 is a row of 1-byte quantiser codes, reconstructed through `lut_prev`,
+// the [2L] signed table of the quantiser of iteration t-1 (the one that wrote them), held in LDS as vn_sweep holds it:
+// 1 + 4 bytes per edge and codeword instead of 8.
 // ------------------------------------------------------------------------------------------
 constexpr int kVnbVarsPerWave = 4;
+constexpr int kVnbLutMax = 256;                // 2 * n_levels, n_levels <= 128 (ldpc_decoder_create)
 
-template <int VEC, bool LOCAL = false>
-__global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *__restrict__ c2v_prev,
+template <int VEC, bool LOCAL = false, bool CODES = false>
+__global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const void *__restrict__ c2v_prev,
                                                       const float *__restrict__ gv2c,
                                                       const int *__restrict__ iterations, long long batch, int t,
                                                       const float *__restrict__ alpha_row,
                                                       const int *__restrict__ alpha_slot,
                                                       float *__restrict__ gc2v_out,
-                                                      float *__restrict__ galpha_part, int var_blocks)
+                                                      float *__restrict__ galpha_part, int var_blocks,
+                                                      const float *__restrict__ lut_prev = nullptr, int lut_entries = 0)
 {
+    static_assert(!CODES || LOCAL, "code rows have a posterior-local backward only");
     constexpr int W = kWave * VEC;
+    Lut<VEC> lut;
+    lut.base = nullptr;
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) lut.off[c] = 0;
+    if constexpr (CODES) {
+        __shared__ float lut_s[kVnbLutMax];
+        for (int k = threadIdx.x; k < lut_entries; k += kBlock) lut_s[k] = lut_prev[k];
+        __syncthreads();                           // before any wave leaves
+        lut.base = lut_s;
+    }
     const int lane = threadIdx.x & (kWave - 1);
     const int tile = uni(blockIdx.x / var_blocks);
     const int jbase = uni(((blockIdx.x % var_blocks) * kWavesPerBlock + (threadIdx.x >> 6)) * kVnbVarsPerWave);
@@ -289,7 +320,7 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
         for (int k = 0; k < kHeld; ++k) {
             if (k < dv) {
                 row[k] = base + (size_t)g.csc_edge[k0 + k] * W;
-                cv[k] = ld<float, VEC>(c2v_prev + row[k]);
+                cv[k] = load_c2v<float, VEC, CODES>(c2v_prev, row[k], lut);
                 gv[k] = ld<float, VEC>(gv2c + row[k]);
             }
         }
@@ -323,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
 #pragma unroll 4
     for (int k = 0; k < dv; ++k) {
         const size_t row = base + (size_t)g.csc_edge[k0 + k] * W;
-        const Pack<float, VEC> cv = ld<float, VEC>(c2v_prev + row);
+        const Pack<float, VEC> cv = load_c2v<float, VEC, CODES>(c2v_prev, row, lut);
         const Pack<float, VEC> gv = ld<float, VEC>(gv2c + row);
 #pragma unroll
         for (int c = 0; c < VEC; ++c)
@@ -332,7 +363,7 @@ __global__ __launch_bounds__(kBlock) void vn_backward(GraphDev g, const float *_
 #pragma unroll 4
     for (int k = 0; k < dv; ++k) {
         const size_t row = base + (size_t)g.csc_edge[k0 + k] * W;
-        const Pack<float, VEC> cv = ld<float, VEC>(c2v_prev + row);
+        const Pack<float, VEC> cv = load_c2v<float, VEC, CODES>(c2v_prev, row, lut);
         const Pack<float, VEC> gv = ld<float, VEC>(gv2c + row);
         Pack<float, VEC> o;
 #pragma unroll

@@ -461,6 +461,18 @@ class DecodeEngine:
     def train_joint_workspace_bytes(self, batch: int) -> int:
         return int(self._lib.ldpc_train_joint_workspace_bytes(self.handle, int(batch)))
 
+    def train_joint_ste_workspace_bytes(self, batch: int) -> int:
+        return int(self._lib.ldpc_train_joint_ste_workspace_bytes(self.handle, int(batch)))
+
+    def train_joint_ste(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                        iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
+                        want_grad_llr: bool = False) -> dict:
+        """train_joint() of the quantised decoder (ldpc_train_joint_ste): the fp32 RCQ flooding decode, unchanged, with
+        the posterior-local gradients of J formed through the straight-through rule of include/ldpc_hip.h (gradient 1
+        through the quantiser below its top level, 0 where the code saturated).  Same arguments and the same dict as
+        train_joint ("grad_oms_alpha" is always None); NotImplementedError for every other decoder."""
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, ste=True)
+
     def train_joint(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                     iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
                     want_grad_llr: bool = False) -> dict:
@@ -471,6 +483,9 @@ class DecodeEngine:
         -> {"loss": 0-d, "loss_per_iter": [T], "bits": int32 [B, n], "posterior": [B, n] (of the last iteration),
             "grad_beta", "grad_alpha": [T, slots] | None, "grad_oms_alpha": [T, slots] | None, "grad_llr": [B, n] | None}
         Everything on this engine's device, fp32."""
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, ste=False)
+
+    def _train_joint(self, llr, targets, iteration_weights, want_grads, want_grad_llr, ste: bool) -> dict:
         llr = self._check_llr(llr)
         B, n = llr.shape
         dev = self.device
@@ -491,11 +506,11 @@ class DecodeEngine:
         gb = torch.empty(self._table_shapes[0], dtype=torch.float32, device=dev) if want_grads else None
         ga = torch.empty(self._table_shapes[1], dtype=torch.float32, device=dev) if want_grads else None
         goa = (torch.empty(self._table_shapes[2], dtype=torch.float32, device=dev)
-               if want_grads and self._table_shapes[2] is not None else None)
+               if want_grads and not ste and self._table_shapes[2] is not None else None)
         gl = torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr else None
         ws = None
         if B > 0:
-            need = self.train_joint_workspace_bytes(B)
+            need = self.train_joint_ste_workspace_bytes(B) if ste else self.train_joint_workspace_bytes(B)
             ws = getattr(self, "_joint_ws", None)
             if ws is None or ws.numel() < need:
                 self._joint_ws = None
@@ -503,9 +518,14 @@ class DecodeEngine:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            nat.check(self._lib.ldpc_train_joint(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
-                                                 p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),
-                                                 C.c_void_p(stream)), "ldpc_train_joint")
+            if ste:
+                nat.check(self._lib.ldpc_train_joint_ste(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
+                                                         p(gb), p(ga), p(gl), p(ws), 0 if ws is None else ws.numel(),
+                                                         C.c_void_p(stream)), "ldpc_train_joint_ste")
+            else:
+                nat.check(self._lib.ldpc_train_joint(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
+                                                     p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),
+                                                     C.c_void_p(stream)), "ldpc_train_joint")
         return {"loss": (w[:T] * lpi).sum(), "loss_per_iter": lpi, "bits": bits, "posterior": post,
                 "grad_beta": gb, "grad_alpha": ga, "grad_oms_alpha": goa, "grad_llr": gl}
 

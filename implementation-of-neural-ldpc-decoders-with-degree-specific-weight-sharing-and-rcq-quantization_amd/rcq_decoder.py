@@ -39,7 +39,18 @@ then hard decisions (P < 0) and the syndrome; with early_stop a codeword that sa
 posteriors, iterations t+1.  beta is indexed exactly as in the flooding forward (same slots and tables, all four sharing
 types).  alpha is NOT used: a layered update has no separate variable-node sum for it to scale.  Posteriors are fp32;
 ``bv`` stays stored and unused.  With every beta 1.0 the result is bit-identical to RCQMinSumDecoder(layered="paper").
-Every other value of ``layered`` (True included) runs the flooding decode, as the reference does.  No backward pass.
+Every other value of ``layered`` (True included) runs the flooding decode, as the reference does.  The layered schedule
+has no backward pass.
+
+Training the flooding ``WeightedRCQDecoder`` (an extension; under the reference's autograd the quantiser is a chain of
+``torch.where`` over comparisons, rcq_decoder.py:59-91, and beta never receives a gradient): with
+``quantizer_gradient="straight_through"`` -- constructor argument, or keyword of ``joint_posterior_loss`` --
+``joint_posterior_loss`` runs the decoder's own fixed-T decode and gives the posterior-local gradient of the per-iteration
+loss (as the min-sum decoders' ``joint_posterior_loss``) with the quantiser treated as
+    c2v = Q^-1(code)                       (the forward's value, exact)
+    d c2v / d m := 1  where the code the forward wrote lies below the top level (the dead zone included)
+                   0  where it saturated,      m = beta_t[slot(e)] * sign product * min
+(include/ldpc_hip.h ldpc_train_joint_ste).  Without the option the decoder refuses to train, as before.
 """
 
 from __future__ import annotations
@@ -190,11 +201,15 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
     """Weighted RCQ decoder: degree-shared neural weights + RCQ quantisation."""
 
     def __init__(self, code: LDPCCode, bc: int, bv: int, quantizer_params: List[Tuple[float, float]],
-                 weight_sharing_type: int = 2, max_iterations: int = 50, layered: bool = False):
+                 weight_sharing_type: int = 2, max_iterations: int = 50, layered: bool = False, *,
+                 quantizer_gradient=None):
         super().__init__()
+        import autograd_bridge as ab
         self.bc = bc
         self.bv = bv
         self.layered = layered            # stored; forward ignores it like the reference's, except "paper" (module docstring)
+        # how joint_posterior_loss differentiates the quantiser: None (it refuses) or "straight_through"
+        self.quantizer_gradient = ab.check_quantizer_gradient(quantizer_gradient)
         self.quantizers = [NonUniformQuantizer(bc, C, gamma) for C, gamma in quantizer_params]
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized Weighted RCQ decoder: bc={bc}, bv={bv}, "
@@ -219,9 +234,28 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
                     thresholds=_threshold_table(self.quantizers),
                     q_of_iter=_quantizer_schedule(len(self.quantizers), self.max_iterations))
 
-    def joint_posterior_loss(self, llr, targets=None, iteration_weights=None, device=None):
-        """not available: the RCQ quantiser passes no gradient, so there is nothing to train through"""
-        raise NotImplementedError("WeightedRCQDecoder has no gradient path: the RCQ quantiser passes no gradient")
+    def joint_posterior_loss(self, llr, targets=None, iteration_weights=None, device=None, *, quantizer_gradient=None):
+        """Posterior joint training of the quantised decoder.  ``quantizer_gradient`` (default: the constructor's) names
+        the estimator the quantiser is differentiated with: None -- the RCQ quantiser passes no gradient, so there is
+        nothing to train through (NotImplementedError); "straight_through" -- the decoder's own fixed-T flooding decode
+        with the loss of ``Neural2DMinSumDecoder.joint_posterior_loss`` and the rule of the module docstring.
+        -> (loss 0-d, loss_per_iteration [T], bits int32, posterior of the last iteration)"""
+        import autograd_bridge as ab
+        how = ab.check_quantizer_gradient(self.quantizer_gradient if quantizer_gradient is None else quantizer_gradient)
+        if how is None:
+            raise NotImplementedError("WeightedRCQDecoder has no gradient path: the RCQ quantiser passes no gradient "
+                                      "(quantizer_gradient=\"straight_through\" trains through it with that estimator)")
+        if not isinstance(llr, torch.Tensor):
+            raise TypeError("llr must be a torch.Tensor")
+        ab.check_joint_args(self.code.n, int(self.max_iterations), llr, targets, iteration_weights)
+        import _native as nat
+        if self._schedule() != nat.SCHED_FLOODING:
+            raise NotImplementedError("the straight-through joint loss exists for the flooding schedule only "
+                                      "(layered=\"paper\" has no gradient path)")
+        eng = self._get_engine(llr.device if llr.is_cuda else device)
+        bt, at = self._sharing_layout().tables_torch(self.beta_weights, self.alpha_weights, int(self.max_iterations),
+                                                     self._beta_default, self._alpha_default)
+        return ab.joint_loss_ste(bt, at, eng, llr, targets, iteration_weights)
 
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):
         """

@@ -30,6 +30,13 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
      posterior, whose gradients the forward already formed (no saved history); differentiable in `loss` only, the
      backward scales the last three outputs (and d loss/d w_t = loss_per_iter[t]).
 
+  ldpc::rcq_joint_loss(Tensor llr, Tensor? targets, Tensor beta, Tensor alpha, Tensor iteration_weights, int engine,
+                       bool want_grads=True, bool want_grad_llr=False)
+        -> the same seven outputs
+     the same for the quantised WeightedRCQDecoder (ldpc_train_joint_ste): the forward is its fixed-T flooding decode
+     bit for bit; the gradients treat the quantiser with the straight-through rule -- d c2v/d m := 1 where the code the
+     forward wrote lies below the top level (the dead zone included), 0 where it saturated, m = beta * sign product * min.
+
 ``engine`` is an integer handle of a live ``engine.DecodeEngine`` (``engine_handle(eng)``): operator schemas
 carry tensors and scalars, and the native decoder handle is neither.  There is no CPU implementation: the
 ops exist for ROCm tensors only and fail loudly otherwise (no fallback).
@@ -268,3 +275,55 @@ def _joint_backward(ctx, g_loss, *_unused):
 
 
 minsum_joint_loss.register_autograd(_joint_backward, setup_context=_joint_setup)
+
+
+@torch.library.custom_op("ldpc::rcq_joint_loss", mutates_args=())
+def rcq_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, iteration_weights: Tensor,
+                   engine: int, want_grads: bool = True,
+                   want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """minsum_joint_loss of the quantised decoder (ldpc_train_joint_ste): the fixed-T W-RCQ decode, its per-iteration
+    loss, and the straight-through gradients d loss/d beta [T, Sb], d loss/d alpha [T, Sa] (variable side),
+    d loss/d llr [B, n]"""
+    eng = _engine(engine)
+    restore = _with_tables(eng, _np_table(beta), _np_table(alpha), False)
+    try:
+        r = eng.train_joint_ste(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
+                                want_grads=want_grads, want_grad_llr=want_grad_llr)
+    finally:
+        restore()
+    if want_grads:
+        gb = r["grad_beta"].to(device=beta.device, dtype=beta.dtype)
+        ga = r["grad_alpha"].to(device=alpha.device, dtype=alpha.dtype)
+    else:
+        gb, ga = torch.empty((0,), dtype=beta.dtype, device=beta.device), torch.empty((0,), dtype=alpha.dtype, device=alpha.device)
+    gl = r["grad_llr"] if want_grad_llr else torch.empty((0,), dtype=torch.float32, device=llr.device)
+    return r["loss"], r["loss_per_iter"], r["posterior"], r["bits"], gb, ga, gl
+
+
+@rcq_joint_loss.register_fake
+def _(llr, targets, beta, alpha, iteration_weights, engine, want_grads=True, want_grad_llr=False):
+    B, n = llr.shape
+    dev = llr.device
+    T = iteration_weights.shape[0]
+    return (torch.empty((), dtype=torch.float32, device=dev), torch.empty((T,), dtype=torch.float32, device=dev),
+            torch.empty((B, n), dtype=torch.float32, device=dev), torch.empty((B, n), dtype=torch.int32, device=dev),
+            torch.empty_like(beta) if want_grads else torch.empty((0,), dtype=beta.dtype, device=beta.device),
+            torch.empty_like(alpha) if want_grads else torch.empty((0,), dtype=alpha.dtype, device=alpha.device),
+            torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr
+            else torch.empty((0,), dtype=torch.float32, device=dev))
+
+
+def _rcq_joint_setup(ctx, inputs, output):
+    _llr, _targets, _beta, _alpha, _w, _engine_h, want_grads, want_grad_llr = inputs
+    _loss, lpi, post, bits, gb, ga, gl = output
+    ctx.want_grads, ctx.want_grad_llr = want_grads, want_grad_llr
+    ctx.save_for_backward(lpi, gb, ga, gl)
+    ctx.mark_non_differentiable(lpi, post, bits, gb, ga, gl)
+    ctx.set_materialize_grads(False)
+
+
+def _rcq_joint_backward(ctx, g_loss, *_unused):
+    return _joint_backward(ctx, g_loss)[:-1]         # one input fewer: no alpha_is_oms
+
+
+rcq_joint_loss.register_autograd(_rcq_joint_backward, setup_context=_rcq_joint_setup)

@@ -222,6 +222,29 @@ int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets
                      void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- posterior joint training of the quantised decoder (straight-through estimator) ----------
+ * ldpc_train_joint for the fp32 LDPC_C2V_RCQ flooding decoders (LDPC_ERR_UNSUPPORTED for every other decoder;
+ * ldpc_train_joint itself keeps refusing these).  Same loss, same outputs, same empty-batch / NULL-output /
+ * alignment rules, no grad_oms_alpha; scratch ldpc_train_joint_ste_workspace_bytes (the C2V rows it keeps are 1-byte codes).
+ *   Forward : the decoder's own fixed-T two-sweep decode, unchanged -- bits, posterior and every iteration's posterior l_t
+ *             equal ldpc_decode / ldpc_decode_capped with early_stop = 0 bit for bit.
+ *   Gradient: posterior-local as above (J_t reaches beta_t, alpha_t-1 and the LLRs; alpha_T-1 gets 0), with the quantiser
+ *             differentiated by the straight-through rule.  With m = beta_t[slot(e)] * s * min the value the forward
+ *             quantises (min / min2 / first-index arg-min / sign(0) = 0 / degree-1 rules and second-minimum tie split of
+ *             the LDPC_C2V_NMS backward), code_t[e] the code the forward wrote and L = n_levels:
+ *                 c2v_t[e]          = deq_t(code_t[e])                         (value, exact)
+ *                 d c2v_t[e] / d m := 1  if (code_t[e] mod L) < L - 1          (below the top level, dead zone included)
+ *                                     0  otherwise                             (saturated)
+ *             The mask is a function of the code the forward stored, not of a repeated comparison.  The constants of the
+ *             alpha_t-1 partial are leave-one-out sums of deq_t-1(code_t-1[.]): the quantiser of iteration t-1
+ *             (q_of_iter[t-1]), not of iteration t.
+ * Deterministic: no atomics. */
+size_t ldpc_train_joint_ste_workspace_bytes(const ldpc_decoder *d, int64_t batch);
+int ldpc_train_joint_ste(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                         const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                         void *grad_beta, void *grad_alpha, void *grad_llr,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
 /* sha256 (hex) over the sources and the compile recipe this library was built from, embedded at build time

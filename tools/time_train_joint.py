@@ -3,12 +3,16 @@
 posterior-local HIP gradients, backward scaling, Adam) next to the existing full-backpropagation step (forward with saved
 messages, HIP backward sweeps, Adam) at the same size.
 
-    python tools/time_train_joint.py [--steps 10]
+    python tools/time_train_joint.py [--steps 10] [--decoder neural2d|wrcq]
 Prints one JSON line with a result per workload: (1998,1512) Neural-2D type 2 at T = 10 with B = 4096 and 32768, and
 (16200,7200) at T = 20 with B = 1024.  Device events around each step.  Algorithmic HBM bytes of a PJT step, per codeword
 and iteration: forward sweeps 16E + 8n (check: read v2c, write c2v; variable: read c2v + llr, write v2c + posterior), loss
 8n (read posterior, write g_l), local backward 20E (check: read v2c, gathered g_l and write d/dv2c; variable: read c2v_t-1
-and d/dv2c)."""
+and d/dv2c).
+--decoder wrcq times the same step of the quantised WeightedRCQDecoder (type 2, bc = 3, three quantisers,
+quantizer_gradient="straight_through") on the same workloads; it has no full-backpropagation step to stand next to.  Its
+C2V rows are 1-byte codes: forward sweeps 10E + 8n, loss 8n, local backward 18E (check: v2c, codes, gathered g_l, write
+d/dv2c; variable: codes of t-1 and d/dv2c) -- 28E + 16n against 36E + 16n."""
 import argparse, json, os, sys
 os.environ.setdefault("LDPC_TRAIN_MAX_SAVED_BYTES", str(64 << 30))     # let the BPTT step run where the HBM holds it
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,12 +38,18 @@ def time_steps(step, steps):
     return e0.elapsed_time(e1) / steps, float(loss.item())
 
 
-def run(name, T, B, steps, snr_db, dev):
+WRCQ_QUANTIZERS = [(3.0, 1.3), (5.0, 1.3), (7.0, 1.3)]
+
+
+def run(name, T, B, steps, snr_db, dev, decoder="neural2d"):
     import autograd_bridge as ab
     import codes
     from neural_2d_decoder import Neural2DMinSumDecoder
+    from rcq_decoder import WeightedRCQDecoder
     code = codes.load_code(name, max_iterations=T)
-    model = Neural2DMinSumDecoder(code, 2, T)
+    wrcq = decoder == "wrcq"
+    model = (WeightedRCQDecoder(code, 3, 8, WRCQ_QUANTIZERS, 2, T, quantizer_gradient="straight_through") if wrcq
+             else Neural2DMinSumDecoder(code, 2, T))
     with torch.no_grad():
         for p in model.beta_weights.values():
             p.fill_(0.7)
@@ -67,10 +77,15 @@ def run(name, T, B, steps, snr_db, dev):
 
     eng = model._get_engine(dev)
     ms, loss = time_steps(pjt, steps)
-    alg = B * T * (36 * g.E + 16 * g.n)
-    out = {"workload": f"{name} Neural2D type 2, T={T}, batch {B}", "pjt_ms_per_step": ms,
+    alg = B * T * ((28 if wrcq else 36) * g.E + 16 * g.n)
+    ws = eng.train_joint_ste_workspace_bytes(B) if wrcq else eng.train_joint_workspace_bytes(B)
+    out = {"workload": f"{name} {'W-RCQ bc=3' if wrcq else 'Neural2D'} type 2, T={T}, batch {B}", "pjt_ms_per_step": ms,
            "pjt_codewords_per_s": B / ms * 1e3, "pjt_algorithmic_GBps": alg / (ms * 1e-3) / 1e9,
-           "pjt_workspace_bytes_per_codeword": eng.train_joint_workspace_bytes(B) / B, "pjt_loss": loss}
+           "pjt_workspace_bytes_per_codeword": ws / B, "pjt_loss": loss}
+    if wrcq:                                               # no saved-history path exists for the quantised decoder
+        del model, opt, eng
+        torch.cuda.empty_cache()
+        return out
     saved = eng.train_saved_bytes(B)
     out["bptt_saved_bytes_per_codeword"] = saved / B
     if saved <= ab.MAX_SAVED_BYTES:
@@ -90,12 +105,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--snr-db", type=float, default=3.0)
     ap.add_argument("--workload", type=int, default=None, help="run only WORKLOADS[i]")
+    ap.add_argument("--decoder", choices=("neural2d", "wrcq"), default="neural2d")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     todo = WORKLOADS if a.workload is None else WORKLOADS[a.workload:a.workload + 1]
-    res = [run(name, T, B, a.steps, a.snr_db, dev) for name, T, B in todo]
-    print(json.dumps({"tool": "time_train_joint", "steps": a.steps, "results": res}))
+    res = [run(name, T, B, a.steps, a.snr_db, dev, a.decoder) for name, T, B in todo]
+    print(json.dumps({"tool": "time_train_joint", "decoder": a.decoder, "steps": a.steps, "results": res}))
 
 
 if __name__ == "__main__":
