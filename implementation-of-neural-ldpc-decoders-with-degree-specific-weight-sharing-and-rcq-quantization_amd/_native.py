@@ -60,12 +60,21 @@ def source_hash(defines=()) -> str:
     return h.hexdigest()
 
 
+def _dlopen(path: str):
+    """dlopen with torch imported first.  A ROCm wheel of torch ships its own libamdhip64 / libhsa-runtime64; loading this
+    library before torch maps the system's copies through its NEEDED entries, the process then holds two HIP runtimes and the
+    one that initialises second finds no device (ldpc_graph_create: "no HIP device available" in build() followed by smoke()).
+    With torch's runtime already mapped the loader resolves the NEEDED entries to it: one runtime, whatever the import order."""
+    import torch  # noqa: F401
+    return C.CDLL(path)
+
+
 def built_hash(target: Optional[str] = None) -> Optional[str]:
     """the source hash EMBEDDED in a built library (ldpc_source_hash(); None: not a library of this project, or a build
     that predates the symbol).  Read through a private dlopen handle -- loading a stale library to ask what it is is harmless."""
     target = target or os.path.join(_HERE, LIB_NAME)
     try:
-        lib = C.CDLL(target)
+        lib = _dlopen(target)
         fn = lib.ldpc_source_hash
         fn.restype = C.c_char_p
         fn.argtypes = []
@@ -150,7 +159,7 @@ def load():
                 f"{LIB_PATH} was not built from the sources in csrc/ (content hash {built_hash(LIB_PATH)} != "
                 f"{source_hash()}): run `python -c 'import __graft_entry__ as g; g.build()'` -- a stale engine is never loaded")
         try:
-            lib = C.CDLL(LIB_PATH)
+            lib = _dlopen(LIB_PATH)
         except OSError as e:
             raise NativeEngineError(f"cannot load {LIB_PATH}: {e}") from e
         vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64

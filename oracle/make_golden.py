@@ -8,8 +8,8 @@ restatement (oracle/ldpc_oracle.c) against it while doing so.
 
 The fixtures are data only: graphs (dense H for the small codes, the name of a
 committed edge list for the large ones), input LLRs, weight values, and the
-reference's outputs (bits, success/posterior, iterations, per-iteration 3-bit
-quantiser codes).  Nothing of the reference's source text is stored.
+reference's outputs (bits, success/posterior, iterations, per-iteration
+quantiser codes, one byte each).  Nothing of the reference's source text is stored.
 
 Sets:
   quantizer      NonUniformQuantizer known answers + threshold-boundary sweep
@@ -22,6 +22,8 @@ Sets:
   dvbs2_wrcq     (16200,7200) W-RCQ T=20, 1 codeword              (--slow, ~15 min)
   grad_toy/small d loss/d beta, d loss/d alpha of the reference under torch autograd (the loss of
                  training_framework.py:101), Neural2D types 1-4 and the per-edge NeuralMinSumDecoder
+  rcq_widths     the RCQ decoders on the 48x96 code at 2, 32, 64 and 128 quantiser levels (bc 2, 6, 7, 8: codes that use
+                 bit 7), flooding with code traces and layered, plus a threshold-boundary sweep at bc 6, 7 and 8
   grad_ties      the same plus d loss/d llr on half-integer LLRs: exact ties for the second minimum (autograd splits evenly)
 """
 import argparse
@@ -194,34 +196,8 @@ def gen_quantizer():
     check_equal("kat thr", np.asarray(oracle.quantizer_thresholds(3, 5.0, 1.5)), out["kat_thresholds"])
     check_equal("kat codes", oracle.quantize(out["kat_x"], out["kat_thresholds"]), out["kat_codes"])
     check_bits_exact("kat deq", oracle.dequantize(out["kat_codes"], out["kat_thresholds"]), out["kat_deq"])
-    rng = np.random.default_rng(7)
     cfgs = [(3, 3.0, 1.3), (3, 5.0, 1.3), (3, 7.0, 1.3), (4, 6.0, 1.7), (2, 2.0, 1.0), (5, 8.0, 0.7)]
-    out["sweep_cfg"] = np.asarray(cfgs, dtype=np.float64)
-    for ci, (bc, C_, gm) in enumerate(cfgs):
-        q = ref_rcq.NonUniformQuantizer(bc=bc, C=C_, gamma=gm)
-        thr32 = np.asarray(q.thresholds, dtype=np.float32)
-        edge = []
-        for t in thr32:
-            for s in (1.0, -1.0):
-                v = np.float32(s * t)
-                edge += [v, np.nextafter(v, np.float32(np.inf)), np.nextafter(v, np.float32(-np.inf))]
-        # double-rounded neighbours: float32 of the fp64 threshold's neighbours
-        edge += [np.float32(np.nextafter(t, np.inf)) for t in q.thresholds]
-        edge += [np.float32(np.nextafter(t, -np.inf)) for t in q.thresholds]
-        edge += [np.float32(0.0), np.float32(-0.0), np.float32(np.inf), np.float32(-np.inf),
-                 np.float32(1e-30), np.float32(-1e-30), np.float32(1e30), np.float32(-1e30)]
-        x = np.concatenate([np.asarray(edge, dtype=np.float32),
-                            (rng.standard_normal(2000) * C_).astype(np.float32)])
-        xt = torch.from_numpy(x)
-        codes = q.quantize(xt).numpy()
-        deq = q.dequantize(torch.from_numpy(codes)).numpy()
-        out[f"sweep{ci}_thresholds"] = np.asarray(q.thresholds, dtype=np.float64)
-        out[f"sweep{ci}_x"] = x
-        out[f"sweep{ci}_codes"] = codes
-        out[f"sweep{ci}_deq"] = deq
-        check_equal(f"sweep{ci} thr", np.asarray(oracle.quantizer_thresholds(bc, C_, gm)), out[f"sweep{ci}_thresholds"])
-        check_equal(f"sweep{ci} codes", oracle.quantize(x, q.thresholds), codes)
-        check_bits_exact(f"sweep{ci} deq", oracle.dequantize(codes, q.thresholds), deq)
+    quantizer_sweep(out, "sweep", cfgs, np.random.default_rng(7))
     return out
 
 
@@ -836,6 +812,73 @@ def gen_grad_ties():
     return out
 
 
+QP_WIDTHS = [(3.0, 1.3), (5.0, 1.0), (6.0, 0.8)]
+
+
+def quantizer_sweep(out, prefix, cfgs, rng):
+    """threshold-boundary sweep of NonUniformQuantizer, keys {prefix}_cfg and {prefix}{i}_thresholds/_x/_codes/_deq"""
+    out[f"{prefix}_cfg"] = np.asarray(cfgs, dtype=np.float64)
+    for ci, (bc, C_, gm) in enumerate(cfgs):
+        q = ref_rcq.NonUniformQuantizer(bc=bc, C=C_, gamma=gm)
+        thr32 = np.asarray(q.thresholds, dtype=np.float32)
+        edge = []
+        for t in thr32:
+            for s in (1.0, -1.0):
+                v = np.float32(s * t)
+                edge += [v, np.nextafter(v, np.float32(np.inf)), np.nextafter(v, np.float32(-np.inf))]
+        # double-rounded neighbours: float32 of the fp64 threshold's neighbours
+        edge += [np.float32(np.nextafter(t, np.inf)) for t in q.thresholds]
+        edge += [np.float32(np.nextafter(t, -np.inf)) for t in q.thresholds]
+        edge += [np.float32(0.0), np.float32(-0.0), np.float32(np.inf), np.float32(-np.inf),
+                 np.float32(1e-30), np.float32(-1e-30), np.float32(1e30), np.float32(-1e30)]
+        x = np.concatenate([np.asarray(edge, dtype=np.float32),
+                            (rng.standard_normal(2000) * C_).astype(np.float32)])
+        codes = q.quantize(torch.from_numpy(x)).numpy()
+        deq = q.dequantize(torch.from_numpy(codes)).numpy()
+        out[f"{prefix}{ci}_thresholds"] = np.asarray(q.thresholds, dtype=np.float64)
+        out[f"{prefix}{ci}_x"] = x
+        out[f"{prefix}{ci}_codes"] = codes
+        out[f"{prefix}{ci}_deq"] = deq
+        check_equal(f"{prefix}{ci} thr", np.asarray(oracle.quantizer_thresholds(bc, C_, gm)), out[f"{prefix}{ci}_thresholds"])
+        check_equal(f"{prefix}{ci} codes", oracle.quantize(x, q.thresholds), codes)
+        check_bits_exact(f"{prefix}{ci} deq", oracle.dequantize(codes, q.thresholds), deq)
+
+
+def gen_rcq_widths():
+    """The RCQ decoders at 2, 32, 64 and 128 levels on the 48x96 code.  A code is one byte, sign * L + level: at bc = 8 the
+    negative codes use bit 7.  Flooding blocks carry every iteration's codes; the layered blocks are
+    RCQMinSumDecoder(layered=True) as the reference executes it."""
+    H = load_edge_list("small_96_48")
+    code = CachedCode(n=96, k=48, H=H, max_iterations=10)
+    rng = np.random.default_rng(8128)
+    llrs = np.concatenate([awgn_llr_decoder_convention(rng, 6, 96, 2.0, np.float32),
+                           awgn_llr_decoder_convention(rng, 6, 96, 5.0, np.float32),
+                           special_llrs(rng, 96, 4).astype(np.float32)])
+    T = 6
+    out = {"graph": np.asarray("small_96_48")}
+    for bc in (2, 6, 7, 8):
+        for k, v in run_rcq(code, H, llrs, T, bc=bc, qp=QP_WIDTHS).items():
+            out[f"rcq{bc}_{k}"] = v
+    for wtype, bc in ((2, 6), (2, 8), (1, 8)):
+        for k, v in run_wrcq(code, H, llrs, wtype, T, rng=rng, bc=bc, qp=QP_WIDTHS).items():
+            out[f"w{wtype}b{bc}_{k}"] = v
+    g = oracle.OracleGraph(H)
+    for bc in (2, 8):
+        dec = ref_rcq.RCQMinSumDecoder(code, bc=bc, bv=8, quantizer_params=QP_WIDTHS, max_iterations=T, layered=True)
+        bits, succ, its = [], [], []
+        for x in llrs:
+            b, s_, i = dec.decode(torch.from_numpy(x.copy()))
+            bits.append(b.numpy().copy()); succ.append(bool(s_)); its.append(int(i))
+        bits, succ, its = np.stack(bits), np.asarray(succ), np.asarray(its, np.int32)
+        ob, op, oi, os_ = oracle.rcq_layered(g, llrs, bc, QP_WIDTHS, T)
+        check_equal("layered bits", ob, bits); check_equal("layered iters", oi, its); check_equal("layered success", os_, succ)
+        out.update({f"lay{bc}_llr": llrs, f"lay{bc}_bits": bits.astype(np.uint8), f"lay{bc}_success": succ,
+                    f"lay{bc}_iters": its, f"lay{bc}_T": np.int32(T), f"lay{bc}_bc": np.int32(bc),
+                    f"lay{bc}_qp": np.asarray(QP_WIDTHS, np.float64), f"lay{bc}_oracle_posterior": op})
+    quantizer_sweep(out, "wsweep", [(6, 5.0, 1.3), (7, 6.0, 0.8), (8, 7.0, 1.0), (8, 3.0, 1.7)], np.random.default_rng(77))
+    return out
+
+
 SETS = {
     "quantizer": gen_quantizer,
     "sums": gen_sums,
@@ -857,6 +900,7 @@ SETS = {
     "grad_ira": lambda: gen_grad("ira"),
     "grad_llr_toy": gen_grad_llr,
     "grad_ties": gen_grad_ties,
+    "rcq_widths": gen_rcq_widths,
 }
 SLOW = {"dvbs2_wrcq": gen_dvbs2_wrcq}
 

@@ -53,6 +53,10 @@ FAMILIES = {
     "wrcq4-2-g0": Family("wrcq", 2, 4, QPN_G0, ("RCQ", True, 0, False, False, False)),
     # RCQ, run-time level count, beta slot per edge
     "wrcq4-1": Family("wrcq", 1, 4, QPN, ("RCQ", False, 0, True, True, False)),
+    # RCQ, 32 and 128 levels: the threshold loop well past the register path; at 128 the negative codes use bit 7
+    "wrcq6-2": Family("wrcq", 2, 6, QPN, ("RCQ", True, 0, False, True, False)),
+    "wrcq8-2": Family("wrcq", 2, 8, QPN, ("RCQ", True, 0, False, True, False)),
+    "wrcq8-1": Family("wrcq", 1, 8, QPN, ("RCQ", False, 0, True, True, False)),
 }
 # the eight instantiations (FORM, BPC, NL) and a family of each for the cases run once per instantiation
 INSTANTIATIONS = {
@@ -93,6 +97,7 @@ SNR = {
     ("wrcq5-2", "spread"): (3.0, 6.0), ("wrcq5-2", "ira"): (3.0, 6.0),
     ("wrcq4-2-g0", "tails"): (3.0, 6.0), ("wrcq4-2-g0", "spread"): (3.0, 6.0), ("wrcq4-2-g0", "ira"): (3.0, 7.0),
     ("wrcq4-1", "tails"): (3.0, 6.0), ("wrcq4-1", "spread"): (3.0, 6.0), ("wrcq4-1", "ira"): (3.0, 6.0),
+    ("wrcq6-2", "spread"): (3.0, 6.0),
 }
 
 

@@ -28,6 +28,14 @@ CASES = [
     ("small", 1, 3, QP3, 70, (7.0, 10.0), "saturate"),
     ("wide", 2, 3, QP3, 70, (0.5, 4.0), "wide"),
     ("wide", 2, 4, QP3, 33, (0.5, 4.0), "wide"),
+    # 2, 32, 64 and 128 levels: at bc = 8 the negative codes use bit 7 and the variable pass's LUT is full (2 * 128 entries)
+    ("small", 2, 2, QP3, 70, (0.5, 4.0), None),
+    ("small", 1, 6, QP3, 70, (0.5, 4.0), None),
+    ("small", 2, 7, QP3, 64, (0.5, 4.0), None),
+    ("small", 2, 8, QP3, 300, (0.5, 4.0), None),
+    ("wide", 2, 8, QP3, 70, (0.5, 4.0), "wide"),
+    ("small", 2, 8, QP3, 50, (0.5, 4.0), "negbeta"),
+    ("ira", 2, 8, QP3, 40, (0.5, 4.0), None),
 ]
 
 

@@ -32,7 +32,8 @@ def close(got, want, what, rtol=2e-3, rel_atol=2e-4):
 
 
 # ---------------------------------------------------------------------------------------------------- 1. forward
-@pytest.mark.parametrize("name,wtype,bc,B", [("toy", 2, 3, 37), ("small", 1, 4, 300), ("ira", 2, 3, 70)])
+@pytest.mark.parametrize("name,wtype,bc,B", [("toy", 2, 3, 37), ("small", 1, 4, 300), ("ira", 2, 3, 70),
+                                           ("small", 2, 8, 300), ("small", 1, 6, 70)])
 def test_forward_is_the_fixed_iteration_decode(gpu_device, name, wtype, bc, B):
     T = 6                                           # three quantisers: the schedule changes twice (0, 0, 1, 1, 2, 2)
     code = cases.load(name, T)
@@ -89,13 +90,13 @@ def test_gradients_match_the_restatement(gpu_device, case, oracle_mod):
 
 
 # ---------------------------------------------------------------------------------------------------- 3. T = 1 anchor
-@pytest.mark.parametrize("B", [50, 200])
-def test_one_iteration_closed_form(gpu_device, oracle_mod, B):
+@pytest.mark.parametrize("B,bc", [(50, 3), (200, 3), (200, 8)], ids=["50", "200", "200-bc8"])
+def test_one_iteration_closed_form(gpu_device, oracle_mod, B, bc):
     """d J/d beta_0[s] = sum over b and the edges e of slot s of g_l[b, v(e)] * mask[b, e] * s_excl[b, e] * minval[b, e],
     g_l = -sigmoid(-l_0) / (B n), l_0 = llr + sum of the reconstructed codes -- numpy, fp64, from the LLRs and the codes"""
     import pjt_rcq_reference as ref
     code = cases.load("small", 1)
-    dec = cases.make_decoder(code, 2, 3, [(3.0, 1.3)], 1, seed=11, **STE)
+    dec = cases.make_decoder(code, 2, bc, [(3.0, 1.3)], 1, seed=11, **STE)
     llr = cases.channel(np.random.default_rng(12), B, code.n, (2.0, 5.0))
     x = torch.from_numpy(llr).to(gpu_device)
     dec.joint_posterior_loss(x)[0].backward()
@@ -137,6 +138,42 @@ def test_one_iteration_closed_form(gpu_device, oracle_mod, B):
         np.testing.assert_allclose(got[f"beta_weights.{k}"].numpy(), want_p[f"beta_weights.{k}"].numpy(), rtol=1e-5, atol=1e-7,
                                    err_msg=k)
     assert all(float(got[f"alpha_weights.{k}"].abs().max()) == 0.0 for k in dec.alpha_weights.keys())   # alpha_T-1 gets 0
+
+
+@pytest.mark.parametrize("tau0", [0.0, 1.5])
+def test_one_level_passes_no_gradient_to_the_weights(gpu_device, oracle_mod, tau0):
+    """L = 1 (the C ABI's smallest decoder; with tau = 1.5 its one level reconstructs a non-zero value): every code is the top
+    level, so the straight-through mask `level < L - 1` is never set and no gradient reaches a beta or an alpha -- exactly
+    zero.  The posterior of iteration t is llr + (a constant the codes alone fix), so d J/d llr is the gradient of the loss
+    through l_t = llr + const_t: torch autograd on the CPU in fp64, tolerances of test_gradients_match_the_restatement."""
+    import _native as nat
+    import quantiser_width_cases as qw
+    from engine import DecodeEngine
+    case = qw.Level(1, tau0, 70, 70)
+    code, T, kw = qw.level_tables(oracle_mod, case)
+    eng = DecodeEngine(code.tanner_graph(), dtype=torch.float32, c2v_form=nat.C2V_RCQ, iters=T, device=gpu_device, **kw)
+    rng = np.random.default_rng(21)
+    llr = cases.channel(rng, case.B, code.n, (0.5, 4.0))
+    y = torch.from_numpy(rng.uniform(0, 1, llr.shape).astype(np.float32) * (rng.random(llr.shape) < 0.3))
+    w = torch.tensor(rng.uniform(0.1, 1.0, T), dtype=torch.float32)
+    x = torch.from_numpy(llr).to(gpu_device)
+    out = eng.train_joint_ste(x, y.to(gpu_device), w.to(gpu_device), want_grads=True, want_grad_llr=True)
+    assert out["grad_beta"].shape == kw["beta"].shape and out["grad_alpha"].shape == kw["alpha"].shape
+    assert float(out["grad_beta"].abs().max()) == 0.0 and float(out["grad_alpha"].abs().max()) == 0.0
+    xl = torch.from_numpy(llr).double().requires_grad_(True)
+    J, per = 0.0, []
+    for t in range(T):
+        post = eng.decode(x, early_stop=False, max_iters=t + 1).posterior
+        const = (post - x).cpu().double()
+        if tau0 == 0.0:
+            assert float(const.abs().max()) == 0.0
+        per.append(F.binary_cross_entropy_with_logits(-(xl + const), y.double()))
+        J = J + w[t].double() * per[-1]
+    assert tau0 == 0.0 or float(const.abs().max()) > 0.0
+    J.backward()
+    np.testing.assert_allclose(out["loss_per_iter"].cpu().numpy(), [float(v.detach()) for v in per], rtol=1e-4)
+    assert float(xl.grad.abs().max()) > 0
+    close(out["grad_llr"].cpu().numpy(), xl.grad.numpy(), f"d J/d llr, one level, tau = {tau0}")
 
 
 # ---------------------------------------------------------------------------------------------------- 4. plumbing

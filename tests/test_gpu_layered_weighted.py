@@ -76,8 +76,9 @@ def edge_betas(dec, T):
     return out
 
 
-def restate(code, llr, bc, qp, T, beta_e, early_stop=True):
-    """the paper's layered W-RCQ decode (module docstring of rcq_decoder.py): -> bits, posteriors, iterations, success"""
+def restate(code, llr, bc, qp, T, beta_e, early_stop=True, want_messages=False):
+    """the paper's layered W-RCQ decode (module docstring of rcq_decoder.py): -> bits, posteriors, iterations, success
+    (want_messages: and the code (w < 0) * L + level every edge holds when its codeword's decode ends, 255 = no message)"""
     g = code.tanner_graph()
     thr = thresholds(bc, qp)
     sched = q_schedule(len(qp), T)
@@ -85,6 +86,7 @@ def restate(code, llr, bc, qp, T, beta_e, early_stop=True):
     P = np.array(llr, dtype=np.float32, copy=True)
     B = P.shape[0]
     R = np.zeros((B, g.E), dtype=np.float32)          # reconstructed previous message of every edge ("none" = 0)
+    K = np.full((B, g.E), 255, dtype=np.int64)
     open_ = np.ones(B, dtype=bool)
     iters = np.full(B, T, dtype=np.int32)
     succ = np.zeros(B, dtype=bool)
@@ -131,6 +133,7 @@ def restate(code, llr, bc, qp, T, beta_e, early_stop=True):
             rec = (np.float32(1) - np.float32(2) * (w < 0).astype(np.float32)) * th[lvl]
             P[np.ix_(rows, V)] = u + rec
             R[rows, e0:e1] = rec
+            K[rows, e0:e1] = (w < 0) * L + lvl
         bad = unsat(P)
         if early_stop:
             done = open_ & ~bad
@@ -139,7 +142,8 @@ def restate(code, llr, bc, qp, T, beta_e, early_stop=True):
             open_ &= bad
     if not early_stop:
         succ = ~unsat(P)
-    return (P < 0).astype(np.int32), P, iters, succ
+    out = (P < 0).astype(np.int32), P, iters, succ
+    return out + (K,) if want_messages else out
 
 
 def randomise_betas(dec, rng, zero_neg=True):

@@ -336,7 +336,10 @@ def test_wrcq_dvbs2_golden(gpu_device):
 # every golden block with a per-iteration code trace: (file, prefix of the block or None)
 RCQ_TRACE_BLOCKS = [("toy_rcq", "rcq"), ("toy_rcq", "rcq4"), ("toy_rcq", "w1"), ("toy_rcq", "w2"), ("toy_rcq", "w3"),
                     ("toy_rcq", "w4"), ("toy_rcq", "w2d"), ("small_rcq", "rcq"), ("small_rcq", "w1"), ("small_rcq", "w2"),
-                    ("ira_rcq", None), ("ira_wrcq", None), ("dvbs2_wrcq", None)]
+                    ("ira_rcq", None), ("ira_wrcq", None), ("dvbs2_wrcq", None),
+                    # 2, 32, 64 and 128 levels (bc 2, 6, 7, 8): codes with bit 7 set, level 127
+                    ("rcq_widths", "rcq2"), ("rcq_widths", "rcq6"), ("rcq_widths", "rcq7"), ("rcq_widths", "rcq8"),
+                    ("rcq_widths", "w2b6"), ("rcq_widths", "w2b8"), ("rcq_widths", "w1b8")]
 
 
 def rcq_trace_block(name, tag):
@@ -859,6 +862,28 @@ def test_layered_rcq_golden_and_oracle(gpu_device, oracle_mod):
     assert len(np.unique(oi)) >= 2                                          # early stop was exercised
 
 
+@pytest.mark.parametrize("bc", [2, 8])
+def test_layered_rcq_widths_golden(bc, gpu_device, engine_mode):
+    """RCQMinSumDecoder(layered=True) against the reference's own outputs at 2 and 128 levels (tests/golden/rcq_widths.npz),
+    on the LDS-resident kernel (auto) and the streaming kernel (every other engine mode)"""
+    from rcq_decoder import RCQMinSumDecoder
+    g = load_golden("rcq_widths")
+    sub = golden_sub(g, f"lay{bc}")
+    dec = RCQMinSumDecoder(make_code(g, 10), bc, 8, [tuple(x) for x in sub["qp"]], max_iterations=int(sub["T"]), layered=True)
+    x = torch.from_numpy(sub["llr"]).to(gpu_device)
+    eng = dec._get_engine(gpu_device)
+    assert eng.info()["kernel"] == ("layered_lds" if engine_mode == "auto" else "layered_rcq<ref>")
+    bits, succ, iters = dec.decode(x)
+    np.testing.assert_array_equal(iters.cpu().numpy(), sub["iters"])
+    np.testing.assert_array_equal(succ.cpu().numpy(), sub["success"])
+    np.testing.assert_array_equal(bits.cpu().numpy(), sub["bits"].astype(np.int32))
+    res = eng.decode(x, early_stop=True)
+    np.testing.assert_array_equal(res.posterior.cpu().numpy(), sub["oracle_posterior"])
+    b1, s1, i1 = dec.decode(torch.from_numpy(sub["llr"])[3])
+    assert (s1, i1) == (bool(sub["success"][3]), int(sub["iters"][3]))
+    np.testing.assert_array_equal(b1.numpy(), sub["bits"][3].astype(np.int32))
+
+
 @pytest.mark.parametrize("early_stop", [True, False])
 def test_layered_paper_schedule_vs_cpu_restatement(early_stop, gpu_device, oracle_mod):
     """RCQMinSumDecoder(layered="paper"): the layered schedule the reference's _decode_layered sets out to implement
@@ -910,11 +935,12 @@ def _layered_case_code(rng, n, m, dc_lo, dc_hi, deg1=False):
     return LDPCCode(n=n, k=max(n - m, 1), H=H, max_iterations=6)     # some variables may be in no check at all
 
 
-@pytest.mark.parametrize("case", ["lw1", "lw2", "lw4", "lw8", "lw16", "lw32", "lw64", "deg1", "gamma0", "bc4", "bc5", "bign"])
+@pytest.mark.parametrize("case", ["lw1", "lw2", "lw4", "lw8", "lw16", "lw32", "lw64", "deg1", "gamma0", "bc4", "bc5", "bign",
+                                  "bc2", "bc6", "bc8"])
 def test_layered_lds_kernel_every_lane_width_vs_oracle_and_streaming_kernel(case, gpu_device, oracle_mod, engine_mode):
     """RCQMinSumDecoder(layered=True) on the LDS-resident kernel (lanes over the edges of a check, ldpc_layered.hip): every
     lane width 1..64, a degree-1 check, a quantiser whose zero level is not zero (gamma = 0: general sign rule), 8 and 16
-    levels, a code whose posteriors leave room for fewer codewords per wave than lane groups, ragged batches, both stop
+    levels, 2, 32 and 128 levels (bc 8: the negative codes use bit 7, level 127 fills the low seven), a code whose posteriors leave room for fewer codewords per wave than lane groups, ragged batches, both stop
     modes, packed bits -- against the oracle's restatement of rcq_decoder.py:281-350 and, bit for bit, against the
     streaming kernel (engine modes other than auto run that one)."""
     from rcq_decoder import RCQMinSumDecoder
@@ -930,8 +956,8 @@ def test_layered_lds_kernel_every_lane_width_vs_oracle_and_streaming_kernel(case
         code, qp = _layered_case_code(rng, 80, 28, 3, 8), [(1.5, 0.0), (3.0, 1.3), (2.0, 0.0)]
     elif case == "bc4":
         code, bc = _layered_case_code(rng, 80, 28, 3, 8), 4
-    elif case == "bc5":
-        code, bc = _layered_case_code(rng, 80, 28, 3, 8), 5
+    elif case in ("bc5", "bc2", "bc6", "bc8"):                  # 16 levels; 2, 32 and 128 (bit 7 of a code, level 127)
+        code, bc = _layered_case_code(rng, 80, 28, 3, 8), int(case[2:])
     else:                                                       # 4n bytes per codeword: only 2 of the 8 lane groups hold one
         code = _layered_case_code(rng, 16000, 40, 5, 8)
     tg = code.tanner_graph()

@@ -180,6 +180,61 @@ def test_layered_rcq_golden(oracle_mod):
         np.testing.assert_array_equal(succ, g[f"{tag}_success"])
 
 
+# ------------------------------------------------------------------ 2, 32, 64 and 128 quantiser levels
+WIDTH_RCQ = ["rcq2", "rcq6", "rcq7", "rcq8"]
+WIDTH_WRCQ = ["w2b6", "w2b8", "w1b8"]
+
+
+def test_rcq_widths_golden(oracle_mod):
+    """RCQMinSumDecoder at bc 2, 6, 7, 8, WeightedRCQDecoder type 2 at bc 6, 8 and type 1 at bc 8, every iteration's codes:
+    a code is one byte, sign * L + level, and at bc = 8 the oracle's uint8 trace has to carry bit 7 and level 127"""
+    g = load_golden("rcq_widths")
+    og = graph_of(oracle_mod, g)
+    for tag in WIDTH_RCQ:
+        sub = golden_sub(g, tag)
+        assert int(sub["bc"]) == int(tag[3:]) and int(sub["T"]) == 6 and sub["llr"].shape == (16, 96)
+        _check_rcq(oracle_mod, og, sub)
+    for tag in WIDTH_WRCQ:
+        sub = golden_sub(g, tag)
+        assert (int(sub["wtype"]), int(sub["bc"])) == (int(tag[1]), int(tag[3:]))
+        _check_wrcq(oracle_mod, og, sub)
+    # the fixture itself: the reference wrote codes with bit 7 set, the saturated code of either sign among them
+    for tag in ("rcq8", "w2b8", "w1b8"):
+        sub = golden_sub(g, tag)
+        ran = np.concatenate([sub["codes"][r, :it].ravel() for r, it in enumerate(sub["iters"])])
+        assert (ran >= 128).any() and (ran == 127).any() and (ran == 255).any(), tag
+    assert 0 < int(golden_sub(g, "rcq8")["success"].sum()) < 16
+
+
+@pytest.mark.parametrize("bc", [2, 8])
+def test_layered_rcq_widths_golden(bc, oracle_mod):
+    """RCQMinSumDecoder(layered=True) of the reference at 2 and 128 levels"""
+    g = load_golden("rcq_widths")
+    sub = golden_sub(g, f"lay{bc}")
+    assert int(sub["bc"]) == bc
+    og = graph_of(oracle_mod, g)
+    bits, post, iters, succ = oracle_mod.rcq_layered(og, sub["llr"], bc, [tuple(x) for x in sub["qp"]], int(sub["T"]))
+    np.testing.assert_array_equal(bits, sub["bits"])
+    np.testing.assert_array_equal(iters, sub["iters"])
+    np.testing.assert_array_equal(succ, sub["success"])
+    assert bitwise_equal(post, sub["oracle_posterior"])
+    assert len(np.unique(sub["iters"])) >= 2
+
+
+def test_quantizer_width_sweeps(oracle_mod):
+    """quantize / dequantize on, one ulp below and one ulp above every threshold of 32-, 64- and 128-level quantisers"""
+    g = load_golden("rcq_widths")
+    assert sorted(int(c[0]) for c in g["wsweep_cfg"]) == [6, 7, 8, 8]
+    for ci, (bc, C_, gm) in enumerate(g["wsweep_cfg"]):
+        thr = oracle_mod.quantizer_thresholds(int(bc), float(C_), float(gm))
+        assert len(thr) == 2 ** (int(bc) - 1)
+        np.testing.assert_array_equal(np.asarray(thr), g[f"wsweep{ci}_thresholds"])
+        codes = g[f"wsweep{ci}_codes"]
+        np.testing.assert_array_equal(oracle_mod.quantize(g[f"wsweep{ci}_x"], thr), codes)
+        assert bitwise_equal(oracle_mod.dequantize(codes, thr), g[f"wsweep{ci}_deq"])
+        assert len(np.unique(codes)) == 2 * len(thr)                     # every code value, both signs of every level
+
+
 # ------------------------------------------------------------------ oracle self-consistency
 def test_fixed_iteration_mode_and_threads(oracle_mod):
     """early_stop=False runs T iterations; success = final syndrome; threads do not change results"""
@@ -208,7 +263,8 @@ def test_basic_fp32_posterior_equals_neural2d_type3(oracle_mod):
 
 # ------------------------------------------------------------------ capped decodes (the GPU tests' per-iteration reference)
 @pytest.mark.parametrize("name,tag", [("toy_rcq", "rcq"), ("toy_rcq", "rcq4"), ("toy_rcq", "w2d"), ("small_rcq", "rcq"),
-                                      ("small_rcq", "w1"), ("ira_rcq", None), ("ira_wrcq", None), ("dvbs2_wrcq", None)])
+                                      ("small_rcq", "w1"), ("ira_rcq", None), ("ira_wrcq", None), ("dvbs2_wrcq", None)]
+                         + [("rcq_widths", tag) for tag in WIDTH_RCQ + WIDTH_WRCQ])
 def test_oracle_capped_is_a_prefix_of_the_full_decode(name, tag, oracle_mod):
     """oracle_capped (tests/test_gpu_parity.py) is what every capped GPU decode is held to: t iterations of the T-iteration
     schedule.  Fixed T: its code trace is the first t slices of the full trace, every iteration count is t, success is the
