@@ -127,13 +127,15 @@ struct ldpc_decoder {
     size_t lay_lds = 0;
     int *lay_slot = nullptr;       // LDPC_SCHED_LAYERED: beta slot of each plan entry (-1: none), [m_pad + 2 * kLayPf][lw]
     float *lay_beta = nullptr;     // ... and beta in plan order, [T][m_pad + 2 * kLayPf][lw] (lay_beta_gather)
-    bool beta_unit = false;        // every beta is 1.0 (fp32): the layered kernels skip the weight
+    bool beta_unit = false;        // every beta is 1.0 (fp32): the layered RCQ kernels skip the weight
+    int *lay_oms_slot = nullptr;   // layered offset min-sum: check-side alpha slot of each plan entry, and the table in plan
+    float *lay_oms = nullptr;      // order, as lay_slot / lay_beta
 };
 
 namespace {
 
 bool use_resident(const ldpc_decoder *d) { return d->res_ok && (d->mode == LDPC_MODE_AUTO || d->mode == LDPC_MODE_RESIDENT); }
-// layered schedule: the LDS-resident kernel unless a streaming mode is forced (then layered_rcq, posteriors in HBM)
+// layered schedule: the LDS-resident kernel unless a streaming mode is forced (then layered_rcq / layered_minsum, posteriors in HBM)
 bool use_layered_lds(const ldpc_decoder *d) { return d->lay_ok && (d->mode == LDPC_MODE_AUTO || d->mode == LDPC_MODE_RESIDENT); }
 // streaming engine, RCQ: one fused kernel per iteration (cn_gather) unless the two-sweep form is forced
 // streaming forms of an fp32 RCQ decoder, best first: code pair (4E + 4n bytes per iteration), fused gather, two sweeps
@@ -622,7 +624,19 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
         if constexpr (sizeof(T) == 4) {
             // posteriors start as the LLRs and are updated in place, check after check, by one wave per tile;
             // LDPC_SCHED_LAYERED keeps every edge's message code in the c2v buffer (subtracted before the check's update)
-            if (d->schedule == LDPC_SCHED_LAYERED)
+            if (d->form != LDPC_C2V_RCQ) {
+                // the min-sum forms keep the message itself (fp32 per edge); "no message yet" is +0
+                HIP_TRY(hipMemsetAsync(w.c2v, 0, (size_t)w.tiles * W * std::max(g.E, 1) * sizeof(float), s));
+                if (d->form == LDPC_C2V_NMS)
+                    hipLaunchKernelGGL((layered_minsum<VEC, FORM_NMS>), dim3(w.tiles), dim3(kWave), 0, s, g, (float *)w.llrT,
+                                       (float *)w.c2v, (const float *)d->beta, d->beta_slot, d->n_beta, (const float *)nullptr,
+                                       (const int *)nullptr, 0, T_it, early_stop ? 1 : 0, w.bitsT, w.done, w.iters);
+                else
+                    hipLaunchKernelGGL((layered_minsum<VEC, FORM_OMS>), dim3(w.tiles), dim3(kWave), 0, s, g, (float *)w.llrT,
+                                       (float *)w.c2v, (const float *)d->beta, d->beta_slot, d->n_beta,
+                                       (const float *)d->oms_alpha, d->oms_alpha_slot, d->n_oms_alpha, T_it,
+                                       early_stop ? 1 : 0, w.bitsT, w.done, w.iters);
+            } else if (d->schedule == LDPC_SCHED_LAYERED)
                 hipLaunchKernelGGL((layered_rcq<VEC, true>), dim3(w.tiles), dim3(kWave), 0, s, g, (float *)w.llrT, d->thresholds,
                                    d->n_levels, (const int *)d->q_of_iter_dev, T_it, early_stop ? 1 : 0, w.bitsT, w.done, w.iters,
                                    d->g->max_dc, (uint8_t *)w.c2v, d->beta_unit ? nullptr : (const float *)d->beta,
@@ -1041,21 +1055,35 @@ int gather_layered_beta(const ldpc_decoder *d, hipStream_t s)
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
+// layered offset min-sum: the check-side alpha table in plan order (d->lay_oms), likewise
+int gather_layered_oms(const ldpc_decoder *d, hipStream_t s)
+{
+    if (!d->lay_oms || d->T == 0) return LDPC_OK;
+    const int entries = (d->lay.m_pad + 2 * kLayPf) * d->lay.lw;
+    const long long cnt = (long long)entries * d->T;
+    hipLaunchKernelGGL(lay_beta_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, (const float *)d->oms_alpha,
+                       d->n_oms_alpha, (const int *)d->lay_oms_slot, entries, d->T, d->lay_oms);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
 
 constexpr size_t kLayPaperMinWaves = 4;           // LDPC_SCHED_LAYERED takes the LDS kernel only with a wave per SIMD
 int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
 {
     const ldpc_graph *g = d->g;
     d->lay_ok = false;
-    if (d->schedule == LDPC_SCHED_FLOODING || d->form != LDPC_C2V_RCQ || d->dtype != LDPC_F32) return LDPC_OK;
+    if (d->schedule == LDPC_SCHED_FLOODING || d->dtype != LDPC_F32) return LDPC_OK;
     if (g->E == 0 || g->m == 0 || g->max_dc > 64) return LDPC_OK;     // a check wider than a wavefront: streaming kernel
     const bool paper = d->schedule == LDPC_SCHED_LAYERED;
+    const bool minsum = d->form != LDPC_C2V_RCQ;                      // layered_minsum_lds: check records in place of the codes
     int lw = 1;
     while (lw < g->max_dc) lw <<= 1;
     const int m_pad = (g->m + kLayPf - 1) / kLayPf * kLayPf;
     // LDPC_SCHED_LAYERED also keeps one code byte per plan entry of the codeword's walk after its posteriors
     const size_t code_off = lay_row_bytes(g->n);
-    const size_t row_bytes = paper ? code_off + ((size_t)m_pad * lw + 3) / 4 * 4 : lay_row_bytes(g->n);
+    // ... the min-sum forms one record per plan row: 16 bytes up to 32 lanes, 24 at 64 (ldpc_layered.hip)
+    const size_t row_bytes = minsum ? code_off + (size_t)m_pad * (lw <= 32 ? 16 : 24)
+                             : paper ? code_off + ((size_t)m_pad * lw + 3) / 4 * 4 : lay_row_bytes(g->n);
     int cw = 64 / lw;
     while (cw > 1 && (size_t)cw * row_bytes > kLdsBytes) cw >>= 1;
     if ((size_t)cw * row_bytes > kLdsBytes) return LDPC_OK;           // one codeword's state exceeds LDS
@@ -1095,7 +1123,7 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     // magnitude 0 reconstructs to 0 under every quantiser (rcq_decoder.py:79-85, :107-119): tau_0 == 0 and no later
     // threshold <= 0 -- true for the reference's C * (j / (2^(bc-1) - 1))^gamma with gamma > 0
     bool zero0 = true;
-    for (int q = 0; q < d->n_quant; ++q) {
+    for (int q = 0; q < (minsum ? 0 : d->n_quant); ++q) {
         float rec = desc->thresholds[(size_t)q * d->n_levels];
         for (int k = 1; k < d->n_levels; ++k)
             if (0.0f >= desc->thresholds[(size_t)q * d->n_levels + k]) rec = desc->thresholds[(size_t)q * d->n_levels + k];
@@ -1104,7 +1132,7 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     int rc = upload(&d->lay_off, off.data(), off.size());
     if (rc) return rc;
     bool sorted = true;                                               // tau_1 <= tau_2 <= ... under every quantiser
-    for (int q = 0; q < d->n_quant; ++q)
+    for (int q = 0; q < (minsum ? 0 : d->n_quant); ++q)
         for (int k = 2; k < d->n_levels; ++k)
             sorted = sorted && desc->thresholds[(size_t)q * d->n_levels + k - 1] <= desc->thresholds[(size_t)q * d->n_levels + k];
     // A power-of-two region per codeword (address = offset | row bits, one v_and_or_b32) was measured and dropped: 4 x 8192 bytes
@@ -1112,7 +1140,7 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     // ((1998,1512): 11.2 vs 9.6 ms, profiles/r03_layered_variants.txt).  The kernel keeps the template flag for A/B builds.
     const int row_shift = 0;
     d->lay = LayeredPlan{g->n, g->m, lw, cw, m_pad, deg1 ? 1 : 0, zero0 ? 1 : 0, sorted ? 1 : 0, row_shift, d->lay_off,
-                         (unsigned)row_bytes, (unsigned)code_off, nullptr};
+                         (unsigned)row_bytes, (unsigned)code_off, nullptr, nullptr};
     d->lay_lds = row_shift ? ((size_t)cw << row_shift) : (size_t)cw * row_bytes;
     if (paper) {
         // beta of every plan entry, per iteration: gathered on the device from the decoder's table (again on set_weights)
@@ -1124,9 +1152,21 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
         rc = upload(&d->lay_slot, slot.data(), slot.size());
         if (!rc) rc = upload(&d->lay_beta, (const float *)nullptr, slot.size() * (size_t)std::max(d->T, 1));
         if (!rc) rc = gather_layered_beta(d, nullptr);
+        if (!rc && minsum && d->oms_alpha) {
+            // the offset form's check-side alpha, the same way
+            std::fill(slot.begin(), slot.end(), -1);
+            for (int i = 0; i < g->m; ++i) {
+                const int e0 = g->h_check_ptr[i], dc = g->h_check_ptr[i + 1] - e0;
+                for (int k = 0; k < dc; ++k) slot[(size_t)i * lw + (lw - dc) + k] = desc->oms_alpha_slot[e0 + k];
+            }
+            rc = upload(&d->lay_oms_slot, slot.data(), slot.size());
+            if (!rc) rc = upload(&d->lay_oms, (const float *)nullptr, slot.size() * (size_t)std::max(d->T, 1));
+            if (!rc) rc = gather_layered_oms(d, nullptr);
+        }
         if (!rc) HIP_TRY(hipStreamSynchronize(nullptr));
         if (rc) return rc;
         d->lay.beta_lay = d->lay_beta;
+        d->lay.oms_lay = d->lay_oms;
     }
     d->lay_ok = true;
     return LDPC_OK;
@@ -1139,6 +1179,34 @@ int decode_layered_lds(const ldpc_decoder *d, const void *llr, int64_t batch, in
     hipStream_t s = (hipStream_t)stream;
     const LayeredPlan &pl = d->lay;
     const unsigned blocks = (unsigned)((batch + pl.cw - 1) / pl.cw);
+    if (d->form != LDPC_C2V_RCQ) {
+#define LDPC_LMS_K(LW_, FORM_, ES_, OA_)                                                                             \
+    do {                                                                                                             \
+        auto kfn = layered_minsum_lds<LW_, FORM_, ES_, OA_>;                                                         \
+        if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                                   \
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kWave), d->lay_lds, s, pl, (const float *)llr, (long long)batch, \
+                           capped_T(d), bits, (float *)posterior, iterations, success, packed_bits);                \
+    } while (0)
+#define LDPC_LMS_LW(LW_)                                                                                             \
+    do {                                                                                                             \
+        if (d->form == LDPC_C2V_NMS) { if (early_stop) LDPC_LMS_K(LW_, FORM_NMS, true, false); else LDPC_LMS_K(LW_, FORM_NMS, false, false); } \
+        else if (pl.oms_lay) { if (early_stop) LDPC_LMS_K(LW_, FORM_OMS, true, true); else LDPC_LMS_K(LW_, FORM_OMS, false, true); } \
+        else { if (early_stop) LDPC_LMS_K(LW_, FORM_OMS, true, false); else LDPC_LMS_K(LW_, FORM_OMS, false, false); } \
+    } while (0)
+        switch (pl.lw) {
+        case 1: LDPC_LMS_LW(1); break;
+        case 2: LDPC_LMS_LW(2); break;
+        case 4: LDPC_LMS_LW(4); break;
+        case 8: LDPC_LMS_LW(8); break;
+        case 16: LDPC_LMS_LW(16); break;
+        case 32: LDPC_LMS_LW(32); break;
+        default: LDPC_LMS_LW(64); break;
+        }
+#undef LDPC_LMS_LW
+#undef LDPC_LMS_K
+        HIP_TRY(hipGetLastError());
+        return LDPC_OK;
+    }
     if (d->schedule == LDPC_SCHED_LAYERED) {
 #define LDPC_PAP_K(LW_, NL_, ES_, WB_)                                                                               \
     do {                                                                                                             \
@@ -1322,8 +1390,10 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
     if (desc->dtype == LDPC_F64 && g->max_dv > 128) return fail(LDPC_ERR_UNSUPPORTED, "variable degree %d > 128 (fp64 sum order)", g->max_dv);
     if (desc->schedule < LDPC_SCHED_FLOODING || desc->schedule > LDPC_SCHED_LAYERED) return fail(LDPC_ERR_ARG, "bad schedule");
     if (desc->schedule != LDPC_SCHED_FLOODING) {
-        if (desc->c2v_form != LDPC_C2V_RCQ || desc->dtype != LDPC_F32)
-            return fail(LDPC_ERR_UNSUPPORTED, "the layered schedule exists for the fp32 RCQ decoder only (rcq_decoder.py:281-350)");
+        if (desc->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "layered schedule is fp32 only");
+        if (desc->c2v_form != LDPC_C2V_RCQ && desc->schedule == LDPC_SCHED_LAYERED_REF)
+            return fail(LDPC_ERR_UNSUPPORTED, "the reference's layered schedule exists for the RCQ decoder only (rcq_decoder.py:281-350); "
+                                              "the min-sum forms take LDPC_SCHED_LAYERED");
         if (g->m == 1 && desc->schedule == LDPC_SCHED_LAYERED_REF)
             return fail(LDPC_ERR_UNSUPPORTED, "the reference's layered schedule on a single-check code");
     }
@@ -1510,6 +1580,7 @@ int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alph
     if (oms_alpha) {
         if (!d->oms_alpha) return fail(LDPC_ERR_ARG, "decoder was created without oms_alpha");
         HIP_TRY(hipMemcpyAsync(d->oms_alpha, oms_alpha, rows * d->n_oms_alpha * es, hipMemcpyHostToDevice, s));
+        if (int rc = gather_layered_oms(d, s)) return rc;
     }
     return LDPC_OK;
 }
@@ -1523,7 +1594,7 @@ void ldpc_decoder_destroy(ldpc_decoder *d)
     (void)hipFree(d->thresholds); (void)hipFree(d->lut); (void)hipFree(d->q_of_iter_dev);
     for (void *p : d->res_bufs) (void)hipFree(p);
     (void)hipFree(d->gat_meta); (void)hipFree(d->gat_nbr); (void)hipFree(d->lay_off);
-    (void)hipFree(d->lay_slot); (void)hipFree(d->lay_beta);
+    (void)hipFree(d->lay_slot); (void)hipFree(d->lay_beta); (void)hipFree(d->lay_oms_slot); (void)hipFree(d->lay_oms);
     (void)hipFree(d->beta_inv_ptr); (void)hipFree(d->beta_inv_items); (void)hipFree(d->alpha_inv_ptr);
     (void)hipFree(d->alpha_inv_items); (void)hipFree(d->oms_inv_ptr); (void)hipFree(d->oms_inv_items);
     delete d;
@@ -1577,6 +1648,9 @@ namespace {
 int train_supported(const ldpc_decoder *d)
 {
     if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
+    if (d->schedule != LDPC_SCHED_FLOODING && d->form != LDPC_C2V_RCQ)
+        return fail(LDPC_ERR_UNSUPPORTED, "the layered schedule (LDPC_SCHED_LAYERED) has no gradient path: gradients exist for "
+                                          "the fp32 normalised / offset min-sum decoders under LDPC_SCHED_FLOODING");
     if (d->dtype != LDPC_F32 || d->form == LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_FLOODING)
         return fail(LDPC_ERR_UNSUPPORTED, "gradients exist for the fp32 normalised / offset min-sum flooding decoders "
                                           "(the reference's RCQ quantiser passes no gradient)");

@@ -2401,6 +2401,144 @@ __global__ __launch_bounds__(kWave) void layered_rcq(GraphDev g, float *__restri
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Layered schedule of the min-sum decoders (LDPC_SCHED_LAYERED with LDPC_C2V_NMS / LDPC_C2V_OMS): the unquantised form of
+// layered_rcq<VEC, true>.  Per check, on its edges e = (i, v):  u = P_v - R_e;  raw = min |u| over the OTHER edges (first
+// minimum is the arg-min, ties keep min2 == min1, degree 1: min2 = min1);  r = lay_ms_msg(raw, parity of the others' sign
+// bits);  P_v = u + r;  R_e = r.  Nothing in the reference executes this: the yardstick is a CPU restatement.
+// ------------------------------------------------------------------------------------------
+// The message of one edge.  Every step is ONE rounded operation (no summation order anywhere), so a scalar restatement
+// gives the same bits; __fmul_rn / __fsub_rn keep the compiler from contracting the product into the caller's u + r.
+// With sign bits in place of sgn(), "the product of the other signs is 0" holds exactly when raw == 0: the NMS message
+// is then +-0 either way (no later operation observes a zero's sign as a value), the OMS message is forced to +0 --
+// otherwise -+a of the offset would leak out.  The one exception is a degree-1 check (`lone`): its edge has no others, the
+// product is 1 and raw is the edge's own |u|, so raw == 0 does NOT zero the offset message there (relu(0 - beta) - a stays).
+template <int FORM>
+__device__ __forceinline__ float lay_ms_msg(float raw, unsigned neg, float b, float a, bool lone)
+{
+    if constexpr (FORM == FORM_NMS) {
+        return flip_sign<float>(__fmul_rn(b, raw), neg);             // (beta * raw) * prod, prod = +-1
+    } else {
+        const float d = __fsub_rn(raw, b);
+        const float r = d > 0.0f ? d : 0.0f;                          // F.relu
+        const float v = flip_sign<float>(__fsub_rn(r, a), neg);       // prod * (relu - a)
+        return (raw == 0.0f && !lone) ? 0.0f : v;                     // some other edge is exactly 0: prod = 0
+    }
+}
+
+// One wave owns W codewords (a lane per codeword, VEC of them per lane): posteriors post[tile][n][W] (initialised with the
+// LLRs) and every edge's message msgs[tile][E][W] (fp32, zeroed by the launcher: "none" = +0) in HBM; check degree unbounded.
+// Both passes over a check recompute u from P and R, which the first pass leaves untouched.  A stopped codeword keeps
+// posterior and message.  Results are identical to layered_minsum_lds (ldpc_layered.hip).
+template <int VEC, int FORM>
+__global__ __launch_bounds__(kWave) void layered_minsum(GraphDev g, float *__restrict__ post, float *__restrict__ msgs,
+                                                        const float *__restrict__ beta, const int *__restrict__ beta_slot, int n_beta,
+                                                        const float *__restrict__ oms_alpha, const int *__restrict__ oms_alpha_slot,
+                                                        int n_oms_alpha, int T, int early_stop,
+                                                        uint64_t *__restrict__ bitsT, uint64_t *__restrict__ done,
+                                                        int *__restrict__ iters)
+{
+    static_assert(FORM == FORM_NMS || FORM == FORM_OMS, "min-sum forms");
+    constexpr int W = kWave * VEC;
+    const int lane = threadIdx.x, tile = blockIdx.x;
+    float *P = post + (size_t)tile * g.n * W + (size_t)lane * VEC;
+    float *R = msgs + (size_t)tile * g.E * W + (size_t)lane * VEC;
+    unsigned frozen = 0;                                    // bit c: codeword c of this lane has stopped (or is padding)
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) frozen |= (unsigned)((done[(size_t)tile * VEC + c] >> lane) & 1ull) << c;
+    const unsigned kAll = (1u << VEC) - 1u;
+
+    auto syndrome = [&]() {                                 // bit c set: some check of codeword c is unsatisfied
+        unsigned unsat = 0;
+        for (int i = 0; i < g.m; ++i) {
+            const int e0 = g.check_ptr[i], e1 = g.check_ptr[i + 1];
+            unsigned par = 0;
+            for (int e = e0; e < e1; ++e) {
+                const Pack<float, VEC> v = ld<float, VEC>(P + (size_t)g.var_idx[e] * W);
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) par ^= (v.x[c] < 0.0f ? 1u : 0u) << c;
+            }
+            unsat |= par;
+        }
+        return unsat;
+    };
+
+    for (int it = 0; it < T; ++it) {
+        if (early_stop && __ballot(frozen != kAll) == 0ull) break;
+        const float *beta_row = beta + (size_t)it * n_beta;
+        const float *oa_row = (FORM == FORM_OMS && oms_alpha) ? oms_alpha + (size_t)it * n_oms_alpha : nullptr;
+        for (int i = 0; i < g.m; ++i) {
+            const int e0 = uni(g.check_ptr[i]);
+            const int dc = uni(g.check_ptr[i + 1]) - e0;
+            if (dc == 0 || frozen == kAll) continue;
+            float m1[VEC], m2[VEC];
+            unsigned par[VEC];
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) { m1[c] = inf_of<float>(); m2[c] = inf_of<float>(); par[c] = 0; }
+#pragma unroll 4
+            for (int t = 0; t < dc; ++t) {
+                const Pack<float, VEC> x = ld<float, VEC>(P + (size_t)g.var_idx[e0 + t] * W);
+                const Pack<float, VEC> ro = ld<float, VEC>(R + (size_t)(e0 + t) * W);
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    const float u = __fsub_rn(x.x[c], ro.x[c]);
+                    const float a = __builtin_fabsf(u);
+                    par[c] ^= signbit_of<float>(u);
+                    if (a < m1[c]) { m2[c] = m1[c]; m1[c] = a; }
+                    else if (a < m2[c]) { m2[c] = a; }
+                }
+            }
+            if (dc == 1) {
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) m2[c] = m1[c];
+            }
+#pragma unroll 2
+            for (int t = 0; t < dc; ++t) {
+                float *prow = P + (size_t)g.var_idx[e0 + t] * W, *rrow = R + (size_t)(e0 + t) * W;
+                const float b = beta_row[beta_slot[e0 + t]];
+                const float oa = oa_row ? oa_row[oms_alpha_slot[e0 + t]] : 0.0f;
+                Pack<float, VEC> x = ld<float, VEC>(prow);
+                Pack<float, VEC> ro = ld<float, VEC>(rrow);
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    const float u = __fsub_rn(x.x[c], ro.x[c]);
+                    const float a = __builtin_fabsf(u);
+                    const float raw = (a == m1[c]) ? m2[c] : m1[c];       // arg-min edge; ties make min2 == min1
+                    const float rn = lay_ms_msg<FORM>(raw, par[c] ^ signbit_of<float>(u), b, oa, dc == 1);
+                    if (!((frozen >> c) & 1u)) {
+                        x.x[c] = __fadd_rn(u, rn);                        // never an fma with the product inside rn
+                        ro.x[c] = rn;
+                    }
+                }
+                st<float, VEC>(prow, x);
+                st<float, VEC>(rrow, ro);
+            }
+        }
+        if (early_stop) {
+            const unsigned newly = ~syndrome() & ~frozen & kAll;
+#pragma unroll
+            for (int c = 0; c < VEC; ++c)
+                if ((newly >> c) & 1u) iters[(size_t)tile * W + lane * VEC + c] = it + 1;
+            frozen |= newly;
+        }
+    }
+    unsigned ok = frozen;
+    if (!early_stop) ok = ~syndrome() & kAll;               // fixed-T mode: success = final syndrome is zero
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) {
+        const uint64_t m = __ballot((ok >> c) & 1u);
+        if (lane == 0) done[(size_t)tile * VEC + c] = m;
+    }
+    for (int j = 0; j < g.n; ++j) {                         // hard decisions as ballots, like the sweep engine
+        const Pack<float, VEC> v = ld<float, VEC>(P + (size_t)j * W);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+            const uint64_t m = __ballot(v.x[c] < 0.0f);
+            if (lane == 0) bitsT[((size_t)tile * g.n + j) * VEC + c] = m;
+        }
+    }
+}
+
 // done masks: padding codewords (>= batch) start frozen; iterations start at T
 template <int VEC>
 __global__ void init_state(uint64_t *__restrict__ done, int *__restrict__ iters, long long batch,

@@ -32,6 +32,9 @@
 //
 // layered_paper_lds (below): the same walk for LDPC_SCHED_LAYERED, the paper's schedule (previous message subtracted, optional
 // beta), with each edge's message code kept in LDS beside the posteriors.
+//
+// layered_minsum_lds (below that): the same schedule with unquantised messages for the min-sum decoders (LDPC_C2V_NMS /
+// LDPC_C2V_OMS), with a check record per check in LDS from which each lane recomputes its previous message.
 #pragma once
 
 #include "ldpc_kernels.hip"
@@ -57,6 +60,8 @@ struct LayeredPlan {
     unsigned row_bytes;            // LDS bytes of one codeword: posteriors + the +inf word, then the codes
     unsigned code_off;             // byte offset of the codes inside a codeword's region: code of plan entry (i, t) at + i * lw + t
     const float *beta_lay;         // [T][m_pad + 2 * kLayPf][lw] beta_t of the edge in plan entry (i, t) (1 where none)
+    // layered_minsum_lds: row_bytes / code_off describe the check records that take the place of the codes (one per plan row)
+    const float *oms_lay;          // offset form with a check-side alpha table: a_t in plan order, as beta_lay; else NULL
 };
 
 constexpr int kLayPf = 4;          // plan entries in flight ahead of the check being processed (= the unroll of the walk)
@@ -455,6 +460,194 @@ __global__ __launch_bounds__(kWave) void layered_paper_lds(LayeredPlan pl, const
             for (int k = 0; k < kLayPf; ++k) step(cur[k], bc[k], i0 + k);
 #pragma unroll
             for (int k = 0; k < kLayPf; ++k) { cur[k] = nxt[k]; bc[k] = bn[k]; }
+        }
+        if (ES) {
+            const unsigned unsat = syndrome();
+            if (frozen == 0u && unsat == 0u) { frozen = 1u; my_iters = it + 1; }
+        }
+    }
+    asm volatile("" ::: "memory");
+
+    unsigned ok;
+    if (ES) ok = (row_live && frozen != 0u) ? 1u : 0u;
+    else ok = syndrome() == 0u ? 1u : 0u;
+    if (row_live && row < cw && t == 0) {
+        if (iterations) iterations[b0 + row] = (ES && ok) ? my_iters : T;
+        if (success) success[b0 + row] = (uint8_t)ok;
+    }
+    const int nbytes = (n + 7) / 8;
+    for (int r = 0; r < cw; ++r) {
+        if (b0 + r >= batch) break;
+        const size_t ob = (size_t)(b0 + r) * n;
+        for (int j0 = 0; j0 < n; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool in = j < n;
+            const float v = in ? lay_lds_ld((unsigned)r * row_bytes + (unsigned)j * 4u) : 0.0f;
+            const bool neg = in && v < 0.0f;
+            if (in && posterior) __builtin_nontemporal_store(v, posterior + ob + j);
+            if (in && bits) __builtin_nontemporal_store(neg ? 1 : 0, bits + ob + j);
+            if (packed) {
+                const unsigned long long mk = __ballot(neg);
+                if (lane < 8 && j0 + 8 * lane < n) packed[(size_t)(b0 + r) * nbytes + (j0 >> 3) + lane] = (uint8_t)(mk >> (8 * lane));
+            }
+        }
+    }
+}
+
+// ---- layered schedule of the min-sum decoders (LDPC_SCHED_LAYERED with LDPC_C2V_NMS / LDPC_C2V_OMS): the unquantised
+// baseline of layered_paper_lds.  Same walk, lanes, butterfly, plan prefetch and epilogue.  Per check, lane (row, t) on
+// edge e = (c, v):
+//   u     = P_v - R_e                                         (R_e: the edge's message of the previous iteration, +0 before any)
+//   m1 / m2 / parity over the u of the check                  (butterfly on the bit patterns of |u|)
+//   raw   = (|u| == m1) ? m2 : m1 ;  s = parity of the OTHER edges' sign bits
+//   NMS:  r = +-(beta_t[slot(e)] * raw)                       OMS:  r = raw == 0 ? +0 : +-(relu(raw - beta_t) - a_t)
+//   P_v   = u + r ;  R_e = r
+// What is kept of R is not an fp32 word per plan entry (31 KB per codeword on the (1998,1512) code) but the CHECK RECORD
+// of the iteration that produced the messages: m1, m2, one sign bit and one "was the arg-min" bit per lane of the row --
+// 16 bytes per check for LW <= 32 { m1, m2, signs, argmins }, 24 for LW = 64 { m1, m2, signs lo, hi, argmins lo, hi } --
+// read by all lanes of a row at one address.  The lane recomputes R_e from the record with beta_{t-1} (a_{t-1}) of its
+// plan entry: the same operands through the same single operation give the same bits as a stored value would.
+//
+// Why the results equal a scalar restatement bit for bit:
+//   no contraction -- every step (x - R, beta * raw, raw - beta, relu - a, u + r) is ONE rounded operation on values that
+//     involve no summation order; the one hazard is u + (beta * raw) becoming an fma, hence __fmul_rn / __fadd_rn;
+//   signs and zeros -- with sign bits in place of sgn(), "the product over the others is 0" holds exactly when raw == 0.
+//     NMS: the message is then +-0 either way, which no later operation observes as a value (x + (+-0) == x, |.|, the
+//     compares; a zero's own sign bit never enters its own message).  OMS: the message is forced to +0, otherwise -+a of
+//     the offset would leak out -- except on a degree-1 check, whose edge has no others (product 1, raw = its own |u|).
+// Lanes without an edge (they hold the +inf word) carry no message: R = r = 0, so inf - 0 + 0 = inf is written back (a
+// message recomputed from an all-inf row would be inf, and inf - inf poisons the word).  LLRs must be finite.
+// A frozen codeword (early stop) writes back what it read: posterior and record.  Results are identical to the streaming
+// kernel's (layered_minsum, ldpc_kernels.hip), which keeps R_e itself.
+// OA: the decoder has a check-side alpha table (FORM_OMS only; a = 0 without one)
+template <int LW, int FORM, bool ES, bool OA>
+__global__ __launch_bounds__(kWave) void layered_minsum_lds(LayeredPlan pl, const float *__restrict__ llr, long long batch, int T,
+                                                            int *__restrict__ bits, float *__restrict__ posterior,
+                                                            int *__restrict__ iterations, uint8_t *__restrict__ success,
+                                                            uint8_t *__restrict__ packed)
+{
+    static_assert(FORM == FORM_NMS || FORM == FORM_OMS, "min-sum forms");
+    extern __shared__ __align__(16) unsigned char lay_smem[];       // the only LDS object: codeword regions start at offset 0
+    if (__builtin_amdgcn_groupstaticsize() != 0) __builtin_trap();
+    constexpr unsigned kRec = LW <= 32 ? 16u : 24u;                 // bytes of a check record
+    constexpr unsigned kMaskOff = 8u, kArgOff = LW <= 32 ? 12u : 16u;
+    const int lane = threadIdx.x;
+    const int n = pl.n, m = pl.m_pad, cw = pl.cw;
+    const int row = lane / LW, t = lane % LW;
+    const long long b0 = (long long)blockIdx.x * cw;
+    const int row_eff = min(row, cw - 1);                           // shadow lanes: see layered_lds
+    const bool row_live = b0 + row_eff < batch;
+    const unsigned row_bytes = pl.row_bytes;
+    const unsigned row_base = (unsigned)row_eff * row_bytes;
+    const unsigned rec_base = row_base + pl.code_off;               // record of plan row i at + i * kRec
+    const unsigned none_off = (unsigned)n * 4u;                     // plan offset of a lane without an edge
+    const unsigned word = LW <= 32 ? 0u : 4u * ((unsigned)t >> 5), bit = (unsigned)t & 31u;
+
+    for (int r = 0; r < cw; ++r) {
+        const bool have = b0 + r < batch;
+        const float *src = llr + (size_t)(b0 + r) * n;
+        const unsigned rb = (unsigned)r * row_bytes;
+        for (int j = lane; j < n; j += kWave)
+            lay_lds_st(rb + (unsigned)j * 4u, have ? __builtin_nontemporal_load(src + j) : 1.0f);
+        if (lane == 0) lay_lds_st(rb + (unsigned)n * 4u, inf_of<float>());
+        for (unsigned k = pl.code_off + 4u * (unsigned)lane; k < row_bytes; k += 4u * kWave) lay_lds_st(rb + k, 0.0f);   // records: none
+    }
+    asm volatile("" ::: "memory");
+
+    unsigned frozen = row_live ? 0u : 1u;
+    int my_iters = T;
+    const uint32_t *plan = pl.off + t;
+    const size_t plan_rows = (size_t)m + 2 * kLayPf;
+
+    auto syndrome = [&]() {
+        unsigned unsat = 0;
+#pragma unroll 4
+        for (int i = 0; i < m; ++i) {
+            const uint32_t o = plan[(size_t)i * LW];
+            unsigned s = lay_lds_ld(row_base + (o & kLayOffMask)) < 0.0f ? 1u : 0u;
+            lay_step_xor<1, LW>(s); lay_step_xor<2, LW>(s); lay_step_xor<4, LW>(s);
+            lay_step_xor<8, LW>(s); lay_step_xor<16, LW>(s); lay_step_xor<32, LW>(s);
+            unsat |= s;
+        }
+        return unsat & 1u;
+    };
+
+    for (int it = 0; it < T; ++it) {
+        if (ES && __ballot(frozen == 0u) == 0ull) break;
+        const bool first = it == 0;                                 // no record yet: R = +0
+        const float *bet = pl.beta_lay + (size_t)it * plan_rows * LW + t;
+        const float *betp = pl.beta_lay + (size_t)(first ? 0 : it - 1) * plan_rows * LW + t;
+        const float *oma = OA ? pl.oms_lay + (size_t)it * plan_rows * LW + t : nullptr;
+        const float *omap = OA ? pl.oms_lay + (size_t)(first ? 0 : it - 1) * plan_rows * LW + t : nullptr;
+        auto step = [&](uint32_t o, float b, float bp, float a, float ap, int i) {
+            const unsigned po = o & kLayOffMask, addr = row_base + po, raddr = rec_base + (unsigned)i * kRec;
+            const bool edge = po != none_off;
+            const float x = lay_lds_ld(addr);
+            const unsigned m1o = __float_as_uint(lay_lds_ld(raddr)), m2o = __float_as_uint(lay_lds_ld(raddr + 4u));
+            const unsigned sgo = __float_as_uint(lay_lds_ld(raddr + kMaskOff + word));
+            const unsigned ago = __float_as_uint(lay_lds_ld(raddr + kArgOff + word));
+            // the previous message, from the record: raw of this lane, its sign, beta_{t-1} (a_{t-1}) of its entry
+            const float rawo = __uint_as_float(((ago >> bit) & 1u) ? m2o : m1o);
+            const bool lone = (o & kLayDeg1Bit) != 0u;              // degree-1 check: no other edge, its product is 1
+            float ro = lay_ms_msg<FORM>(rawo, (sgo >> bit) & 1u, bp, ap, lone);
+            ro = (first || !edge) ? 0.0f : ro;
+            const float u = __fsub_rn(x, ro);
+            const unsigned ub = __float_as_uint(u), au = ub & 0x7fffffffu;
+            unsigned m1 = au, m2 = 0x7f800000u, par = ub;
+            lay_step<1, LW>(m1, m2, par); lay_step<2, LW>(m1, m2, par); lay_step<4, LW>(m1, m2, par);
+            lay_step<8, LW>(m1, m2, par); lay_step<16, LW>(m1, m2, par); lay_step<32, LW>(m1, m2, par);
+            if (lone) m2 = m1;                                      // degree-1 check: min2 = min
+            const bool arg = au == m1;                              // arg-min edge; ties make min2 == min1
+            const unsigned neg = (par ^ ub) >> 31;                  // parity of the OTHER edges' sign bits
+            float rn = lay_ms_msg<FORM>(__uint_as_float(arg ? m2 : m1), neg, b, a, lone);
+            rn = edge ? rn : 0.0f;
+            float upd = __fadd_rn(u, rn);                           // never an fma with the product inside rn
+            // the row's bits of the two ballots (shadow rows hold the bits of the row they shadow at their own position)
+            const unsigned long long sb = __ballot(neg != 0u), ab = __ballot(arg);
+            unsigned sgn, agn;
+            if constexpr (LW == 64) {
+                sgn = t < 32 ? (unsigned)sb : (unsigned)(sb >> 32);
+                agn = t < 32 ? (unsigned)ab : (unsigned)(ab >> 32);
+            } else {
+                constexpr unsigned keep = LW == 32 ? 0xffffffffu : ((1u << LW) - 1u);
+                sgn = (unsigned)(sb >> (row * LW)) & keep;
+                agn = (unsigned)(ab >> (row * LW)) & keep;
+            }
+            if (ES && frozen) { upd = x; m1 = m1o; m2 = m2o; sgn = sgo; agn = ago; }   // a stopped codeword keeps posterior and record
+            lay_lds_st(addr, upd);
+            // lanes 0 and 32 of the row write the record (LW = 64: each its half of the masks; the same m1 / m2 twice)
+            if (bit == 0u) {
+                lay_lds_st(raddr, __uint_as_float(m1));
+                lay_lds_st(raddr + 4u, __uint_as_float(m2));
+                lay_lds_st(raddr + kMaskOff + word, __uint_as_float(sgn));
+                lay_lds_st(raddr + kArgOff + word, __uint_as_float(agn));
+            }
+        };
+        // plan entries and weights a group ahead, as layered_paper_lds: m is a multiple of kLayPf, 2 * kLayPf rows follow
+        uint32_t cur[kLayPf], nxt[kLayPf];
+        float bc[kLayPf], bn[kLayPf], pc[kLayPf], pn[kLayPf], ac[kLayPf], an[kLayPf], qc[kLayPf], qn[kLayPf];
+#pragma unroll
+        for (int k = 0; k < kLayPf; ++k) {
+            cur[k] = plan[(size_t)k * LW];
+            bc[k] = bet[(size_t)k * LW];
+            pc[k] = betp[(size_t)k * LW];
+            ac[k] = OA ? oma[(size_t)k * LW] : 0.0f;
+            qc[k] = OA ? omap[(size_t)k * LW] : 0.0f;
+        }
+        for (int i0 = 0; i0 < m; i0 += kLayPf) {
+#pragma unroll
+            for (int k = 0; k < kLayPf; ++k) {
+                const size_t e = (size_t)(i0 + kLayPf + k) * LW;
+                nxt[k] = plan[e];
+                bn[k] = bet[e];
+                pn[k] = betp[e];
+                an[k] = OA ? oma[e] : 0.0f;
+                qn[k] = OA ? omap[e] : 0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < kLayPf; ++k) step(cur[k], bc[k], pc[k], ac[k], qc[k], i0 + k);
+#pragma unroll
+            for (int k = 0; k < kLayPf; ++k) { cur[k] = nxt[k]; bc[k] = bn[k]; pc[k] = pn[k]; ac[k] = an[k]; qc[k] = qn[k]; }
         }
         if (ES) {
             const unsigned unsat = syndrome();

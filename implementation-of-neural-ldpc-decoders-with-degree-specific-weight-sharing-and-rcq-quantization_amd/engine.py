@@ -193,10 +193,13 @@ class DecodeEngine:
         resident = int(out[0]) == nat.MODE_RESIDENT
         if self.schedule == nat.SCHED_FLOODING:
             kernel = "resident" if resident else {3: "sweeps", 4: "cn_gather", 5: "code_pair"}[int(out[0])]
-        else:   # the layered schedules: LDS-resident walk (ldpc_layered.hip) or the HBM-streaming one (layered_rcq)
+        else:   # the layered schedules: LDS-resident walk (ldpc_layered.hip) or the HBM-streaming one (layered_rcq / layered_minsum)
             paper = self.schedule == nat.SCHED_LAYERED
-            kernel = ("layered_paper_lds" if paper else "layered_lds") if resident else \
-                     ("layered_rcq<paper>" if paper else "layered_rcq<ref>")
+            if self.c2v_form != nat.C2V_RCQ:      # the min-sum forms: check records in LDS, or fp32 messages in HBM
+                kernel = "layered_minsum_lds" if resident else "layered_minsum"
+            else:
+                kernel = ("layered_paper_lds" if paper else "layered_lds") if resident else \
+                         ("layered_rcq<paper>" if paper else "layered_rcq<ref>")
         # workgroups per CU as LDS (160 KiB) and the wave slots (32 per CU) allow; 0 on the streaming engine
         threads, lds = int(out[2]), int(out[3])
         per_cu = min((160 * 1024) // lds, (32 * 64) // threads) if resident and threads and lds else 0

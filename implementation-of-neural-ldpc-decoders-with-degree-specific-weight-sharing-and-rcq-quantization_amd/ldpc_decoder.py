@@ -19,6 +19,15 @@ torch tensor already on the GPU) -> ``(bits[B, n], success[B], iterations[B])``,
 row-wise map of the single-codeword call; keyword ``early_stop=False`` runs exactly T
 iterations.  Arithmetic type follows the input: float64 in -> fp64 kernels with
 np.sum's association order (results identical to the reference), float32 in -> fp32.
+
+``schedule="layered"`` (keyword only; also on the neural min-sum decoders of neural_2d_decoder.py and
+neural_minsum_decoder.py) runs the layered schedule in place of flooding: checks are walked in order on running
+posteriors, each check first takes its previous message off (``u = P - R``), forms the min-sum message of the decoder's
+form from the ``u`` of its edges and adds it (``P = u + r``).  It is the unquantised baseline of
+``WeightedRCQDecoder(layered="paper")``: same schedule, fp32 messages.  fp32 only (a float64 input is refused by the
+engine); the variable-side alpha is not used (a layered update has no separate variable-node sum for it to scale -- the
+decision taken for the layered W-RCQ decoder), the check-side alpha of the offset form is; LLRs must be finite; there
+is no gradient path.  Nothing in the reference executes this schedule.
 """
 
 from __future__ import annotations
@@ -95,12 +104,20 @@ def _as_batch(llr, n: int):
     raise ValueError(f"llr must have shape [{n}] or [B, {n}], got {tuple(x.shape)}")
 
 
-class BasicMinSumDecoder:
-    """Basic (normalised) MinSum LDPC decoder, flooding schedule."""
+def check_schedule(schedule) -> str:
+    """the ``schedule`` keyword of the min-sum decoders: "flooding" (the reference's) or "layered" (module docstring)"""
+    if schedule not in ("flooding", "layered"):
+        raise ValueError(f'schedule must be "flooding" or "layered", got {schedule!r}')
+    return schedule
 
-    def __init__(self, code: LDPCCode, factor: float = 0.7):
+
+class BasicMinSumDecoder:
+    """Basic (normalised) MinSum LDPC decoder; flooding schedule, ``schedule="layered"``: the layered one (fp32 only)."""
+
+    def __init__(self, code: LDPCCode, factor: float = 0.7, *, schedule: str = "flooding"):
         self.code = code
         self.factor = factor
+        self.schedule = check_schedule(schedule)
         self._engines = {}
 
     def _engine(self, torch_dtype, device):
@@ -110,16 +127,17 @@ class BasicMinSumDecoder:
         dev = _require_gpu(device)
         g = self.code.tanner_graph()
         T = int(self.code.max_iterations)
-        key = (torch_dtype, dev.index, id(g), T, float(self.factor))
+        key = (torch_dtype, dev.index, id(g), T, float(self.factor), self.schedule)
         eng = self._engines.get(key)
         if eng is None:
             np_dt = np.float32 if torch_dtype == torch.float32 else np.float64
             rows = max(T, 1)
+            extra = {"schedule": nat.SCHED_LAYERED} if self.schedule == "layered" else {}
             eng = DecodeEngine(g, dtype=torch_dtype, c2v_form=nat.C2V_NMS, iters=T,
                                beta=np.full((rows, 1), self.factor, dtype=np_dt),     # factor * min * prod(signs)
                                beta_slot=np.zeros(g.E, np.int32),
                                alpha=np.ones((rows, 1), dtype=np_dt),                 # llr + 1 * sum(others)
-                               alpha_slot=np.zeros(g.n, np.int32), device=dev)
+                               alpha_slot=np.zeros(g.n, np.int32), device=dev, **extra)
             self._engines = {key: eng}
         return eng
 

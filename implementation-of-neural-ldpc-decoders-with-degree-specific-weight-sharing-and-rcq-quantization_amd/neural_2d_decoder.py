@@ -15,7 +15,10 @@ Reference behaviour mirrored (file:line in /root/reference):
   invalid sharing type -> ValueError                       neural_2d_decoder.py:81-82
 
 Extensions: ``llr`` of shape ``[B, n]`` -> ``(bits[B,n] int32, posterior[B,n] fp32,
-iterations[B] int32)``; ``early_stop=False`` keyword.  With autograd enabled and parameters (or the
+iterations[B] int32)``; ``early_stop=False`` keyword; ``schedule="layered"`` (keyword only) runs the layered schedule
+(ldpc_decoder.py module docstring: beta and the offset form's check-side alpha are used, the variable-side alpha of the
+normalised form is not; no gradient path -- ``forward`` with autograd on and ``joint_posterior_loss`` raise
+NotImplementedError).  With autograd enabled and parameters (or the
 LLRs) requiring grad, the returned posterior carries a grad_fn back to beta / alpha (and the LLRs) exactly as
 the reference's chain of torch operations does; the derivative is computed by the HIP backward sweeps behind
 ``torch.ops.ldpc.minsum_decode_train`` (torch_ops.py, autograd_bridge.py).  Under ``torch.no_grad()`` the
@@ -31,7 +34,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ldpc_decoder import LDPCCode, _as_batch
+from ldpc_decoder import LDPCCode, _as_batch, check_schedule
 from weight_sharing import SharingLayout, init_parameter_dicts, unique_degrees
 
 logger = logging.getLogger(__name__)
@@ -44,6 +47,8 @@ class _DegreeSharedDecoder(nn.Module):
     _beta_default = 0.7
     _alpha_default = 1.0
     _alpha_is_oms = False          # True: alpha is the check-side offset of the offset form (engine slot oms_alpha)
+
+    schedule = "flooding"          # "layered": the layered schedule (ldpc_decoder.py module docstring); no gradient path
 
     def _init_sharing(self, code: LDPCCode, weight_sharing_type: int, max_iterations: int, strict=True):
         self.code = code
@@ -88,7 +93,7 @@ class _DegreeSharedDecoder(nn.Module):
         dev = _require_gpu(device)
         g = self.code.tanner_graph()
         layout = self._sharing_layout()
-        key = (dev.index, id(g), int(self.max_iterations), self._extra_key())
+        key = (dev.index, id(g), int(self.max_iterations), self._extra_key(), self.schedule)
         # Flattening the ParameterDicts costs ~40 us -- a third of a one-codeword call (the reference's own call shape) -- so it is
         # skipped while no parameter changed: every in-place update (optimizer step, load_state_dict, fill_) bumps the tensor's
         # version counter, a replaced tensor (`p.data = ...`, a new Parameter under the key) shows in its identity / storage.
@@ -120,6 +125,16 @@ class _DegreeSharedDecoder(nn.Module):
 
     def _extra_key(self):
         return ()
+
+    def _schedule_kwargs(self) -> dict:
+        """engine keywords of the schedule: none for flooding (the engine's default)"""
+        import _native as nat
+        return {"schedule": nat.SCHED_LAYERED} if self.schedule == "layered" else {}
+
+    def _refuse_layered_grad(self, what: str):
+        if self.schedule == "layered":
+            raise NotImplementedError(f"{type(self).__name__}(schedule=\"layered\") has no gradient path: {what} exists "
+                                      "for the flooding schedule only")
 
     # ---- I/O ------------------------------------------------------------------------
     def _decode(self, llr: torch.Tensor, early_stop: bool, device=None):
@@ -163,6 +178,7 @@ class _DegreeSharedDecoder(nn.Module):
         memory does not grow with T.
         -> (loss 0-d, loss_per_iteration [T], bits int32, posterior of the last iteration)"""
         import autograd_bridge as ab
+        self._refuse_layered_grad("joint_posterior_loss")
         if not isinstance(llr, torch.Tensor):
             raise TypeError("llr must be a torch.Tensor")
         ab.check_joint_args(self.code.n, int(self.max_iterations), llr, targets, iteration_weights)
@@ -183,8 +199,10 @@ class Neural2DMinSumDecoder(_DegreeSharedDecoder):
     - Type 4: alpha per variable node degree only
     """
 
-    def __init__(self, code: LDPCCode, weight_sharing_type: int = 2, max_iterations: int = 50):
+    def __init__(self, code: LDPCCode, weight_sharing_type: int = 2, max_iterations: int = 50, *,
+                 schedule: str = "flooding"):
         super().__init__()
+        self.schedule = check_schedule(schedule)
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized N-2D-NMS decoder (Type {weight_sharing_type}) with "
                     f"{len(self.beta_weights)} beta weights and {len(self.alpha_weights)} alpha weights")
@@ -192,7 +210,7 @@ class Neural2DMinSumDecoder(_DegreeSharedDecoder):
     def _engine_kwargs(self, layout, beta, alpha):
         import _native as nat
         return dict(c2v_form=nat.C2V_NMS, beta=beta, beta_slot=layout.beta_slot,
-                    alpha=alpha, alpha_slot=layout.alpha_slot)
+                    alpha=alpha, alpha_slot=layout.alpha_slot, **self._schedule_kwargs())
 
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):
         """
@@ -204,6 +222,7 @@ class Neural2DMinSumDecoder(_DegreeSharedDecoder):
         """
         import autograd_bridge as ab
         if ab.wants_grad(self, llr):
+            self._refuse_layered_grad("a posterior with a grad_fn")
             out = self._decode_with_grad(llr, early_stop, device)
             if out is not None:
                 return out
@@ -223,8 +242,10 @@ class Neural2DOffsetMinSumDecoder(_DegreeSharedDecoder):
     _alpha_default = 0.0
     _alpha_is_oms = True
 
-    def __init__(self, code: LDPCCode, weight_sharing_type: int = 2, max_iterations: int = 50):
+    def __init__(self, code: LDPCCode, weight_sharing_type: int = 2, max_iterations: int = 50, *,
+                 schedule: str = "flooding"):
         super().__init__()
+        self.schedule = check_schedule(schedule)
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized N-2D-OMS decoder (Type {weight_sharing_type}) with "
                     f"{len(self.beta_weights)} beta weights and {len(self.alpha_weights)} alpha weights")
@@ -235,7 +256,7 @@ class Neural2DOffsetMinSumDecoder(_DegreeSharedDecoder):
         rows = beta.shape[0]
         return dict(c2v_form=nat.C2V_OMS, beta=beta, beta_slot=layout.beta_slot,
                     alpha=np.ones((rows, 1), np.float32), alpha_slot=np.zeros(g.n, np.int32),
-                    oms_alpha=alpha, oms_alpha_slot=layout.alpha_edge_slot)
+                    oms_alpha=alpha, oms_alpha_slot=layout.alpha_edge_slot, **self._schedule_kwargs())
 
     def _tables_for_upload(self, beta, alpha):
         return beta, None, alpha
@@ -243,6 +264,7 @@ class Neural2DOffsetMinSumDecoder(_DegreeSharedDecoder):
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):
         import autograd_bridge as ab
         if ab.wants_grad(self, llr):       # relu / offset are differentiable in the reference too (:396-401)
+            self._refuse_layered_grad("a posterior with a grad_fn")
             out = self._decode_with_grad(llr, early_stop, device)
             if out is not None:
                 return out

@@ -12,7 +12,9 @@ Reference behaviour mirrored (file:line in /root/reference):
       init randn*0.1; C2V = prod(signs) * relu(min - beta)
   analyze_weight_patterns(decoder, code)                   neural_minsum_decoder.py:288-349
 
-Extensions as everywhere: ``[B, n]`` batches, ``early_stop=False``.
+Extensions as everywhere: ``[B, n]`` batches, ``early_stop=False``; keyword-only ``schedule="layered"`` runs the layered
+schedule with the per-edge weights (ldpc_decoder.py module docstring; no gradient path: ``forward`` with autograd on and
+``joint_posterior_loss`` raise NotImplementedError).
 """
 
 from __future__ import annotations
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ldpc_decoder import LDPCCode, _as_batch
+from ldpc_decoder import LDPCCode, _as_batch, check_schedule
 
 logger = logging.getLogger(__name__)
 
@@ -33,6 +35,12 @@ class _EdgeWeightDecoder(nn.Module):
     """one beta per (iteration, edge); table column = CSR edge id"""
 
     _c2v_form = "nms"
+    schedule = "flooding"          # "layered": the layered schedule (ldpc_decoder.py module docstring); no gradient path
+
+    def _refuse_layered_grad(self, what: str):
+        if self.schedule == "layered":
+            raise NotImplementedError(f"{type(self).__name__}(schedule=\"layered\") has no gradient path: {what} exists "
+                                      "for the flooding schedule only")
 
     def _init_edges(self, code: LDPCCode, max_iterations: int, offset: float):
         self.code = code
@@ -75,15 +83,16 @@ class _EdgeWeightDecoder(nn.Module):
         g = self.code.tanner_graph()
         T = int(self.max_iterations)
         versions = (len(self.beta_weights), sum(p._version for p in self.beta_weights.values()))
-        key = (dev.index, id(g), T)
+        key = (dev.index, id(g), T, self.schedule)
         if self._engine is None or self._engine_key != key:
             beta = self.weight_table()
             rows = max(T, 1)
+            extra = {"schedule": nat.SCHED_LAYERED} if self.schedule == "layered" else {}
             self._engine = DecodeEngine(
                 g, dtype=torch.float32, iters=T, device=dev,
                 c2v_form=nat.C2V_NMS if self._c2v_form == "nms" else nat.C2V_OMS,
                 beta=beta, beta_slot=np.arange(g.E, dtype=np.int32),
-                alpha=np.ones((rows, 1), np.float32), alpha_slot=np.zeros(g.n, np.int32))
+                alpha=np.ones((rows, 1), np.float32), alpha_slot=np.zeros(g.n, np.int32), **extra)
             self._engine_key, self._uploaded, self._versions = key, beta, versions
         elif versions != self._versions:
             beta = self.weight_table()
@@ -96,10 +105,12 @@ class _EdgeWeightDecoder(nn.Module):
         """-> decoded_bits (int32), posterior (float32), iterations (int / int32[B])"""
         if not isinstance(llr, torch.Tensor):
             raise TypeError("llr must be a torch.Tensor")
+        import autograd_bridge as ab
+        if ab.wants_grad(self, llr):
+            self._refuse_layered_grad("a posterior with a grad_fn")
         _, x, single = _as_batch(llr, self.code.n)
         eng = self._get_engine(x.device if x.is_cuda else device)
         out_dev = llr.device
-        import autograd_bridge as ab
         if ab.wants_grad(self, llr) and ab.saved_state_fits(eng, x.shape[0]):
             # posterior with a grad_fn back to the edge weights, as in the reference (neural_minsum_decoder.py:100-139)
             g, T = self.code.tanner_graph(), int(self.max_iterations)
@@ -126,6 +137,7 @@ class _EdgeWeightDecoder(nn.Module):
         ``loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets)`` and its posterior-local gradient, as
         ``Neural2DMinSumDecoder.joint_posterior_loss`` -> (loss, loss_per_iteration [T], bits, posterior)"""
         import autograd_bridge as ab
+        self._refuse_layered_grad("joint_posterior_loss")
         if not isinstance(llr, torch.Tensor):
             raise TypeError("llr must be a torch.Tensor")
         g, T = self.code.tanner_graph(), int(self.max_iterations)
@@ -144,8 +156,9 @@ class NeuralMinSumDecoder(_EdgeWeightDecoder):
 
     _c2v_form = "nms"
 
-    def __init__(self, code: LDPCCode, max_iterations: int = 50):
+    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding"):
         super().__init__()
+        self.schedule = check_schedule(schedule)
         self._init_edges(code, max_iterations, offset=0.7)
         num_edges = int(code.tanner_graph().E)
         logger.info(f"Initialized Neural MinSum decoder with {len(self.beta_weights)} parameters")
@@ -157,8 +170,9 @@ class LdpcDecoderNeuralMinSumDecoder(_EdgeWeightDecoder):
     normalised min-sum forward, but weights initialised ``randn*0.1`` WITHOUT the +0.7 and an (empty)
     ``alpha_weights`` ParameterDict.  Exported as ``ldpc_decoder.NeuralMinSumDecoder``."""
 
-    def __init__(self, code: LDPCCode, max_iterations: int = 50):
+    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding"):
         super().__init__()
+        self.schedule = check_schedule(schedule)
         self._init_edges(code, max_iterations, offset=0.0)
         self.alpha_weights = nn.ParameterDict()
         logger.info(f"Initialized Neural MinSum decoder with {len(self.beta_weights)} parameters")
@@ -172,8 +186,9 @@ class NeuralOffsetMinSumDecoder(_EdgeWeightDecoder):
 
     _c2v_form = "oms"
 
-    def __init__(self, code: LDPCCode, max_iterations: int = 50):
+    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding"):
         super().__init__()
+        self.schedule = check_schedule(schedule)
         self._init_edges(code, max_iterations, offset=0.0)
         logger.info(f"Initialized Neural Offset MinSum decoder with {len(self.beta_weights)} parameters")
 

@@ -70,7 +70,15 @@ enum {
  * table exactly as the flooding RCQ check update does (c2v = deq(quant(beta_t[beta_slot[e]] * s * min)); alpha is not used) --
  * WeightedRCQDecoder(layered="paper"); a table of all 1.0 is the unweighted schedule.  Two kernels with identical results: LDS-resident
  * (posteriors AND the per-edge message codes in LDS; LDPC_MODE_AUTO / RESIDENT when checks have <= 64 edges and at least four one-wave
- * workgroups fit a CU's LDS) and streaming (every other case). */
+ * workgroups fit a CU's LDS) and streaming (every other case).
+ * LAYERED with LDPC_C2V_NMS / LDPC_C2V_OMS (fp32 only) is the same schedule with unquantised messages, the baseline of the quantised
+ * one: on the edges of a check u = P - R, min1 / min2 / sign product over the u as in the flooding check update (first minimum is the
+ * arg-min, ties keep min2 == min1, sign(0) = 0), r = (beta * min_others) * sign_others (NMS) or sign_others * (relu(min_others - beta)
+ * - oms_alpha) (OMS), P = u + r, R = r; the variable-side alpha is not used, the check-side oms_alpha is; LLRs must be finite.  Two
+ * kernels with identical results: LDS-resident (posteriors and a 16-byte record per check -- min1, min2, a sign and an arg-min bit per
+ * edge -- from which each lane recomputes R; same qualification as above) and streaming (R as fp32 per edge in the workspace).  No
+ * gradient path: ldpc_decode_saving, ldpc_backward and ldpc_train_joint return LDPC_ERR_UNSUPPORTED.  LAYERED_REF with these forms is
+ * unsupported (the reference has no such path), as is a float64 layered decoder. */
 enum { LDPC_SCHED_FLOODING = 0, LDPC_SCHED_LAYERED_REF = 1, LDPC_SCHED_LAYERED = 2 };
 
 typedef struct ldpc_graph ldpc_graph;      /* Tanner graph, CSR + CSC, device resident */
