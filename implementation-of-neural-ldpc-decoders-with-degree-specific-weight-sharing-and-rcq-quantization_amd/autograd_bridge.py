@@ -106,6 +106,19 @@ def check_quantizer_gradient(value):
     return value
 
 
+LAYERED_GRADIENTS = ("posterior_local",)
+
+
+def check_layered_gradient(value, schedule="layered"):
+    """the gradients joint_posterior_loss of a ``schedule="layered"`` min-sum decoder knows: None (no gradient path) or one
+    of LAYERED_GRADIENTS; ValueError otherwise, and for any value but None on a flooding decoder (nothing to choose there)"""
+    if value is not None and value not in LAYERED_GRADIENTS:
+        raise ValueError(f"layered_gradient must be None or one of {LAYERED_GRADIENTS}, got {value!r}")
+    if value is not None and schedule != "layered":
+        raise ValueError(f"layered_gradient={value!r} applies to schedule=\"layered\" only, this decoder runs {schedule!r}")
+    return value
+
+
 def joint_loss_ste(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets,
                    iteration_weights):
     """joint_loss() of the quantised WeightedRCQDecoder through ``torch.ops.ldpc.rcq_joint_loss``: the same loss on the
@@ -115,11 +128,13 @@ def joint_loss_ste(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, 
 
 
 def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets, iteration_weights,
-               alpha_is_oms: bool, quantised: bool = False):
+               alpha_is_oms: bool, quantised: bool = False, layered: bool = False):
     """posterior joint training through ``torch.ops.ldpc.minsum_joint_loss`` (torch_ops.py) -> (loss, loss_per_iteration,
     bits, posterior): loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets) over the T iterations of the fixed-T
     decode, differentiable in the tables (and in `llr` when it requires grad) with the posterior-local gradient of the
-    paper's training method.  No saved history: MAX_SAVED_BYTES does not apply."""
+    paper's training method.  No saved history: MAX_SAVED_BYTES does not apply.
+    ``layered``: the engine runs the layered schedule -- ``torch.ops.ldpc.minsum_layered_joint_loss``, whose gradient is the
+    layered posterior-local one of include/ldpc_hip.h (ldpc_train_joint_layered)."""
     import torch_ops
     from ldpc_decoder import _as_batch
     T = int(engine.iters)
@@ -141,7 +156,8 @@ def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr:
         loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.rcq_joint_loss(
             xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(want_grads), bool(want_llr))
     else:
-        loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.minsum_joint_loss(
+        op = torch.ops.ldpc.minsum_layered_joint_loss if layered else torch.ops.ldpc.minsum_joint_loss
+        loss, lpi, post, bits, _gb, _ga, _gl = op(
             xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(alpha_is_oms),
             bool(want_grads), bool(want_llr))
     out_dev = llr.device

@@ -1460,8 +1460,10 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
         rc = up_bytes(&d->oms_alpha, desc->oms_alpha, rows * d->n_oms_alpha * es);
         if (!rc) rc = upload(&d->oms_alpha_slot, desc->oms_alpha_slot, (size_t)g->E);
     }
-    // inverse slot maps of the gradient paths: the min-sum forms (ldpc_backward, ldpc_train_joint) and RCQ (ldpc_train_joint_ste)
-    if (!rc && d->dtype == LDPC_F32 && d->schedule == LDPC_SCHED_FLOODING) {
+    // inverse slot maps of the gradient paths: the min-sum forms (ldpc_backward, ldpc_train_joint), RCQ (ldpc_train_joint_ste)
+    // and the layered min-sum forms (ldpc_train_joint_layered: beta and the check-side alpha; the schedule has no variable-side alpha)
+    const bool lay_ms = d->schedule == LDPC_SCHED_LAYERED && d->form != LDPC_C2V_RCQ;
+    if (!rc && d->dtype == LDPC_F32 && (d->schedule == LDPC_SCHED_FLOODING || lay_ms)) {
         auto invert = [&](const int32_t *slot, int count, int n_slots, int **ptr_dev, int **items_dev) {
             std::vector<int> ptr((size_t)n_slots + 1, 0), items((size_t)std::max(count, 1), 0);
             for (int x = 0; x < count; ++x) ptr[slot[x] + 1]++;
@@ -1473,7 +1475,7 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
             return r;
         };
         rc = invert(desc->beta_slot, g->E, d->n_beta, &d->beta_inv_ptr, &d->beta_inv_items);
-        if (!rc) rc = invert(desc->alpha_slot, g->n, d->n_alpha, &d->alpha_inv_ptr, &d->alpha_inv_items);
+        if (!rc && !lay_ms) rc = invert(desc->alpha_slot, g->n, d->n_alpha, &d->alpha_inv_ptr, &d->alpha_inv_items);
         if (!rc && d->oms_alpha) rc = invert(desc->oms_alpha_slot, g->E, d->n_oms_alpha, &d->oms_inv_ptr, &d->oms_inv_items);
     }
     if (!rc && d->form == LDPC_C2V_RCQ && d->dtype == LDPC_F32 && d->schedule == LDPC_SCHED_FLOODING &&
@@ -1911,6 +1913,145 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
+
+// ---- posterior joint training of the layered min-sum decoders (ldpc_train_joint_layered) --------------------
+// joint_impl's loop on the layered schedule: layered_minsum_iter walks the checks once per launch on the running
+// posteriors and keeps u_e = P_v - R_e of every edge; J_t and its seed g_l are formed on a COPY of the posterior rows
+// (the walk still needs P), and cn_backward<..., LOCAL> differentiates the check update with v2c_t := u.  Scratch, whatever
+// T is --  n rows: posterior, its copy (then g_l), targets, d J/d llr;  E rows: R, U, d J/d u;  per-tile partials of the
+// table gradients and of the loss.  Layered decoders run at VEC = 1 (pick_vec).
+struct LayJointWs {
+    int tiles = 0;
+    float *postT = nullptr, *glT = nullptr, *yT = nullptr, *gllrT = nullptr, *msgs = nullptr, *urows = nullptr, *gu = nullptr;
+    float *gbeta = nullptr, *goa = nullptr;
+    uint64_t *bitsT = nullptr;
+    double *loss_part = nullptr, *item_sum = nullptr;
+    size_t total = 0;
+};
+LayJointWs carve_joint_layered(const ldpc_decoder *d, int64_t batch, void *base)
+{
+    LayJointWs w;
+    constexpr int W = kWave;
+    w.tiles = (int)std::max<int64_t>((batch + W - 1) / W, 1);
+    const size_t n = d->g->n, E = std::max(d->g->E, 1), tw = (size_t)w.tiles * W;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
+    const size_t o_post = take(tw * n * 4), o_gl = take(tw * n * 4), o_y = take(tw * n * 4), o_gx = take(tw * n * 4);
+    const size_t o_r = take(tw * E * 4), o_u = take(tw * E * 4), o_gu = take(tw * E * 4);
+    const size_t o_bits = take((size_t)w.tiles * n * sizeof(uint64_t));
+    const size_t o_gb = take((size_t)w.tiles * E * 4), o_goa = take(d->form == LDPC_C2V_OMS ? (size_t)w.tiles * E * 4 : 0);
+    const size_t vb = (n + kWavesPerBlock - 1) / kWavesPerBlock;
+    const size_t o_lp = take((size_t)w.tiles * vb * sizeof(double)), o_is = take(E * sizeof(double));
+    w.total = off;
+    if (base) {
+        char *b = (char *)base;
+        w.postT = (float *)(b + o_post); w.glT = (float *)(b + o_gl); w.yT = (float *)(b + o_y); w.gllrT = (float *)(b + o_gx);
+        w.msgs = (float *)(b + o_r); w.urows = (float *)(b + o_u); w.gu = (float *)(b + o_gu);
+        w.bitsT = (uint64_t *)(b + o_bits); w.gbeta = (float *)(b + o_gb); w.goa = (float *)(b + o_goa);
+        w.loss_part = (double *)(b + o_lp); w.item_sum = (double *)(b + o_is);
+    }
+    return w;
+}
+
+int joint_layered_impl(const ldpc_decoder *d, const float *llr, const float *targets, int64_t batch, const float *weights,
+                       float *loss_per_iter, int32_t *bits, float *posterior, float *grad_beta, float *grad_alpha,
+                       float *grad_oms_alpha, float *grad_llr, const LayJointWs &w, hipStream_t s)
+{
+    constexpr int VEC = 1, W = kWave;
+    constexpr int JT = transpose_vars<float>();
+    const GraphDev g = d->g->dev();
+    const int T = d->T, tiles = w.tiles, vc = (g.n + JT - 1) / JT;
+    const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
+    const bool oms = d->form == LDPC_C2V_OMS;
+    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
+    const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
+    const size_t nrow_bytes = (size_t)tiles * W * g.n * sizeof(float), erow_bytes = (size_t)tiles * W * g.E * sizeof(float);
+    // P = llr, R = +0 ("no message yet"), as the decode starts
+    hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, w.postT, (long long)batch, g.n, vc);
+    if (targets)
+        hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, targets, w.yT, (long long)batch, g.n, vc);
+    HIP_TRY(hipMemsetAsync(w.msgs, 0, erow_bytes, s));
+    // the schedule has no variable-side alpha: every row of its gradient is 0
+    if (grad_alpha) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)T * d->n_alpha * 4, s));
+    if (grad_oms_alpha && !oa_grad && d->n_oms_alpha > 0)
+        HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)T * d->n_oms_alpha * 4, s));
+    if (grad_llr) HIP_TRY(hipMemsetAsync(w.gllrT, 0, nrow_bytes, s));
+    const int cb = (g.m + kWavesPerBlock - 1) / kWavesPerBlock, vb = (g.n + kWavesPerBlock - 1) / kWavesPerBlock;
+    const dim3 cgrid((unsigned)((size_t)tiles * cb)), vgrid((unsigned)((size_t)tiles * vb));
+    const double inv_bn = 1.0 / ((double)batch * (double)g.n);
+    auto reduce_step = [&](const float *part, int count, const int *slot_ptr, const int *slot_items, int n_slots, float *row) {
+        hipLaunchKernelGGL(reduce_tiles, dim3((unsigned)((count + kBlock - 1) / kBlock)), blk, 0, s, part, tiles, count, w.item_sum);
+        hipLaunchKernelGGL(reduce_table_grads<double>, dim3((unsigned)n_slots), dim3(kWave), 0, s, (const double *)w.item_sum, 1,
+                           count, slot_ptr, slot_items, n_slots, row);
+    };
+    const float *yT = targets ? w.yT : nullptr;
+    for (int t = 0; t < T; ++t) {
+        const bool last = t == T - 1;
+        const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
+        const float *oa_row = (oms && d->oms_alpha) ? (const float *)d->oms_alpha + (size_t)t * d->n_oms_alpha : nullptr;
+        uint64_t *bitsT = (last && bits) ? w.bitsT : nullptr;
+        // forward iteration t: one walk over the checks, a wave per tile; P_t in postT, u of every edge in urows
+        if (oms)
+            hipLaunchKernelGGL((layered_minsum_iter<VEC, FORM_OMS>), dim3(tiles), dim3(kWave), 0, s, g, w.postT, w.msgs, w.urows,
+                               beta_row, (const int *)d->beta_slot, oa_row, (const int *)d->oms_alpha_slot, bitsT);
+        else
+            hipLaunchKernelGGL((layered_minsum_iter<VEC, FORM_NMS>), dim3(tiles), dim3(kWave), 0, s, g, w.postT, w.msgs, w.urows,
+                               beta_row, (const int *)d->beta_slot, (const float *)nullptr, (const int *)nullptr, bitsT);
+        if (last && (bits || posterior))
+            hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.postT, (const uint64_t *)w.bitsT,
+                               posterior, bits, (long long)batch, g.n, vc);
+        // J_t; with a gradient, g_l over a copy of the posterior rows (joint_loss_grad writes in place, the walk goes on with P)
+        if (want) {
+            HIP_TRY(hipMemcpyAsync(w.glT, w.postT, nrow_bytes, hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL((joint_loss_grad<VEC, true>), vgrid, blk, 0, s, g.n, w.glT, yT, weights, t, (long long)batch,
+                               (float)inv_bn, grad_llr ? w.gllrT : nullptr, w.loss_part, vb);
+        } else {
+            hipLaunchKernelGGL((joint_loss_grad<VEC, false>), vgrid, blk, 0, s, g.n, w.postT, yT, weights, t, (long long)batch,
+                               (float)inv_bn, (float *)nullptr, w.loss_part, vb);
+        }
+        hipLaunchKernelGGL(joint_loss_reduce, dim3(1), blk, 0, s, (const double *)w.loss_part, (long long)tiles * vb, inv_bn,
+                           loss_per_iter + t);
+        HIP_TRY(hipGetLastError());
+        if (!want) continue;
+        // posterior-local backward of iteration t through the check update alone: beta_t, the offset alpha_t, d J_t/d u
+        float *gu_out = grad_llr ? w.gu : nullptr;
+        float *goa = oa_grad ? w.goa : nullptr;
+#define LDPC_CNL(FORM_)                                                                                                \
+    hipLaunchKernelGGL((cn_backward<VEC, false, FORM_, true>), cgrid, blk, 0, s, g, (const float *)w.urows,           \
+                       (const float *)nullptr, (const float *)w.glT, (const int *)nullptr, (long long)batch, t, beta_row, \
+                       (const int *)d->beta_slot, gu_out, w.gbeta, goa, cb)
+        if (oms) LDPC_CNL(FORM_OMS); else LDPC_CNL(FORM_NMS);
+#undef LDPC_CNL
+        if (grad_beta) reduce_step(w.gbeta, g.E, d->beta_inv_ptr, d->beta_inv_items, d->n_beta, grad_beta + (size_t)t * d->n_beta);
+        if (oa_grad)
+            reduce_step(w.goa, g.E, d->oms_inv_ptr, d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha + (size_t)t * d->n_oms_alpha);
+        if (grad_llr)                                      // u_e = llr_v + const: d J_t/d llr_v = g_t[v] + sum of d J_t/d u_e at v
+            hipLaunchKernelGGL((llr_backward_accumulate<VEC>), vgrid, blk, 0, s, g, (const float *)w.gu, w.gllrT, vb);
+        HIP_TRY(hipGetLastError());
+    }
+    if (grad_llr)
+        hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.gllrT, (const uint64_t *)nullptr, grad_llr,
+                           (int *)nullptr, (long long)batch, g.n, vc);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+// ldpc_train_joint_layered: the fp32 layered normalised / offset min-sum decoders
+int layered_joint_supported(const ldpc_decoder *d)
+{
+    if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
+    if (d->dtype != LDPC_F32)
+        return fail(LDPC_ERR_UNSUPPORTED, "the layered joint loss exists for fp32 decoders only (a float64 decoder has no layered schedule)");
+    if (d->schedule == LDPC_SCHED_FLOODING && d->form == LDPC_C2V_RCQ)
+        return fail(LDPC_ERR_UNSUPPORTED, "a flooding RCQ decoder takes ldpc_train_joint_ste, not ldpc_train_joint_layered");
+    if (d->schedule == LDPC_SCHED_FLOODING)
+        return fail(LDPC_ERR_UNSUPPORTED, "a flooding min-sum decoder takes ldpc_train_joint, not ldpc_train_joint_layered");
+    if (d->form == LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_LAYERED)
+        return fail(LDPC_ERR_UNSUPPORTED, "the layered joint loss exists for the min-sum forms (LDPC_C2V_NMS / LDPC_C2V_OMS) under "
+                                          "LDPC_SCHED_LAYERED; the layered RCQ decoders (LDPC_SCHED_LAYERED_REF, LDPC_SCHED_LAYERED) "
+                                          "have no gradient path, their flooding form takes ldpc_train_joint_ste");
+    return LDPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1988,16 +2129,18 @@ size_t ldpc_train_joint_workspace_bytes(const ldpc_decoder *d, int64_t batch)
     return carve_joint(d, batch, nullptr).total;
 }
 
-// ldpc_train_joint (ste = false) and ldpc_train_joint_ste (ste = true): the same argument rules, the same loop
-static int train_joint_entry(const ldpc_decoder *d, bool ste, const void *llr, const void *targets, int64_t batch,
+// ldpc_train_joint, ldpc_train_joint_ste and ldpc_train_joint_layered: the same argument rules; the first two share joint_impl
+enum { kJointMinsum = 0, kJointSte = 1, kJointLayered = 2 };
+static int train_joint_entry(const ldpc_decoder *d, int kind, const void *llr, const void *targets, int64_t batch,
                              const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
                              void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
                              size_t workspace_bytes, void *stream)
 {
-    if (int rc = ste ? ste_supported(d) : train_supported(d)) return rc;
+    const bool ste = kind == kJointSte, layered = kind == kJointLayered;
+    if (int rc = layered ? layered_joint_supported(d) : ste ? ste_supported(d) : train_supported(d)) return rc;
     if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
     if (d->T < 1) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs at least one iteration");
-    if (!d->beta_inv_ptr || !d->alpha_inv_ptr) return fail(LDPC_ERR_UNSUPPORTED, "internal: the decoder has no inverse slot maps");
+    if (!d->beta_inv_ptr || (!layered && !d->alpha_inv_ptr)) return fail(LDPC_ERR_UNSUPPORTED, "internal: the decoder has no inverse slot maps");
     if (ste && d->n_levels > kVnbLutMax / 2) return fail(LDPC_ERR_UNSUPPORTED, "more than %d quantiser levels", kVnbLutMax / 2);
     if (!loss_per_iter) return fail(LDPC_ERR_ARG, "NULL loss_per_iter");
     const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
@@ -2014,6 +2157,14 @@ static int train_joint_entry(const ldpc_decoder *d, bool ste, const void *llr, c
     if (d->g->n == 0 || d->g->E == 0) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs a graph with edges");
     if (!llr || !workspace) return fail(LDPC_ERR_ARG, "NULL llr/workspace");
     if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
+    if (layered) {
+        const LayJointWs lw = carve_joint_layered(d, batch, workspace);
+        if (lw.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, lw.total);
+        if ((size_t)lw.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+        return joint_layered_impl(d, (const float *)llr, (const float *)targets, batch, (const float *)iteration_weights,
+                                  (float *)loss_per_iter, bits, (float *)posterior, (float *)grad_beta, (float *)grad_alpha,
+                                  (float *)grad_oms_alpha, (float *)grad_llr, lw, s);
+    }
     const JointWs w = carve_joint(d, batch, workspace, ste);
     if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
     if ((size_t)w.fw.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
@@ -2031,7 +2182,7 @@ int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets
                      void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
                      size_t workspace_bytes, void *stream)
 {
-    return train_joint_entry(d, false, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
+    return train_joint_entry(d, kJointMinsum, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
                              grad_alpha, grad_oms_alpha, grad_llr, workspace, workspace_bytes, stream);
 }
 
@@ -2046,8 +2197,23 @@ int ldpc_train_joint_ste(const ldpc_decoder *d, const void *llr, const void *tar
                          void *grad_beta, void *grad_alpha, void *grad_llr, void *workspace, size_t workspace_bytes,
                          void *stream)
 {
-    return train_joint_entry(d, true, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
+    return train_joint_entry(d, kJointSte, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
                              grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream);
+}
+
+size_t ldpc_train_joint_layered_workspace_bytes(const ldpc_decoder *d, int64_t batch)
+{
+    if (!d || batch < 0) return 0;
+    return carve_joint_layered(d, batch, nullptr).total;
+}
+
+int ldpc_train_joint_layered(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                             const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                             void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    return train_joint_entry(d, kJointLayered, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior,
+                             grad_beta, grad_alpha, grad_oms_alpha, grad_llr, workspace, workspace_bytes, stream);
 }
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

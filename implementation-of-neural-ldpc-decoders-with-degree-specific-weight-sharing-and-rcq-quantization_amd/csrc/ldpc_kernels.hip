@@ -2539,6 +2539,85 @@ __global__ __launch_bounds__(kWave) void layered_minsum(GraphDev g, float *__res
     }
 }
 
+// Training form of layered_minsum (ldpc_train_joint_layered): ONE iteration per launch, posteriors and messages left in
+// post / msgs between launches, and the second pass over a check also stores u_e = P_v - R_e -- the value the check update
+// consumed, the `v2c` of the posterior-local backward (cn_backward) -- into urows[tile][E][W].  Same arithmetic as
+// layered_minsum, step for step, so the posterior after launch t is that of a fixed-T decode capped at t + 1 iterations.
+// No early stop and no frozen state: padding codewords (LLR 1) are walked like the others, the gradient kernels leave
+// them out.  bitsT (the last launch only): hard decisions as ballots.
+template <int VEC, int FORM>
+__global__ __launch_bounds__(kWave) void layered_minsum_iter(GraphDev g, float *__restrict__ post, float *__restrict__ msgs,
+                                                             float *__restrict__ urows, const float *__restrict__ beta_row,
+                                                             const int *__restrict__ beta_slot,
+                                                             const float *__restrict__ oa_row,
+                                                             const int *__restrict__ oms_alpha_slot,
+                                                             uint64_t *__restrict__ bitsT)
+{
+    static_assert(FORM == FORM_NMS || FORM == FORM_OMS, "min-sum forms");
+    constexpr int W = kWave * VEC;
+    const int lane = threadIdx.x, tile = blockIdx.x;
+    float *P = post + (size_t)tile * g.n * W + (size_t)lane * VEC;
+    float *R = msgs + (size_t)tile * g.E * W + (size_t)lane * VEC;
+    float *U = urows + (size_t)tile * g.E * W + (size_t)lane * VEC;
+    for (int i = 0; i < g.m; ++i) {
+        const int e0 = uni(g.check_ptr[i]);
+        const int dc = uni(g.check_ptr[i + 1]) - e0;
+        if (dc == 0) continue;
+        float m1[VEC], m2[VEC];
+        unsigned par[VEC];
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) { m1[c] = inf_of<float>(); m2[c] = inf_of<float>(); par[c] = 0; }
+#pragma unroll 4
+        for (int t = 0; t < dc; ++t) {
+            const Pack<float, VEC> x = ld<float, VEC>(P + (size_t)g.var_idx[e0 + t] * W);
+            const Pack<float, VEC> ro = ld<float, VEC>(R + (size_t)(e0 + t) * W);
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) {
+                const float u = __fsub_rn(x.x[c], ro.x[c]);
+                const float a = __builtin_fabsf(u);
+                par[c] ^= signbit_of<float>(u);
+                if (a < m1[c]) { m2[c] = m1[c]; m1[c] = a; }
+                else if (a < m2[c]) { m2[c] = a; }
+            }
+        }
+        if (dc == 1) {
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) m2[c] = m1[c];
+        }
+#pragma unroll 2
+        for (int t = 0; t < dc; ++t) {
+            float *prow = P + (size_t)g.var_idx[e0 + t] * W, *rrow = R + (size_t)(e0 + t) * W;
+            const float b = beta_row[beta_slot[e0 + t]];
+            const float oa = oa_row ? oa_row[oms_alpha_slot[e0 + t]] : 0.0f;
+            Pack<float, VEC> x = ld<float, VEC>(prow);
+            Pack<float, VEC> ro = ld<float, VEC>(rrow);
+            Pack<float, VEC> uo;
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) {
+                const float u = __fsub_rn(x.x[c], ro.x[c]);
+                const float a = __builtin_fabsf(u);
+                const float raw = (a == m1[c]) ? m2[c] : m1[c];       // arg-min edge; ties make min2 == min1
+                const float rn = lay_ms_msg<FORM>(raw, par[c] ^ signbit_of<float>(u), b, oa, dc == 1);
+                x.x[c] = __fadd_rn(u, rn);                            // never an fma with the product inside rn
+                ro.x[c] = rn;
+                uo.x[c] = u;
+            }
+            st<float, VEC>(prow, x);
+            st<float, VEC>(rrow, ro);
+            st<float, VEC>(U + (size_t)(e0 + t) * W, uo);
+        }
+    }
+    if (!bitsT) return;
+    for (int j = 0; j < g.n; ++j) {                             // hard decisions as ballots, like the sweep engine
+        const Pack<float, VEC> v = ld<float, VEC>(P + (size_t)j * W);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+            const uint64_t m = __ballot(v.x[c] < 0.0f);
+            if (lane == 0) bitsT[((size_t)tile * g.n + j) * VEC + c] = m;
+        }
+    }
+}
+
 // done masks: padding codewords (>= batch) start frozen; iterations start at T
 template <int VEC>
 __global__ void init_state(uint64_t *__restrict__ done, int *__restrict__ iters, long long batch,

@@ -467,6 +467,19 @@ class DecodeEngine:
     def train_joint_ste_workspace_bytes(self, batch: int) -> int:
         return int(self._lib.ldpc_train_joint_ste_workspace_bytes(self.handle, int(batch)))
 
+    def train_joint_layered_workspace_bytes(self, batch: int) -> int:
+        return int(self._lib.ldpc_train_joint_layered_workspace_bytes(self.handle, int(batch)))
+
+    def train_joint_layered(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                            iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
+                            want_grad_llr: bool = False) -> dict:
+        """train_joint() of a layered normalised / offset min-sum decoder (ldpc_train_joint_layered): the fixed-T layered
+        decode, unchanged, one iteration per launch, with the layered posterior-local gradients of J defined in
+        include/ldpc_hip.h (iteration t's loss reaches beta_t, the check-side offset alpha_t and the LLRs through the
+        check update alone).  Same arguments and the same dict as train_joint; "grad_alpha" (the variable-side table
+        the schedule does not use) is all zero.  NotImplementedError for every other decoder."""
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="layered")
+
     def train_joint_ste(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                         iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
                         want_grad_llr: bool = False) -> dict:
@@ -474,7 +487,7 @@ class DecodeEngine:
         the posterior-local gradients of J formed through the straight-through rule of include/ldpc_hip.h (gradient 1
         through the quantiser below its top level, 0 where the code saturated).  Same arguments and the same dict as
         train_joint ("grad_oms_alpha" is always None); NotImplementedError for every other decoder."""
-        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, ste=True)
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="ste")
 
     def train_joint(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                     iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
@@ -486,9 +499,10 @@ class DecodeEngine:
         -> {"loss": 0-d, "loss_per_iter": [T], "bits": int32 [B, n], "posterior": [B, n] (of the last iteration),
             "grad_beta", "grad_alpha": [T, slots] | None, "grad_oms_alpha": [T, slots] | None, "grad_llr": [B, n] | None}
         Everything on this engine's device, fp32."""
-        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, ste=False)
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="minsum")
 
-    def _train_joint(self, llr, targets, iteration_weights, want_grads, want_grad_llr, ste: bool) -> dict:
+    def _train_joint(self, llr, targets, iteration_weights, want_grads, want_grad_llr, kind: str) -> dict:
+        ste, layered = kind == "ste", kind == "layered"
         llr = self._check_llr(llr)
         B, n = llr.shape
         dev = self.device
@@ -513,7 +527,8 @@ class DecodeEngine:
         gl = torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr else None
         ws = None
         if B > 0:
-            need = self.train_joint_ste_workspace_bytes(B) if ste else self.train_joint_workspace_bytes(B)
+            need = (self.train_joint_ste_workspace_bytes(B) if ste else self.train_joint_layered_workspace_bytes(B) if layered
+                    else self.train_joint_workspace_bytes(B))
             ws = getattr(self, "_joint_ws", None)
             if ws is None or ws.numel() < need:
                 self._joint_ws = None
@@ -525,6 +540,10 @@ class DecodeEngine:
                 nat.check(self._lib.ldpc_train_joint_ste(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
                                                          p(gb), p(ga), p(gl), p(ws), 0 if ws is None else ws.numel(),
                                                          C.c_void_p(stream)), "ldpc_train_joint_ste")
+            elif layered:
+                nat.check(self._lib.ldpc_train_joint_layered(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
+                                                             p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),
+                                                             C.c_void_p(stream)), "ldpc_train_joint_layered")
             else:
                 nat.check(self._lib.ldpc_train_joint(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
                                                      p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),

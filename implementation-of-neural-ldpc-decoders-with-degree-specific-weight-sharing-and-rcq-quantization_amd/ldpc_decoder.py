@@ -26,8 +26,10 @@ posteriors, each check first takes its previous message off (``u = P - R``), for
 form from the ``u`` of its edges and adds it (``P = u + r``).  It is the unquantised baseline of
 ``WeightedRCQDecoder(layered="paper")``: same schedule, fp32 messages.  fp32 only (a float64 input is refused by the
 engine); the variable-side alpha is not used (a layered update has no separate variable-node sum for it to scale -- the
-decision taken for the layered W-RCQ decoder), the check-side alpha of the offset form is; LLRs must be finite; there
-is no gradient path.  Nothing in the reference executes this schedule.
+decision taken for the layered W-RCQ decoder), the check-side alpha of the offset form is; LLRs must be finite.  The
+trainable classes train under it with ``joint_posterior_loss(..., layered_gradient="posterior_local")`` (the layered
+posterior-local gradient of include/ldpc_hip.h, ldpc_train_joint_layered); a ``forward`` that would owe a grad_fn stays
+refused.  Nothing in the reference executes this schedule.
 """
 
 from __future__ import annotations

@@ -17,8 +17,9 @@ Reference behaviour mirrored (file:line in /root/reference):
 Extensions: ``llr`` of shape ``[B, n]`` -> ``(bits[B,n] int32, posterior[B,n] fp32,
 iterations[B] int32)``; ``early_stop=False`` keyword; ``schedule="layered"`` (keyword only) runs the layered schedule
 (ldpc_decoder.py module docstring: beta and the offset form's check-side alpha are used, the variable-side alpha of the
-normalised form is not; no gradient path -- ``forward`` with autograd on and ``joint_posterior_loss`` raise
-NotImplementedError).  With autograd enabled and parameters (or the
+normalised form is not; ``forward`` with autograd on raises NotImplementedError, and so does ``joint_posterior_loss``
+unless ``layered_gradient="posterior_local"`` -- constructor argument, or keyword of ``joint_posterior_loss`` -- asks for the
+layered posterior-local gradient of include/ldpc_hip.h, ldpc_train_joint_layered).  With autograd enabled and parameters (or the
 LLRs) requiring grad, the returned posterior carries a grad_fn back to beta / alpha (and the LLRs) exactly as
 the reference's chain of torch operations does; the derivative is computed by the HIP backward sweeps behind
 ``torch.ops.ldpc.minsum_decode_train`` (torch_ops.py, autograd_bridge.py).  Under ``torch.no_grad()`` the
@@ -48,7 +49,8 @@ class _DegreeSharedDecoder(nn.Module):
     _alpha_default = 1.0
     _alpha_is_oms = False          # True: alpha is the check-side offset of the offset form (engine slot oms_alpha)
 
-    schedule = "flooding"          # "layered": the layered schedule (ldpc_decoder.py module docstring); no gradient path
+    schedule = "flooding"          # "layered": the layered schedule (ldpc_decoder.py module docstring)
+    layered_gradient = None        # "posterior_local": joint_posterior_loss of a layered decoder trains with that gradient
 
     def _init_sharing(self, code: LDPCCode, weight_sharing_type: int, max_iterations: int, strict=True):
         self.code = code
@@ -134,7 +136,8 @@ class _DegreeSharedDecoder(nn.Module):
     def _refuse_layered_grad(self, what: str):
         if self.schedule == "layered":
             raise NotImplementedError(f"{type(self).__name__}(schedule=\"layered\") has no gradient path: {what} exists "
-                                      "for the flooding schedule only")
+                                      "for the flooding schedule only (joint_posterior_loss trains a layered decoder "
+                                      "with layered_gradient=\"posterior_local\")")
 
     # ---- I/O ------------------------------------------------------------------------
     def _decode(self, llr: torch.Tensor, early_stop: bool, device=None):
@@ -168,7 +171,7 @@ class _DegreeSharedDecoder(nn.Module):
         return bits.to(out_dev), post.to(out_dev), iters.to(out_dev)
 
     def joint_posterior_loss(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
-                             iteration_weights: Optional[torch.Tensor] = None, device=None):
+                             iteration_weights: Optional[torch.Tensor] = None, device=None, *, layered_gradient=None):
         """Posterior joint training (the paper's training loss): decode ``llr`` ``[n]`` / ``[B, n]`` for exactly
         ``max_iterations`` iterations and take the loss on every iteration's posterior,
         ``loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets)`` (targets in [0, 1], default all zero = the
@@ -176,16 +179,22 @@ class _DegreeSharedDecoder(nn.Module):
         parameter the posterior-local gradient: iteration t's loss reaches beta_t (offset form: alpha_t), alpha_t-1 and
         the LLRs, nothing earlier (include/ldpc_hip.h ldpc_train_joint).  Keeps no per-iteration history, so the
         memory does not grow with T.
+        ``schedule="layered"``: refused (NotImplementedError) unless ``layered_gradient`` (default: the constructor's) is
+        ``"posterior_local"`` -- iteration t's loss then reaches beta_t (offset form: alpha_t) and the LLRs through the
+        check update that wrote each message, the variable's other messages held constant (ldpc_train_joint_layered);
+        the variable-side alpha of the normalised form is not used by the schedule and gets a zero gradient.
         -> (loss 0-d, loss_per_iteration [T], bits int32, posterior of the last iteration)"""
         import autograd_bridge as ab
-        self._refuse_layered_grad("joint_posterior_loss")
+        how = ab.check_layered_gradient(self.layered_gradient if layered_gradient is None else layered_gradient, self.schedule)
+        if how is None:
+            self._refuse_layered_grad("joint_posterior_loss")
         if not isinstance(llr, torch.Tensor):
             raise TypeError("llr must be a torch.Tensor")
         ab.check_joint_args(self.code.n, int(self.max_iterations), llr, targets, iteration_weights)
         eng = self._get_engine(llr.device if llr.is_cuda else device)
         bt, at = self._sharing_layout().tables_torch(self.beta_weights, self.alpha_weights, int(self.max_iterations),
                                                      self._beta_default, self._alpha_default)
-        return ab.joint_loss(bt, at, eng, llr, targets, iteration_weights, self._alpha_is_oms)
+        return ab.joint_loss(bt, at, eng, llr, targets, iteration_weights, self._alpha_is_oms, layered=how is not None)
 
 
 class Neural2DMinSumDecoder(_DegreeSharedDecoder):
@@ -200,9 +209,11 @@ class Neural2DMinSumDecoder(_DegreeSharedDecoder):
     """
 
     def __init__(self, code: LDPCCode, weight_sharing_type: int = 2, max_iterations: int = 50, *,
-                 schedule: str = "flooding"):
+                 schedule: str = "flooding", layered_gradient=None):
+        import autograd_bridge as ab
         super().__init__()
         self.schedule = check_schedule(schedule)
+        self.layered_gradient = ab.check_layered_gradient(layered_gradient, self.schedule)
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized N-2D-NMS decoder (Type {weight_sharing_type}) with "
                     f"{len(self.beta_weights)} beta weights and {len(self.alpha_weights)} alpha weights")
@@ -243,9 +254,11 @@ class Neural2DOffsetMinSumDecoder(_DegreeSharedDecoder):
     _alpha_is_oms = True
 
     def __init__(self, code: LDPCCode, weight_sharing_type: int = 2, max_iterations: int = 50, *,
-                 schedule: str = "flooding"):
+                 schedule: str = "flooding", layered_gradient=None):
+        import autograd_bridge as ab
         super().__init__()
         self.schedule = check_schedule(schedule)
+        self.layered_gradient = ab.check_layered_gradient(layered_gradient, self.schedule)
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized N-2D-OMS decoder (Type {weight_sharing_type}) with "
                     f"{len(self.beta_weights)} beta weights and {len(self.alpha_weights)} alpha weights")

@@ -13,8 +13,9 @@ Reference behaviour mirrored (file:line in /root/reference):
   analyze_weight_patterns(decoder, code)                   neural_minsum_decoder.py:288-349
 
 Extensions as everywhere: ``[B, n]`` batches, ``early_stop=False``; keyword-only ``schedule="layered"`` runs the layered
-schedule with the per-edge weights (ldpc_decoder.py module docstring; no gradient path: ``forward`` with autograd on and
-``joint_posterior_loss`` raise NotImplementedError).
+schedule with the per-edge weights (ldpc_decoder.py module docstring; ``forward`` with autograd on raises
+NotImplementedError, and so does ``joint_posterior_loss`` unless ``layered_gradient="posterior_local"`` -- constructor
+argument, or keyword of ``joint_posterior_loss`` -- asks for the layered posterior-local gradient of include/ldpc_hip.h).
 """
 
 from __future__ import annotations
@@ -35,12 +36,14 @@ class _EdgeWeightDecoder(nn.Module):
     """one beta per (iteration, edge); table column = CSR edge id"""
 
     _c2v_form = "nms"
-    schedule = "flooding"          # "layered": the layered schedule (ldpc_decoder.py module docstring); no gradient path
+    schedule = "flooding"          # "layered": the layered schedule (ldpc_decoder.py module docstring)
+    layered_gradient = None        # "posterior_local": joint_posterior_loss of a layered decoder trains with that gradient
 
     def _refuse_layered_grad(self, what: str):
         if self.schedule == "layered":
             raise NotImplementedError(f"{type(self).__name__}(schedule=\"layered\") has no gradient path: {what} exists "
-                                      "for the flooding schedule only")
+                                      "for the flooding schedule only (joint_posterior_loss trains a layered decoder "
+                                      "with layered_gradient=\"posterior_local\")")
 
     def _init_edges(self, code: LDPCCode, max_iterations: int, offset: float):
         self.code = code
@@ -132,12 +135,15 @@ class _EdgeWeightDecoder(nn.Module):
         return res.bits.to(out_dev), res.posterior.to(out_dev), res.iterations.to(out_dev)
 
     def joint_posterior_loss(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
-                             iteration_weights: Optional[torch.Tensor] = None, device=None):
+                             iteration_weights: Optional[torch.Tensor] = None, device=None, *, layered_gradient=None):
         """Posterior joint training with the per-edge weights: the fixed-T decode with
         ``loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets)`` and its posterior-local gradient, as
-        ``Neural2DMinSumDecoder.joint_posterior_loss`` -> (loss, loss_per_iteration [T], bits, posterior)"""
+        ``Neural2DMinSumDecoder.joint_posterior_loss`` (``layered_gradient`` likewise)
+        -> (loss, loss_per_iteration [T], bits, posterior)"""
         import autograd_bridge as ab
-        self._refuse_layered_grad("joint_posterior_loss")
+        how = ab.check_layered_gradient(self.layered_gradient if layered_gradient is None else layered_gradient, self.schedule)
+        if how is None:
+            self._refuse_layered_grad("joint_posterior_loss")
         if not isinstance(llr, torch.Tensor):
             raise TypeError("llr must be a torch.Tensor")
         g, T = self.code.tanner_graph(), int(self.max_iterations)
@@ -148,7 +154,7 @@ class _EdgeWeightDecoder(nn.Module):
         where = [(t, e) for t in range(T) for e in range(g.E)]
         bt = ab.table_from_params(params, where, (max(T, 1), max(g.E, 1)), 0.0)
         at = torch.ones((max(T, 1), 1), dtype=torch.float32)
-        return ab.joint_loss(bt, at, eng, llr, targets, iteration_weights, False)
+        return ab.joint_loss(bt, at, eng, llr, targets, iteration_weights, False, layered=how is not None)
 
 
 class NeuralMinSumDecoder(_EdgeWeightDecoder):
@@ -156,9 +162,11 @@ class NeuralMinSumDecoder(_EdgeWeightDecoder):
 
     _c2v_form = "nms"
 
-    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding"):
+    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding", layered_gradient=None):
+        import autograd_bridge as ab
         super().__init__()
         self.schedule = check_schedule(schedule)
+        self.layered_gradient = ab.check_layered_gradient(layered_gradient, self.schedule)
         self._init_edges(code, max_iterations, offset=0.7)
         num_edges = int(code.tanner_graph().E)
         logger.info(f"Initialized Neural MinSum decoder with {len(self.beta_weights)} parameters")
@@ -170,9 +178,11 @@ class LdpcDecoderNeuralMinSumDecoder(_EdgeWeightDecoder):
     normalised min-sum forward, but weights initialised ``randn*0.1`` WITHOUT the +0.7 and an (empty)
     ``alpha_weights`` ParameterDict.  Exported as ``ldpc_decoder.NeuralMinSumDecoder``."""
 
-    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding"):
+    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding", layered_gradient=None):
+        import autograd_bridge as ab
         super().__init__()
         self.schedule = check_schedule(schedule)
+        self.layered_gradient = ab.check_layered_gradient(layered_gradient, self.schedule)
         self._init_edges(code, max_iterations, offset=0.0)
         self.alpha_weights = nn.ParameterDict()
         logger.info(f"Initialized Neural MinSum decoder with {len(self.beta_weights)} parameters")
@@ -186,9 +196,11 @@ class NeuralOffsetMinSumDecoder(_EdgeWeightDecoder):
 
     _c2v_form = "oms"
 
-    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding"):
+    def __init__(self, code: LDPCCode, max_iterations: int = 50, *, schedule: str = "flooding", layered_gradient=None):
+        import autograd_bridge as ab
         super().__init__()
         self.schedule = check_schedule(schedule)
+        self.layered_gradient = ab.check_layered_gradient(layered_gradient, self.schedule)
         self._init_edges(code, max_iterations, offset=0.0)
         logger.info(f"Initialized Neural Offset MinSum decoder with {len(self.beta_weights)} parameters")
 

@@ -37,6 +37,12 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
      bit for bit; the gradients treat the quantiser with the straight-through rule -- d c2v/d m := 1 where the code the
      forward wrote lies below the top level (the dead zone included), 0 where it saturated, m = beta * sign product * min.
 
+  ldpc::minsum_layered_joint_loss(... the arguments of minsum_joint_loss ...) -> the same seven outputs
+     the same for a min-sum decoder under ``schedule="layered"`` (ldpc_train_joint_layered): the forward is its fixed-T layered
+     decode bit for bit; the gradients are layered posterior-local -- iteration t's loss reaches beta_t, the check-side offset
+     alpha_t and the LLRs through the check update that wrote each message, the variable's other messages held constant.  The
+     variable-side alpha of the normalised form is not used by the schedule: its gradient is all zero.
+
 ``engine`` is an integer handle of a live ``engine.DecodeEngine`` (``engine_handle(eng)``): operator schemas
 carry tensors and scalars, and the native decoder handle is neither.  There is no CPU implementation: the
 ops exist for ROCm tensors only and fail loudly otherwise (no fallback).
@@ -212,18 +218,12 @@ minsum_decode_train.register_autograd(_train_backward, setup_context=_train_setu
 
 
 # ------------------------------------------------------------------------------------------ posterior joint training
-@torch.library.custom_op("ldpc::minsum_joint_loss", mutates_args=())
-def minsum_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, iteration_weights: Tensor,
-                      engine: int, alpha_is_oms: bool, want_grads: bool = True,
-                      want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """fixed-T decode with the loss on every iteration's posterior (ldpc_train_joint):
-    loss = sum_t w_t J_t, loss_per_iter = J_t, posterior / bits of the last iteration, and the gradients of `loss`
-    the autograd formula scales: d loss/d beta [T, Sb], d loss/d alpha [T, Sa] (alpha_is_oms: the check-side offset)
-    -- empty when not want_grads -- and d loss/d llr [B, n] (empty when not want_grad_llr)"""
+def _minsum_joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, layered):
     eng = _engine(engine)
     restore = _with_tables(eng, _np_table(beta), _np_table(alpha), alpha_is_oms)
     try:
-        r = eng.train_joint(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
+        run = eng.train_joint_layered if layered else eng.train_joint
+        r = run(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
                             want_grads=want_grads, want_grad_llr=want_grad_llr)
     finally:
         restore()
@@ -239,6 +239,28 @@ def minsum_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alph
     return r["loss"], r["loss_per_iter"], r["posterior"], r["bits"], gb, ga, gl
 
 
+@torch.library.custom_op("ldpc::minsum_joint_loss", mutates_args=())
+def minsum_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, iteration_weights: Tensor,
+                      engine: int, alpha_is_oms: bool, want_grads: bool = True,
+                      want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """fixed-T decode with the loss on every iteration's posterior (ldpc_train_joint):
+    loss = sum_t w_t J_t, loss_per_iter = J_t, posterior / bits of the last iteration, and the gradients of `loss`
+    the autograd formula scales: d loss/d beta [T, Sb], d loss/d alpha [T, Sa] (alpha_is_oms: the check-side offset)
+    -- empty when not want_grads -- and d loss/d llr [B, n] (empty when not want_grad_llr)"""
+    return _minsum_joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, False)
+
+
+@torch.library.custom_op("ldpc::minsum_layered_joint_loss", mutates_args=())
+def minsum_layered_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, iteration_weights: Tensor,
+                              engine: int, alpha_is_oms: bool, want_grads: bool = True,
+                              want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """minsum_joint_loss of a decoder under the layered schedule (ldpc_train_joint_layered): the fixed-T layered decode, its
+    per-iteration loss, and the layered posterior-local gradients d loss/d beta [T, Sb], d loss/d alpha [T, Sa]
+    (alpha_is_oms: the check-side offset; otherwise the unused variable-side table, all zero), d loss/d llr [B, n]"""
+    return _minsum_joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, True)
+
+
+@minsum_layered_joint_loss.register_fake
 @minsum_joint_loss.register_fake
 def _(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads=True, want_grad_llr=False):
     B, n = llr.shape
@@ -275,6 +297,7 @@ def _joint_backward(ctx, g_loss, *_unused):
 
 
 minsum_joint_loss.register_autograd(_joint_backward, setup_context=_joint_setup)
+minsum_layered_joint_loss.register_autograd(_joint_backward, setup_context=_joint_setup)
 
 
 @torch.library.custom_op("ldpc::rcq_joint_loss", mutates_args=())

@@ -76,8 +76,9 @@ enum {
  * arg-min, ties keep min2 == min1, sign(0) = 0), r = (beta * min_others) * sign_others (NMS) or sign_others * (relu(min_others - beta)
  * - oms_alpha) (OMS), P = u + r, R = r; the variable-side alpha is not used, the check-side oms_alpha is; LLRs must be finite.  Two
  * kernels with identical results: LDS-resident (posteriors and a 16-byte record per check -- min1, min2, a sign and an arg-min bit per
- * edge -- from which each lane recomputes R; same qualification as above) and streaming (R as fp32 per edge in the workspace).  No
- * gradient path: ldpc_decode_saving, ldpc_backward and ldpc_train_joint return LDPC_ERR_UNSUPPORTED.  LAYERED_REF with these forms is
+ * edge -- from which each lane recomputes R; same qualification as above) and streaming (R as fp32 per edge in the workspace).
+ * Gradients: ldpc_train_joint_layered (posterior joint training with a posterior-local gradient, below) and nothing else --
+ * ldpc_decode_saving, ldpc_backward and ldpc_train_joint return LDPC_ERR_UNSUPPORTED.  LAYERED_REF with these forms is
  * unsupported (the reference has no such path), as is a float64 layered decoder. */
 enum { LDPC_SCHED_FLOODING = 0, LDPC_SCHED_LAYERED_REF = 1, LDPC_SCHED_LAYERED = 2 };
 
@@ -252,6 +253,38 @@ int ldpc_train_joint_ste(const ldpc_decoder *d, const void *llr, const void *tar
                          const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
                          void *grad_beta, void *grad_alpha, void *grad_llr,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- posterior joint training of the layered min-sum decoders -----------------------------------
+ * ldpc_train_joint for the fp32 LDPC_SCHED_LAYERED decoders of LDPC_C2V_NMS / LDPC_C2V_OMS.  LDPC_ERR_UNSUPPORTED for every
+ * other decoder, with a message naming the entry point to take: flooding min-sum -> ldpc_train_joint, flooding RCQ ->
+ * ldpc_train_joint_ste; the layered RCQ decoders (LAYERED_REF, LAYERED) and float64 have none.  ldpc_train_joint itself keeps
+ * refusing layered decoders.  Same outputs, same empty-batch / NULL-output / alignment / T < 1 / no-edges rules; scratch
+ * ldpc_train_joint_layered_workspace_bytes (256-byte aligned, independent of T).  An extension like the schedule: nothing in
+ * the reference executes it, the yardstick is a CPU restatement.
+ *   Forward : the decoder's own fixed-T layered decode, no early stop, one iteration per kernel launch with posteriors and
+ *             messages kept in the scratch -- bits and posterior equal ldpc_decode(early_stop = 0) bit for bit, and the
+ *             posterior P_t after the last check of iteration t equals ldpc_decode_capped(max_iterations = t + 1,
+ *             early_stop = 0) bit for bit.
+ *   Loss    : J_t = mean over b, j of BCEWithLogits(-P_t[b][j], targets[b][j]),  J = sum_t w_t * J_t, with the seed
+ *             g_t = w_t * (y - sigmoid(-P_t)) / (B n), as ldpc_train_joint.
+ *   Gradient (layered posterior-local): when check i is processed in iteration t each of its edges e = (i, v) has
+ *             u_e = P_v - R_e.  Write u_e = llr_v + x_e: x_e, the sum of the variable's other messages (new and old), is a
+ *             constant, and the posterior is taken as P_t[v] = llr_v + sum over the edges e at v of r_t,e.  So J_t reaches
+ *             beta_t, the offset form's oms_alpha_t and the LLRs -- nothing earlier, and nothing through another check of
+ *             the same iteration.  The derivatives of r are those of the flooding check update with v2c_t := u:
+ *                 NMS  d r_e/d beta = raw_e * prod_e                d r_e/d raw_e = beta * prod_e
+ *                 OMS  d r_e/d beta = -prod_e * [raw_e - beta > 0]  d r_e/d a = -prod_e  d r_e/d raw_e = prod_e * [raw_e - beta > 0]
+ *             prod_e = 0 when another edge of the check has u == 0 exactly (a degree-1 check: prod = 1, min2 = min1);
+ *             d|x| = sgn(x), sgn(0) = 0; the minimum's gradient goes to the first arg-min edge, the second minimum's is
+ *             split evenly over the edges tied for it.
+ *                 d J/d llr_v = sum_t ( g_t[v] + sum over the edges e at v of d J_t/d u_e )
+ *             The variable-side alpha is not used by the schedule: grad_alpha, when given, is zero-filled [T][n_alpha_slots].
+ * Deterministic: no atomics. */
+size_t ldpc_train_joint_layered_workspace_bytes(const ldpc_decoder *d, int64_t batch);
+int ldpc_train_joint_layered(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                             const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                             void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
