@@ -1,6 +1,8 @@
 """
 ctypes binding of the C ABI in include/ldpc_hip.h (libldpc_hip.so, built from
-csrc/ by build_native()).
+csrc/ by build_native(): one compiled unit, ldpc_hip.hip, which includes the kernel
+files and the host side of the gradient path, ldpc_train_host.hip -- every file of
+it is named in SOURCES, whose content the library's embedded hash covers).
 
 There is NO CPU fallback: when the library is missing or no HIP device is
 usable every decode raises ``NativeEngineError``.  The host classes only add
@@ -40,7 +42,7 @@ class NativeEngineError(RuntimeError):
 
 # the one compiled unit first, then everything it includes
 SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
-           "ldpc_resident_geom.h", "ldpc_plan.h")
+           "ldpc_train_host.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
 
 
 def _source_files():

@@ -152,14 +152,10 @@ def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr:
     w = (torch.full((T,), 1.0 / T, dtype=torch.float32) if iteration_weights is None
          else torch.as_tensor(iteration_weights).detach().to(torch.float32))
     w = w.to(engine.device).contiguous()
-    if quantised:
-        loss, lpi, post, bits, _gb, _ga, _gl = torch.ops.ldpc.rcq_joint_loss(
-            xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(want_grads), bool(want_llr))
-    else:
-        op = torch.ops.ldpc.minsum_layered_joint_loss if layered else torch.ops.ldpc.minsum_joint_loss
-        loss, lpi, post, bits, _gb, _ga, _gl = op(
-            xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine), bool(alpha_is_oms),
-            bool(want_grads), bool(want_llr))
+    op, form = ((torch.ops.ldpc.rcq_joint_loss, ()) if quantised else           # the quantised operator has no alpha_is_oms
+                (torch.ops.ldpc.minsum_layered_joint_loss if layered else torch.ops.ldpc.minsum_joint_loss, (bool(alpha_is_oms),)))
+    loss, lpi, post, bits, _gb, _ga, _gl = op(xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine),
+                                              *form, bool(want_grads), bool(want_llr))
     out_dev = llr.device
     if single:
         bits, post = bits[0], post[0]

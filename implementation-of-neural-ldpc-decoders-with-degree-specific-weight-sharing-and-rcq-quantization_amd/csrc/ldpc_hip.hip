@@ -2,7 +2,9 @@
 //
 // Host side only: handle lifetime, table upload, workspace carving and the launch
 // sequence of one decode.  Nothing here allocates or synchronises inside ldpc_decode
-// (graph-capturable); all work goes to the caller's stream.
+// (graph-capturable); all work goes to the caller's stream.  The host side of the gradient
+// path (ldpc_decode_saving, ldpc_backward, ldpc_train_joint*) is ldpc_train_host.hip,
+// included below the decode entry points: still this one compiled unit.
 #include "ldpc_kernels.hip"
 #include "ldpc_resident.hip"
 #include "ldpc_train.hip"
@@ -1645,576 +1647,10 @@ int ldpc_decode_capped(const ldpc_decoder *d, const void *llr, int64_t batch, in
 
 }  // extern "C"
 
-// ---- gradient (training) path: ldpc_train.hip ----------------------------------------------------------------
-namespace {
-int train_supported(const ldpc_decoder *d)
-{
-    if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
-    if (d->schedule != LDPC_SCHED_FLOODING && d->form != LDPC_C2V_RCQ)
-        return fail(LDPC_ERR_UNSUPPORTED, "the layered schedule (LDPC_SCHED_LAYERED) has no gradient path: gradients exist for "
-                                          "the fp32 normalised / offset min-sum decoders under LDPC_SCHED_FLOODING");
-    if (d->dtype != LDPC_F32 || d->form == LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_FLOODING)
-        return fail(LDPC_ERR_UNSUPPORTED, "gradients exist for the fp32 normalised / offset min-sum flooding decoders "
-                                          "(the reference's RCQ quantiser passes no gradient)");
-    return LDPC_OK;
-}
-
-// ldpc_train_joint_ste: the quantised decoder, differentiated with the straight-through rule
-int ste_supported(const ldpc_decoder *d)
-{
-    if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
-    if (d->dtype != LDPC_F32 || d->form != LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_FLOODING)
-        return fail(LDPC_ERR_UNSUPPORTED, "the straight-through joint loss exists for the fp32 RCQ flooding decoders "
-                                          "(ldpc_train_joint has the min-sum forms; the layered schedules have no gradient path)");
-    return LDPC_OK;
-}
-
-struct BackwardWs {
-    int vec = 0, tiles = 0;
-    float *llrT = nullptr, *gpostT = nullptr, *gv2c = nullptr, *gc2v = nullptr, *gbeta = nullptr, *galpha = nullptr;
-    float *goa = nullptr;             // offset form: per-edge partials of the check-side alpha
-    float *gllrT = nullptr;           // accumulator of d loss/d llr (starts as a copy of gpostT)
-    size_t part_bytes = 0, total = 0;
-};
-BackwardWs carve_backward(const ldpc_decoder *d, int64_t batch, void *base)
-{
-    BackwardWs w;
-    w.vec = pick_vec(d, batch);
-    const int W = 64 * w.vec;
-    w.tiles = (int)std::max<int64_t>((batch + W - 1) / W, 1);
-    const size_t n = d->g->n, E = std::max(d->g->E, 1), tw = (size_t)w.tiles * W, T = std::max(d->T, 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_llr = take(tw * n * 4), o_gp = take(tw * n * 4), o_gv = take(tw * E * 4), o_gc = take(tw * E * 4);
-    const size_t o_gb = take(T * w.tiles * E * 4), o_ga = take(T * w.tiles * n * 4);
-    const size_t o_goa = take(d->form == LDPC_C2V_OMS ? T * w.tiles * E * 4 : 0);
-    w.part_bytes = off - o_gb;
-    const size_t o_gl = take(tw * n * 4);
-    w.total = off;
-    if (base) {
-        char *b = (char *)base;
-        w.llrT = (float *)(b + o_llr); w.gpostT = (float *)(b + o_gp); w.gv2c = (float *)(b + o_gv);
-        w.gc2v = (float *)(b + o_gc); w.gbeta = (float *)(b + o_gb); w.galpha = (float *)(b + o_ga);
-        w.goa = (float *)(b + o_goa);
-        w.gllrT = (float *)(b + o_gl);
-    }
-    return w;
-}
-
-template <int VEC>
-int backward_impl(const ldpc_decoder *d, const char *saved, const float *llr, int64_t batch, const int32_t *iterations,
-                  const float *grad_posterior, float *grad_beta, float *grad_alpha, float *grad_oms_alpha,
-                  float *grad_llr, const BackwardWs &w, hipStream_t s)
-{
-    constexpr int W = 64 * VEC;
-    constexpr int JT = transpose_vars<float>();
-    const GraphDev g = d->g->dev();
-    const int T = d->T, vc = (g.n + JT - 1) / JT;
-    const SavedLayout sl = saved_layout(d, w.tiles, W);
-    const dim3 tgrid((unsigned)((size_t)w.tiles * VEC * vc)), blk(kBlock);
-    hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, w.llrT, (long long)batch, g.n, vc);
-    hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, grad_posterior, w.gpostT, (long long)batch, g.n, vc);
-    HIP_TRY(hipMemsetAsync(w.gbeta, 0, w.part_bytes, s));
-    if (grad_llr)
-        HIP_TRY(hipMemcpyAsync(w.gllrT, w.gpostT, (size_t)w.tiles * W * g.n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const int cb = (g.m + kWavesPerBlock - 1) / kWavesPerBlock, vb = (g.n + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int vbb = (g.n + kWavesPerBlock * kVnbVarsPerWave - 1) / (kWavesPerBlock * kVnbVarsPerWave);   // vn_backward: several variables per wave
-    const dim3 cgrid((unsigned)((size_t)w.tiles * cb)), vgrid((unsigned)((size_t)w.tiles * vb)), vbgrid((unsigned)((size_t)w.tiles * vbb));
-    const size_t epart = (size_t)w.tiles * g.E, vpart = (size_t)w.tiles * g.n;
-    for (int t = T - 1; t >= 0; --t) {
-        const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
-        // d loss/d c2v_t is in w.gc2v (written by the variable pass of step t+1; unread at t == T-1)
-        const bool oms = d->form == LDPC_C2V_OMS;
-        float *goa = (oms && d->oms_alpha) ? w.goa + (size_t)t * epart : nullptr;
-#define LDPC_CNB(FIRST_, FORM_, SRC_, OUT_)                                                                            \
-    hipLaunchKernelGGL((cn_backward<VEC, FIRST_, FORM_>), cgrid, blk, 0, s, g, (const float *)(SRC_),                  \
-                       (const float *)w.gc2v, (const float *)w.gpostT, iterations, (long long)batch, t, beta_row,     \
-                       (const int *)d->beta_slot, (float *)(OUT_), w.gbeta + (size_t)t * epart, goa, cb)
-        float *gv0 = grad_llr ? w.gv2c : nullptr;        // d loss/d v2c_0 is needed only for the input gradient
-        if (t == 0) {
-            if (oms) LDPC_CNB(true, FORM_OMS, w.llrT, gv0); else LDPC_CNB(true, FORM_NMS, w.llrT, gv0);
-        } else {
-            if (oms) LDPC_CNB(false, FORM_OMS, saved + sl.v2c_off(t), w.gv2c);
-            else LDPC_CNB(false, FORM_NMS, saved + sl.v2c_off(t), w.gv2c);
-            const float *alpha_row = (const float *)d->alpha + (size_t)(t - 1) * d->n_alpha;
-            hipLaunchKernelGGL((vn_backward<VEC>), vbgrid, blk, 0, s, g, (const float *)(saved + sl.c2v_off(t - 1)),
-                               (const float *)w.gv2c, iterations, (long long)batch, t, alpha_row, (const int *)d->alpha_slot,
-                               w.gc2v, w.galpha + (size_t)(t - 1) * vpart, vbb);
-        }
-        if (grad_llr)                                     // g_llr += sum over the edges of every variable of g_v2c_t
-            hipLaunchKernelGGL((llr_backward_accumulate<VEC>), vgrid, blk, 0, s, g, (const float *)w.gv2c, w.gllrT, vb);
-#undef LDPC_CNB
-    }
-    HIP_TRY(hipGetLastError());
-    if (grad_llr)
-        hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.gllrT, (const uint64_t *)nullptr, grad_llr,
-                           (int *)nullptr, (long long)batch, g.n, vc);     // [tile][n][W] -> [batch][n], padding rows dropped
-    // fixed-order reductions (one wave per slot and iteration): every table entry is written, no memset, no atomics
-    if (grad_beta)
-        hipLaunchKernelGGL(reduce_table_grads<float>, dim3((unsigned)d->n_beta, (unsigned)T), dim3(kWave), 0, s,
-                           (const float *)w.gbeta, w.tiles, g.E, (const int *)d->beta_inv_ptr,
-                           (const int *)d->beta_inv_items, d->n_beta, grad_beta);
-    if (grad_oms_alpha && d->form == LDPC_C2V_OMS && d->oms_alpha)
-        hipLaunchKernelGGL(reduce_table_grads<float>, dim3((unsigned)d->n_oms_alpha, (unsigned)T), dim3(kWave), 0, s,
-                           (const float *)w.goa, w.tiles, g.E, (const int *)d->oms_inv_ptr,
-                           (const int *)d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha);
-    if (grad_alpha)
-        hipLaunchKernelGGL(reduce_table_grads<float>, dim3((unsigned)d->n_alpha, (unsigned)T), dim3(kWave), 0, s,
-                           (const float *)w.galpha, w.tiles, g.n, (const int *)d->alpha_inv_ptr,
-                           (const int *)d->alpha_inv_items, d->n_alpha, grad_alpha);
-    HIP_TRY(hipGetLastError());
-    return LDPC_OK;
-}
-
-// ---- posterior joint training (ldpc_train_joint) ------------------------------------------------------------
-// The fixed-T decode with the loss of every iteration's posterior and its posterior-local gradient formed while that
-// iteration is decoded: nothing of earlier iterations is kept but c2v_t-1 (the alpha_t-1 partial reads its
-// leave-one-out sums), so the scratch is a constant number of rows per codeword whatever T is --
-// E rows: v2c_t / v2c_t+1 and c2v_t-1 / c2v_t (ping-pong), d J/d v2c_t;  n rows: llr, posterior (then g_l in place),
-// targets, d J/d llr;  plus per-tile partials of the table gradients and of the loss.
-// ldpc_train_joint_ste (RCQ, `codes`): the same loop on the two-sweep RCQ form -- the two C2V buffers hold 1-byte codes.
-struct JointWs {
-    Workspace fw;                            // forward view: llrT, postT, bitsT (v2c / c2v chosen per iteration)
-    char *v2c[2] = {nullptr, nullptr}, *c2v[2] = {nullptr, nullptr};
-    float *yT = nullptr, *gv2c = nullptr, *gllrT = nullptr, *gbeta = nullptr, *goa = nullptr, *galpha = nullptr;
-    double *loss_part = nullptr, *item_sum = nullptr;
-    size_t total = 0;
-};
-JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, bool codes = false)
-{
-    JointWs w;
-    w.fw.vec = pick_vec(d, batch);
-    const int W = 64 * w.fw.vec;
-    const int tiles = (int)std::max<int64_t>((batch + W - 1) / W, 1);
-    w.fw.tiles = tiles;
-    const size_t n = d->g->n, E = std::max(d->g->E, 1), tw = (size_t)tiles * W;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_llr = take(tw * n * 4), o_post = take(tw * n * 4), o_y = take(tw * n * 4), o_gl = take(tw * n * 4);
-    const size_t cs = codes ? 1 : 4;
-    const size_t o_v0 = take(tw * E * 4), o_v1 = take(tw * E * 4), o_c0 = take(tw * E * cs), o_c1 = take(tw * E * cs);
-    const size_t o_gv = take(tw * E * 4);
-    const size_t o_bits = take((size_t)tiles * n * w.fw.vec * sizeof(uint64_t));
-    const size_t o_gb = take((size_t)tiles * E * 4), o_goa = take(d->form == LDPC_C2V_OMS ? (size_t)tiles * E * 4 : 0);
-    const size_t vb = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-    const size_t o_ga = take((size_t)tiles * n * 4), o_lp = take((size_t)tiles * vb * sizeof(double));
-    const size_t o_is = take(std::max(n, E) * sizeof(double));
-    w.total = off;
-    if (base) {
-        char *b = (char *)base;
-        w.fw.llrT = b + o_llr; w.fw.postT = b + o_post; w.fw.bitsT = (uint64_t *)(b + o_bits);
-        w.v2c[0] = b + o_v0; w.v2c[1] = b + o_v1; w.c2v[0] = b + o_c0; w.c2v[1] = b + o_c1;
-        w.yT = (float *)(b + o_y); w.gllrT = (float *)(b + o_gl); w.gv2c = (float *)(b + o_gv);
-        w.gbeta = (float *)(b + o_gb); w.goa = (float *)(b + o_goa); w.galpha = (float *)(b + o_ga);
-        w.loss_part = (double *)(b + o_lp); w.item_sum = (double *)(b + o_is);
-    }
-    return w;
-}
-
-template <int VEC>
-int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, int64_t batch, const float *weights,
-               float *loss_per_iter, int32_t *bits, float *posterior, float *grad_beta, float *grad_alpha,
-               float *grad_oms_alpha, float *grad_llr, const JointWs &w, hipStream_t s)
-{
-    constexpr int W = 64 * VEC;
-    constexpr int JT = transpose_vars<float>();
-    const GraphDev g = d->g->dev();
-    const int T = d->T, tiles = w.fw.tiles, vc = (g.n + JT - 1) / JT;
-    const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
-    const bool oms = d->form == LDPC_C2V_OMS, rcq = d->form == LDPC_C2V_RCQ;
-    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
-    const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
-    hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, (float *)w.fw.llrT, (long long)batch, g.n, vc);
-    if (targets)
-        hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, targets, w.yT, (long long)batch, g.n, vc);
-    // rows no step writes: alpha_T-1 (and every alpha row of the offset forms, whose variable update has no parameter)
-    if (grad_alpha) {
-        const size_t row = (size_t)d->n_alpha * 4;
-        if (oms) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)T * row, s));
-        else HIP_TRY(hipMemsetAsync((char *)grad_alpha + (size_t)(T - 1) * row, 0, row, s));
-    }
-    if (grad_oms_alpha && !oa_grad && d->n_oms_alpha > 0)
-        HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)T * d->n_oms_alpha * 4, s));
-    if (grad_llr) HIP_TRY(hipMemsetAsync(w.gllrT, 0, (size_t)tiles * W * g.n * sizeof(float), s));
-    const int cb = (g.m + kWavesPerBlock - 1) / kWavesPerBlock, vb = (g.n + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int vbb = (g.n + kWavesPerBlock * kVnbVarsPerWave - 1) / (kWavesPerBlock * kVnbVarsPerWave);
-    const dim3 cgrid((unsigned)((size_t)tiles * cb)), vgrid((unsigned)((size_t)tiles * vb)), vbgrid((unsigned)((size_t)tiles * vbb));
-    const double inv_bn = 1.0 / ((double)batch * (double)g.n);
-    float *postT = (float *)w.fw.postT;
-    // one iteration's partials [tile][item] -> its row of a gradient table: per-item sums over the tiles, then per slot
-    auto reduce_step = [&](const float *part, int count, const int *slot_ptr, const int *slot_items, int n_slots, float *row) {
-        hipLaunchKernelGGL(reduce_tiles, dim3((unsigned)((count + kBlock - 1) / kBlock)), blk, 0, s, part, tiles, count, w.item_sum);
-        hipLaunchKernelGGL(reduce_table_grads<double>, dim3((unsigned)n_slots), dim3(kWave), 0, s, (const double *)w.item_sum, 1,
-                           count, slot_ptr, slot_items, n_slots, row);
-    };
-    for (int t = 0; t < T; ++t) {
-        const bool last = t == T - 1;
-        // forward iteration t: the decode's own sweeps (fixed T, no stop latch); the variable sweep keeps l_t in postT
-        Workspace wc = w.fw, wv = w.fw;
-        wc.v2c = w.v2c[t & 1]; wc.c2v = w.c2v[t & 1];
-        wv.c2v = w.c2v[t & 1]; wv.v2c = w.v2c[(t + 1) & 1];
-        int rc = launch_cn<float, VEC>(d, wc, t, /*use_done=*/false, s);
-        if (rc) return rc;
-        rc = launch_vn<float, VEC>(d, wv, t, last, /*use_done=*/false, s, /*store_posterior=*/true, nullptr, /*keep_posterior=*/true);
-        if (rc) return rc;
-        if (last && (bits || posterior))
-            hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)postT, (const uint64_t *)w.fw.bitsT,
-                               posterior, bits, (long long)batch, g.n, vc);
-        // J_t, and g_l over postT
-        if (want)
-            hipLaunchKernelGGL((joint_loss_grad<VEC, true>), vgrid, blk, 0, s, g.n, postT, (const float *)(targets ? w.yT : nullptr),
-                               weights, t, (long long)batch, (float)inv_bn, grad_llr ? w.gllrT : nullptr, w.loss_part, vb);
-        else
-            hipLaunchKernelGGL((joint_loss_grad<VEC, false>), vgrid, blk, 0, s, g.n, postT, (const float *)(targets ? w.yT : nullptr),
-                               weights, t, (long long)batch, (float)inv_bn, (float *)nullptr, w.loss_part, vb);
-        hipLaunchKernelGGL(joint_loss_reduce, dim3(1), blk, 0, s, (const double *)w.loss_part, (long long)tiles * vb, inv_bn,
-                           loss_per_iter + t);
-        HIP_TRY(hipGetLastError());
-        if (!want) continue;
-        // posterior-local backward of iteration t: check side (beta_t, offset alpha_t, d J/d v2c_t), then the alpha_t-1
-        // partial of the normalised forms and the LLR gradient
-        const bool need_gv = grad_llr || (!oms && t >= 1 && grad_alpha);
-        const float *src = t == 0 ? (const float *)w.fw.llrT : (const float *)w.v2c[t & 1];
-        const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
-        float *gv_out = need_gv ? w.gv2c : nullptr;
-        float *goa = oa_grad ? w.goa : nullptr;
-#define LDPC_CNJ(FIRST_, FORM_)                                                                                        \
-    hipLaunchKernelGGL((cn_backward<VEC, FIRST_, FORM_, true>), cgrid, blk, 0, s, g, src, (const float *)nullptr,     \
-                       (const float *)postT, (const int *)nullptr, (long long)batch, t, beta_row, (const int *)d->beta_slot, \
-                       gv_out, w.gbeta, goa, cb, (const uint8_t *)(rcq ? w.c2v[t & 1] : nullptr), d->n_levels)
-        if (t == 0) { if (oms) LDPC_CNJ(true, FORM_OMS); else if (rcq) LDPC_CNJ(true, FORM_RCQ); else LDPC_CNJ(true, FORM_NMS); }
-        else { if (oms) LDPC_CNJ(false, FORM_OMS); else if (rcq) LDPC_CNJ(false, FORM_RCQ); else LDPC_CNJ(false, FORM_NMS); }
-#undef LDPC_CNJ
-        if (grad_beta) reduce_step(w.gbeta, g.E, d->beta_inv_ptr, d->beta_inv_items, d->n_beta, grad_beta + (size_t)t * d->n_beta);
-        if (oa_grad)
-            reduce_step(w.goa, g.E, d->oms_inv_ptr, d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha + (size_t)t * d->n_oms_alpha);
-        if (!oms && t >= 1 && grad_alpha) {
-            const float *alpha_row = (const float *)d->alpha + (size_t)(t - 1) * d->n_alpha;
-            if (rcq) {                                    // code rows of iteration t-1, reconstructed with ITS quantiser
-                const int lut_entries = 2 * d->n_levels;
-                hipLaunchKernelGGL((vn_backward<VEC, true, true>), vbgrid, blk, 0, s, g, (const void *)w.c2v[(t - 1) & 1],
-                                   (const float *)w.gv2c, (const int *)nullptr, (long long)batch, t, alpha_row,
-                                   (const int *)d->alpha_slot, (float *)nullptr, w.galpha, vbb,
-                                   (const float *)d->lut + (size_t)d->q_of_iter[t - 1] * lut_entries, lut_entries);
-            } else {
-                hipLaunchKernelGGL((vn_backward<VEC, true>), vbgrid, blk, 0, s, g, (const void *)w.c2v[(t - 1) & 1],
-                                   (const float *)w.gv2c, (const int *)nullptr, (long long)batch, t, alpha_row,
-                                   (const int *)d->alpha_slot, (float *)nullptr, w.galpha, vbb);
-            }
-            reduce_step(w.galpha, g.n, d->alpha_inv_ptr, d->alpha_inv_items, d->n_alpha, grad_alpha + (size_t)(t - 1) * d->n_alpha);
-        }
-        if (grad_llr)
-            hipLaunchKernelGGL((llr_backward_accumulate<VEC>), vgrid, blk, 0, s, g, (const float *)w.gv2c, w.gllrT, vb);
-        HIP_TRY(hipGetLastError());
-    }
-    if (grad_llr)
-        hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.gllrT, (const uint64_t *)nullptr, grad_llr,
-                           (int *)nullptr, (long long)batch, g.n, vc);
-    HIP_TRY(hipGetLastError());
-    return LDPC_OK;
-}
-
-// ---- posterior joint training of the layered min-sum decoders (ldpc_train_joint_layered) --------------------
-// joint_impl's loop on the layered schedule: layered_minsum_iter walks the checks once per launch on the running
-// posteriors and keeps u_e = P_v - R_e of every edge; J_t and its seed g_l are formed on a COPY of the posterior rows
-// (the walk still needs P), and cn_backward<..., LOCAL> differentiates the check update with v2c_t := u.  Scratch, whatever
-// T is --  n rows: posterior, its copy (then g_l), targets, d J/d llr;  E rows: R, U, d J/d u;  per-tile partials of the
-// table gradients and of the loss.  Layered decoders run at VEC = 1 (pick_vec).
-struct LayJointWs {
-    int tiles = 0;
-    float *postT = nullptr, *glT = nullptr, *yT = nullptr, *gllrT = nullptr, *msgs = nullptr, *urows = nullptr, *gu = nullptr;
-    float *gbeta = nullptr, *goa = nullptr;
-    uint64_t *bitsT = nullptr;
-    double *loss_part = nullptr, *item_sum = nullptr;
-    size_t total = 0;
-};
-LayJointWs carve_joint_layered(const ldpc_decoder *d, int64_t batch, void *base)
-{
-    LayJointWs w;
-    constexpr int W = kWave;
-    w.tiles = (int)std::max<int64_t>((batch + W - 1) / W, 1);
-    const size_t n = d->g->n, E = std::max(d->g->E, 1), tw = (size_t)w.tiles * W;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-    const size_t o_post = take(tw * n * 4), o_gl = take(tw * n * 4), o_y = take(tw * n * 4), o_gx = take(tw * n * 4);
-    const size_t o_r = take(tw * E * 4), o_u = take(tw * E * 4), o_gu = take(tw * E * 4);
-    const size_t o_bits = take((size_t)w.tiles * n * sizeof(uint64_t));
-    const size_t o_gb = take((size_t)w.tiles * E * 4), o_goa = take(d->form == LDPC_C2V_OMS ? (size_t)w.tiles * E * 4 : 0);
-    const size_t vb = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-    const size_t o_lp = take((size_t)w.tiles * vb * sizeof(double)), o_is = take(E * sizeof(double));
-    w.total = off;
-    if (base) {
-        char *b = (char *)base;
-        w.postT = (float *)(b + o_post); w.glT = (float *)(b + o_gl); w.yT = (float *)(b + o_y); w.gllrT = (float *)(b + o_gx);
-        w.msgs = (float *)(b + o_r); w.urows = (float *)(b + o_u); w.gu = (float *)(b + o_gu);
-        w.bitsT = (uint64_t *)(b + o_bits); w.gbeta = (float *)(b + o_gb); w.goa = (float *)(b + o_goa);
-        w.loss_part = (double *)(b + o_lp); w.item_sum = (double *)(b + o_is);
-    }
-    return w;
-}
-
-int joint_layered_impl(const ldpc_decoder *d, const float *llr, const float *targets, int64_t batch, const float *weights,
-                       float *loss_per_iter, int32_t *bits, float *posterior, float *grad_beta, float *grad_alpha,
-                       float *grad_oms_alpha, float *grad_llr, const LayJointWs &w, hipStream_t s)
-{
-    constexpr int VEC = 1, W = kWave;
-    constexpr int JT = transpose_vars<float>();
-    const GraphDev g = d->g->dev();
-    const int T = d->T, tiles = w.tiles, vc = (g.n + JT - 1) / JT;
-    const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
-    const bool oms = d->form == LDPC_C2V_OMS;
-    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
-    const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
-    const size_t nrow_bytes = (size_t)tiles * W * g.n * sizeof(float), erow_bytes = (size_t)tiles * W * g.E * sizeof(float);
-    // P = llr, R = +0 ("no message yet"), as the decode starts
-    hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, w.postT, (long long)batch, g.n, vc);
-    if (targets)
-        hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, targets, w.yT, (long long)batch, g.n, vc);
-    HIP_TRY(hipMemsetAsync(w.msgs, 0, erow_bytes, s));
-    // the schedule has no variable-side alpha: every row of its gradient is 0
-    if (grad_alpha) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)T * d->n_alpha * 4, s));
-    if (grad_oms_alpha && !oa_grad && d->n_oms_alpha > 0)
-        HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)T * d->n_oms_alpha * 4, s));
-    if (grad_llr) HIP_TRY(hipMemsetAsync(w.gllrT, 0, nrow_bytes, s));
-    const int cb = (g.m + kWavesPerBlock - 1) / kWavesPerBlock, vb = (g.n + kWavesPerBlock - 1) / kWavesPerBlock;
-    const dim3 cgrid((unsigned)((size_t)tiles * cb)), vgrid((unsigned)((size_t)tiles * vb));
-    const double inv_bn = 1.0 / ((double)batch * (double)g.n);
-    auto reduce_step = [&](const float *part, int count, const int *slot_ptr, const int *slot_items, int n_slots, float *row) {
-        hipLaunchKernelGGL(reduce_tiles, dim3((unsigned)((count + kBlock - 1) / kBlock)), blk, 0, s, part, tiles, count, w.item_sum);
-        hipLaunchKernelGGL(reduce_table_grads<double>, dim3((unsigned)n_slots), dim3(kWave), 0, s, (const double *)w.item_sum, 1,
-                           count, slot_ptr, slot_items, n_slots, row);
-    };
-    const float *yT = targets ? w.yT : nullptr;
-    for (int t = 0; t < T; ++t) {
-        const bool last = t == T - 1;
-        const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
-        const float *oa_row = (oms && d->oms_alpha) ? (const float *)d->oms_alpha + (size_t)t * d->n_oms_alpha : nullptr;
-        uint64_t *bitsT = (last && bits) ? w.bitsT : nullptr;
-        // forward iteration t: one walk over the checks, a wave per tile; P_t in postT, u of every edge in urows
-        if (oms)
-            hipLaunchKernelGGL((layered_minsum_iter<VEC, FORM_OMS>), dim3(tiles), dim3(kWave), 0, s, g, w.postT, w.msgs, w.urows,
-                               beta_row, (const int *)d->beta_slot, oa_row, (const int *)d->oms_alpha_slot, bitsT);
-        else
-            hipLaunchKernelGGL((layered_minsum_iter<VEC, FORM_NMS>), dim3(tiles), dim3(kWave), 0, s, g, w.postT, w.msgs, w.urows,
-                               beta_row, (const int *)d->beta_slot, (const float *)nullptr, (const int *)nullptr, bitsT);
-        if (last && (bits || posterior))
-            hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.postT, (const uint64_t *)w.bitsT,
-                               posterior, bits, (long long)batch, g.n, vc);
-        // J_t; with a gradient, g_l over a copy of the posterior rows (joint_loss_grad writes in place, the walk goes on with P)
-        if (want) {
-            HIP_TRY(hipMemcpyAsync(w.glT, w.postT, nrow_bytes, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL((joint_loss_grad<VEC, true>), vgrid, blk, 0, s, g.n, w.glT, yT, weights, t, (long long)batch,
-                               (float)inv_bn, grad_llr ? w.gllrT : nullptr, w.loss_part, vb);
-        } else {
-            hipLaunchKernelGGL((joint_loss_grad<VEC, false>), vgrid, blk, 0, s, g.n, w.postT, yT, weights, t, (long long)batch,
-                               (float)inv_bn, (float *)nullptr, w.loss_part, vb);
-        }
-        hipLaunchKernelGGL(joint_loss_reduce, dim3(1), blk, 0, s, (const double *)w.loss_part, (long long)tiles * vb, inv_bn,
-                           loss_per_iter + t);
-        HIP_TRY(hipGetLastError());
-        if (!want) continue;
-        // posterior-local backward of iteration t through the check update alone: beta_t, the offset alpha_t, d J_t/d u
-        float *gu_out = grad_llr ? w.gu : nullptr;
-        float *goa = oa_grad ? w.goa : nullptr;
-#define LDPC_CNL(FORM_)                                                                                                \
-    hipLaunchKernelGGL((cn_backward<VEC, false, FORM_, true>), cgrid, blk, 0, s, g, (const float *)w.urows,           \
-                       (const float *)nullptr, (const float *)w.glT, (const int *)nullptr, (long long)batch, t, beta_row, \
-                       (const int *)d->beta_slot, gu_out, w.gbeta, goa, cb)
-        if (oms) LDPC_CNL(FORM_OMS); else LDPC_CNL(FORM_NMS);
-#undef LDPC_CNL
-        if (grad_beta) reduce_step(w.gbeta, g.E, d->beta_inv_ptr, d->beta_inv_items, d->n_beta, grad_beta + (size_t)t * d->n_beta);
-        if (oa_grad)
-            reduce_step(w.goa, g.E, d->oms_inv_ptr, d->oms_inv_items, d->n_oms_alpha, grad_oms_alpha + (size_t)t * d->n_oms_alpha);
-        if (grad_llr)                                      // u_e = llr_v + const: d J_t/d llr_v = g_t[v] + sum of d J_t/d u_e at v
-            hipLaunchKernelGGL((llr_backward_accumulate<VEC>), vgrid, blk, 0, s, g, (const float *)w.gu, w.gllrT, vb);
-        HIP_TRY(hipGetLastError());
-    }
-    if (grad_llr)
-        hipLaunchKernelGGL((transpose_out<float, VEC>), tgrid, blk, 0, s, (const float *)w.gllrT, (const uint64_t *)nullptr, grad_llr,
-                           (int *)nullptr, (long long)batch, g.n, vc);
-    HIP_TRY(hipGetLastError());
-    return LDPC_OK;
-}
-
-// ldpc_train_joint_layered: the fp32 layered normalised / offset min-sum decoders
-int layered_joint_supported(const ldpc_decoder *d)
-{
-    if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
-    if (d->dtype != LDPC_F32)
-        return fail(LDPC_ERR_UNSUPPORTED, "the layered joint loss exists for fp32 decoders only (a float64 decoder has no layered schedule)");
-    if (d->schedule == LDPC_SCHED_FLOODING && d->form == LDPC_C2V_RCQ)
-        return fail(LDPC_ERR_UNSUPPORTED, "a flooding RCQ decoder takes ldpc_train_joint_ste, not ldpc_train_joint_layered");
-    if (d->schedule == LDPC_SCHED_FLOODING)
-        return fail(LDPC_ERR_UNSUPPORTED, "a flooding min-sum decoder takes ldpc_train_joint, not ldpc_train_joint_layered");
-    if (d->form == LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_LAYERED)
-        return fail(LDPC_ERR_UNSUPPORTED, "the layered joint loss exists for the min-sum forms (LDPC_C2V_NMS / LDPC_C2V_OMS) under "
-                                          "LDPC_SCHED_LAYERED; the layered RCQ decoders (LDPC_SCHED_LAYERED_REF, LDPC_SCHED_LAYERED) "
-                                          "have no gradient path, their flooding form takes ldpc_train_joint_ste");
-    return LDPC_OK;
-}
-}  // namespace
+// ---- gradient (training) path: ldpc_train_host.hip over the kernels of ldpc_train.hip --------------------------
+#include "ldpc_train_host.hip"
 
 extern "C" {
-
-size_t ldpc_train_saved_bytes(const ldpc_decoder *d, int64_t batch)
-{
-    if (!d || batch <= 0) return 0;
-    const int vec = pick_vec(d, batch), W = 64 * vec;
-    const size_t total = saved_layout(d, (int)((batch + W - 1) / W), W).total();
-    return total ? total : kAlign;
-}
-
-size_t ldpc_train_workspace_bytes(const ldpc_decoder *d, int64_t batch)
-{
-    if (!d || batch < 0) return 0;
-    return std::max(carve(d, batch, nullptr).total, carve_backward(d, batch, nullptr).total);
-}
-
-int ldpc_decode_saving(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop, int32_t *bits,
-                       void *posterior, int32_t *iterations, uint8_t *success, void *saved, size_t saved_bytes,
-                       void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (int rc = train_supported(d)) return rc;
-    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
-    if (batch == 0 || d->g->n == 0) return LDPC_OK;
-    if (!llr || !workspace || !saved) return fail(LDPC_ERR_ARG, "NULL llr/workspace/saved");
-    if (((uintptr_t)workspace % kAlign) != 0 || ((uintptr_t)saved % kAlign) != 0)
-        return fail(LDPC_ERR_ARG, "workspace and saved state must be %zu-byte aligned", kAlign);
-    const Workspace w = carve(d, batch, workspace);
-    if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
-    if (ldpc_train_saved_bytes(d, batch) > saved_bytes) return fail(LDPC_ERR_WORKSPACE, "saved-state buffer too small");
-    if ((size_t)w.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
-    DeviceGuard guard(d->g->device);
-    return decode_dispatch<float>(d, llr, batch, early_stop != 0, bits, posterior, iterations, success, nullptr, w,
-                                  (hipStream_t)stream, (char *)saved);
-}
-
-int ldpc_backward(const ldpc_decoder *d, const void *saved, size_t saved_bytes, const void *llr, int64_t batch,
-                  const int32_t *iterations, const void *grad_posterior, void *grad_beta, void *grad_alpha,
-                  void *grad_oms_alpha, void *grad_llr, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (int rc = train_supported(d)) return rc;
-    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
-    if (!grad_beta && !grad_alpha && !grad_oms_alpha && !grad_llr) return LDPC_OK;
-    DeviceGuard guard(d->g->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (batch == 0 || d->g->n == 0 || d->T == 0 || d->g->E == 0) {       // no iteration ran: the posterior is the LLR
-        if (grad_beta) HIP_TRY(hipMemsetAsync(grad_beta, 0, (size_t)std::max(d->T, 1) * d->n_beta * 4, s));
-        if (grad_alpha) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)std::max(d->T, 1) * d->n_alpha * 4, s));
-        if (grad_oms_alpha && d->n_oms_alpha > 0)
-            HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)std::max(d->T, 1) * d->n_oms_alpha * 4, s));
-        if (grad_llr && batch > 0 && d->g->n > 0) {              // no iteration ran: posterior == llr
-            if (!grad_posterior) return fail(LDPC_ERR_ARG, "NULL grad_posterior");
-            HIP_TRY(hipMemcpyAsync(grad_llr, grad_posterior, (size_t)batch * d->g->n * 4, hipMemcpyDeviceToDevice, s));
-        }
-        return LDPC_OK;
-    }
-    if (!saved || !llr || !iterations || !grad_posterior || !workspace) return fail(LDPC_ERR_ARG, "NULL argument");
-    if (((uintptr_t)workspace % kAlign) != 0 || ((uintptr_t)saved % kAlign) != 0)
-        return fail(LDPC_ERR_ARG, "workspace and saved state must be %zu-byte aligned", kAlign);
-    if (ldpc_train_saved_bytes(d, batch) > saved_bytes) return fail(LDPC_ERR_WORKSPACE, "saved-state buffer too small");
-    const BackwardWs w = carve_backward(d, batch, workspace);
-    if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
-    if ((size_t)w.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
-    if (w.vec == 1)
-        return backward_impl<1>(d, (const char *)saved, (const float *)llr, batch, iterations, (const float *)grad_posterior,
-                                (float *)grad_beta, (float *)grad_alpha, (float *)grad_oms_alpha, (float *)grad_llr, w, s);
-    return backward_impl<4>(d, (const char *)saved, (const float *)llr, batch, iterations, (const float *)grad_posterior,
-                            (float *)grad_beta, (float *)grad_alpha, (float *)grad_oms_alpha, (float *)grad_llr, w, s);
-}
-
-size_t ldpc_train_joint_workspace_bytes(const ldpc_decoder *d, int64_t batch)
-{
-    if (!d || batch < 0) return 0;
-    return carve_joint(d, batch, nullptr).total;
-}
-
-// ldpc_train_joint, ldpc_train_joint_ste and ldpc_train_joint_layered: the same argument rules; the first two share joint_impl
-enum { kJointMinsum = 0, kJointSte = 1, kJointLayered = 2 };
-static int train_joint_entry(const ldpc_decoder *d, int kind, const void *llr, const void *targets, int64_t batch,
-                             const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
-                             void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
-                             size_t workspace_bytes, void *stream)
-{
-    const bool ste = kind == kJointSte, layered = kind == kJointLayered;
-    if (int rc = layered ? layered_joint_supported(d) : ste ? ste_supported(d) : train_supported(d)) return rc;
-    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
-    if (d->T < 1) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs at least one iteration");
-    if (!d->beta_inv_ptr || (!layered && !d->alpha_inv_ptr)) return fail(LDPC_ERR_UNSUPPORTED, "internal: the decoder has no inverse slot maps");
-    if (ste && d->n_levels > kVnbLutMax / 2) return fail(LDPC_ERR_UNSUPPORTED, "more than %d quantiser levels", kVnbLutMax / 2);
-    if (!loss_per_iter) return fail(LDPC_ERR_ARG, "NULL loss_per_iter");
-    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
-    if (want && !iteration_weights) return fail(LDPC_ERR_ARG, "NULL iteration_weights");
-    DeviceGuard guard(d->g->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (batch == 0) {                                 // an empty batch: every loss term and every gradient is 0
-        HIP_TRY(hipMemsetAsync(loss_per_iter, 0, (size_t)d->T * 4, s));
-        if (grad_beta) HIP_TRY(hipMemsetAsync(grad_beta, 0, (size_t)d->T * d->n_beta * 4, s));
-        if (grad_alpha) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)d->T * d->n_alpha * 4, s));
-        if (grad_oms_alpha && d->n_oms_alpha > 0) HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)d->T * d->n_oms_alpha * 4, s));
-        return LDPC_OK;
-    }
-    if (d->g->n == 0 || d->g->E == 0) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs a graph with edges");
-    if (!llr || !workspace) return fail(LDPC_ERR_ARG, "NULL llr/workspace");
-    if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
-    if (layered) {
-        const LayJointWs lw = carve_joint_layered(d, batch, workspace);
-        if (lw.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, lw.total);
-        if ((size_t)lw.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
-        return joint_layered_impl(d, (const float *)llr, (const float *)targets, batch, (const float *)iteration_weights,
-                                  (float *)loss_per_iter, bits, (float *)posterior, (float *)grad_beta, (float *)grad_alpha,
-                                  (float *)grad_oms_alpha, (float *)grad_llr, lw, s);
-    }
-    const JointWs w = carve_joint(d, batch, workspace, ste);
-    if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
-    if ((size_t)w.fw.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
-#define LDPC_JOINT(V_)                                                                                                 \
-    joint_impl<V_>(d, (const float *)llr, (const float *)targets, batch, (const float *)iteration_weights,             \
-                   (float *)loss_per_iter, bits, (float *)posterior, (float *)grad_beta, (float *)grad_alpha,          \
-                   (float *)grad_oms_alpha, (float *)grad_llr, w, s)
-    if (w.fw.vec == 1) return LDPC_JOINT(1);
-    return LDPC_JOINT(4);
-#undef LDPC_JOINT
-}
-
-int ldpc_train_joint(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
-                     const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
-                     void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
-                     size_t workspace_bytes, void *stream)
-{
-    return train_joint_entry(d, kJointMinsum, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
-                             grad_alpha, grad_oms_alpha, grad_llr, workspace, workspace_bytes, stream);
-}
-
-size_t ldpc_train_joint_ste_workspace_bytes(const ldpc_decoder *d, int64_t batch)
-{
-    if (!d || batch < 0) return 0;
-    return carve_joint(d, batch, nullptr, /*codes=*/true).total;
-}
-
-int ldpc_train_joint_ste(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
-                         const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
-                         void *grad_beta, void *grad_alpha, void *grad_llr, void *workspace, size_t workspace_bytes,
-                         void *stream)
-{
-    return train_joint_entry(d, kJointSte, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
-                             grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream);
-}
-
-size_t ldpc_train_joint_layered_workspace_bytes(const ldpc_decoder *d, int64_t batch)
-{
-    if (!d || batch < 0) return 0;
-    return carve_joint_layered(d, batch, nullptr).total;
-}
-
-int ldpc_train_joint_layered(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
-                             const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
-                             void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
-                             size_t workspace_bytes, void *stream)
-{
-    return train_joint_entry(d, kJointLayered, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior,
-                             grad_beta, grad_alpha, grad_oms_alpha, grad_llr, workspace, workspace_bytes, stream);
-}
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,
                     uint8_t *keys_compare, void *stream)

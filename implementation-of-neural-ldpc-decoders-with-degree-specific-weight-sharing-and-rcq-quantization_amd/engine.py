@@ -501,8 +501,13 @@ class DecodeEngine:
         Everything on this engine's device, fp32."""
         return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="minsum")
 
+    # kind -> (entry point, its workspace-bytes function, the entry point takes grad_oms_alpha)
+    _JOINT_ENTRY = {"minsum": ("ldpc_train_joint", "ldpc_train_joint_workspace_bytes", True),
+                    "ste": ("ldpc_train_joint_ste", "ldpc_train_joint_ste_workspace_bytes", False),
+                    "layered": ("ldpc_train_joint_layered", "ldpc_train_joint_layered_workspace_bytes", True)}
+
     def _train_joint(self, llr, targets, iteration_weights, want_grads, want_grad_llr, kind: str) -> dict:
-        ste, layered = kind == "ste", kind == "layered"
+        entry, ws_bytes, has_goa = self._JOINT_ENTRY[kind]
         llr = self._check_llr(llr)
         B, n = llr.shape
         dev = self.device
@@ -523,12 +528,11 @@ class DecodeEngine:
         gb = torch.empty(self._table_shapes[0], dtype=torch.float32, device=dev) if want_grads else None
         ga = torch.empty(self._table_shapes[1], dtype=torch.float32, device=dev) if want_grads else None
         goa = (torch.empty(self._table_shapes[2], dtype=torch.float32, device=dev)
-               if want_grads and not ste and self._table_shapes[2] is not None else None)
+               if want_grads and has_goa and self._table_shapes[2] is not None else None)
         gl = torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr else None
         ws = None
         if B > 0:
-            need = (self.train_joint_ste_workspace_bytes(B) if ste else self.train_joint_layered_workspace_bytes(B) if layered
-                    else self.train_joint_workspace_bytes(B))
+            need = int(getattr(self._lib, ws_bytes)(self.handle, B))
             ws = getattr(self, "_joint_ws", None)
             if ws is None or ws.numel() < need:
                 self._joint_ws = None
@@ -536,18 +540,9 @@ class DecodeEngine:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            if ste:
-                nat.check(self._lib.ldpc_train_joint_ste(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
-                                                         p(gb), p(ga), p(gl), p(ws), 0 if ws is None else ws.numel(),
-                                                         C.c_void_p(stream)), "ldpc_train_joint_ste")
-            elif layered:
-                nat.check(self._lib.ldpc_train_joint_layered(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
-                                                             p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),
-                                                             C.c_void_p(stream)), "ldpc_train_joint_layered")
-            else:
-                nat.check(self._lib.ldpc_train_joint(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post),
-                                                     p(gb), p(ga), p(goa), p(gl), p(ws), 0 if ws is None else ws.numel(),
-                                                     C.c_void_p(stream)), "ldpc_train_joint")
+            grads = (p(gb), p(ga), p(goa), p(gl)) if has_goa else (p(gb), p(ga), p(gl))
+            nat.check(getattr(self._lib, entry)(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post), *grads,
+                                                p(ws), 0 if ws is None else ws.numel(), C.c_void_p(stream)), entry)
         return {"loss": (w[:T] * lpi).sum(), "loss_per_iter": lpi, "bits": bits, "posterior": post,
                 "grad_beta": gb, "grad_alpha": ga, "grad_oms_alpha": goa, "grad_llr": gl}
 

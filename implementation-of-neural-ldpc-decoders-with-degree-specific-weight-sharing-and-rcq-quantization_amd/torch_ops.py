@@ -218,13 +218,13 @@ minsum_decode_train.register_autograd(_train_backward, setup_context=_train_setu
 
 
 # ------------------------------------------------------------------------------------------ posterior joint training
-def _minsum_joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, layered):
+def _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, method):
+    """the three joint-loss operators; `method`: the engine's train_joint | train_joint_ste | train_joint_layered"""
     eng = _engine(engine)
     restore = _with_tables(eng, _np_table(beta), _np_table(alpha), alpha_is_oms)
     try:
-        run = eng.train_joint_layered if layered else eng.train_joint
-        r = run(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
-                            want_grads=want_grads, want_grad_llr=want_grad_llr)
+        r = getattr(eng, method)(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
+                                 want_grads=want_grads, want_grad_llr=want_grad_llr)
     finally:
         restore()
     dev = llr.device
@@ -247,7 +247,7 @@ def minsum_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alph
     loss = sum_t w_t J_t, loss_per_iter = J_t, posterior / bits of the last iteration, and the gradients of `loss`
     the autograd formula scales: d loss/d beta [T, Sb], d loss/d alpha [T, Sa] (alpha_is_oms: the check-side offset)
     -- empty when not want_grads -- and d loss/d llr [B, n] (empty when not want_grad_llr)"""
-    return _minsum_joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, False)
+    return _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, "train_joint")
 
 
 @torch.library.custom_op("ldpc::minsum_layered_joint_loss", mutates_args=())
@@ -257,47 +257,8 @@ def minsum_layered_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tens
     """minsum_joint_loss of a decoder under the layered schedule (ldpc_train_joint_layered): the fixed-T layered decode, its
     per-iteration loss, and the layered posterior-local gradients d loss/d beta [T, Sb], d loss/d alpha [T, Sa]
     (alpha_is_oms: the check-side offset; otherwise the unused variable-side table, all zero), d loss/d llr [B, n]"""
-    return _minsum_joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, True)
-
-
-@minsum_layered_joint_loss.register_fake
-@minsum_joint_loss.register_fake
-def _(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads=True, want_grad_llr=False):
-    B, n = llr.shape
-    dev = llr.device
-    T = iteration_weights.shape[0]
-    return (torch.empty((), dtype=torch.float32, device=dev), torch.empty((T,), dtype=torch.float32, device=dev),
-            torch.empty((B, n), dtype=torch.float32, device=dev), torch.empty((B, n), dtype=torch.int32, device=dev),
-            torch.empty_like(beta) if want_grads else torch.empty((0,), dtype=beta.dtype, device=beta.device),
-            torch.empty_like(alpha) if want_grads else torch.empty((0,), dtype=alpha.dtype, device=alpha.device),
-            torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr
-            else torch.empty((0,), dtype=torch.float32, device=dev))
-
-
-def _joint_setup(ctx, inputs, output):
-    _llr, _targets, _beta, _alpha, _w, _engine_h, _oms, want_grads, want_grad_llr = inputs
-    _loss, lpi, post, bits, gb, ga, gl = output
-    ctx.want_grads, ctx.want_grad_llr = want_grads, want_grad_llr
-    ctx.save_for_backward(lpi, gb, ga, gl)
-    # only the scalar loss is differentiable: the gradients above are d loss / d input
-    ctx.mark_non_differentiable(lpi, post, bits, gb, ga, gl)
-    ctx.set_materialize_grads(False)
-
-
-def _joint_backward(ctx, g_loss, *_unused):
-    lpi, gb, ga, gl = ctx.saved_tensors
-    if g_loss is None:
-        return None, None, None, None, None, None, None, None, None
-    # J is linear in its seed: the saved gradients of `loss` scale by the incoming gradient
-    g_beta = gb * g_loss.to(gb.device) if ctx.want_grads and ctx.needs_input_grad[2] else None
-    g_alpha = ga * g_loss.to(ga.device) if ctx.want_grads and ctx.needs_input_grad[3] else None
-    g_llr = gl * g_loss if ctx.want_grad_llr and ctx.needs_input_grad[0] else None
-    g_w = lpi * g_loss if ctx.needs_input_grad[4] else None          # d loss / d w_t = J_t
-    return g_llr, None, g_beta, g_alpha, g_w, None, None, None, None
-
-
-minsum_joint_loss.register_autograd(_joint_backward, setup_context=_joint_setup)
-minsum_layered_joint_loss.register_autograd(_joint_backward, setup_context=_joint_setup)
+    return _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr,
+                  "train_joint_layered")
 
 
 @torch.library.custom_op("ldpc::rcq_joint_loss", mutates_args=())
@@ -307,24 +268,12 @@ def rcq_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: 
     """minsum_joint_loss of the quantised decoder (ldpc_train_joint_ste): the fixed-T W-RCQ decode, its per-iteration
     loss, and the straight-through gradients d loss/d beta [T, Sb], d loss/d alpha [T, Sa] (variable side),
     d loss/d llr [B, n]"""
-    eng = _engine(engine)
-    restore = _with_tables(eng, _np_table(beta), _np_table(alpha), False)
-    try:
-        r = eng.train_joint_ste(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
-                                want_grads=want_grads, want_grad_llr=want_grad_llr)
-    finally:
-        restore()
-    if want_grads:
-        gb = r["grad_beta"].to(device=beta.device, dtype=beta.dtype)
-        ga = r["grad_alpha"].to(device=alpha.device, dtype=alpha.dtype)
-    else:
-        gb, ga = torch.empty((0,), dtype=beta.dtype, device=beta.device), torch.empty((0,), dtype=alpha.dtype, device=alpha.device)
-    gl = r["grad_llr"] if want_grad_llr else torch.empty((0,), dtype=torch.float32, device=llr.device)
-    return r["loss"], r["loss_per_iter"], r["posterior"], r["bits"], gb, ga, gl
+    return _joint(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr, "train_joint_ste")
 
 
-@rcq_joint_loss.register_fake
-def _(llr, targets, beta, alpha, iteration_weights, engine, want_grads=True, want_grad_llr=False):
+@minsum_layered_joint_loss.register_fake
+@minsum_joint_loss.register_fake
+def _joint_fake(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads=True, want_grad_llr=False):
     B, n = llr.shape
     dev = llr.device
     T = iteration_weights.shape[0]
@@ -336,17 +285,35 @@ def _(llr, targets, beta, alpha, iteration_weights, engine, want_grads=True, wan
             else torch.empty((0,), dtype=torch.float32, device=dev))
 
 
-def _rcq_joint_setup(ctx, inputs, output):
-    _llr, _targets, _beta, _alpha, _w, _engine_h, want_grads, want_grad_llr = inputs
+# the dispatcher drops trailing arguments that equal their defaults, so a fake cannot read the two flags from the tail of
+# *args without knowing whether alpha_is_oms (no default) precedes them: the quantised operator, which has none, binds its
+# own signature and calls the one fake
+@rcq_joint_loss.register_fake
+def _(llr, targets, beta, alpha, iteration_weights, engine, want_grads=True, want_grad_llr=False):
+    return _joint_fake(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr)
+
+
+def _joint_setup(ctx, inputs, output):
+    ctx.want_grads, ctx.want_grad_llr = inputs[-2:]
+    ctx.n_inputs = len(inputs)
     _loss, lpi, post, bits, gb, ga, gl = output
-    ctx.want_grads, ctx.want_grad_llr = want_grads, want_grad_llr
     ctx.save_for_backward(lpi, gb, ga, gl)
+    # only the scalar loss is differentiable: the gradients above are d loss / d input
     ctx.mark_non_differentiable(lpi, post, bits, gb, ga, gl)
     ctx.set_materialize_grads(False)
 
 
-def _rcq_joint_backward(ctx, g_loss, *_unused):
-    return _joint_backward(ctx, g_loss)[:-1]         # one input fewer: no alpha_is_oms
+def _joint_backward(ctx, g_loss, *_unused):
+    lpi, gb, ga, gl = ctx.saved_tensors
+    if g_loss is None:
+        return (None,) * ctx.n_inputs
+    # J is linear in its seed: the saved gradients of `loss` scale by the incoming gradient
+    g_beta = gb * g_loss.to(gb.device) if ctx.want_grads and ctx.needs_input_grad[2] else None
+    g_alpha = ga * g_loss.to(ga.device) if ctx.want_grads and ctx.needs_input_grad[3] else None
+    g_llr = gl * g_loss if ctx.want_grad_llr and ctx.needs_input_grad[0] else None
+    g_w = lpi * g_loss if ctx.needs_input_grad[4] else None          # d loss / d w_t = J_t
+    return (g_llr, None, g_beta, g_alpha, g_w) + (None,) * (ctx.n_inputs - 5)    # engine and the flags: no gradient
 
 
-rcq_joint_loss.register_autograd(_rcq_joint_backward, setup_context=_rcq_joint_setup)
+for _op in (minsum_joint_loss, minsum_layered_joint_loss, rcq_joint_loss):
+    _op.register_autograd(_joint_backward, setup_context=_joint_setup)

@@ -432,6 +432,22 @@ def test_native_library_staleness_is_decided_by_content_hash(tmp_path, monkeypat
         _native.load()
 
 
+def test_source_hash_covers_every_file_of_the_compiled_unit():
+    """the embedded content hash can only call a library stale over files it reads: the source files in csrc/ are exactly
+    _native.SOURCES, and every local file one of them includes is among the hashed files"""
+    import re
+    import _native
+    csrc = os.path.join(PKG, "csrc")
+    sources = {fn for fn in os.listdir(csrc) if fn.endswith((".hip", ".h", ".hpp", ".inc", ".cpp"))}
+    assert sources == set(_native.SOURCES) and len(set(_native.SOURCES)) == len(_native.SOURCES)
+    hashed = {os.path.realpath(p) for p in _native._source_files()}
+    for fn in _native.SOURCES:
+        with open(os.path.join(csrc, fn)) as f:
+            text = f.read()
+        for inc in re.findall(r'^\s*#\s*include\s*"([^"]+)"', text, re.M):
+            assert os.path.realpath(os.path.join(csrc, inc)) in hashed, f"{fn} includes {inc}, which the hash does not cover"
+
+
 def test_native_graph_cache_holds_graphs_weakly():
     """one device graph per (TannerGraph, device) while the host graph lives; entries go when it dies (no GPU needed:
     the factory is injected)"""
