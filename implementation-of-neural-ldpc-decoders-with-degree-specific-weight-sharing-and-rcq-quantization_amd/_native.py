@@ -134,7 +134,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_train_saved_bytes", "ldpc_train_workspace_bytes", "ldpc_decode_saving", "ldpc_backward",
                    "ldpc_train_joint_workspace_bytes", "ldpc_train_joint",
                    "ldpc_train_joint_ste_workspace_bytes", "ldpc_train_joint_ste",
-                   "ldpc_train_joint_layered_workspace_bytes", "ldpc_train_joint_layered")
+                   "ldpc_train_joint_layered_workspace_bytes", "ldpc_train_joint_layered",
+                   "ldpc_train_joint_layered_ste_workspace_bytes", "ldpc_train_joint_layered_ste")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -224,6 +225,10 @@ def load():
         lib.ldpc_train_joint_layered_workspace_bytes.argtypes = [vp, i64]
         lib.ldpc_train_joint_layered.restype = C.c_int
         lib.ldpc_train_joint_layered.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+        lib.ldpc_train_joint_layered_ste_workspace_bytes.restype = C.c_size_t
+        lib.ldpc_train_joint_layered_ste_workspace_bytes.argtypes = [vp, i64]
+        lib.ldpc_train_joint_layered_ste.restype = C.c_int
+        lib.ldpc_train_joint_layered_ste.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_last_error.restype = C.c_char_p
         lib.ldpc_last_error.argtypes = []
         lib.ldpc_abi_version.restype = C.c_int

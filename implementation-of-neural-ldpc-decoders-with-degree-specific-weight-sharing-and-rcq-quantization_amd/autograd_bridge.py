@@ -110,7 +110,7 @@ LAYERED_GRADIENTS = ("posterior_local",)
 
 
 def check_layered_gradient(value, schedule="layered"):
-    """the gradients joint_posterior_loss of a ``schedule="layered"`` min-sum decoder knows: None (no gradient path) or one
+    """the gradients joint_posterior_loss of a ``schedule="layered"`` decoder (min-sum, or W-RCQ ``layered="paper"``) knows: None (no gradient path) or one
     of LAYERED_GRADIENTS; ValueError otherwise, and for any value but None on a flooding decoder (nothing to choose there)"""
     if value is not None and value not in LAYERED_GRADIENTS:
         raise ValueError(f"layered_gradient must be None or one of {LAYERED_GRADIENTS}, got {value!r}")
@@ -120,11 +120,12 @@ def check_layered_gradient(value, schedule="layered"):
 
 
 def joint_loss_ste(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets,
-                   iteration_weights):
+                   iteration_weights, layered: bool = False):
     """joint_loss() of the quantised WeightedRCQDecoder through ``torch.ops.ldpc.rcq_joint_loss``: the same loss on the
     decoder's own fixed-T decode, differentiable with the straight-through rule of include/ldpc_hip.h
-    (ldpc_train_joint_ste) -> (loss, loss_per_iteration, bits, posterior)"""
-    return joint_loss(beta_table, alpha_table, engine, llr, targets, iteration_weights, False, quantised=True)
+    (ldpc_train_joint_ste) -> (loss, loss_per_iteration, bits, posterior).  ``layered``: the engine runs the paper's
+    layered schedule -- ``torch.ops.ldpc.rcq_layered_joint_loss`` (ldpc_train_joint_layered_ste)."""
+    return joint_loss(beta_table, alpha_table, engine, llr, targets, iteration_weights, False, quantised=True, layered=layered)
 
 
 def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets, iteration_weights,
@@ -134,7 +135,8 @@ def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr:
     decode, differentiable in the tables (and in `llr` when it requires grad) with the posterior-local gradient of the
     paper's training method.  No saved history: MAX_SAVED_BYTES does not apply.
     ``layered``: the engine runs the layered schedule -- ``torch.ops.ldpc.minsum_layered_joint_loss``, whose gradient is the
-    layered posterior-local one of include/ldpc_hip.h (ldpc_train_joint_layered)."""
+    layered posterior-local one of include/ldpc_hip.h (ldpc_train_joint_layered); with ``quantised``
+    ``torch.ops.ldpc.rcq_layered_joint_loss`` (ldpc_train_joint_layered_ste)."""
     import torch_ops
     from ldpc_decoder import _as_batch
     T = int(engine.iters)
@@ -152,7 +154,8 @@ def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr:
     w = (torch.full((T,), 1.0 / T, dtype=torch.float32) if iteration_weights is None
          else torch.as_tensor(iteration_weights).detach().to(torch.float32))
     w = w.to(engine.device).contiguous()
-    op, form = ((torch.ops.ldpc.rcq_joint_loss, ()) if quantised else           # the quantised operator has no alpha_is_oms
+    op, form = ((torch.ops.ldpc.rcq_layered_joint_loss if layered else torch.ops.ldpc.rcq_joint_loss, ())
+                if quantised else                                               # the quantised operators have no alpha_is_oms
                 (torch.ops.ldpc.minsum_layered_joint_loss if layered else torch.ops.ldpc.minsum_joint_loss, (bool(alpha_is_oms),)))
     loss, lpi, post, bits, _gb, _ga, _gl = op(xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine),
                                               *form, bool(want_grads), bool(want_llr))

@@ -1463,9 +1463,10 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
         if (!rc) rc = upload(&d->oms_alpha_slot, desc->oms_alpha_slot, (size_t)g->E);
     }
     // inverse slot maps of the gradient paths: the min-sum forms (ldpc_backward, ldpc_train_joint), RCQ (ldpc_train_joint_ste)
-    // and the layered min-sum forms (ldpc_train_joint_layered: beta and the check-side alpha; the schedule has no variable-side alpha)
-    const bool lay_ms = d->schedule == LDPC_SCHED_LAYERED && d->form != LDPC_C2V_RCQ;
-    if (!rc && d->dtype == LDPC_F32 && (d->schedule == LDPC_SCHED_FLOODING || lay_ms)) {
+    // and the LDPC_SCHED_LAYERED decoders (ldpc_train_joint_layered: beta and the check-side alpha; ldpc_train_joint_layered_ste:
+    // beta; the schedule has no variable-side alpha)
+    const bool lay = d->schedule == LDPC_SCHED_LAYERED;
+    if (!rc && d->dtype == LDPC_F32 && (d->schedule == LDPC_SCHED_FLOODING || lay)) {
         auto invert = [&](const int32_t *slot, int count, int n_slots, int **ptr_dev, int **items_dev) {
             std::vector<int> ptr((size_t)n_slots + 1, 0), items((size_t)std::max(count, 1), 0);
             for (int x = 0; x < count; ++x) ptr[slot[x] + 1]++;
@@ -1477,7 +1478,7 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
             return r;
         };
         rc = invert(desc->beta_slot, g->E, d->n_beta, &d->beta_inv_ptr, &d->beta_inv_items);
-        if (!rc && !lay_ms) rc = invert(desc->alpha_slot, g->n, d->n_alpha, &d->alpha_inv_ptr, &d->alpha_inv_items);
+        if (!rc && !lay) rc = invert(desc->alpha_slot, g->n, d->n_alpha, &d->alpha_inv_ptr, &d->alpha_inv_items);
         if (!rc && d->oms_alpha) rc = invert(desc->oms_alpha_slot, g->E, d->n_oms_alpha, &d->oms_inv_ptr, &d->oms_inv_items);
     }
     if (!rc && d->form == LDPC_C2V_RCQ && d->dtype == LDPC_F32 && d->schedule == LDPC_SCHED_FLOODING &&

@@ -2618,6 +2618,170 @@ __global__ __launch_bounds__(kWave) void layered_minsum_iter(GraphDev g, float *
     }
 }
 
+// Training form of layered_rcq<VEC, true> (ldpc_train_joint_layered_ste): ONE iteration per launch, posteriors and the
+// 1-byte message codes left in post / codes between launches, and the update of every edge also stores u_e = P_v -
+// Q^-1_t'(code_e) -- the value the check update consumed, the `v2c` of the posterior-local backward (cn_backward) -- into
+// urows[tile][E][W].  `thr` is the quantiser of this iteration, `thr_prev` the one that wrote the codes it subtracts;
+// `first`: iteration 0, no code is read or subtracted.  beta_row is this iteration's row; the product b * raw is rounded
+// before the sign, u + r adds a table value -- the single rounded operations of layered_rcq<VEC, true>, step for step, so
+// the posterior after launch t is that of a fixed-T decode capped at t + 1 iterations.  No early stop and no frozen state:
+// padding codewords (LLR 1) are walked like the others, the gradient kernels leave them out.  bitsT (the last launch
+// only): hard decisions as ballots.
+template <int VEC>
+__global__ __launch_bounds__(kWave) void layered_rcq_iter(GraphDev g, float *__restrict__ post, uint8_t *__restrict__ codes,
+                                                          float *__restrict__ urows, const float *__restrict__ beta_row,
+                                                          const int *__restrict__ beta_slot,
+                                                          const float *__restrict__ thr, const float *__restrict__ thr_prev,
+                                                          int n_levels, int first, int max_dc,
+                                                          uint64_t *__restrict__ bitsT)
+{
+    constexpr int W = kWave * VEC;
+    const int lane = threadIdx.x, tile = blockIdx.x;
+    float *P = post + (size_t)tile * g.n * W + (size_t)lane * VEC;
+    uint8_t *Cd = codes + (size_t)tile * g.E * W + (size_t)lane * VEC;
+    float *U = urows + (size_t)tile * g.E * W + (size_t)lane * VEC;
+    // value of a stored code under the quantiser that produced it: (1 - 2*sign) * tau[level]
+    auto rec_of = [&](unsigned code) {
+        const unsigned lvl = code >= (unsigned)n_levels ? code - (unsigned)n_levels : code;
+        float mag = thr_prev[0];
+        for (int q = 1; q < n_levels; ++q) mag = (lvl == (unsigned)q) ? thr_prev[q] : mag;
+        return flip_sign<float>(mag, code >= (unsigned)n_levels ? 1u : 0u);
+    };
+    // the new message of an edge from its weighted check output w: reconstruction (signed) and code
+    auto quantise = [&](float w, float &msg, unsigned &code) {
+        const float mag = __builtin_fabsf(w);
+        float rec = thr[0];
+        unsigned lvl = 0;
+        for (int q = 1; q < n_levels; ++q) { const bool ge = mag >= thr[q]; rec = ge ? thr[q] : rec; lvl = ge ? (unsigned)q : lvl; }
+        msg = flip_sign<float>(rec, (w < 0.0f) ? 1u : 0u);
+        code = ((w < 0.0f) ? (unsigned)n_levels : 0u) + lvl;
+    };
+    constexpr int kHeld = 32;
+    if (VEC == 1 && max_dc <= kHeld) {
+        // the held form of layered_rcq<1, true>: next check's indices in flight, all rows and codes of a check requested
+        // at once, values in registers for both passes
+        int var_n[kHeld];
+        int dc_n = 0, e0_n = 0;
+        auto fetch_idx = [&](int i) {
+            e0_n = g.check_ptr[i];
+            dc_n = g.check_ptr[i + 1] - e0_n;
+#pragma unroll
+            for (int t = 0; t < kHeld; ++t)
+                if (t < max_dc) var_n[t] = g.var_idx[min(e0_n + t, g.E - 1)];      // past the check: unused
+        };
+        if (g.m > 0) fetch_idx(0);
+        for (int i = 0; i < g.m; ++i) {
+            int var[kHeld];
+            const int dc = uni(dc_n), e0 = uni(e0_n);
+#pragma unroll
+            for (int t = 0; t < kHeld; ++t) var[t] = var_n[t];
+            if (i + 1 < g.m) fetch_idx(i + 1);
+            float x[kHeld];
+            unsigned old[kHeld];
+#pragma unroll
+            for (int t = 0; t < kHeld; ++t)
+                if (t < dc) {
+                    x[t] = P[(size_t)var[t] * W];
+                    if (!first) old[t] = Cd[(size_t)(e0 + t) * W];
+                }
+            if (!first) {
+#pragma unroll
+                for (int t = 0; t < kHeld; ++t)
+                    if (t < dc) x[t] = x[t] - rec_of(old[t]);
+            }
+            float m1 = inf_of<float>(), m2 = inf_of<float>();
+            unsigned par = 0;
+#pragma unroll
+            for (int t = 0; t < kHeld; ++t)
+                if (t < dc) {
+                    const float a = __builtin_fabsf(x[t]);
+                    par ^= signbit_of<float>(x[t]);
+                    if (a < m1) { m2 = m1; m1 = a; }
+                    else if (a < m2) { m2 = a; }
+                }
+            if (dc == 1) m2 = m1;
+#pragma unroll
+            for (int t = 0; t < kHeld; ++t)
+                if (t < dc) {
+                    const float a = __builtin_fabsf(x[t]);
+                    const float raw = (a == m1) ? m2 : m1;     // arg-min edge; ties make min2 == min1
+                    const float w = flip_sign<float>(beta_row[beta_slot[e0 + t]] * raw, par ^ signbit_of<float>(x[t]));
+                    float msg;
+                    unsigned code;
+                    quantise(w, msg, code);
+                    P[(size_t)var[t] * W] = x[t] + msg;
+                    Cd[(size_t)(e0 + t) * W] = (uint8_t)code;
+                    U[(size_t)(e0 + t) * W] = x[t];
+                }
+        }
+    } else {
+        for (int i = 0; i < g.m; ++i) {
+            const int e0 = uni(g.check_ptr[i]);
+            const int dc = uni(g.check_ptr[i + 1]) - e0;
+            if (dc == 0) continue;
+            float m1[VEC], m2[VEC];
+            unsigned par[VEC];
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) { m1[c] = inf_of<float>(); m2[c] = inf_of<float>(); par[c] = 0; }
+            // the posterior minus the check's previous message, recomputed identically in both passes
+            auto input = [&](int t) {
+                Pack<float, VEC> v = ld<float, VEC>(P + (size_t)g.var_idx[e0 + t] * W);
+                if (!first) {
+                    const Pack<uint8_t, VEC> oc = ld<uint8_t, VEC>(Cd + (size_t)(e0 + t) * W);
+#pragma unroll
+                    for (int c = 0; c < VEC; ++c) v.x[c] = v.x[c] - rec_of(oc.x[c]);
+                }
+                return v;
+            };
+#pragma unroll 4
+            for (int t = 0; t < dc; ++t) {
+                const Pack<float, VEC> v = input(t);
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    const float a = __builtin_fabsf(v.x[c]);
+                    par[c] ^= signbit_of<float>(v.x[c]);
+                    if (a < m1[c]) { m2[c] = m1[c]; m1[c] = a; }
+                    else if (a < m2[c]) { m2[c] = a; }
+                }
+            }
+            if (dc == 1) {
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) m2[c] = m1[c];
+            }
+#pragma unroll 2
+            for (int t = 0; t < dc; ++t) {
+                const float b = beta_row[beta_slot[e0 + t]];
+                const Pack<float, VEC> u = input(t);
+                Pack<float, VEC> v;
+                Pack<uint8_t, VEC> nc;
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    const float a = __builtin_fabsf(u.x[c]);
+                    const float raw = (a == m1[c]) ? m2[c] : m1[c];       // arg-min edge; ties make min2 == min1
+                    const float w = flip_sign<float>(b * raw, par[c] ^ signbit_of<float>(u.x[c]));
+                    float msg;
+                    unsigned code;
+                    quantise(w, msg, code);
+                    v.x[c] = u.x[c] + msg;
+                    nc.x[c] = (uint8_t)code;
+                }
+                st<float, VEC>(P + (size_t)g.var_idx[e0 + t] * W, v);
+                st<uint8_t, VEC>(Cd + (size_t)(e0 + t) * W, nc);
+                st<float, VEC>(U + (size_t)(e0 + t) * W, u);
+            }
+        }
+    }
+    if (!bitsT) return;
+    for (int j = 0; j < g.n; ++j) {                             // hard decisions as ballots, like the sweep engine
+        const Pack<float, VEC> v = ld<float, VEC>(P + (size_t)j * W);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+            const uint64_t m = __ballot(v.x[c] < 0.0f);
+            if (lane == 0) bitsT[((size_t)tile * g.n + j) * VEC + c] = m;
+        }
+    }
+}
+
 // done masks: padding codewords (>= batch) start frozen; iterations start at T
 template <int VEC>
 __global__ void init_state(uint64_t *__restrict__ done, int *__restrict__ iters, long long batch,

@@ -1,6 +1,6 @@
 // ldpc_train_host.hip -- host side of the gradient (training) path over the kernels in ldpc_train.hip: the saving decode and
 // its backward sweeps (ldpc_decode_saving / ldpc_backward), and posterior joint training (ldpc_train_joint,
-// ldpc_train_joint_ste, ldpc_train_joint_layered: one workspace carver and one loop for the three).
+// ldpc_train_joint_ste, ldpc_train_joint_layered, ldpc_train_joint_layered_ste: one workspace carver and one loop for the four).
 //
 // Not a unit of its own: ldpc_hip.hip includes it after the decode entry points and it uses that file's Workspace, carve,
 // pick_vec, launch_cn, launch_vn, decode_dispatch, saved_layout, fail, HIP_TRY and DeviceGuard.
@@ -116,10 +116,10 @@ int backward_impl(const ldpc_decoder *d, const char *saved, const float *llr, in
     return LDPC_OK;
 }
 
-// ---- posterior joint training (ldpc_train_joint, ldpc_train_joint_ste, ldpc_train_joint_layered) ------------
+// ---- posterior joint training (ldpc_train_joint, ldpc_train_joint_ste, ldpc_train_joint_layered, ldpc_train_joint_layered_ste) ----
 // The fixed-T decode with the loss of every iteration's posterior and its posterior-local gradient formed while that
 // iteration is decoded: nothing of earlier iterations is kept, so the scratch is a constant number of rows per codeword
-// whatever T is.  One loop (joint_impl) for the three entry points; the entry point passes the kind:
+// whatever T is.  One loop (joint_impl) for the four entry points; the entry point passes the kind:
 //   kJointMinsum   flooding NMS / OMS.  E rows: v2c_t / v2c_t+1 and c2v_t-1 / c2v_t (ping-pong; the alpha_t-1 partial reads the
 //                  leave-one-out sums of c2v_t-1), d J/d v2c_t;  n rows: llr, posterior (then g_l in place), targets, d J/d llr.
 //   kJointSte      flooding RCQ (`codes`): the same on the two-sweep RCQ form -- the two C2V buffers hold 1-byte codes.
@@ -127,8 +127,12 @@ int backward_impl(const ldpc_decoder *d, const char *saved, const float *llr, in
 //                  u_e = P_v - R_e of every edge; J_t and its seed g_l are formed on a COPY of the posterior rows (the walk
 //                  still needs P), and cn_backward<..., LOCAL> differentiates the check update with v2c_t := u.  E rows: R, U,
 //                  d J/d u;  n rows: posterior, its copy (then g_l), targets, d J/d llr.  Layered decoders run at VEC = 1.
+//   kJointLayeredSte  layered RCQ (LDPC_SCHED_LAYERED): layered_rcq_iter is the walk, the messages it keeps are 1-byte codes
+//                  (one row set: iteration t reads and rewrites the code of every edge), and cn_backward<..., FORM_RCQ, LOCAL>
+//                  differentiates the check update with v2c_t := u and the straight-through mask read from the codes the walk
+//                  just wrote.  E rows: U and d J/d u in fp32, the codes as bytes;  n rows as kJointLayered.
 // Every kind adds per-tile partials of the table gradients and of the loss.
-enum { kJointMinsum = 0, kJointSte = 1, kJointLayered = 2 };
+enum { kJointMinsum = 0, kJointSte = 1, kJointLayered = 2, kJointLayeredSte = 3 };
 
 int joint_supported(const ldpc_decoder *d, int kind)
 {
@@ -137,7 +141,24 @@ int joint_supported(const ldpc_decoder *d, int kind)
     if (kind == kJointSte) {     // the quantised decoder, differentiated with the straight-through rule
         if (d->dtype != LDPC_F32 || d->form != LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_FLOODING)
             return fail(LDPC_ERR_UNSUPPORTED, "the straight-through joint loss exists for the fp32 RCQ flooding decoders "
-                                              "(ldpc_train_joint has the min-sum forms; the layered schedules have no gradient path)");
+                                              "(ldpc_train_joint has the min-sum forms; the RCQ decoder under LDPC_SCHED_LAYERED takes "
+                                              "ldpc_train_joint_layered_ste, the reference's layered schedule has no gradient path)");
+        return LDPC_OK;
+    }
+    if (kind == kJointLayeredSte) {     // the quantised decoder on the paper's layered schedule
+        if (d->dtype != LDPC_F32)
+            return fail(LDPC_ERR_UNSUPPORTED, "the layered straight-through joint loss exists for fp32 decoders only (a float64 "
+                                              "decoder has no layered schedule and no RCQ form)");
+        if (d->schedule == LDPC_SCHED_FLOODING && d->form == LDPC_C2V_RCQ)
+            return fail(LDPC_ERR_UNSUPPORTED, "a flooding RCQ decoder takes ldpc_train_joint_ste, not ldpc_train_joint_layered_ste");
+        if (d->schedule == LDPC_SCHED_FLOODING)
+            return fail(LDPC_ERR_UNSUPPORTED, "a flooding min-sum decoder takes ldpc_train_joint, not ldpc_train_joint_layered_ste");
+        if (d->form != LDPC_C2V_RCQ)
+            return fail(LDPC_ERR_UNSUPPORTED, "a layered min-sum decoder takes ldpc_train_joint_layered, not ldpc_train_joint_layered_ste");
+        if (d->schedule != LDPC_SCHED_LAYERED)
+            return fail(LDPC_ERR_UNSUPPORTED, "the layered straight-through joint loss exists for the RCQ decoder under "
+                                              "LDPC_SCHED_LAYERED; the reference's layered schedule (LDPC_SCHED_LAYERED_REF) has no "
+                                              "gradient path");
         return LDPC_OK;
     }
     // kJointLayered: the fp32 layered normalised / offset min-sum decoders
@@ -149,8 +170,9 @@ int joint_supported(const ldpc_decoder *d, int kind)
         return fail(LDPC_ERR_UNSUPPORTED, "a flooding min-sum decoder takes ldpc_train_joint, not ldpc_train_joint_layered");
     if (d->form == LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_LAYERED)
         return fail(LDPC_ERR_UNSUPPORTED, "the layered joint loss exists for the min-sum forms (LDPC_C2V_NMS / LDPC_C2V_OMS) under "
-                                          "LDPC_SCHED_LAYERED; the layered RCQ decoders (LDPC_SCHED_LAYERED_REF, LDPC_SCHED_LAYERED) "
-                                          "have no gradient path, their flooding form takes ldpc_train_joint_ste");
+                                          "LDPC_SCHED_LAYERED; the RCQ decoder takes ldpc_train_joint_layered_ste under "
+                                          "LDPC_SCHED_LAYERED and ldpc_train_joint_ste under flooding, the reference's layered "
+                                          "schedule (LDPC_SCHED_LAYERED_REF) has no gradient path");
     return LDPC_OK;
 }
 
@@ -163,14 +185,15 @@ struct JointWs {
     // flooding: v2c / c2v are chosen per iteration (1-byte c2v rows for kJointSte)
     float *llrT = nullptr, *galpha = nullptr;
     char *v2c[2] = {nullptr, nullptr}, *c2v[2] = {nullptr, nullptr};
-    // layered: the posterior copy g_l is formed on, R, U
+    // layered: the posterior copy g_l is formed on, R (kJointLayeredSte: 1-byte codes in its place), U
     float *glT = nullptr, *msgs = nullptr, *urows = nullptr;
+    uint8_t *codes = nullptr;
     size_t total = 0;
 };
 JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, int kind)
 {
     JointWs w;
-    const bool layered = kind == kJointLayered;
+    const bool layered = kind == kJointLayered || kind == kJointLayeredSte;
     w.vec = layered ? 1 : pick_vec(d, batch);             // the layered walk is one wave per 64-codeword tile
     const int W = 64 * w.vec;
     w.tiles = (int)std::max<int64_t>((batch + W - 1) / W, 1);
@@ -187,7 +210,9 @@ JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, int kind)
     take(w.postT, nrow);
     if (layered) take(w.glT, nrow);
     take(w.yT, nrow); take(w.gllrT, nrow);
-    if (layered) {
+    if (kind == kJointLayeredSte) {
+        take(w.codes, tw * E); take(w.urows, erow);
+    } else if (layered) {
         take(w.msgs, erow); take(w.urows, erow);
     } else {
         take(w.v2c[0], erow); take(w.v2c[1], erow); take(w.c2v[0], crow); take(w.c2v[1], crow);
@@ -222,7 +247,12 @@ void joint_forward_layered(const ldpc_decoder *d, const JointWs &w, int t, uint6
 {
     const GraphDev g = d->g->dev();
     const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
-    if (d->form == LDPC_C2V_OMS) {
+    if (d->form == LDPC_C2V_RCQ) {      // the quantiser of this iteration, and the one that wrote the codes it subtracts
+        const float *thr = d->thresholds + (size_t)d->q_of_iter[t] * d->n_levels;
+        const float *thr_prev = d->thresholds + (size_t)d->q_of_iter[t > 0 ? t - 1 : 0] * d->n_levels;
+        hipLaunchKernelGGL((layered_rcq_iter<1>), dim3(w.tiles), dim3(kWave), 0, s, g, w.postT, w.codes, w.urows, beta_row,
+                           (const int *)d->beta_slot, thr, thr_prev, d->n_levels, t == 0 ? 1 : 0, d->g->max_dc, bitsT);
+    } else if (d->form == LDPC_C2V_OMS) {
         const float *oa_row = d->oms_alpha ? (const float *)d->oms_alpha + (size_t)t * d->n_oms_alpha : nullptr;
         hipLaunchKernelGGL((layered_minsum_iter<1, FORM_OMS>), dim3(w.tiles), dim3(kWave), 0, s, g, w.postT, w.msgs, w.urows,
                            beta_row, (const int *)d->beta_slot, oa_row, (const int *)d->oms_alpha_slot, bitsT);
@@ -242,15 +272,16 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
     const GraphDev g = d->g->dev();
     const int T = d->T, tiles = w.tiles, vc = (g.n + JT - 1) / JT;
     const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
-    const bool layered = kind == kJointLayered, oms = d->form == LDPC_C2V_OMS, rcq = d->form == LDPC_C2V_RCQ;
+    const bool layered = kind == kJointLayered || kind == kJointLayeredSte, oms = d->form == LDPC_C2V_OMS, rcq = d->form == LDPC_C2V_RCQ;
     const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
     const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
     const size_t nrow_bytes = (size_t)tiles * W * g.n * sizeof(float);
-    // flooding: the LLR rows stay; layered: P = llr, R = +0 ("no message yet"), as the decode starts
+    // flooding: the LLR rows stay; layered: P = llr, R = +0 ("no message yet"; the RCQ walk reads no code in iteration 0),
+    // as the decode starts
     hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, llr, layered ? w.postT : w.llrT, (long long)batch, g.n, vc);
     if (targets)
         hipLaunchKernelGGL((transpose_in<float, VEC>), tgrid, blk, 0, s, targets, w.yT, (long long)batch, g.n, vc);
-    if (layered) HIP_TRY(hipMemsetAsync(w.msgs, 0, (size_t)tiles * W * g.E * sizeof(float), s));
+    if (kind == kJointLayered) HIP_TRY(hipMemsetAsync(w.msgs, 0, (size_t)tiles * W * g.E * sizeof(float), s));
     // rows no step writes: alpha_T-1, and every alpha row where the variable update has no parameter (the offset forms,
     // the layered schedule)
     if (grad_alpha) {
@@ -304,7 +335,7 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
         const bool alpha_step = !layered && !oms && t >= 1 && grad_alpha;
         const bool first = !layered && t == 0;            // v2c_0 = llr; the layered u rows are messages in every iteration
         const float *src = layered ? w.urows : first ? w.llrT : (const float *)w.v2c[t & 1];
-        const uint8_t *codes = rcq ? (const uint8_t *)w.c2v[t & 1] : nullptr;
+        const uint8_t *codes = !rcq ? nullptr : layered ? (const uint8_t *)w.codes : (const uint8_t *)w.c2v[t & 1];
         const float *beta_row = (const float *)d->beta + (size_t)t * d->n_beta;
         float *gedge_out = (grad_llr || alpha_step) ? w.gedge : nullptr;
         float *goa = oa_grad ? w.goa : nullptr;
@@ -357,13 +388,13 @@ size_t joint_workspace_bytes(const ldpc_decoder *d, int64_t batch, int kind)
     return carve_joint(d, batch, nullptr, kind).total;
 }
 
-// ldpc_train_joint, ldpc_train_joint_ste and ldpc_train_joint_layered: the same argument rules
+// ldpc_train_joint, ldpc_train_joint_ste, ldpc_train_joint_layered and ldpc_train_joint_layered_ste: the same argument rules
 int train_joint_entry(const ldpc_decoder *d, int kind, const void *llr, const void *targets, int64_t batch,
                       const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
                       void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
                       size_t workspace_bytes, void *stream)
 {
-    const bool ste = kind == kJointSte, layered = kind == kJointLayered;
+    const bool ste = kind == kJointSte, layered = kind == kJointLayered || kind == kJointLayeredSte;
     if (int rc = joint_supported(d, kind)) return rc;
     if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
     if (d->T < 1) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs at least one iteration");
@@ -507,6 +538,20 @@ int ldpc_train_joint_layered(const ldpc_decoder *d, const void *llr, const void 
 {
     return train_joint_entry(d, kJointLayered, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior,
                              grad_beta, grad_alpha, grad_oms_alpha, grad_llr, workspace, workspace_bytes, stream);
+}
+
+size_t ldpc_train_joint_layered_ste_workspace_bytes(const ldpc_decoder *d, int64_t batch)
+{
+    return joint_workspace_bytes(d, batch, kJointLayeredSte);
+}
+
+int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                                 const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                                 void *grad_beta, void *grad_alpha, void *grad_llr, void *workspace,
+                                 size_t workspace_bytes, void *stream)
+{
+    return train_joint_entry(d, kJointLayeredSte, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior,
+                             grad_beta, grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -470,6 +470,20 @@ class DecodeEngine:
     def train_joint_layered_workspace_bytes(self, batch: int) -> int:
         return int(self._lib.ldpc_train_joint_layered_workspace_bytes(self.handle, int(batch)))
 
+    def train_joint_layered_ste_workspace_bytes(self, batch: int) -> int:
+        return int(self._lib.ldpc_train_joint_layered_ste_workspace_bytes(self.handle, int(batch)))
+
+    def train_joint_layered_ste(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                                iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
+                                want_grad_llr: bool = False) -> dict:
+        """train_joint() of the quantised decoder under the paper's layered schedule (ldpc_train_joint_layered_ste): the
+        fixed-T layered W-RCQ decode, unchanged, one iteration per launch, with the layered posterior-local gradients of J
+        formed through the straight-through rule of include/ldpc_hip.h (iteration t's loss reaches beta_t and the LLRs
+        through the check update that wrote each message; gradient 1 through the quantiser below its top level, 0 where
+        the code saturated).  Same arguments and the same dict as train_joint_ste; "grad_alpha" (the table the schedule
+        does not use) is all zero.  NotImplementedError for every other decoder."""
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="layered_ste")
+
     def train_joint_layered(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                             iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
                             want_grad_llr: bool = False) -> dict:
@@ -504,7 +518,8 @@ class DecodeEngine:
     # kind -> (entry point, its workspace-bytes function, the entry point takes grad_oms_alpha)
     _JOINT_ENTRY = {"minsum": ("ldpc_train_joint", "ldpc_train_joint_workspace_bytes", True),
                     "ste": ("ldpc_train_joint_ste", "ldpc_train_joint_ste_workspace_bytes", False),
-                    "layered": ("ldpc_train_joint_layered", "ldpc_train_joint_layered_workspace_bytes", True)}
+                    "layered": ("ldpc_train_joint_layered", "ldpc_train_joint_layered_workspace_bytes", True),
+                    "layered_ste": ("ldpc_train_joint_layered_ste", "ldpc_train_joint_layered_ste_workspace_bytes", False)}
 
     def _train_joint(self, llr, targets, iteration_weights, want_grads, want_grad_llr, kind: str) -> dict:
         entry, ws_bytes, has_goa = self._JOINT_ENTRY[kind]

@@ -39,8 +39,8 @@ then hard decisions (P < 0) and the syndrome; with early_stop a codeword that sa
 posteriors, iterations t+1.  beta is indexed exactly as in the flooding forward (same slots and tables, all four sharing
 types).  alpha is NOT used: a layered update has no separate variable-node sum for it to scale.  Posteriors are fp32;
 ``bv`` stays stored and unused.  With every beta 1.0 the result is bit-identical to RCQMinSumDecoder(layered="paper").
-Every other value of ``layered`` (True included) runs the flooding decode, as the reference does.  The layered schedule
-has no backward pass.
+Every other value of ``layered`` (True included) runs the flooding decode, as the reference does.  ``forward`` of the
+layered schedule has no backward pass; ``joint_posterior_loss`` trains it (below).
 
 Training the flooding ``WeightedRCQDecoder`` (an extension; under the reference's autograd the quantiser is a chain of
 ``torch.where`` over comparisons, rcq_decoder.py:59-91, and beta never receives a gradient): with
@@ -51,6 +51,14 @@ loss (as the min-sum decoders' ``joint_posterior_loss``) with the quantiser trea
     d c2v / d m := 1  where the code the forward wrote lies below the top level (the dead zone included)
                    0  where it saturated,      m = beta_t[slot(e)] * sign product * min
 (include/ldpc_hip.h ldpc_train_joint_ste).  Without the option the decoder refuses to train, as before.
+
+Training ``WeightedRCQDecoder(layered="paper")``: ``joint_posterior_loss`` needs BOTH ``quantizer_gradient="straight_through"``
+and ``layered_gradient="posterior_local"`` (each a keyword-only constructor argument or a keyword of the call; the call's
+value wins) and refuses with either missing.  The forward is the fixed-T layered decode above, bit for bit; iteration t's
+loss reaches beta_t and the LLRs through the one check update that wrote each message -- P_t[v] = llr_v + the messages at v,
+u = llr_v + a constant, d Q^-1(Q(m)) / d m by the rule above on the code the update stored -- nothing earlier and nothing
+through another check of the same iteration; alpha, which the schedule does not use, gets a zero gradient
+(include/ldpc_hip.h ldpc_train_joint_layered_ste).  ``layered_gradient`` on a flooding W-RCQ decoder is a ValueError.
 """
 
 from __future__ import annotations
@@ -202,7 +210,7 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
 
     def __init__(self, code: LDPCCode, bc: int, bv: int, quantizer_params: List[Tuple[float, float]],
                  weight_sharing_type: int = 2, max_iterations: int = 50, layered: bool = False, *,
-                 quantizer_gradient=None):
+                 quantizer_gradient=None, layered_gradient=None):
         super().__init__()
         import autograd_bridge as ab
         self.bc = bc
@@ -210,6 +218,8 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
         self.layered = layered            # stored; forward ignores it like the reference's, except "paper" (module docstring)
         # how joint_posterior_loss differentiates the quantiser: None (it refuses) or "straight_through"
         self.quantizer_gradient = ab.check_quantizer_gradient(quantizer_gradient)
+        # how joint_posterior_loss differentiates the layered schedule (layered="paper" only): None (it refuses) or "posterior_local"
+        self.layered_gradient = ab.check_layered_gradient(layered_gradient, self._schedule_name())
         self.quantizers = [NonUniformQuantizer(bc, C, gamma) for C, gamma in quantizer_params]
         self._init_sharing(code, weight_sharing_type, max_iterations)
         logger.info(f"Initialized Weighted RCQ decoder: bc={bc}, bv={bv}, "
@@ -224,6 +234,10 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
         import _native as nat
         return nat.SCHED_LAYERED if isinstance(self.layered, str) and self.layered == "paper" else nat.SCHED_FLOODING
 
+    def _schedule_name(self) -> str:
+        """the schedule in the min-sum decoders' words (autograd_bridge.check_layered_gradient)"""
+        return "layered" if isinstance(self.layered, str) and self.layered == "paper" else "flooding"
+
     def _extra_key(self):
         return (_threshold_table(self.quantizers).tobytes(), self._schedule())
 
@@ -234,28 +248,34 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
                     thresholds=_threshold_table(self.quantizers),
                     q_of_iter=_quantizer_schedule(len(self.quantizers), self.max_iterations))
 
-    def joint_posterior_loss(self, llr, targets=None, iteration_weights=None, device=None, *, quantizer_gradient=None):
+    def joint_posterior_loss(self, llr, targets=None, iteration_weights=None, device=None, *, quantizer_gradient=None,
+                             layered_gradient=None):
         """Posterior joint training of the quantised decoder.  ``quantizer_gradient`` (default: the constructor's) names
         the estimator the quantiser is differentiated with: None -- the RCQ quantiser passes no gradient, so there is
-        nothing to train through (NotImplementedError); "straight_through" -- the decoder's own fixed-T flooding decode
+        nothing to train through (NotImplementedError); "straight_through" -- the decoder's own fixed-T decode
         with the loss of ``Neural2DMinSumDecoder.joint_posterior_loss`` and the rule of the module docstring.
+        ``layered_gradient`` (default: the constructor's): ``layered="paper"`` trains only with "posterior_local" as well
+        (NotImplementedError without it); any value but None on a flooding decoder is a ValueError.
         -> (loss 0-d, loss_per_iteration [T], bits int32, posterior of the last iteration)"""
         import autograd_bridge as ab
         how = ab.check_quantizer_gradient(self.quantizer_gradient if quantizer_gradient is None else quantizer_gradient)
+        lay = ab.check_layered_gradient(self.layered_gradient if layered_gradient is None else layered_gradient,
+                                        self._schedule_name())
         if how is None:
             raise NotImplementedError("WeightedRCQDecoder has no gradient path: the RCQ quantiser passes no gradient "
                                       "(quantizer_gradient=\"straight_through\" trains through it with that estimator)")
         if not isinstance(llr, torch.Tensor):
             raise TypeError("llr must be a torch.Tensor")
         ab.check_joint_args(self.code.n, int(self.max_iterations), llr, targets, iteration_weights)
-        import _native as nat
-        if self._schedule() != nat.SCHED_FLOODING:
-            raise NotImplementedError("the straight-through joint loss exists for the flooding schedule only "
-                                      "(layered=\"paper\" has no gradient path)")
+        paper = self._schedule_name() == "layered"
+        if paper and lay is None:
+            raise NotImplementedError("WeightedRCQDecoder(layered=\"paper\") has no gradient path without "
+                                      "layered_gradient=\"posterior_local\": the straight-through joint loss alone exists "
+                                      "for the flooding schedule")
         eng = self._get_engine(llr.device if llr.is_cuda else device)
         bt, at = self._sharing_layout().tables_torch(self.beta_weights, self.alpha_weights, int(self.max_iterations),
                                                      self._beta_default, self._alpha_default)
-        return ab.joint_loss_ste(bt, at, eng, llr, targets, iteration_weights)
+        return ab.joint_loss_ste(bt, at, eng, llr, targets, iteration_weights, layered=paper)
 
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):
         """

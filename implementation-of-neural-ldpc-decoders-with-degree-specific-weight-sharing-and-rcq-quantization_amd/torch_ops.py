@@ -43,6 +43,11 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
      alpha_t and the LLRs through the check update that wrote each message, the variable's other messages held constant.  The
      variable-side alpha of the normalised form is not used by the schedule: its gradient is all zero.
 
+  ldpc::rcq_layered_joint_loss(... the arguments of rcq_joint_loss ...) -> the same seven outputs
+     the same for ``WeightedRCQDecoder(layered="paper")`` (ldpc_train_joint_layered_ste): the forward is its fixed-T layered decode
+     bit for bit; the gradients are layered posterior-local with the straight-through rule on the code each check update wrote.
+     alpha is not used by the schedule: its gradient is all zero.
+
 ``engine`` is an integer handle of a live ``engine.DecodeEngine`` (``engine_handle(eng)``): operator schemas
 carry tensors and scalars, and the native decoder handle is neither.  There is no CPU implementation: the
 ops exist for ROCm tensors only and fail loudly otherwise (no fallback).
@@ -219,7 +224,8 @@ minsum_decode_train.register_autograd(_train_backward, setup_context=_train_setu
 
 # ------------------------------------------------------------------------------------------ posterior joint training
 def _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, method):
-    """the three joint-loss operators; `method`: the engine's train_joint | train_joint_ste | train_joint_layered"""
+    """the four joint-loss operators; `method`: the engine's train_joint | train_joint_ste | train_joint_layered |
+    train_joint_layered_ste"""
     eng = _engine(engine)
     restore = _with_tables(eng, _np_table(beta), _np_table(alpha), alpha_is_oms)
     try:
@@ -271,6 +277,17 @@ def rcq_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: 
     return _joint(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr, "train_joint_ste")
 
 
+@torch.library.custom_op("ldpc::rcq_layered_joint_loss", mutates_args=())
+def rcq_layered_joint_loss(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, iteration_weights: Tensor,
+                           engine: int, want_grads: bool = True,
+                           want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """rcq_joint_loss of the quantised decoder under the paper's layered schedule (ldpc_train_joint_layered_ste): the fixed-T
+    layered W-RCQ decode, its per-iteration loss, and the layered straight-through gradients d loss/d beta [T, Sb],
+    d loss/d alpha [T, Sa] (the unused table, all zero), d loss/d llr [B, n]"""
+    return _joint(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr,
+                  "train_joint_layered_ste")
+
+
 @minsum_layered_joint_loss.register_fake
 @minsum_joint_loss.register_fake
 def _joint_fake(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads=True, want_grad_llr=False):
@@ -286,8 +303,9 @@ def _joint_fake(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_o
 
 
 # the dispatcher drops trailing arguments that equal their defaults, so a fake cannot read the two flags from the tail of
-# *args without knowing whether alpha_is_oms (no default) precedes them: the quantised operator, which has none, binds its
-# own signature and calls the one fake
+# *args without knowing whether alpha_is_oms (no default) precedes them: the quantised operators, which have none, bind their
+# own signature and call the one fake
+@rcq_layered_joint_loss.register_fake
 @rcq_joint_loss.register_fake
 def _(llr, targets, beta, alpha, iteration_weights, engine, want_grads=True, want_grad_llr=False):
     return _joint_fake(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr)
@@ -315,5 +333,5 @@ def _joint_backward(ctx, g_loss, *_unused):
     return (g_llr, None, g_beta, g_alpha, g_w) + (None,) * (ctx.n_inputs - 5)    # engine and the flags: no gradient
 
 
-for _op in (minsum_joint_loss, minsum_layered_joint_loss, rcq_joint_loss):
+for _op in (minsum_joint_loss, minsum_layered_joint_loss, rcq_joint_loss, rcq_layered_joint_loss):
     _op.register_autograd(_joint_backward, setup_context=_joint_setup)

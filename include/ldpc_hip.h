@@ -70,7 +70,8 @@ enum {
  * table exactly as the flooding RCQ check update does (c2v = deq(quant(beta_t[beta_slot[e]] * s * min)); alpha is not used) --
  * WeightedRCQDecoder(layered="paper"); a table of all 1.0 is the unweighted schedule.  Two kernels with identical results: LDS-resident
  * (posteriors AND the per-edge message codes in LDS; LDPC_MODE_AUTO / RESIDENT when checks have <= 64 edges and at least four one-wave
- * workgroups fit a CU's LDS) and streaming (every other case).
+ * workgroups fit a CU's LDS) and streaming (every other case).  Gradients of the RCQ form under LAYERED: ldpc_train_joint_layered_ste
+ * (below) and nothing else.
  * LAYERED with LDPC_C2V_NMS / LDPC_C2V_OMS (fp32 only) is the same schedule with unquantised messages, the baseline of the quantised
  * one: on the edges of a check u = P - R, min1 / min2 / sign product over the u as in the flooding check update (first minimum is the
  * arg-min, ties keep min2 == min1, sign(0) = 0), r = (beta * min_others) * sign_others (NMS) or sign_others * (relu(min_others - beta)
@@ -257,7 +258,7 @@ int ldpc_train_joint_ste(const ldpc_decoder *d, const void *llr, const void *tar
 /* ---- posterior joint training of the layered min-sum decoders -----------------------------------
  * ldpc_train_joint for the fp32 LDPC_SCHED_LAYERED decoders of LDPC_C2V_NMS / LDPC_C2V_OMS.  LDPC_ERR_UNSUPPORTED for every
  * other decoder, with a message naming the entry point to take: flooding min-sum -> ldpc_train_joint, flooding RCQ ->
- * ldpc_train_joint_ste; the layered RCQ decoders (LAYERED_REF, LAYERED) and float64 have none.  ldpc_train_joint itself keeps
+ * ldpc_train_joint_ste, LAYERED RCQ -> ldpc_train_joint_layered_ste; LAYERED_REF and float64 have none.  ldpc_train_joint itself keeps
  * refusing layered decoders.  Same outputs, same empty-batch / NULL-output / alignment / T < 1 / no-edges rules; scratch
  * ldpc_train_joint_layered_workspace_bytes (256-byte aligned, independent of T).  An extension like the schedule: nothing in
  * the reference executes it, the yardstick is a CPU restatement.
@@ -285,6 +286,41 @@ int ldpc_train_joint_layered(const ldpc_decoder *d, const void *llr, const void 
                              const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
                              void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- posterior joint training of the layered quantised decoder (straight-through estimator) -----
+ * ldpc_train_joint_ste for the fp32 LDPC_C2V_RCQ decoders under LDPC_SCHED_LAYERED (WeightedRCQDecoder(layered="paper")).
+ * LDPC_ERR_UNSUPPORTED for every other decoder, with a message naming the entry point to take: flooding RCQ ->
+ * ldpc_train_joint_ste, layered min-sum -> ldpc_train_joint_layered, flooding min-sum -> ldpc_train_joint; LAYERED_REF and
+ * float64 have none.  The other three entry points keep refusing this decoder.  Argument list and rules of
+ * ldpc_train_joint_ste (empty batch, NULL outputs, alignment, no grad_oms_alpha); scratch
+ * ldpc_train_joint_layered_ste_workspace_bytes: (2E + 4n) * 4 + E bytes per codeword of the 64-codeword tiles plus per-tile
+ * partials, independent of T.  A definition: nothing in the reference executes it, the yardstick is a CPU restatement.
+ *   Forward : the decoder's own fixed-T LAYERED decode, no early stop, one iteration per kernel launch with the posteriors
+ *             and the 1-byte message codes kept in the scratch.  In iteration t, on the edges e = (c, v) of check c:
+ *             u_e = P_v - deq_t'(code_e), t' the iteration that wrote the code (its quantiser is q_of_iter[t-1]; nothing is
+ *             subtracted in iteration 0); min1 / min2 / sign product over the u as in the flooding RCQ check update;
+ *             m_e = +-(beta_t[beta_slot[e]] * raw_e), the product rounded before the sign; code_e = quant_t(m_e) =
+ *             (m_e < 0) * L + level, r_e = deq_t(code_e), P_v = u_e + r_e.  bits and posterior equal
+ *             ldpc_decode(early_stop = 0) bit for bit, and the posterior P_t after the last check of iteration t equals
+ *             ldpc_decode_capped(max_iterations = t + 1, early_stop = 0) bit for bit, on either decode kernel.
+ *   Loss    : that of ldpc_train_joint on P_t, with the seed g_t = w_t * (y - sigmoid(-P_t)) / (B n).
+ *   Gradient: the layered posterior-local rule of ldpc_train_joint_layered composed with the straight-through rule of
+ *             ldpc_train_joint_ste.  P_t[v] = llr_v + sum over the edges e at v of r_t,e;  u_e = llr_v + x_e, x_e a constant;
+ *                 d r_e / d m_e := 1  if (code_t[e] mod L) < L - 1      (below the top level, dead zone included)
+ *                                  0  otherwise                         (saturated)
+ *             with the mask read from the code the walk stored, and m_e differentiated in beta_t and in the |u| of the
+ *             check's other edges by the rules of the flooding RCQ backward (first-index arg-min, a tied second minimum
+ *             split evenly, sgn(0) = 0 and a zero product when another edge is exactly 0, degree 1: product 1 and
+ *             min2 = min1).  J_t reaches beta_t and the LLRs through the one check update that wrote each message -- nothing
+ *             earlier, nothing through another check of the same iteration:
+ *                 d J/d llr_v = sum_t ( g_t[v] + sum over the edges e at v of d J_t/d u_e )
+ *             alpha is not used by the schedule: grad_alpha, when given, is zero-filled [T][n_alpha_slots].
+ * Deterministic: no atomics. */
+size_t ldpc_train_joint_layered_ste_workspace_bytes(const ldpc_decoder *d, int64_t batch);
+int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                                 const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                                 void *grad_beta, void *grad_alpha, void *grad_llr,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);

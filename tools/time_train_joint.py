@@ -3,7 +3,7 @@
 posterior-local HIP gradients, backward scaling, Adam) next to the existing full-backpropagation step (forward with saved
 messages, HIP backward sweeps, Adam) at the same size.
 
-    python tools/time_train_joint.py [--steps 10] [--decoder neural2d|wrcq|layered]
+    python tools/time_train_joint.py [--steps 10] [--decoder neural2d|wrcq|layered|wrcq_layered]
 Prints one JSON line with a result per workload: (1998,1512) Neural-2D type 2 at T = 10 with B = 4096 and 32768, and
 (16200,7200) at T = 20 with B = 1024.  Device events around each step.  Algorithmic HBM bytes of a PJT step, per codeword
 and iteration: forward sweeps 16E + 8n (check: read v2c, write c2v; variable: read c2v + llr, write v2c + posterior), loss
@@ -17,7 +17,12 @@ d/dv2c; variable: codes of t-1 and d/dv2c) -- 28E + 16n against 36E + 16n.
 same workloads (no full-backpropagation step exists for it) and, beside it, the forward alone (the one-wave-per-tile walk
 and the per-iteration loss, no gradient kernels: engine.train_joint_layered(want_grads=False)) -- `forward_share` is that
 time over the step's.  Algorithmic bytes: walk 28E (two passes reading P and R, the second writing P, R and u), posterior
-copy and loss 16n, check backward 12E (u, gathered g_l, write d/du) -- 40E + 16n."""
+copy and loss 16n, check backward 12E (u, gathered g_l, write d/du) -- 40E + 16n.
+--decoder wrcq_layered times the step of WeightedRCQDecoder(layered="paper", quantizer_gradient="straight_through",
+layered_gradient="posterior_local") (type 2, bc = 3, three quantisers) on the same workloads, with `forward_share` as for
+--decoder layered (engine.train_joint_layered_ste(want_grads=False)).  Algorithmic bytes: walk 14E (the held form: one read
+of P and of the 1-byte codes, writing P, codes and u), posterior copy and loss 16n, check backward 13E (u, codes, gathered
+g_l, write d/du) -- 27E + 16n."""
 import argparse, json, os, sys
 os.environ.setdefault("LDPC_TRAIN_MAX_SAVED_BYTES", str(64 << 30))     # let the BPTT step run where the HBM holds it
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,8 +57,10 @@ def run(name, T, B, steps, snr_db, dev, decoder="neural2d"):
     from neural_2d_decoder import Neural2DMinSumDecoder
     from rcq_decoder import WeightedRCQDecoder
     code = codes.load_code(name, max_iterations=T)
-    wrcq, layered = decoder == "wrcq", decoder == "layered"
+    wrcq, layered, wrcq_lay = decoder == "wrcq", decoder == "layered", decoder == "wrcq_layered"
     model = (WeightedRCQDecoder(code, 3, 8, WRCQ_QUANTIZERS, 2, T, quantizer_gradient="straight_through") if wrcq
+             else WeightedRCQDecoder(code, 3, 8, WRCQ_QUANTIZERS, 2, T, layered="paper", quantizer_gradient="straight_through",
+                                     layered_gradient="posterior_local") if wrcq_lay
              else Neural2DMinSumDecoder(code, 2, T, schedule="layered", layered_gradient="posterior_local") if layered
              else Neural2DMinSumDecoder(code, 2, T))
     with torch.no_grad():
@@ -83,19 +90,21 @@ def run(name, T, B, steps, snr_db, dev, decoder="neural2d"):
 
     eng = model._get_engine(dev)
     ms, loss = time_steps(pjt, steps)
-    alg = B * T * ((28 if wrcq else 40 if layered else 36) * g.E + 16 * g.n)
+    alg = B * T * ((28 if wrcq else 40 if layered else 27 if wrcq_lay else 36) * g.E + 16 * g.n)
     ws = (eng.train_joint_ste_workspace_bytes(B) if wrcq else eng.train_joint_layered_workspace_bytes(B) if layered
-          else eng.train_joint_workspace_bytes(B))
-    label = "W-RCQ bc=3" if wrcq else "layered Neural2D" if layered else "Neural2D"
+          else eng.train_joint_layered_ste_workspace_bytes(B) if wrcq_lay else eng.train_joint_workspace_bytes(B))
+    label = "W-RCQ bc=3" if wrcq else "layered Neural2D" if layered else "layered W-RCQ bc=3" if wrcq_lay else "Neural2D"
     out = {"workload": f"{name} {label} type 2, T={T}, batch {B}", "pjt_ms_per_step": ms,
            "pjt_codewords_per_s": B / ms * 1e3, "pjt_algorithmic_GBps": alg / (ms * 1e-3) / 1e9,
            "pjt_workspace_bytes_per_codeword": ws / B, "pjt_loss": loss}
-    if layered:                                            # the forward alone: the walk and the loss, no gradient kernels
+    if layered or wrcq_lay:                                # the forward alone: the walk and the loss, no gradient kernels
+        forward = eng.train_joint_layered if layered else eng.train_joint_layered_ste
+
         def forward_only():
-            return eng.train_joint_layered(llr, want_grads=False)["loss"]
+            return forward(llr, want_grads=False)["loss"]
         ms_f, _ = time_steps(forward_only, steps)
         out.update({"forward_ms_per_step": ms_f, "forward_share": ms_f / ms})
-    if wrcq or layered:                                    # no saved-history path exists for these decoders
+    if wrcq or layered or wrcq_lay:                        # no saved-history path exists for these decoders
         del model, opt, eng
         torch.cuda.empty_cache()
         return out
@@ -118,7 +127,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--snr-db", type=float, default=3.0)
     ap.add_argument("--workload", type=int, default=None, help="run only WORKLOADS[i]")
-    ap.add_argument("--decoder", choices=("neural2d", "wrcq", "layered"), default="neural2d")
+    ap.add_argument("--decoder", choices=("neural2d", "wrcq", "layered", "wrcq_layered"), default="neural2d")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
