@@ -139,7 +139,7 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
-                 "ldpc_debug_resident_kernel")
+                 "ldpc_debug_resident_kernel", "ldpc_debug_min2")
 EXPORTS = PRODUCT_EXPORTS + DEBUG_EXPORTS
 
 _lib = None
@@ -195,6 +195,8 @@ def load():
         lib.ldpc_debug_workspace_layout.argtypes = [vp, i64, i32, vp]
         lib.ldpc_debug_key4.restype = C.c_int
         lib.ldpc_debug_key4.argtypes = [vp, i64, C.c_float, vp, vp, vp, vp]
+        lib.ldpc_debug_min2.restype = C.c_int
+        lib.ldpc_debug_min2.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
         lib.ldpc_debug_resident_c2v.restype = C.c_int
         lib.ldpc_debug_resident_c2v.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp]
         lib.ldpc_debug_compact_layout.restype = C.c_int

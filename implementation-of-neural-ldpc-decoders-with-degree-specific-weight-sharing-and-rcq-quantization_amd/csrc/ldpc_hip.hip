@@ -1664,6 +1664,19 @@ int ldpc_debug_key4(const float *values, int64_t count, float beta, const float 
     return LDPC_OK;
 }
 
+int ldpc_debug_min2(const float *values, int64_t rows, int32_t d, float *m12_chain, uint32_t *par_chain, float *m12_pair,
+                    uint32_t *par_pair, void *stream)
+{
+    if (!values || !m12_chain || !par_chain || !m12_pair || !par_pair || rows <= 0 || d < 1 || d > 32)
+        return fail(LDPC_ERR_ARG, "bad argument");
+    const long long threads = (rows + 1) / 2;
+    if ((threads + 255) / 256 > 0x7fffffffll) return fail(LDPC_ERR_ARG, "too many rows for one launch");
+    hipLaunchKernelGGL(debug_min2, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, values,
+                       (long long)rows, (int)d, m12_chain, par_chain, m12_pair, par_pair);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
 int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int64_t out8[8])
 {
     if (!d || !out8 || batch <= 0) return fail(LDPC_ERR_ARG, "bad argument");

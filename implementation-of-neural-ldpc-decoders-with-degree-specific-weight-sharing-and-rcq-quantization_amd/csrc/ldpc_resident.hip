@@ -271,6 +271,117 @@ __device__ __forceinline__ void res_select4_out(float (&y)[4], float x0, float x
         : "vcc");
 }
 
+// Pass 1 of the check phase: the running two smallest magnitudes (m1 <= m2) of a check's inputs.
+// One value at a time: m2' = med3(a, m1, m2), m1' = med3(a, m1, -inf) = min(a, m1) as ONE v_med3 (`ninf` is -inf in a
+// register the optimiser cannot see through: a literal -inf is folded into canonicalise + v_min, three instructions).
+__device__ __forceinline__ void res_min2_step(float &m1, float &m2, float x, float ninf)
+{
+    const float a = __builtin_fabsf(x);
+    m2 = __builtin_amdgcn_fmed3f(a, m1, m2);
+    m1 = __builtin_amdgcn_fmed3f(a, m1, ninf);
+}
+// Two values a, b of TWO codewords at a time: the two smallest of {m1, m2, a, b} are min3(m1, a, b) and
+// min(m2, med3(m1, a, b)) -- the second smallest is m2 or the middle one of the other three, whichever is smaller.
+// Three instructions of the slow class per two values instead of four, and the same bits for every input without a
+// NaN: the two smallest elements of a multiset do not depend on how they are found (a magnitude has no -0).
+// Written as asm because fminf in C gets a canonicalising v_max in front of it under IEEE mode.
+__device__ __forceinline__ void res_min2_pair2(float &m1a, float &m2a, float &m1b, float &m2b, float xa0, float xa1,
+                                               float xb0, float xb1)
+{
+    float ta, tb;
+    asm("v_med3_f32 %4, %0, |%6|, |%8|\n\t"
+        "v_med3_f32 %5, %2, |%7|, |%9|\n\t"
+        "v_min3_f32 %0, %0, |%6|, |%8|\n\t"
+        "v_min3_f32 %2, %2, |%7|, |%9|\n\t"
+        "v_min_f32_e32 %1, %1, %4\n\t"
+        "v_min_f32_e32 %3, %3, %5"
+        : "+v"(m1a), "+v"(m2a), "+v"(m1b), "+v"(m2b), "=&v"(ta), "=&v"(tb)
+        : "v"(xa0), "v"(xa1), "v"(xb0), "v"(xb1));
+}
+// the same for one codeword (the fp32 kernels with one codeword per workgroup, G == 1)
+__device__ __forceinline__ void res_min2_pair(float &m1, float &m2, float xa, float xb)
+{
+    float t;
+    asm("v_med3_f32 %2, %0, |%3|, |%4|\n\t"
+        "v_min3_f32 %0, %0, |%3|, |%4|\n\t"
+        "v_min_f32_e32 %1, %1, %2"
+        : "+v"(m1), "+v"(m2), "=&v"(t)
+        : "v"(xa), "v"(xb));
+}
+// sign accumulator over two values: ONE v_bitop3_b32 (a ^ b ^ c = 0x96) instead of two v_xor_b32
+__device__ __forceinline__ uint32_t res_xor3(uint32_t acc, float xa, float xb)
+{
+    return __builtin_amdgcn_bitop3_b32(acc, __float_as_uint(xa), __float_as_uint(xb), 0x96);
+}
+// Two edges (xa, xb: the slots of the codeword pair) into the running state of G codewords.  FORM_RCQ keeps the one-value
+// chain for the magnitudes: DESIGN.md 4 defines its NaN behaviour, which rests on v_med3's NaN rule; the parity is the
+// same bits in either form.
+template <int FORM, int G>
+__device__ __forceinline__ void res_absorb2(float (&m1)[G], float (&m2)[G], uint32_t (&sacc)[G], const Pack<float, G> &xa,
+                                            const Pack<float, G> &xb, float ninf)
+{
+#pragma unroll
+    for (int g = 0; g < G; ++g) sacc[g] = res_xor3(sacc[g], xa.x[g], xb.x[g]);
+    if constexpr (FORM == FORM_RCQ) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            res_min2_step(m1[g], m2[g], xa.x[g], ninf);
+            res_min2_step(m1[g], m2[g], xb.x[g], ninf);
+        }
+    } else if constexpr (G == 2) {
+        res_min2_pair2(m1[0], m2[0], m1[1], m2[1], xa.x[0], xa.x[1], xb.x[0], xb.x[1]);
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; ++g) res_min2_pair(m1[g], m2[g], xa.x[g], xb.x[g]);
+    }
+}
+
+// test hook (ldpc_debug_min2): both forms of pass 1 on rows of d arbitrary values, two rows per thread as the two
+// codewords of a pair -- the one-value chain with a two-input xor, and the edges in pairs with an odd last one through
+// the one-value step (the walk of res_check_body_uniform and res_check_body).  No degree-1 rule is applied.
+__global__ void debug_min2(const float *__restrict__ vals, long long rows, int d, float *__restrict__ m12_chain,
+                           uint32_t *__restrict__ par_chain, float *__restrict__ m12_pair, uint32_t *__restrict__ par_pair)
+{
+    using P = Pack<float, 2>;
+    const long long r0 = 2 * ((long long)blockIdx.x * blockDim.x + threadIdx.x);
+    if (r0 >= rows) return;
+    const bool two = r0 + 1 < rows;
+    const float *ra = vals + r0 * d, *rb = vals + (two ? r0 + 1 : r0) * d;
+    float ninf = -inf_of<float>();
+    asm volatile("" : "+v"(ninf));
+    float c1[2], c2[2], p1[2], p2[2];
+    uint32_t cs[2], ps[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        c1[g] = c2[g] = p1[g] = p2[g] = inf_of<float>();
+        cs[g] = ps[g] = 0;
+    }
+    for (int t = 0; t < d; ++t) {
+        const P v{{ra[t], rb[t]}};
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            cs[g] ^= __float_as_uint(v.x[g]);
+            res_min2_step(c1[g], c2[g], v.x[g], ninf);
+        }
+    }
+    int t = 0;
+    for (; t + 1 < d; t += 2) res_absorb2<FORM_NMS, 2>(p1, p2, ps, P{{ra[t], rb[t]}}, P{{ra[t + 1], rb[t + 1]}}, ninf);
+    if (t < d) {
+        const P v{{ra[t], rb[t]}};
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            ps[g] ^= __float_as_uint(v.x[g]);
+            res_min2_step(p1[g], p2[g], v.x[g], ninf);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        if (g == 1 && !two) break;
+        m12_chain[2 * (r0 + g)] = c1[g]; m12_chain[2 * (r0 + g) + 1] = c2[g]; par_chain[r0 + g] = cs[g];
+        m12_pair[2 * (r0 + g)] = p1[g];  m12_pair[2 * (r0 + g) + 1] = p2[g];  par_pair[r0 + g] = ps[g];
+    }
+}
+
 // the same for FOUR edges of one float64 codeword: compares on the 64-bit values, selects and sign on the 32-bit halves
 __device__ __forceinline__ void res_select4_f64(double (&x)[4], double m1, double o1, double o2, uint32_t sign_v)
 {
@@ -357,15 +468,17 @@ __device__ __forceinline__ void res_check_body_uniform(int p, int dc, unsigned c
         P v[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) v[k] = lds_load<P>(addr + k * stride);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
+        // the edges of a group in pairs (res_absorb2); a group of one -- the odd tail, and each spread edge of a
+        // mixed-degree wave -- takes the one-value step
+        if constexpr (K == 1) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                const float a = __builtin_fabsf(v[k].x[g]);
-                sacc[g] ^= __float_as_uint(v[k].x[g]);
-                m2[g] = __builtin_amdgcn_fmed3f(a, m1[g], m2[g]);
-                m1[g] = __builtin_amdgcn_fmed3f(a, m1[g], ninf);
+                sacc[g] ^= __float_as_uint(v[0].x[g]);
+                res_min2_step(m1[g], m2[g], v[0].x[g], ninf);
             }
+        } else {
+#pragma unroll
+            for (int k = 0; k < K; k += 2) res_absorb2<FORM, G>(m1, m2, sacc, v[k], v[k + 1], ninf);
         }
     });
 
@@ -405,7 +518,8 @@ __device__ __forceinline__ void res_check_body_uniform(int p, int dc, unsigned c
     });
 }
 
-template <int G, int FORM, bool BPC, int NL, int MS, typename T, bool SPLIT = false>
+// PAIRS = false keeps pass 1 one edge at a time: the compact OMS kernels, which spill more with the pair form
+template <int G, int FORM, bool BPC, int NL, int MS, typename T, bool SPLIT = false, bool PAIRS = true>
 __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned char *smem, int p, int dc,
                                                T b_check, const T *__restrict__ beta_row,
                                                const T *__restrict__ oa_row, const float (&th)[8],
@@ -503,18 +617,39 @@ __device__ __forceinline__ void res_check_body(const ResidentPlan &pl, unsigned 
         m1[g] = inf_of<float>(); m2[g] = inf_of<float>(); sacc[g] = 0; nz[g] = 0;
     }
     // generic form (any degree, per-lane trip counts, per-edge beta, OMS): pass 1 streams the slots, pass 2 re-reads them
-#pragma unroll 4
-    for (int t = 0; t < trip; ++t) {
-        const P v = lds_load<P>(base + t * stride);
+    // the edges in pairs (res_absorb2), an odd last one through the one-value step.  One pair per trip: with two pairs (four
+    // loads) in flight the compact RCQ kernels at four levels spilled one VGPR more than the parent's loop
+    if constexpr (PAIRS) {
+        int t = 0;
+#pragma unroll 1
+        for (; t + 1 < trip; t += 2) {
+            const unsigned addr = base + t * stride;
+            const P va = lds_load<P>(addr), vb = lds_load<P>(addr + stride);
+            if (FORM == FORM_OMS) {
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const float a = __builtin_fabsf(v.x[g]);
-            sacc[g] ^= __float_as_uint(v.x[g]);
-            if (FORM == FORM_OMS) nz[g] += (a == 0.0f) ? 1u : 0u;
-            m2[g] = __builtin_amdgcn_fmed3f(a, m1[g], m2[g]);
-            m1[g] = __builtin_amdgcn_fmed3f(a, m1[g], ninf);               // = min(a, min1) as ONE v_med3 (a
-                                                                           // literal -inf is folded into
-                                                                           // canonicalise + v_min: 3 ops)
+                for (int g = 0; g < G; ++g) nz[g] += ((va.x[g] == 0.0f) ? 1u : 0u) + ((vb.x[g] == 0.0f) ? 1u : 0u);
+            }
+            res_absorb2<FORM, G>(m1, m2, sacc, va, vb, ninf);
+        }
+        if (t < trip) {
+            const P v = lds_load<P>(base + t * stride);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                sacc[g] ^= __float_as_uint(v.x[g]);
+                if (FORM == FORM_OMS) nz[g] += (v.x[g] == 0.0f) ? 1u : 0u;
+                res_min2_step(m1[g], m2[g], v.x[g], ninf);
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int t = 0; t < trip; ++t) {
+            const P v = lds_load<P>(base + t * stride);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                sacc[g] ^= __float_as_uint(v.x[g]);
+                if (FORM == FORM_OMS) nz[g] += (__builtin_fabsf(v.x[g]) == 0.0f) ? 1u : 0u;
+                res_min2_step(m1[g], m2[g], v.x[g], ninf);
+            }
         }
     }
     if constexpr (SPLIT) group_combine<G, float>(gs, m1, m2, sacc, nz);
@@ -680,7 +815,8 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
         // whatever the mix of degrees.  At two workgroups per CU it measured fastest against scalar per-degree forms
         // (DESIGN.md 3c table); at six waves per SIMD the loop control it spends in the vector unit counts, and the compact
         // kernels of the select form take res_check_body_uniform above instead.
-        res_check_body<G, FORM, BPC, NL, MS, T>(pl, smem, p, dc, b_check, beta_row, oa_row, th, thr, n_levels, rcq_zero0);
+        res_check_body<G, FORM, BPC, NL, MS, T, false, !(CPT && FORM == FORM_OMS)>(pl, smem, p, dc, b_check, beta_row, oa_row, th,
+                                                                                   thr, n_levels, rcq_zero0);
     }
 }
 
@@ -978,8 +1114,13 @@ __device__ __forceinline__ void res_syndrome_slots(const ResidentPlan &pl, unsig
         int dcw;
         unsigned x = 0;
         if (wave_uniform(dc, dcw)) {
-#pragma unroll 8
-            for (int t = 0; t < dcw; ++t) x ^= lds_load<unsigned>((unsigned)(t * pl.mstride + p) * kSlot);
+            // two slots per step: x ^ a ^ b is one v_bitop3_b32
+            int t = 0;
+#pragma unroll 4
+            for (; t + 1 < dcw; t += 2)
+                x = __builtin_amdgcn_bitop3_b32(x, lds_load<unsigned>((unsigned)(t * pl.mstride + p) * kSlot),
+                                                lds_load<unsigned>((unsigned)((t + 1) * pl.mstride + p) * kSlot), 0x96);
+            if (t < dcw) x ^= lds_load<unsigned>((unsigned)(t * pl.mstride + p) * kSlot);
         } else {
             for (int t = 0; t < dc; ++t) x ^= lds_load<unsigned>((unsigned)(t * pl.mstride + p) * kSlot);
         }

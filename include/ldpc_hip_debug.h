@@ -90,6 +90,14 @@ int ldpc_debug_compact_banks(const ldpc_decoder *d, int32_t n, int32_t m, int32_
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,
                     uint8_t *keys_compare, void *stream);
 
+/* Pass 1 of the resident check phase keeps the two smallest magnitudes m1 <= m2 and the xor of the bit patterns of a
+ * check's inputs.  Runs BOTH device forms of it on values[rows][d] (device pointers, 1 <= d <= 32, row-major fp32, no
+ * NaN): the one-value chain, and the edges in pairs (min3 / med3 / min and a three-input xor, csrc/ldpc_resident.hip
+ * res_absorb2) with an odd last one through the one-value step.  m12_*[rows][2] receive { m1, m2 }, par_*[rows] the xor
+ * word (bit 31 is the sign parity).  No degree-1 rule is applied: d == 1 leaves m2 = +inf. */
+int ldpc_debug_min2(const float *values, int64_t rows, int32_t d, float *m12_chain, uint32_t *par_chain, float *m12_pair,
+                    uint32_t *par_pair, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
