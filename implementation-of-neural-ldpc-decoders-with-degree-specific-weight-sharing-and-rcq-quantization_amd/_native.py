@@ -42,7 +42,7 @@ class NativeEngineError(RuntimeError):
 
 # the one compiled unit first, then everything it includes
 SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
-           "ldpc_train_host.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
+           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
 
 
 def _source_files():
@@ -126,6 +126,13 @@ class DecoderDesc(C.Structure):
                 ("schedule", C.c_int32)]
 
 
+class SimDesc(C.Structure):
+    """ldpc_sim_desc of include/ldpc_hip.h: one SNR point of ldpc_simulate"""
+    _fields_ = [("seed", C.c_uint64), ("stream_id", C.c_uint32), ("first_frame", C.c_uint64),
+                ("scale", C.c_float), ("shift", C.c_float), ("codeword_packed", C.c_void_p),
+                ("max_frames", C.c_int64), ("max_errors", C.c_int64), ("block", C.c_int64), ("poll_blocks", C.c_int32)]
+
+
 # every symbol include/ldpc_hip.h declares (tests check the library exports them all) ...
 PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info", "ldpc_decoder_create",
                    "ldpc_decoder_set_mode", "ldpc_decoder_info",
@@ -135,11 +142,12 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_train_joint_workspace_bytes", "ldpc_train_joint",
                    "ldpc_train_joint_ste_workspace_bytes", "ldpc_train_joint_ste",
                    "ldpc_train_joint_layered_workspace_bytes", "ldpc_train_joint_layered",
-                   "ldpc_train_joint_layered_ste_workspace_bytes", "ldpc_train_joint_layered_ste")
+                   "ldpc_train_joint_layered_ste_workspace_bytes", "ldpc_train_joint_layered_ste",
+                   "ldpc_channel_awgn", "ldpc_sim_count", "ldpc_simulate_workspace_bytes", "ldpc_simulate")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
-                 "ldpc_debug_resident_kernel", "ldpc_debug_min2")
+                 "ldpc_debug_resident_kernel", "ldpc_debug_min2", "ldpc_debug_philox")
 EXPORTS = PRODUCT_EXPORTS + DEBUG_EXPORTS
 
 _lib = None
@@ -231,6 +239,17 @@ def load():
         lib.ldpc_train_joint_layered_ste_workspace_bytes.argtypes = [vp, i64]
         lib.ldpc_train_joint_layered_ste.restype = C.c_int
         lib.ldpc_train_joint_layered_ste.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+        u32, u64, f32 = C.c_uint32, C.c_uint64, C.c_float
+        lib.ldpc_channel_awgn.restype = C.c_int
+        lib.ldpc_channel_awgn.argtypes = [vp, i64, i32, u64, u32, u64, f32, f32, vp, vp]
+        lib.ldpc_sim_count.restype = C.c_int
+        lib.ldpc_sim_count.argtypes = [vp, vp, vp, i64, i32, vp, i64, i64, vp]
+        lib.ldpc_simulate_workspace_bytes.restype = C.c_size_t
+        lib.ldpc_simulate_workspace_bytes.argtypes = [vp, i64]
+        lib.ldpc_simulate.restype = C.c_int
+        lib.ldpc_simulate.argtypes = [vp, C.POINTER(SimDesc), vp, vp, C.c_size_t, vp]
+        lib.ldpc_debug_philox.restype = C.c_int
+        lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p
         lib.ldpc_last_error.argtypes = []
         lib.ldpc_abi_version.restype = C.c_int

@@ -1651,6 +1651,9 @@ int ldpc_decode_capped(const ldpc_decoder *d, const void *llr, int64_t batch, in
 // ---- gradient (training) path: ldpc_train_host.hip over the kernels of ldpc_train.hip --------------------------
 #include "ldpc_train_host.hip"
 
+// ---- on-device Monte-Carlo: AWGN channel, error counters, one SNR point (ldpc_channel_awgn / ldpc_sim_count / ldpc_simulate)
+#include "ldpc_sim.hip"
+
 extern "C" {
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

@@ -50,6 +50,57 @@ def _require_gpu(device) -> torch.device:
     return dev
 
 
+def awgn_scale_shift(snr_db: float, llr_convention: str = "decoder"):
+    """(scale, shift) = (2/sigma, +-2/sigma^2) of the BI-AWGN LLR llr = 2 (symbol + sigma z) / sigma^2 at Es/N0 = snr_db
+    (sigma^2 = 10^(-snr_db/10)), computed in double; "reference" is the reference's literal channel (bit 0 -> -1): -shift"""
+    if llr_convention not in ("decoder", "reference"):
+        raise ValueError(f"llr_convention must be 'decoder' or 'reference', got {llr_convention!r}")
+    noise_power = 1.0 / (10.0 ** (float(snr_db) / 10.0))
+    shift = 2.0 / noise_power
+    return 2.0 / noise_power ** 0.5, shift if llr_convention == "decoder" else -shift
+
+
+def pack_codeword(codeword, n: int, device) -> torch.Tensor:
+    """a 0/1 array of length n -> uint8 [ceil(n/8)] on `device`, bit j at byte j/8, bit j%8 (the decoders' packed format)"""
+    c = np.asarray(codeword)
+    if c.shape != (n,) or not np.isin(c, (0, 1)).all():
+        raise ValueError(f"codeword must be a 0/1 array of length {n}")
+    return torch.from_numpy(np.packbits(c.astype(np.uint8), bitorder="little")).to(device)
+
+
+def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, snr_db: Optional[float] = None,
+             scale: Optional[float] = None, shift: Optional[float] = None, codeword=None, device=None) -> torch.Tensor:
+    """LLRs [batch, n] fp32 of frames first_frame .. first_frame + batch - 1 of the counter-based BI-AWGN stream
+    (ldpc_channel_awgn; the stream is defined in include/ldpc_hip.h and INTEGRATION.md): frame f gets the same noise whatever
+    block it is drawn in.  Give snr_db (Es/N0, positive-mean LLRs for the all-zero codeword) or (scale, shift) = (2/sigma,
+    2/sigma^2).  codeword: 0/1 array of length n, or an already packed uint8 tensor on the device; None: all zero."""
+    dev = _require_gpu(device)
+    if (snr_db is None) == (scale is None or shift is None):
+        raise ValueError("give either snr_db or both scale and shift")
+    if snr_db is not None:
+        scale, shift = awgn_scale_shift(snr_db)
+    batch, n = int(batch), int(n)
+    if batch < 0 or n < 1:
+        raise ValueError("batch must be >= 0 and n >= 1")
+    cw = None
+    if codeword is not None:
+        cw = codeword if isinstance(codeword, torch.Tensor) else pack_codeword(codeword, n, dev)
+        if cw.dtype != torch.uint8 or cw.device != dev or cw.numel() != (n + 7) // 8 or not cw.is_contiguous():
+            raise ValueError(f"packed codeword must be a contiguous uint8 tensor of {(n + 7) // 8} bytes on {dev}")
+    lib = nat.load()
+    out = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(lib.ldpc_channel_awgn(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
+                                        int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), float(scale),
+                                        float(shift), None if cw is None else C.c_void_p(cw.data_ptr()),
+                                        C.c_void_p(stream)), "ldpc_channel_awgn")
+    return out
+
+
+SIM_COUNTERS = ("frames", "frame_errors", "bit_errors", "iterations", "done", "blocks_seen")
+
+
 class _NativeGraph:
     """ldpc_graph* for (graph, device); shared by all engines on that graph.  The cache holds the host graph WEAKLY: when
     the TannerGraph object dies its entries are evicted, and the device copy is destroyed (ldpc_graph_destroy) as soon as
@@ -316,6 +367,66 @@ class DecodeEngine:
                                                            p(bits), p(post), p(iters), p(succ), p(packed), p(ws),
                                                            ws.numel(), C.c_void_p(stream)), "ldpc_decode_capped")
         return DecodeResult(bits, post, iters, succ.bool(), packed)
+
+    # ------------------------------------------------------------------ on-device Monte-Carlo
+    def _packed_codeword(self, codeword) -> Optional[torch.Tensor]:
+        if codeword is None or isinstance(codeword, torch.Tensor):
+            return codeword
+        return pack_codeword(codeword, self.graph.n, self.device)
+
+    def sim_count(self, state: torch.Tensor, packed_bits: torch.Tensor, iterations: torch.Tensor, *, max_frames: int,
+                  max_errors: int, codeword=None) -> torch.Tensor:
+        """Fold one decoded block into `state` (int64 [8] on this engine's GPU, zeroed by the caller to start a point:
+        frames, frame_errors, bit_errors, iterations, done, blocks_seen, 0, 0) with the reference's in-order stop rule
+        (ldpc_sim_count).  packed_bits uint8 [B, ceil(n/8)] and iterations int32 [B] as decode(want_packed=True) returns
+        them.  Asynchronous; returns `state`."""
+        n = self.graph.n
+        if state.dtype != torch.int64 or state.shape != (8,) or state.device != self.device or not state.is_contiguous():
+            raise ValueError("state must be a contiguous int64 tensor of 8 words on the engine's device")
+        B = int(packed_bits.shape[0]) if packed_bits.dim() == 2 else -1
+        if packed_bits.dtype != torch.uint8 or B < 0 or packed_bits.shape[1] != (n + 7) // 8 or packed_bits.device != self.device:
+            raise ValueError(f"packed_bits must be uint8 [B, {(n + 7) // 8}] on the engine's device")
+        if iterations.dtype != torch.int32 or iterations.shape != (B,) or iterations.device != self.device:
+            raise ValueError("iterations must be int32 [B] on the engine's device")
+        packed_bits, iterations = packed_bits.contiguous(), iterations.contiguous()
+        cw = self._packed_codeword(codeword)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            nat.check(self._lib.ldpc_sim_count(p(state), p(packed_bits), p(iterations), B, n, p(cw), int(max_frames),
+                                               int(max_errors), C.c_void_p(stream)), "ldpc_sim_count")
+        return state
+
+    def simulate(self, *, seed: int, max_frames: int, max_errors: int, stream_id: int = 0, first_frame: int = 0,
+                 snr_db: Optional[float] = None, scale: Optional[float] = None, shift: Optional[float] = None,
+                 codeword=None, block: int = 65536, poll_blocks: int = 4) -> dict:
+        """One SNR point on the device (ldpc_simulate): blocks of `block` frames of the counter-based AWGN stream, early-stop
+        decode, in-order error counters, one host round trip every `poll_blocks` blocks.  -> {frames, frame_errors,
+        bit_errors, iterations, done, blocks_seen}; all but blocks_seen are independent of block and poll_blocks.
+        Synchronous."""
+        if (snr_db is None) == (scale is None or shift is None):
+            raise ValueError("give either snr_db or both scale and shift")
+        if snr_db is not None:
+            scale, shift = awgn_scale_shift(snr_db)
+        cw = self._packed_codeword(codeword)
+        desc = nat.SimDesc()
+        desc.seed, desc.stream_id = int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1)
+        desc.first_frame = int(first_frame) & (2 ** 64 - 1)
+        desc.scale, desc.shift = float(scale), float(shift)
+        desc.codeword_packed = None if cw is None else cw.data_ptr()
+        desc.max_frames, desc.max_errors = int(max_frames), int(max_errors)
+        desc.block, desc.poll_blocks = int(block), int(poll_blocks)
+        out = np.zeros(8, dtype=np.int64)
+        need = int(self._lib.ldpc_simulate_workspace_bytes(self.handle, max(int(block), 1)))
+        ws = getattr(self, "_sim_ws", None)
+        if ws is None or ws.numel() < need:
+            self._sim_ws = None
+            self._sim_ws = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(self._lib.ldpc_simulate(self.handle, C.byref(desc), nat.ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                              C.c_void_p(stream)), "ldpc_simulate")
+        return {k: int(v) for k, v in zip(SIM_COUNTERS, out)}
 
     # ------------------------------------------------------------------ small host batches (the reference's call shape)
     HOST_BATCH_MAX = 64

@@ -19,6 +19,13 @@ Channel convention (``SimulationConfig.llr_convention``):
   "reference" the literal recipe of simulate_awgn_channel (ldpc_decoder.py:286-302): bit 0 -> -1,
               i.e. NEGATIVE mean LLR, under which the reference's own simulations report FER = 1.0
               (SURVEY 8a-9).
+
+Channel (``SimulationConfig.channel``):
+  "torch"   (default) the ``torch.randn`` draw above, counters reduced with torch and the stop rule applied on the host;
+  "device"  the native Monte-Carlo path: the counter-based AWGN stream of ``engine.awgn_llr`` (seed = ``config.seed``,
+            stream_id = round(snr_db * 1000) mod 2^32, frame f the same noise whatever ``batch_frames`` is), the device-side
+            counters of ``DecodeEngine.sim_count``, and on the LDS-resident engine the whole point in one native call
+            (``DecodeEngine.simulate``).  ``SimulationConfig.codeword`` sends a codeword other than all-zero.
 """
 
 from __future__ import annotations
@@ -29,7 +36,7 @@ import os
 import time
 from concurrent.futures import ThreadPoolExecutor, as_completed
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Tuple, Union
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -60,6 +67,15 @@ class SimulationConfig:
     llr_convention: str = "decoder"
     staged_early_stop: bool = True          # streaming engine: cap the block's first stage, finish stragglers as a small batch
     stage_min_block: int = 1024             # ... only for blocks of at least this many frames
+    channel: str = "torch"                  # "torch": torch.randn draw, host stop rule; "device": the native Monte-Carlo path
+    codeword: Optional[np.ndarray] = None   # 0/1 array of length n sent instead of the all-zero codeword (channel="device" only)
+    poll_blocks: int = 4                    # channel="device", resident engine: blocks between two looks at the counters
+
+    def __post_init__(self):
+        if self.channel not in ("torch", "device"):
+            raise ValueError(f"channel must be 'torch' or 'device', got {self.channel!r}")
+        if self.codeword is not None and self.channel != "device":
+            raise ValueError("a codeword other than all-zero needs channel='device'")
 
 
 class SimulationResult:
@@ -198,6 +214,12 @@ class LDPSimulator:
         from engine import _require_gpu
         device = _require_gpu(self.config.device)
         eng = _engine_of(decoder, device)
+        if self.config.channel == "device":
+            c = self._simulate_device(eng, code.n, float(snr_db), int(max_frames), int(max_errors))
+            frames = c["frames"]
+            return (c["frame_errors"] / frames if frames > 0 else 0.0,
+                    c["bit_errors"] / (frames * code.n) if frames > 0 else 0.0,
+                    c["iterations"] / frames if frames > 0 else 0.0, time.time() - start_time, frames, c["frame_errors"])
         gen = torch.Generator(device=device)
         gen.manual_seed(int(self.config.seed) * 1_000_003 + int(round(snr_db * 1000)))
         frame_errors = bit_errors = total_iterations = total_frames = 0
@@ -219,6 +241,33 @@ class LDPSimulator:
         ber = bit_errors / (total_frames * code.n) if total_frames > 0 else 0.0
         avg_iterations = total_iterations / total_frames if total_frames > 0 else 0.0
         return fer, ber, avg_iterations, time.time() - start_time, total_frames, frame_errors
+
+    def _simulate_device(self, eng, n: int, snr_db: float, max_frames: int, max_errors: int) -> dict:
+        """channel="device": the counters {frames, frame_errors, bit_errors, iterations, ...} of one SNR point.  The
+        LDS-resident engine stops codeword by codeword, so the whole point runs in one native call; on the streaming engine
+        the loop stays here so that _decode_block's staged early stop still applies -- the same stream, the same counters."""
+        import engine as _engine
+        cfg = self.config
+        scale, shift = _engine.awgn_scale_shift(snr_db, cfg.llr_convention)
+        stream_id = int(round(snr_db * 1000)) % (1 << 32)
+        block = max(1, int(cfg.batch_frames))
+        cw = None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, n, eng.device)
+        if eng.info()["engine"] == "resident":
+            return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, scale=scale, shift=shift, codeword=cw,
+                                max_frames=max_frames, max_errors=max_errors, block=block,
+                                poll_blocks=max(1, int(cfg.poll_blocks)))
+        state = torch.zeros(8, dtype=torch.int64, device=eng.device)
+        drawn, cap, host = 0, None, [0] * 8
+        while drawn < max_frames and not host[4]:
+            frames = min(block, max_frames - drawn)
+            llr = _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn, scale=scale,
+                                   shift=shift, codeword=cw, device=eng.device)
+            packed, iters = _decode_block(eng, llr, cap)
+            cap = _next_cap(eng, iters, int(cfg.stage_min_block)) if cfg.staged_early_stop else None
+            eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw)
+            host = state.tolist()                                               # the one read of the block
+            drawn += frames
+        return dict(zip(_engine.SIM_COUNTERS, host))
 
     # ------------------------------------------------------------------------------ sweeps
     def simulate_decoder(self, decoder: Union[Callable, torch.nn.Module], code: LDPCCode,

@@ -48,6 +48,11 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
      bit for bit; the gradients are layered posterior-local with the straight-through rule on the code each check update wrote.
      alpha is not used by the schedule: its gradient is all zero.
 
+  ldpc::awgn_llr(int batch, int n, int seed, int stream_id, int first_frame, float scale, float shift, Tensor? codeword_packed,
+                 Device device) -> Tensor llr
+     the counter-based BI-AWGN channel (ldpc_channel_awgn): fp32 LLRs [batch, n] of frames first_frame .. of stream
+     (seed, stream_id), the same whatever block a frame is drawn in; needs no engine.
+
 ``engine`` is an integer handle of a live ``engine.DecodeEngine`` (``engine_handle(eng)``): operator schemas
 carry tensors and scalars, and the native decoder handle is neither.  There is no CPU implementation: the
 ops exist for ROCm tensors only and fail loudly otherwise (no fallback).
@@ -127,6 +132,19 @@ def _(llr, engine, early_stop, want_posterior):
     dt = _engine(engine).dtype
     return (torch.empty((B, n), dtype=torch.int32), torch.empty((B, n), dtype=dt) if want_posterior else torch.empty((0,), dtype=dt),
             torch.empty((B,), dtype=torch.int32), torch.empty((B,), dtype=torch.bool))
+
+
+@torch.library.custom_op("ldpc::awgn_llr", mutates_args=())
+def awgn_llr(batch: int, n: int, seed: int, stream_id: int, first_frame: int, scale: float, shift: float,
+             codeword_packed: Optional[Tensor], device: torch.device) -> Tensor:
+    import engine
+    return engine.awgn_llr(batch, n, seed=seed, stream_id=stream_id, first_frame=first_frame, scale=scale, shift=shift,
+                           codeword=codeword_packed, device=device)
+
+
+@awgn_llr.register_fake
+def _(batch, n, seed, stream_id, first_frame, scale, shift, codeword_packed, device):
+    return torch.empty((batch, n), dtype=torch.float32, device=device)
 
 
 # ------------------------------------------------------------------------------------------ training path

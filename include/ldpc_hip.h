@@ -322,6 +322,61 @@ int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const v
                                  void *grad_beta, void *grad_alpha, void *grad_llr,
                                  void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- on-device Monte-Carlo (BI-AWGN) ---------------------------------------------------------
+ * The reference's deliverable is FER / BER curves (simulation_framework.py:85-139: draw, decode, count, stop at max_frames
+ * frames or max_errors frame errors).  These entry points keep a whole SNR point on the device.
+ *
+ * ldpc_channel_awgn : llr[batch][n] fp32 (device, 4-byte aligned, row-major) of frames first_frame .. first_frame + batch - 1
+ *   from a counter-based stream -- frame f gets the same noise whatever block it is drawn in, on whatever device.  Needs no
+ *   decoder; asynchronous on `stream`.  Sample j of frame f:
+ *     (x0, x1, x2, x3) = Philox4x32-10(counter = (f & 0xffffffff, f >> 32, j / 4, stream_id),
+ *                                      key = (seed & 0xffffffff, seed >> 32))
+ *       multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds;
+ *     u(x) = fmaf((float)x, 0x1p-32f, 0x1p-33f)   in (0, 1]; the uint -> float conversion rounds to nearest;
+ *     r = sqrtf(-2.0f * logf(u(x0))), theta = 6.2831853071795865f * u(x1), z[4q] = r * cosf(theta), z[4q+1] = r * sinf(theta),
+ *     (x2, x3) give z[4q+2] and z[4q+3] the same way (accurate fp32 log / sincos / sqrt, no fast-math);
+ *     llr[b][j] = s_j * fmaf(z, scale, shift),  s_j = +1 for codeword bit 0, -1 for bit 1 (codeword_packed: device,
+ *     ceil(n/8) bytes, bit j at byte j/8, bit j%8; NULL = all-zero codeword).
+ *   The smallest uniform is 2^-33: the tails of the normal reach +-6.76 sigma and no further.  Symbol and noise flip together,
+ *   so a nonzero codeword's LLRs are the exact sign mirror of the all-zero draw.  scale = 2/sigma and shift = 2/sigma^2 are
+ *   computed by the caller in double and passed as fp32; the reference's literal channel (bit 0 -> -1) passes -shift.
+ *
+ * ldpc_sim_count : folds one decoded block -- packed_bits[batch][ceil(n/8)] and iterations[batch] as ldpc_decode writes them --
+ *   into state[8] (device, int64) = { frames, frame_errors, bit_errors, iterations, done, blocks_seen, 0, 0 }; the caller
+ *   zeroes the state to start a point.  Per frame wrong = popcount(packed XOR codeword) over bits < n (pad bits of the last
+ *   byte are ignored), a frame error when wrong > 0.  Frames are consumed IN ORDER, as the reference's loop does: at most
+ *   max_frames - frames of them, and none after the frame at which frame_errors reaches max_errors; the frame errors, wrong
+ *   bits and iterations of the consumed frames are added.  done is set once frames >= max_frames or frame_errors >= max_errors;
+ *   a launch that finds done set changes nothing but blocks_seen.  The last two words are scratch between the two kernels of
+ *   a call and zero again after it.  Asynchronous on `stream`; calls on one state must be ordered by the stream.
+ *
+ * ldpc_simulate : one SNR point with an fp32 decoder of any schedule and engine (float64: LDPC_ERR_UNSUPPORTED).  Block k is
+ *   frames first_frame + k * block .. of the stream above (the last block of a point min(block, max_frames - frames drawn)
+ *   frames): channel, ldpc_decode(early_stop = 1) with packed decisions and iterations only, ldpc_sim_count, all inside
+ *   `workspace` (ldpc_simulate_workspace_bytes, 256-byte aligned) with nothing synchronised in between.  Every poll_blocks
+ *   blocks the state is copied to pinned host memory and the stream synchronised; the call returns once done is set, with the
+ *   state in out_state (host).  Blocks queued after the point finished are no-ops in the counter, so the first five words of
+ *   the result do not depend on block or poll_blocks (blocks_seen does).  UNLIKE every other entry point this one is
+ *   SYNCHRONOUS, allocates (64 bytes of pinned host memory per call) and must NOT be called during stream capture. */
+typedef struct {
+    uint64_t seed;
+    uint32_t stream_id;
+    uint64_t first_frame;
+    float scale, shift;
+    const uint8_t *codeword_packed;   /* device, or NULL: all-zero codeword */
+    int64_t max_frames, max_errors;
+    int64_t block;                    /* frames per block, >= 1 */
+    int32_t poll_blocks;              /* blocks between two looks at the state, >= 1 */
+} ldpc_sim_desc;
+
+int ldpc_channel_awgn(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                      float scale, float shift, const uint8_t *codeword_packed, void *stream);
+int ldpc_sim_count(int64_t *state, const uint8_t *packed_bits, const int32_t *iterations, int64_t batch, int32_t n,
+                   const uint8_t *codeword_packed, int64_t max_frames, int64_t max_errors, void *stream);
+size_t ldpc_simulate_workspace_bytes(const ldpc_decoder *d, int64_t block);
+int ldpc_simulate(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_state[8], void *workspace,
+                  size_t workspace_bytes, void *stream);
+
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
 /* sha256 (hex) over the sources and the compile recipe this library was built from, embedded at build time

@@ -98,6 +98,12 @@ int ldpc_debug_key4(const float *values, int64_t count, float beta, const float 
 int ldpc_debug_min2(const float *values, int64_t rows, int32_t d, float *m12_chain, uint32_t *par_chain, float *m12_pair,
                     uint32_t *par_pair, void *stream);
 
+/* The raw Philox4x32-10 words behind ldpc_channel_awgn (include/ldpc_hip.h): out4[count][4] (device) receives, for quad
+ * i < count, the four words of counter (f & 0xffffffff, f >> 32, i % quads_per_frame, stream_id) with
+ * f = first_frame + i / quads_per_frame, under key (seed & 0xffffffff, seed >> 32). */
+int ldpc_debug_philox(uint32_t *out4, int64_t count, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                      int32_t quads_per_frame, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
