@@ -143,7 +143,9 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_train_joint_ste_workspace_bytes", "ldpc_train_joint_ste",
                    "ldpc_train_joint_layered_workspace_bytes", "ldpc_train_joint_layered",
                    "ldpc_train_joint_layered_ste_workspace_bytes", "ldpc_train_joint_layered_ste",
-                   "ldpc_channel_awgn", "ldpc_sim_count", "ldpc_simulate_workspace_bytes", "ldpc_simulate")
+                   "ldpc_channel_awgn", "ldpc_sim_count", "ldpc_simulate_workspace_bytes", "ldpc_simulate",
+                   "ldpc_sim_diag_words", "ldpc_sim_count_diag_scratch_bytes", "ldpc_sim_count_diag",
+                   "ldpc_simulate_diag_workspace_bytes", "ldpc_simulate_diag")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -248,6 +250,16 @@ def load():
         lib.ldpc_simulate_workspace_bytes.argtypes = [vp, i64]
         lib.ldpc_simulate.restype = C.c_int
         lib.ldpc_simulate.argtypes = [vp, C.POINTER(SimDesc), vp, vp, C.c_size_t, vp]
+        lib.ldpc_sim_diag_words.restype = C.c_size_t
+        lib.ldpc_sim_diag_words.argtypes = [i32, i64]
+        lib.ldpc_sim_count_diag_scratch_bytes.restype = C.c_size_t
+        lib.ldpc_sim_count_diag_scratch_bytes.argtypes = [i64]
+        lib.ldpc_sim_count_diag.restype = C.c_int
+        lib.ldpc_sim_count_diag.argtypes = [vp, vp, i32, i64, vp, vp, vp, i64, i32, vp, u64, i64, i64, vp, C.c_size_t, vp]
+        lib.ldpc_simulate_diag_workspace_bytes.restype = C.c_size_t
+        lib.ldpc_simulate_diag_workspace_bytes.argtypes = [vp, i64, i64]
+        lib.ldpc_simulate_diag.restype = C.c_int
+        lib.ldpc_simulate_diag.argtypes = [vp, C.POINTER(SimDesc), i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p

@@ -272,6 +272,175 @@ __global__ __launch_bounds__(kSimFoldBlock) void sim_count_fold(long long *state
     }
 }
 
+// ------------------------------------------------------------------------------------------ diagnostic counters
+// ldpc_sim_count_diag: the same two launches, the same state, plus diag = { undetected, captured, 0, 0, hist[T + 1],
+// records[capture][4] } (include/ldpc_hip.h).  What is added to each launch:
+//   sim_diag_frames (grid)  : one word per frame into scratch -- wrong bits in bits 0..30, the success flag in bit 31 (n and T
+//                             are both full int32 ranges, so the iteration count stays where it is, in iterations[]) -- so the
+//                             fold never reads a packed row; the iterations binned in an LDS histogram of T + 1 counters per
+//                             workgroup (dynamic shared memory; above kSimDiagLdsBins bins straight into the global one), each
+//                             non-empty bin flushed with one global atomic; undetected errors summed WITHOUT order into diag[2].
+//   sim_diag_fold (1 group) : O(1) when no stop frame falls inside the block and there is nothing to record (no frame error in
+//                             it, or the capture full).  Otherwise it walks the per-frame words, 1024 frames per step; the
+//                             ballot prefix of the stop rule is the ordinal of each frame error: a consumed one whose ordinal is
+//                             below `capture` writes its record, a frame past the stop frame is taken back out of the sums, the
+//                             undetected count and the histogram.
+
+constexpr int kSimDiagLdsBins = 8192;   // 32 KiB of LDS at most: two workgroups of the grid pass per CU stay possible
+
+__device__ inline int sim_clamp_bin(int it, int T) { return it < 0 ? 0 : (it > T ? T : it); }
+
+__global__ __launch_bounds__(kSimBlock) void sim_diag_frames(long long *state, long long *diag, int T, int lds_bins,
+                                                             uint32_t *__restrict__ words, const uint8_t *__restrict__ packed,
+                                                             const int *__restrict__ iters, const uint8_t *__restrict__ success,
+                                                             long long B, int n, int rb, const uint8_t *__restrict__ cw,
+                                                             long long max_frames, long long max_errors)
+{
+    extern __shared__ unsigned sim_hist[];      // lds_bins counters (T + 1, or none)
+    unsigned long long *hist = reinterpret_cast<unsigned long long *>(diag) + 4;
+    for (int t = threadIdx.x; t < lds_bins; t += kSimBlock) sim_hist[t] = 0;
+    __syncthreads();
+    const long long take0 = sim_take0(state, B, max_frames, max_errors);
+    const int lane = threadIdx.x & 63;
+    const long long wave = (long long)blockIdx.x * (kSimBlock / 64) + (threadIdx.x >> 6);
+    const long long stride = (long long)gridDim.x * (kSimBlock / 64) * 64;
+    long long s_ferr = 0, s_wrong = 0, s_und = 0, s_it = 0;      // wave-uniform
+    for (long long base = wave * 64; base < take0; base += stride) {
+        const int rows = take0 - base < 64 ? (int)(take0 - base) : 64;
+        int mine = 0;                           // wrong bits of frame base + lane
+        for (int k = 0; k < rows; ++k) {
+            const int w = sim_row_wrong(packed + (size_t)(base + k) * (size_t)rb, cw, rb, n, lane);
+            s_wrong += w;
+            s_ferr += w > 0;
+            if (lane == k) mine = w;
+        }
+        int my_it = 0, und = 0;
+        if (lane < rows) {
+            my_it = iters[base + lane];
+            const unsigned ok = success[base + lane] != 0;
+            und = mine > 0 && ok;
+            words[base + lane] = (uint32_t)mine | (ok << 31);
+            const int bin = sim_clamp_bin(my_it, T);
+            if (lds_bins) atomicAdd(&sim_hist[bin], 1u);
+            else atomicAdd(&hist[bin], 1ull);
+        }
+        s_it += sim_wave_sum(my_it);
+        s_und += __popcll(__ballot(und));
+    }
+    if (lane == 0) {
+        unsigned long long *st = reinterpret_cast<unsigned long long *>(state);
+        if (s_it) atomicAdd(&st[3], (unsigned long long)s_it);
+        if (s_ferr) atomicAdd(&st[6], (unsigned long long)s_ferr);
+        if (s_wrong) atomicAdd(&st[7], (unsigned long long)s_wrong);
+        if (s_und) atomicAdd(reinterpret_cast<unsigned long long *>(diag) + 2, (unsigned long long)s_und);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < lds_bins; t += kSimBlock) {
+        const unsigned c = sim_hist[t];
+        if (c) atomicAdd(&hist[t], (unsigned long long)c);
+    }
+}
+
+__global__ __launch_bounds__(kSimFoldBlock) void sim_diag_fold(long long *state, long long *diag, int T, long long capture,
+                                                               const uint32_t *__restrict__ words,
+                                                               const int *__restrict__ iters, long long B,
+                                                               unsigned long long first_frame, long long max_frames,
+                                                               long long max_errors)
+{
+    constexpr int kWaves = kSimFoldBlock / 64;
+    __shared__ int sh_cnt[kWaves];
+    __shared__ long long sh_sum[kWaves][5];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long long frames0 = state[0], errors0 = state[1], done0 = state[4];
+    const long long take0 = sim_take0(state, B, max_frames, max_errors);
+    const long long e = state[6], w = state[7], u = diag[2], captured0 = diag[1];
+    long long take = take0, d_ferr = e, d_wrong = w, d_it = 0, d_und = u;
+    const bool stop = take0 > 0 && errors0 + e >= max_errors;           // the error limit falls inside this block
+    if (stop || (take0 > 0 && e > 0 && captured0 < capture)) {           // uniform branch
+        const long long need = max_errors - errors0;                     // >= 1 (take0 > 0)
+        long long *rec = diag + 4 + (long long)T + 1;
+        unsigned long long *hist = reinterpret_cast<unsigned long long *>(diag) + 4;
+        long long cum = 0;                                               // frame errors before this step
+        long long acc[5] = {0, 0, 0, 0, 0};   // per thread: frames kept; frame errors, wrong bits, iterations, undetected taken back
+        for (long long tile = 0; tile < take0; tile += kSimFoldBlock) {
+            if (!stop && captured0 + cum >= capture) break;              // capture full and nothing to take back: uniform
+            const long long row = tile + tid;
+            const bool valid = row < take0;
+            const uint32_t word = valid ? words[row] : 0u;
+            const int mine = (int)(word & 0x7fffffffu);
+            const int ferr = mine > 0;
+            const unsigned long long bal = __ballot(ferr);
+            const int incl = __popcll(bal & ((2ull << lane) - 1ull));
+            if (lane == 0) sh_cnt[wv] = __popcll(bal);
+            __syncthreads();
+            int before = 0, total = 0;
+            for (int k = 0; k < kWaves; ++k) {
+                before += k < wv ? sh_cnt[k] : 0;
+                total += sh_cnt[k];
+            }
+            __syncthreads();
+            if (valid) {
+                const long long ordinal = cum + before + incl - ferr;   // frame errors of this block before this frame
+                const int und = ferr && (word >> 31);
+                if (!stop || ordinal < need) {                           // consumed
+                    acc[0] += 1;
+                    const long long k = captured0 + ordinal;
+                    if (ferr && k < capture) {
+                        long long *r = rec + 4 * k;
+                        r[0] = (long long)(first_frame + (unsigned long long)row);
+                        r[1] = mine;
+                        r[2] = iters[row];
+                        r[3] = und;
+                    }
+                } else {
+                    const int it = iters[row];
+                    acc[1] += ferr;
+                    acc[2] += mine;
+                    acc[3] += it;
+                    acc[4] += und;
+                    atomicAdd(&hist[sim_clamp_bin(it, T)], ~0ull);       // minus one: the grid pass counted this frame
+                }
+            }
+            cum += total;
+        }
+        if (stop) {
+            for (int k = 0; k < 5; ++k) {
+                long long v = acc[k];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane == 0) sh_sum[wv][k] = v;
+            }
+            __syncthreads();
+            long long tot[5] = {0, 0, 0, 0, 0};
+            for (int k = 0; k < kWaves; ++k)
+                for (int c = 0; c < 5; ++c) tot[c] += sh_sum[k][c];
+            take = tot[0];
+            d_ferr = e - tot[1];
+            d_wrong = w - tot[2];
+            d_it = -tot[3];
+            d_und = u - tot[4];
+        }
+    }
+    __syncthreads();                                     // every thread has read the state and the diag header
+    if (tid == 0) {
+        const long long frames = frames0 + take, fe = errors0 + d_ferr;
+        state[0] = frames;
+        state[1] = fe;
+        state[2] += d_wrong;
+        state[3] += d_it;
+        state[4] = (done0 != 0 || frames >= max_frames || fe >= max_errors) ? 1 : 0;
+        state[5] += 1;
+        state[6] = 0;
+        state[7] = 0;
+        if (take0 > 0) {                                 // a launch that finds the point done leaves diag alone
+            const long long captured = captured0 + d_ferr;
+            diag[0] += d_und;
+            diag[1] = captured < capture ? captured : capture;
+            diag[2] = 0;
+        }
+    }
+}
+
 }  // namespace ldpc
 
 namespace {
@@ -306,12 +475,42 @@ int sim_count_launch(int64_t *state, const uint8_t *packed, const int32_t *iters
     return LDPC_OK;
 }
 
+size_t sim_diag_words(int32_t T, int64_t capture)
+{
+    if (T < 0 || capture < 0 || capture > (INT64_MAX >> 6)) return 0;
+    return (size_t)4 + (size_t)T + 1 + 4 * (size_t)capture;
+}
+
+size_t sim_diag_scratch_bytes(int64_t batch) { return batch > 0 ? align_up((size_t)batch * sizeof(uint32_t)) : 0; }
+
+int sim_count_diag_launch(int64_t *state, int64_t *diag, int32_t T, int64_t capture, const uint8_t *packed, const int32_t *iters,
+                          const uint8_t *success, int64_t batch, int32_t n, const uint8_t *cw, uint64_t first_frame,
+                          int64_t max_frames, int64_t max_errors, uint32_t *words, hipStream_t s)
+{
+    if (batch == 0)                                      // nothing to bin or record: the plain fold moves the state alone
+        return sim_count_launch(state, packed, iters, 0, n, cw, max_frames, max_errors, s);
+    const int rb = (int)(((int64_t)n + 7) / 8);
+    const int lds_bins = (int64_t)T + 1 <= kSimDiagLdsBins ? T + 1 : 0;
+    const long long groups = (batch + kSimBlock - 1) / kSimBlock;            // 64 frames per wave and pass
+    hipLaunchKernelGGL(sim_diag_frames, dim3((unsigned)std::min<long long>(groups, 2048)), dim3(kSimBlock),
+                       (size_t)lds_bins * sizeof(unsigned), s, (long long *)state, (long long *)diag, (int)T, lds_bins, words,
+                       packed, iters, success, (long long)batch, (int)n, rb, cw, (long long)max_frames, (long long)max_errors);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sim_diag_fold, dim3(1), dim3(kSimFoldBlock), 0, s, (long long *)state, (long long *)diag, (int)T,
+                       (long long)capture, (const uint32_t *)words, iters, (long long)batch, (unsigned long long)first_frame,
+                       (long long)max_frames, (long long)max_errors);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
 // workspace of ldpc_simulate for blocks of `block` frames: LLR rows, packed decisions, iterations, the state, the decoder's own
+// ldpc_simulate_diag (capture >= 0) adds a success row, the per-frame words and the diag buffer behind them
 struct SimWorkspace {
     size_t o_llr = 0, o_packed = 0, o_iters = 0, o_state = 0, o_dec = 0, dec_bytes = 0, total = 0;
+    size_t o_success = 0, o_words = 0, o_diag = 0, diag_words = 0;
 };
 
-SimWorkspace sim_carve(const ldpc_decoder *d, int64_t block)
+SimWorkspace sim_carve(const ldpc_decoder *d, int64_t block, int64_t capture = -1)
 {
     SimWorkspace w;
     const size_t n = (size_t)d->g->n, b = (size_t)block;
@@ -327,6 +526,12 @@ SimWorkspace sim_carve(const ldpc_decoder *d, int64_t block)
     w.o_state = take(8 * sizeof(int64_t));
     w.dec_bytes = ldpc_decoder_workspace_bytes(d, block);
     w.o_dec = take(w.dec_bytes);
+    if (capture >= 0) {
+        w.o_success = take(b);
+        w.o_words = take(sim_diag_scratch_bytes(block));
+        w.diag_words = sim_diag_words(d->T, capture);
+        w.o_diag = take(w.diag_words * sizeof(int64_t));
+    }
     w.total = off;
     return w;
 }
@@ -339,17 +544,21 @@ struct PinnedState {
     }
 };
 
-int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_state[8], void *workspace,
-                  size_t workspace_bytes, void *stream)
+// the host loop of ldpc_simulate (capture < 0, out_diag unused) and of ldpc_simulate_diag (capture >= 0)
+int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t capture, int64_t out_state[8], int64_t *out_diag,
+                  void *workspace, size_t workspace_bytes, void *stream)
 {
+    const bool diagnostics = capture >= 0;
     if (!d || !desc || !out_state) return fail(LDPC_ERR_ARG, "NULL decoder / descriptor / out_state");
+    if (diagnostics && !out_diag) return fail(LDPC_ERR_ARG, "NULL out_diag");
+    if (diagnostics && sim_diag_words(d->T, capture) == 0) return fail(LDPC_ERR_ARG, "capture too large");
     if (desc->block < 1) return fail(LDPC_ERR_ARG, "block < 1");
     if (desc->poll_blocks < 1) return fail(LDPC_ERR_ARG, "poll_blocks < 1");
     if (d->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "ldpc_simulate draws fp32 LLRs: float64 decoders are not supported");
     if (d->g->n < 1) return fail(LDPC_ERR_ARG, "n < 1");
     if (!workspace) return fail(LDPC_ERR_ARG, "NULL workspace");
     if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
-    const SimWorkspace w = sim_carve(d, desc->block);
+    const SimWorkspace w = sim_carve(d, desc->block, capture);
     if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
     DeviceGuard guard(d->g->device);
     hipStream_t s = (hipStream_t)stream;
@@ -358,10 +567,20 @@ int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_
     uint8_t *packed = (uint8_t *)(base + w.o_packed);
     int32_t *iters = (int32_t *)(base + w.o_iters);
     int64_t *state = (int64_t *)(base + w.o_state);
+    uint8_t *success = diagnostics ? (uint8_t *)(base + w.o_success) : nullptr;
+    uint32_t *words = diagnostics ? (uint32_t *)(base + w.o_words) : nullptr;
+    int64_t *diag = diagnostics ? (int64_t *)(base + w.o_diag) : nullptr;
     const int32_t n = d->g->n;
     PinnedState host;
     HIP_TRY(hipHostMalloc((void **)&host.p, 8 * sizeof(int64_t), hipHostMallocDefault));
     HIP_TRY(hipMemsetAsync(state, 0, 8 * sizeof(int64_t), s));
+    if (diagnostics) HIP_TRY(hipMemsetAsync(diag, 0, w.diag_words * sizeof(int64_t), s));
+    auto count = [&](int64_t frames, int64_t first) {    // fold one decoded block (frames = 0: latch `done`)
+        if (diagnostics)
+            return sim_count_diag_launch(state, diag, d->T, capture, packed, iters, success, frames, n, desc->codeword_packed,
+                                         desc->first_frame + (uint64_t)first, desc->max_frames, desc->max_errors, words, s);
+        return sim_count_launch(state, packed, iters, frames, n, desc->codeword_packed, desc->max_frames, desc->max_errors, s);
+    };
     int64_t drawn = 0;                                   // frames drawn so far: block k starts at first_frame + k * block
     for (;;) {
         int queued = 0;
@@ -370,20 +589,21 @@ int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_
             if (int rc = sim_channel_launch(llr, frames, n, desc->seed, desc->stream_id, desc->first_frame + (uint64_t)drawn,
                                             desc->scale, desc->shift, desc->codeword_packed, s))
                 return rc;
-            if (int rc = ldpc_decode(d, llr, frames, 1, nullptr, nullptr, iters, nullptr, packed, base + w.o_dec, w.dec_bytes, s))
+            if (int rc = ldpc_decode(d, llr, frames, 1, nullptr, nullptr, iters, success, packed, base + w.o_dec, w.dec_bytes, s))
                 return rc;
-            if (int rc = sim_count_launch(state, packed, iters, frames, n, desc->codeword_packed, desc->max_frames,
-                                          desc->max_errors, s))
-                return rc;
+            if (int rc = count(frames, drawn)) return rc;
             drawn += frames;
         }
         if (queued == 0)                                 // max_frames <= 0, or every frame drawn: an empty block latches `done`
-            if (int rc = sim_count_launch(state, packed, iters, 0, n, desc->codeword_packed, desc->max_frames, desc->max_errors, s))
-                return rc;
+            if (int rc = count(0, drawn)) return rc;
         HIP_TRY(hipMemcpyAsync(host.p, state, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (host.p[4] != 0) break;
         if (queued == 0) return fail(LDPC_ERR_HIP, "internal error: every frame counted and the point is not done");
+    }
+    if (diagnostics) {
+        HIP_TRY(hipMemcpyAsync(out_diag, diag, w.diag_words * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
     }
     for (int k = 0; k < 8; ++k) out_state[k] = host.p[k];
     return LDPC_OK;
@@ -426,7 +646,46 @@ size_t ldpc_simulate_workspace_bytes(const ldpc_decoder *d, int64_t block)
 int ldpc_simulate(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_state[8], void *workspace,
                   size_t workspace_bytes, void *stream)
 {
-    LDPC_NOTHROW(simulate_impl(d, desc, out_state, workspace, workspace_bytes, stream))
+    LDPC_NOTHROW(simulate_impl(d, desc, -1, out_state, nullptr, workspace, workspace_bytes, stream))
+}
+
+size_t ldpc_sim_diag_words(int32_t T, int64_t capture) { return sim_diag_words(T, capture); }
+
+size_t ldpc_sim_count_diag_scratch_bytes(int64_t batch) { return sim_diag_scratch_bytes(batch); }
+
+int ldpc_sim_count_diag(int64_t *state, int64_t *diag, int32_t T, int64_t capture, const uint8_t *packed_bits,
+                        const int32_t *iterations, const uint8_t *success, int64_t batch, int32_t n,
+                        const uint8_t *codeword_packed, uint64_t block_first_frame, int64_t max_frames, int64_t max_errors,
+                        void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (T < 0) return fail(LDPC_ERR_ARG, "T < 0");
+    if (capture < 0) return fail(LDPC_ERR_ARG, "capture < 0");
+    if (sim_diag_words(T, capture) == 0) return fail(LDPC_ERR_ARG, "capture too large");
+    if (!state) return fail(LDPC_ERR_ARG, "NULL state");
+    if (((uintptr_t)state % sizeof(int64_t)) != 0) return fail(LDPC_ERR_ARG, "state must be 8-byte aligned");
+    if (((uintptr_t)diag % sizeof(int64_t)) != 0) return fail(LDPC_ERR_ARG, "diag must be 8-byte aligned");
+    if (batch > 0 && (!packed_bits || !iterations || !success)) return fail(LDPC_ERR_ARG, "NULL packed_bits / iterations / success");
+    if (batch > 0 && (!diag || !scratch)) return fail(LDPC_ERR_ARG, "NULL diag / scratch");
+    if (((uintptr_t)scratch % sizeof(uint32_t)) != 0) return fail(LDPC_ERR_ARG, "scratch must be 4-byte aligned");
+    if (scratch_bytes < sim_diag_scratch_bytes(batch))
+        return fail(LDPC_ERR_WORKSPACE, "scratch %zu < required %zu", scratch_bytes, sim_diag_scratch_bytes(batch));
+    return sim_count_diag_launch(state, diag, T, capture, packed_bits, iterations, success, batch, n, codeword_packed,
+                                 block_first_frame, max_frames, max_errors, (uint32_t *)scratch, (hipStream_t)stream);
+}
+
+size_t ldpc_simulate_diag_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture)
+{
+    if (!d || block < 1 || capture < 0 || sim_diag_words(d->T, capture) == 0) return 0;
+    return sim_carve(d, block, capture).total;
+}
+
+int ldpc_simulate_diag(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t capture, int64_t out_state[8],
+                       int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (capture < 0) return fail(LDPC_ERR_ARG, "capture < 0");
+    LDPC_NOTHROW(simulate_impl(d, desc, capture, out_state, out_diag, workspace, workspace_bytes, stream))
 }
 
 int ldpc_debug_philox(uint32_t *out4, int64_t count, uint64_t seed, uint32_t stream_id, uint64_t first_frame,

@@ -99,6 +99,33 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
 
 
 SIM_COUNTERS = ("frames", "frame_errors", "bit_errors", "iterations", "done", "blocks_seen")
+ERROR_FRAME_DTYPE = np.dtype([("frame", np.uint64), ("wrong_bits", np.int64), ("iterations", np.int64), ("undetected", np.int64)])
+
+
+def sim_diag_words(T: int, capture: int) -> int:
+    """int64 words of a diag buffer (ldpc_sim_diag_words): 4 header words, T + 1 histogram bins, 4 words per captured frame"""
+    T, capture = int(T), int(capture)
+    if T < 0 or capture < 0:
+        raise ValueError("T and capture must be >= 0")
+    return 4 + T + 1 + 4 * capture
+
+
+def parse_sim_diag(words, T: int, capture: int) -> dict:
+    """a diag buffer of ldpc_sim_count_diag / ldpc_simulate_diag (include/ldpc_hip.h) -> {undetected_errors, captured,
+    iteration_histogram np.int64 [T + 1], error_frames}: error_frames is a structured array (frame uint64, wrong_bits,
+    iterations, undetected) of the `captured` recorded frame errors, in frame order."""
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.int64)).reshape(-1)
+    if w.size != sim_diag_words(T, capture):
+        raise ValueError(f"a diag buffer of T = {T}, capture = {capture} has {sim_diag_words(T, capture)} words, got {w.size}")
+    captured = int(w[1])
+    if not 0 <= captured <= capture:
+        raise ValueError(f"diag buffer records {captured} frames, capture is {capture}")
+    rec = w[4 + T + 1:].reshape(capture, 4)[:captured]
+    frames = np.empty(captured, dtype=ERROR_FRAME_DTYPE)
+    frames["frame"] = rec[:, 0].view(np.uint64) if captured else 0
+    frames["wrong_bits"], frames["iterations"], frames["undetected"] = rec[:, 1], rec[:, 2], rec[:, 3]
+    return {"undetected_errors": int(w[0]), "captured": captured, "iteration_histogram": w[4:4 + T + 1].copy(),
+            "error_frames": frames}
 
 
 class _NativeGraph:
@@ -374,12 +401,19 @@ class DecodeEngine:
             return codeword
         return pack_codeword(codeword, self.graph.n, self.device)
 
+    def sim_diag_buffer(self, capture: int = 0) -> torch.Tensor:
+        """a zeroed diag buffer for sim_count(diag=...) with room for `capture` frame-error records (int64 on this engine's GPU)"""
+        return torch.zeros(sim_diag_words(self.iters, capture), dtype=torch.int64, device=self.device)
+
     def sim_count(self, state: torch.Tensor, packed_bits: torch.Tensor, iterations: torch.Tensor, *, max_frames: int,
-                  max_errors: int, codeword=None) -> torch.Tensor:
+                  max_errors: int, codeword=None, success: Optional[torch.Tensor] = None,
+                  diag: Optional[torch.Tensor] = None, first_frame: int = 0, capture: int = 0) -> torch.Tensor:
         """Fold one decoded block into `state` (int64 [8] on this engine's GPU, zeroed by the caller to start a point:
         frames, frame_errors, bit_errors, iterations, done, blocks_seen, 0, 0) with the reference's in-order stop rule
         (ldpc_sim_count).  packed_bits uint8 [B, ceil(n/8)] and iterations int32 [B] as decode(want_packed=True) returns
-        them.  Asynchronous; returns `state`."""
+        them.  With `diag` (sim_diag_buffer(capture), kept over the blocks of a point) the diagnostics of the consumed frames
+        are kept too (ldpc_sim_count_diag; parse_sim_diag unpacks them): `success` [B] as decode returns it, `first_frame` the
+        stream index of the block's first frame.  Asynchronous; returns `state`."""
         n = self.graph.n
         if state.dtype != torch.int64 or state.shape != (8,) or state.device != self.device or not state.is_contiguous():
             raise ValueError("state must be a contiguous int64 tensor of 8 words on the engine's device")
@@ -390,20 +424,46 @@ class DecodeEngine:
             raise ValueError("iterations must be int32 [B] on the engine's device")
         packed_bits, iterations = packed_bits.contiguous(), iterations.contiguous()
         cw = self._packed_codeword(codeword)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        if diag is None:
+            if success is not None or capture:
+                raise ValueError("success and capture belong to the diagnostic counters: give diag (sim_diag_buffer)")
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                nat.check(self._lib.ldpc_sim_count(p(state), p(packed_bits), p(iterations), B, n, p(cw), int(max_frames),
+                                                   int(max_errors), C.c_void_p(stream)), "ldpc_sim_count")
+            return state
+        capture = int(capture)
+        if capture < 0:
+            raise ValueError("capture must be >= 0")
+        if (diag.dtype != torch.int64 or diag.shape != (sim_diag_words(self.iters, capture),) or diag.device != self.device
+                or not diag.is_contiguous()):
+            raise ValueError(f"diag must be a contiguous int64 tensor of {sim_diag_words(self.iters, capture)} words on the "
+                             f"engine's device (sim_diag_buffer({capture}))")
+        if success is None or success.dtype not in (torch.bool, torch.uint8) or success.shape != (B,) or success.device != self.device:
+            raise ValueError("the diagnostic counters need success, bool or uint8 [B] on the engine's device")
+        success = success.to(torch.uint8).contiguous()
+        need = int(self._lib.ldpc_sim_count_diag_scratch_bytes(B))
         with torch.cuda.device(self.device):
+            scratch = torch.empty(max(need, 4), dtype=torch.uint8, device=self.device)   # stream-ordered by the allocator
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            nat.check(self._lib.ldpc_sim_count(p(state), p(packed_bits), p(iterations), B, n, p(cw), int(max_frames),
-                                               int(max_errors), C.c_void_p(stream)), "ldpc_sim_count")
+            nat.check(self._lib.ldpc_sim_count_diag(p(state), p(diag), int(self.iters), capture, p(packed_bits), p(iterations),
+                                                    p(success), B, n, p(cw), int(first_frame) & (2 ** 64 - 1), int(max_frames),
+                                                    int(max_errors), p(scratch), scratch.numel(), C.c_void_p(stream)),
+                      "ldpc_sim_count_diag")
         return state
 
     def simulate(self, *, seed: int, max_frames: int, max_errors: int, stream_id: int = 0, first_frame: int = 0,
                  snr_db: Optional[float] = None, scale: Optional[float] = None, shift: Optional[float] = None,
-                 codeword=None, block: int = 65536, poll_blocks: int = 4) -> dict:
+                 codeword=None, block: int = 65536, poll_blocks: int = 4, diagnostics: bool = False,
+                 capture: int = 0) -> dict:
         """One SNR point on the device (ldpc_simulate): blocks of `block` frames of the counter-based AWGN stream, early-stop
         decode, in-order error counters, one host round trip every `poll_blocks` blocks.  -> {frames, frame_errors,
         bit_errors, iterations, done, blocks_seen}; all but blocks_seen are independent of block and poll_blocks.
-        Synchronous."""
+        With diagnostics (ldpc_simulate_diag) also undetected_errors (the decisions satisfy H and are not the codeword),
+        detected_errors, iteration_histogram (np.int64 [T + 1] over the consumed frames), captured and error_frames: the
+        first `capture` frame errors as a structured array (frame, wrong_bits, iterations, undetected) -- awgn_llr(1, n,
+        first_frame=frame, ...) draws such a frame again.  Synchronous."""
         if (snr_db is None) == (scale is None or shift is None):
             raise ValueError("give either snr_db or both scale and shift")
         if snr_db is not None:
@@ -417,16 +477,32 @@ class DecodeEngine:
         desc.max_frames, desc.max_errors = int(max_frames), int(max_errors)
         desc.block, desc.poll_blocks = int(block), int(poll_blocks)
         out = np.zeros(8, dtype=np.int64)
-        need = int(self._lib.ldpc_simulate_workspace_bytes(self.handle, max(int(block), 1)))
+        capture = int(capture)
+        if capture < 0 or (capture and not diagnostics):
+            raise ValueError("capture must be >= 0 and needs diagnostics=True")
+        if diagnostics:
+            need = int(self._lib.ldpc_simulate_diag_workspace_bytes(self.handle, max(int(block), 1), capture))
+            words = np.zeros(sim_diag_words(self.iters, capture), dtype=np.int64)
+        else:
+            need = int(self._lib.ldpc_simulate_workspace_bytes(self.handle, max(int(block), 1)))
         ws = getattr(self, "_sim_ws", None)
         if ws is None or ws.numel() < need:
             self._sim_ws = None
             self._sim_ws = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(self._lib.ldpc_simulate(self.handle, C.byref(desc), nat.ptr(out), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                              C.c_void_p(stream)), "ldpc_simulate")
-        return {k: int(v) for k, v in zip(SIM_COUNTERS, out)}
+            if diagnostics:
+                nat.check(self._lib.ldpc_simulate_diag(self.handle, C.byref(desc), capture, nat.ptr(out), nat.ptr(words),
+                                                       C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)),
+                          "ldpc_simulate_diag")
+            else:
+                nat.check(self._lib.ldpc_simulate(self.handle, C.byref(desc), nat.ptr(out), C.c_void_p(ws.data_ptr()),
+                                                  ws.numel(), C.c_void_p(stream)), "ldpc_simulate")
+        res = {k: int(v) for k, v in zip(SIM_COUNTERS, out)}
+        if diagnostics:
+            res.update(parse_sim_diag(words, self.iters, capture))
+            res["detected_errors"] = res["frame_errors"] - res["undetected_errors"]
+        return res
 
     # ------------------------------------------------------------------ small host batches (the reference's call shape)
     HOST_BATCH_MAX = 64

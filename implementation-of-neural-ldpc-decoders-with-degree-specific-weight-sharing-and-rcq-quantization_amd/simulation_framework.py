@@ -26,6 +26,10 @@ Channel (``SimulationConfig.channel``):
             stream_id = round(snr_db * 1000) mod 2^32, frame f the same noise whatever ``batch_frames`` is), the device-side
             counters of ``DecodeEngine.sim_count``, and on the LDS-resident engine the whole point in one native call
             (``DecodeEngine.simulate``).  ``SimulationConfig.codeword`` sends a codeword other than all-zero.
+            ``SimulationConfig.diagnostics`` / ``capture_errors`` (this channel only) also count the undetected frame errors,
+            bin the stop iterations and record the stream index of the first ``capture_errors`` frame errors of every point
+            (``SimulationResult.undetected_errors`` / ``iteration_histograms`` / ``error_frames``);
+            ``LDPSimulator.replay_errors`` draws and decodes recorded frames again.
 """
 
 from __future__ import annotations
@@ -33,6 +37,7 @@ from __future__ import annotations
 import json
 import logging
 import os
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor, as_completed
 from dataclasses import dataclass
@@ -70,12 +75,18 @@ class SimulationConfig:
     channel: str = "torch"                  # "torch": torch.randn draw, host stop rule; "device": the native Monte-Carlo path
     codeword: Optional[np.ndarray] = None   # 0/1 array of length n sent instead of the all-zero codeword (channel="device" only)
     poll_blocks: int = 4                    # channel="device", resident engine: blocks between two looks at the counters
+    diagnostics: bool = False               # channel="device": undetected errors, stop-iteration histogram, failing frames
+    capture_errors: int = 0                 # ... record the first so many frame errors of every point (implies diagnostics)
 
     def __post_init__(self):
         if self.channel not in ("torch", "device"):
             raise ValueError(f"channel must be 'torch' or 'device', got {self.channel!r}")
         if self.codeword is not None and self.channel != "device":
             raise ValueError("a codeword other than all-zero needs channel='device'")
+        if int(self.capture_errors) < 0:
+            raise ValueError("capture_errors must be >= 0")
+        if (self.diagnostics or int(self.capture_errors) > 0) and self.channel != "device":
+            raise ValueError("diagnostics and capture_errors need channel='device'")
 
 
 class SimulationResult:
@@ -90,6 +101,21 @@ class SimulationResult:
         self.simulation_times: List[float] = []
         self.total_frames: List[int] = []
         self.total_errors: List[int] = []
+        # per SNR point, filled only by a run with diagnostics: undetected frame errors, frames per stop iteration (T + 1
+        # bins), the recorded frame errors (engine.ERROR_FRAME_DTYPE: frame, wrong_bits, iterations, undetected)
+        self.undetected_errors: List[int] = []
+        self.iteration_histograms: List[List[int]] = []
+        self.error_frames: List[np.ndarray] = []
+
+    def add_diagnostics(self, snr_idx: int, undetected_errors: int, iteration_histogram, error_frames):
+        import engine as _engine
+        while len(self.undetected_errors) <= snr_idx:
+            self.undetected_errors.append(0)
+            self.iteration_histograms.append([])
+            self.error_frames.append(np.empty(0, dtype=_engine.ERROR_FRAME_DTYPE))
+        self.undetected_errors[snr_idx] = int(undetected_errors)
+        self.iteration_histograms[snr_idx] = [int(v) for v in iteration_histogram]
+        self.error_frames[snr_idx] = np.asarray(error_frames, dtype=_engine.ERROR_FRAME_DTYPE)
 
     def add_result(self, snr_idx: int, fer: float, ber: float, avg_iter: float, sim_time: float,
                    total_frames: int, total_errors: int):
@@ -155,6 +181,22 @@ def _decode_block(eng, llr: torch.Tensor, cap):
     return packed, iters
 
 
+def _decode_block_flags(eng, llr: torch.Tensor, cap):
+    """_decode_block that also returns the success flags (bool [B]) -> (packed, iterations, success): a codeword still open at
+    the cap takes all three from its full decode"""
+    kw = dict(early_stop=True, want_bits=False, want_posterior=False, want_packed=True)
+    res = eng.decode(llr, **kw) if cap is None else eng.decode(llr, max_iters=int(cap), **kw)
+    packed, iters, success = res.packed_bits, res.iterations, res.success
+    if cap is not None:
+        open_idx = torch.nonzero(~success, as_tuple=False).reshape(-1)
+        if open_idx.numel():
+            rest = eng.decode(llr.index_select(0, open_idx).contiguous(), **kw)
+            packed.index_copy_(0, open_idx, rest.packed_bits)
+            iters.index_copy_(0, open_idx, rest.iterations)
+            success.index_copy_(0, open_idx, rest.success)
+    return packed, iters, success
+
+
 _POPCOUNT = {}
 
 
@@ -194,6 +236,7 @@ class LDPSimulator:
     def __init__(self, config: SimulationConfig):
         self.config = config
         self.results: Dict[str, SimulationResult] = {}
+        self._last = threading.local()          # diagnostics of the calling thread's last point (simulate_decoder collects them)
         if config.save_results:
             os.makedirs(config.results_dir, exist_ok=True)
 
@@ -214,8 +257,11 @@ class LDPSimulator:
         from engine import _require_gpu
         device = _require_gpu(self.config.device)
         eng = _engine_of(decoder, device)
+        self._last.diagnostics = None
         if self.config.channel == "device":
             c = self._simulate_device(eng, code.n, float(snr_db), int(max_frames), int(max_errors))
+            if "iteration_histogram" in c:
+                self._last.diagnostics = c
             frames = c["frames"]
             return (c["frame_errors"] / frames if frames > 0 else 0.0,
                     c["bit_errors"] / (frames * code.n) if frames > 0 else 0.0,
@@ -245,9 +291,12 @@ class LDPSimulator:
     def _simulate_device(self, eng, n: int, snr_db: float, max_frames: int, max_errors: int) -> dict:
         """channel="device": the counters {frames, frame_errors, bit_errors, iterations, ...} of one SNR point.  The
         LDS-resident engine stops codeword by codeword, so the whole point runs in one native call; on the streaming engine
-        the loop stays here so that _decode_block's staged early stop still applies -- the same stream, the same counters."""
+        the loop stays here so that _decode_block's staged early stop still applies -- the same stream, the same counters.
+        With cfg.diagnostics / capture_errors the dict also has the keys DecodeEngine.simulate(diagnostics=True) adds."""
         import engine as _engine
         cfg = self.config
+        capture = int(cfg.capture_errors)
+        diagnostics = bool(cfg.diagnostics) or capture > 0
         scale, shift = _engine.awgn_scale_shift(snr_db, cfg.llr_convention)
         stream_id = int(round(snr_db * 1000)) % (1 << 32)
         block = max(1, int(cfg.batch_frames))
@@ -255,19 +304,51 @@ class LDPSimulator:
         if eng.info()["engine"] == "resident":
             return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, scale=scale, shift=shift, codeword=cw,
                                 max_frames=max_frames, max_errors=max_errors, block=block,
-                                poll_blocks=max(1, int(cfg.poll_blocks)))
+                                poll_blocks=max(1, int(cfg.poll_blocks)), diagnostics=diagnostics, capture=capture)
         state = torch.zeros(8, dtype=torch.int64, device=eng.device)
+        diag = eng.sim_diag_buffer(capture) if diagnostics else None
         drawn, cap, host = 0, None, [0] * 8
         while drawn < max_frames and not host[4]:
             frames = min(block, max_frames - drawn)
             llr = _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn, scale=scale,
                                    shift=shift, codeword=cw, device=eng.device)
-            packed, iters = _decode_block(eng, llr, cap)
+            if diagnostics:
+                packed, iters, success = _decode_block_flags(eng, llr, cap)
+                eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw,
+                              success=success, diag=diag, first_frame=drawn, capture=capture)
+            else:
+                packed, iters = _decode_block(eng, llr, cap)
+                eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw)
             cap = _next_cap(eng, iters, int(cfg.stage_min_block)) if cfg.staged_early_stop else None
-            eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw)
             host = state.tolist()                                               # the one read of the block
             drawn += frames
-        return dict(zip(_engine.SIM_COUNTERS, host))
+        res = dict(zip(_engine.SIM_COUNTERS, host))
+        if diagnostics:
+            res.update(_engine.parse_sim_diag(diag.cpu().numpy(), int(eng.iters), capture))
+            res["detected_errors"] = res["frame_errors"] - res["undetected_errors"]
+        return res
+
+    def replay_errors(self, decoder, code: LDPCCode, snr_db: float, frames) -> dict:
+        """Draw the listed frames of the point at `snr_db` again -- stream indices, e.g. error_frames["frame"] of a run with
+        this configuration (same seed, convention and codeword; channel="device") -- and decode them with early stop.
+        -> {frames, llr [F, n], bits int32 [F, n], posterior [F, n], iterations int32 [F], success bool [F]} on the device.
+        A frame has the same noise whatever block it was drawn in, so this reproduces the recorded failure exactly."""
+        import engine as _engine
+        cfg = self.config
+        if cfg.channel != "device":
+            raise ValueError("replay_errors needs channel='device': only the counter-based stream can draw a frame again")
+        eng = _engine_of(decoder, _engine._require_gpu(cfg.device))
+        scale, shift = _engine.awgn_scale_shift(float(snr_db), cfg.llr_convention)
+        stream_id = int(round(float(snr_db) * 1000)) % (1 << 32)
+        cw = None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, code.n, eng.device)
+        frames = [int(f) for f in np.asarray(frames).reshape(-1)]
+        rows = [_engine.awgn_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, scale=scale, shift=shift,
+                                 codeword=cw, device=eng.device) for f in frames]
+        llr = torch.cat(rows, dim=0) if rows else torch.empty((0, code.n), dtype=torch.float32, device=eng.device)
+        with torch.no_grad():
+            res = eng.decode(llr, early_stop=True)
+        return {"frames": frames, "llr": llr, "bits": res.bits, "posterior": res.posterior, "iterations": res.iterations,
+                "success": res.success}
 
     # ------------------------------------------------------------------------------ sweeps
     def simulate_decoder(self, decoder: Union[Callable, torch.nn.Module], code: LDPCCode,
@@ -280,6 +361,9 @@ class LDPSimulator:
             fer, ber, avg_iter, sim_time, total_frames, total_errors = self.simulate_single_snr(
                 decoder, code, snr_db, self.config.max_frames, self.config.max_errors)
             result.add_result(snr_idx, fer, ber, avg_iter, sim_time, total_frames, total_errors)
+            d = getattr(self._last, "diagnostics", None)
+            if d is not None:
+                result.add_diagnostics(snr_idx, d["undetected_errors"], d["iteration_histogram"], d["error_frames"])
             logger.info(f"SNR {snr_db:.1f}dB: FER={fer:.2e}, BER={ber:.2e}, Avg Iter={avg_iter:.1f}, Time={sim_time:.1f}s")
         self.results[decoder_name] = result
         return result
@@ -314,6 +398,12 @@ class LDPSimulator:
                                "average_iterations": r.average_iterations, "simulation_times": r.simulation_times,
                                "total_frames": r.total_frames, "total_errors": r.total_errors}
                         for name, r in results.items()}
+        for name, r in results.items():                  # diagnostics: only where a run filled them
+            if getattr(r, "iteration_histograms", None):
+                serializable[name]["undetected_errors"] = [int(v) for v in r.undetected_errors]
+                serializable[name]["iteration_histograms"] = [[int(v) for v in h] for h in r.iteration_histograms]
+                serializable[name]["error_frames"] = [[[int(v) for v in rec] for rec in np.asarray(e).tolist()]
+                                                      for e in r.error_frames]
         os.makedirs(self.config.results_dir, exist_ok=True)
         filepath = f"{self.config.results_dir}/{filename}"
         with open(filepath, "w") as f:
@@ -333,6 +423,11 @@ class LDPSimulator:
             r.simulation_times = d["simulation_times"]
             r.total_frames = d["total_frames"]
             r.total_errors = d["total_errors"]
+            if "iteration_histograms" in d:
+                import engine as _engine
+                r.undetected_errors = d["undetected_errors"]
+                r.iteration_histograms = d["iteration_histograms"]
+                r.error_frames = [np.array([tuple(rec) for rec in e], dtype=_engine.ERROR_FRAME_DTYPE) for e in d["error_frames"]]
             results[name] = r
         logger.info(f"Results loaded from {filepath}")
         return results

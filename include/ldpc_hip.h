@@ -357,7 +357,26 @@ int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const v
  *   blocks the state is copied to pinned host memory and the stream synchronised; the call returns once done is set, with the
  *   state in out_state (host).  Blocks queued after the point finished are no-ops in the counter, so the first five words of
  *   the result do not depend on block or poll_blocks (blocks_seen does).  UNLIKE every other entry point this one is
- *   SYNCHRONOUS, allocates (64 bytes of pinned host memory per call) and must NOT be called during stream capture. */
+ *   SYNCHRONOUS, allocates (64 bytes of pinned host memory per call) and must NOT be called during stream capture.
+ *
+ * Diagnostics.  ldpc_sim_count_diag is ldpc_sim_count -- the same eight state words for the same block, `done` and
+ *   blocks_seen included -- that also keeps a diag buffer (device, int64 words, 8-byte aligned, ldpc_sim_diag_words(T, capture)
+ *   of them, zeroed by the caller to start a point) over the CONSUMED frames, with `success` as ldpc_decode writes it:
+ *     diag[0]             undetected frame errors: wrong > 0 and success != 0 (the decisions satisfy H and are not the codeword)
+ *     diag[1]             records written = min(frame errors consumed so far, capture)
+ *     diag[2], diag[3]    0 (diag[2] is scratch between the two kernels of a call and zero again after it)
+ *     diag[4 + t]         t = 0 .. T: consumed frames with iterations == t (iterations clamped to [0, T])
+ *     diag[5 + T + 4k ..] record k = { absolute frame index block_first_frame + row, wrong bits, iterations, undetected 0/1 }
+ *   Records are the first `capture` frame errors the point consumes, in frame order; none is written for a frame the stop rule
+ *   does not consume.  Everything is defined on the ordered stream of frames, so nothing in state or diag depends on how the
+ *   point is cut into blocks.  A launch that finds done set changes nothing but blocks_seen.  The frame index is all a failure
+ *   needs: ldpc_channel_awgn(batch = 1, first_frame = record[0]) with the point's seed, stream_id, scale, shift and codeword
+ *   draws that frame again, bit for bit.  T is the decoder's iteration count (any T >= 0; the histogram has T + 1 bins) and
+ *   capture >= 0; both must not change during a point.  scratch: device, 4-byte aligned, ldpc_sim_count_diag_scratch_bytes(batch)
+ *   (4 bytes per frame); NULL success / diag / scratch are accepted only with batch == 0.
+ * ldpc_simulate_diag is ldpc_simulate with a success row, the scratch and the diag buffer carved into its workspace
+ *   (ldpc_simulate_diag_workspace_bytes); it returns the diag buffer in out_diag (host, ldpc_sim_diag_words(T of d, capture)
+ *   words) with the final state.  The first five state words equal ldpc_simulate's.  Synchronous, as ldpc_simulate. */
 typedef struct {
     uint64_t seed;
     uint32_t stream_id;
@@ -376,6 +395,18 @@ int ldpc_sim_count(int64_t *state, const uint8_t *packed_bits, const int32_t *it
 size_t ldpc_simulate_workspace_bytes(const ldpc_decoder *d, int64_t block);
 int ldpc_simulate(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_state[8], void *workspace,
                   size_t workspace_bytes, void *stream);
+
+/* words of a diag buffer: 4 header words, T + 1 histogram bins, 4 words per captured frame (0: T < 0 or capture < 0) */
+size_t ldpc_sim_diag_words(int32_t T, int64_t capture);
+size_t ldpc_sim_count_diag_scratch_bytes(int64_t batch);
+int ldpc_sim_count_diag(int64_t *state, int64_t *diag, int32_t T, int64_t capture,
+                        const uint8_t *packed_bits, const int32_t *iterations, const uint8_t *success,
+                        int64_t batch, int32_t n, const uint8_t *codeword_packed, uint64_t block_first_frame,
+                        int64_t max_frames, int64_t max_errors, void *scratch, size_t scratch_bytes, void *stream);
+size_t ldpc_simulate_diag_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture);
+int ldpc_simulate_diag(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t capture, int64_t out_state[8],
+                       int64_t *out_diag /* host, ldpc_sim_diag_words(T of d, capture) */,
+                       void *workspace, size_t workspace_bytes, void *stream);
 
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
