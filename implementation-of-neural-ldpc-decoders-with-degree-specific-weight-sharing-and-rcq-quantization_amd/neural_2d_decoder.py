@@ -67,7 +67,7 @@ class _DegreeSharedDecoder(nn.Module):
     def __getstate__(self):
         # native handles never travel through pickle / deepcopy; they are rebuilt lazily
         state = self.__dict__.copy()
-        state.update(_layout=None, _engine=None, _engine_key=None, _uploaded=None, _stamp=None)
+        state.update(_layout=None, _engine=None, _engine_key=None, _uploaded=None)
         return state
 
     # ---- tables ---------------------------------------------------------------------
@@ -96,12 +96,10 @@ class _DegreeSharedDecoder(nn.Module):
         g = self.code.tanner_graph()
         layout = self._sharing_layout()
         key = (dev.index, id(g), int(self.max_iterations), self._extra_key(), self.schedule)
-        # Flattening the ParameterDicts costs ~40 us -- a third of a one-codeword call (the reference's own call shape) -- so it is
-        # skipped while no parameter changed: every in-place update (optimizer step, load_state_dict, fill_) bumps the tensor's
-        # version counter, a replaced tensor (`p.data = ...`, a new Parameter under the key) shows in its identity / storage.
-        stamp = self._param_stamp()
-        if self._engine is not None and self._engine_key == key and stamp == getattr(self, "_stamp", None):
-            return self._engine
+        # The tables are flattened on EVERY call and compared with the last upload by value.  That costs ~40 us of a
+        # one-codeword call (DESIGN.md has the measurement), and nothing cheaper is safe: `p.data` carries a version counter
+        # of its own, so `p.data.fill_()` / `.clamp_()` / `.copy_()` / `.mul_()` leave `p._version`, `id(p)` and
+        # `p.data_ptr()` untouched, and a storage replaced twice (`p.data = b; p.data = c`) can come back to the old address.
         beta, alpha = self.weight_tables()
         if self._engine is None or self._engine_key != key:
             self._engine = DecodeEngine(g, dtype=torch.float32, iters=int(self.max_iterations), device=dev,
@@ -111,19 +109,7 @@ class _DegreeSharedDecoder(nn.Module):
         elif not (np.array_equal(self._uploaded[0], beta) and np.array_equal(self._uploaded[1], alpha)):
             self._engine.set_weights(*self._tables_for_upload(beta, alpha))
             self._uploaded = (beta, alpha)
-        self._stamp = stamp
         return self._engine
-
-    def _param_stamp(self):
-        """cheap fingerprint of the parameter set: counts, identities, version counters and storage addresses"""
-        ident = ver = ptr = cnt = 0
-        for d in (self.beta_weights, self.alpha_weights):
-            for p_ in d.values():
-                cnt += 1
-                ident += id(p_)
-                ver += p_._version
-                ptr += p_.data_ptr()
-        return (cnt, ident, ver, ptr, int(self.max_iterations))
 
     def _extra_key(self):
         return ()

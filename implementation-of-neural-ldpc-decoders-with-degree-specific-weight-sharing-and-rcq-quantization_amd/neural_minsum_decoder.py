@@ -60,21 +60,25 @@ class _EdgeWeightDecoder(nn.Module):
         self._engine = None
         self._engine_key = None
         self._uploaded: Optional[np.ndarray] = None
-        self._versions = None
+        self._cells = None
 
     def __getstate__(self):
         state = self.__dict__.copy()
-        state.update(_engine=None, _engine_key=None, _uploaded=None, _versions=None)
+        state.update(_engine=None, _engine_key=None, _uploaded=None, _cells=None)
         return state
 
     def weight_table(self) -> np.ndarray:
-        """beta[T, E] float32 in CSR edge order (KeyError for a missing key, like the reference)"""
+        """beta[T, E] float32 in CSR edge order (KeyError for a missing key, like the reference).  WHICH parameter feeds
+        which cell is resolved once per parameter set; the VALUES are read on every call."""
         g = self.code.tanner_graph()
         T = int(self.max_iterations)
-        rows, cols = g.check_of_edge.tolist(), g.var_idx.tolist()
         out = np.zeros((max(T, 1), max(g.E, 1)), dtype=np.float32)
         if T and g.E:
-            params = [self.beta_weights[f"iter_{t}_c{i}_v{j}"] for t in range(T) for i, j in zip(rows, cols)]
+            who = (tuple(map(id, self.beta_weights.values())), T, id(g))
+            if self._cells is None or self._cells[0] != who:
+                rows, cols = g.check_of_edge.tolist(), g.var_idx.tolist()
+                self._cells = (who, [self.beta_weights[f"iter_{t}_c{i}_v{j}"] for t in range(T) for i, j in zip(rows, cols)])
+            params = self._cells[1]
             out[:T, :g.E] = torch.cat([p.detach().reshape(-1)[:1] for p in params]).to("cpu", torch.float32) \
                 .numpy().reshape(T, g.E)
         return out
@@ -85,10 +89,11 @@ class _EdgeWeightDecoder(nn.Module):
         dev = _require_gpu(device)
         g = self.code.tanner_graph()
         T = int(self.max_iterations)
-        versions = (len(self.beta_weights), sum(p._version for p in self.beta_weights.values()))
         key = (dev.index, id(g), T, self.schedule)
+        # flattened on every call and compared with the last upload by value: a write through `p.data` moves no version
+        # counter (neural_2d_decoder.py, _get_engine)
+        beta = self.weight_table()
         if self._engine is None or self._engine_key != key:
-            beta = self.weight_table()
             rows = max(T, 1)
             extra = {"schedule": nat.SCHED_LAYERED} if self.schedule == "layered" else {}
             self._engine = DecodeEngine(
@@ -96,12 +101,10 @@ class _EdgeWeightDecoder(nn.Module):
                 c2v_form=nat.C2V_NMS if self._c2v_form == "nms" else nat.C2V_OMS,
                 beta=beta, beta_slot=np.arange(g.E, dtype=np.int32),
                 alpha=np.ones((rows, 1), np.float32), alpha_slot=np.zeros(g.n, np.int32), **extra)
-            self._engine_key, self._uploaded, self._versions = key, beta, versions
-        elif versions != self._versions:
-            beta = self.weight_table()
-            if not np.array_equal(beta, self._uploaded):
-                self._engine.set_weights(beta, None)
-            self._uploaded, self._versions = beta, versions
+            self._engine_key, self._uploaded = key, beta
+        elif not np.array_equal(beta, self._uploaded):
+            self._engine.set_weights(beta, None)
+            self._uploaded = beta
         return self._engine
 
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):

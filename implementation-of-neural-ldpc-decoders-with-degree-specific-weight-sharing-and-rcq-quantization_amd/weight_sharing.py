@@ -106,8 +106,10 @@ class SharingLayout:
 
     def _table(self, params, suffixes, T: int, default: float) -> np.ndarray:
         """[max(T,1), len(suffixes)] float32.  WHICH parameter feeds which cell is resolved once per parameter set
-        (the key lookups dominate a one-codeword call otherwise); the VALUES are re-read on every call, so in-place
-        updates of any kind (optimizer, fill_, .data) are always seen."""
+        (the key lookups dominate a one-codeword call otherwise); the VALUES are re-read on every call of this function.
+        A caller sees every update (optimizer, fill_, `.data.fill_()`, `.data = ...`) only if it calls this every time and
+        compares the result by value: no version counter, identity or address shows a write through `.data`
+        (_DegreeSharedDecoder._get_engine does that)."""
         rows = max(T, 1)
         out = np.full((rows, len(suffixes)), default, dtype=np.float32)
         ids = tuple(map(id, params.values()))

@@ -22,6 +22,9 @@
  *   - handles are immutable after creation and may be shared by threads; one
  *     workspace per concurrent ldpc_decode call (two calls that may overlap on the
  *     device -- different streams, different threads -- need two workspaces);
+ *   - workspaces, the `saved` block of the training path and outputs need no initialisation: no result depends on
+ *     what they held before the call; every element of a non-NULL output is written, nothing beyond it is (the pad
+ *     bits of a packed row, bits n .. 8 * ceil(n/8) - 1, are written as 0);
  *   - the library reads no environment variable; measurement and test hooks live in
  *     the separate ldpc_hip_debug.h and are never needed for decoding;
  *   - every function returns LDPC_OK (0) or a negative LDPC_ERR_*;

@@ -76,9 +76,10 @@ def edge_betas(dec, T):
     return out
 
 
-def restate(code, llr, bc, qp, T, beta_e, early_stop=True, want_messages=False):
+def restate(code, llr, bc, qp, T, beta_e, early_stop=True, want_messages=False, max_iters=None):
     """the paper's layered W-RCQ decode (module docstring of rcq_decoder.py): -> bits, posteriors, iterations, success
-    (want_messages: and the code (w < 0) * L + level every edge holds when its codeword's decode ends, 255 = no message)"""
+    (want_messages: and the code (w < 0) * L + level every edge holds when its codeword's decode ends, 255 = no message;
+    max_iters: run at most that many of the T iterations, an open codeword then reports iterations = max_iters)"""
     g = code.tanner_graph()
     thr = thresholds(bc, qp)
     sched = q_schedule(len(qp), T)
@@ -88,7 +89,8 @@ def restate(code, llr, bc, qp, T, beta_e, early_stop=True, want_messages=False):
     R = np.zeros((B, g.E), dtype=np.float32)          # reconstructed previous message of every edge ("none" = 0)
     K = np.full((B, g.E), 255, dtype=np.int64)
     open_ = np.ones(B, dtype=bool)
-    iters = np.full(B, T, dtype=np.int32)
+    T_run = T if max_iters is None else min(T, int(max_iters))
+    iters = np.full(B, T_run, dtype=np.int32)
     succ = np.zeros(B, dtype=bool)
     cp, vi = g.check_ptr, g.var_idx
 
@@ -99,7 +101,7 @@ def restate(code, llr, bc, qp, T, beta_e, early_stop=True, want_messages=False):
             par |= hard[:, vi[cp[i]:cp[i + 1]]].sum(axis=1) & 1
         return par.astype(bool)
 
-    for t in range(T):
+    for t in range(T_run):
         rows = np.flatnonzero(open_)
         if rows.size == 0:
             break

@@ -1248,41 +1248,61 @@ def test_error_behaviour(gpu_device):
     assert b.shape == (0, 7) and s.shape == (0,) and i.shape == (0,)
 
 
-def test_weight_update_is_picked_up(gpu_device, oracle_mod):
-    """parameters changed after the first forward (training step / load_state_dict) reach the GPU tables"""
+@pytest.mark.parametrize("which", ["neural2d", "wrcq", "offset", "edge"])
+def test_weight_update_is_picked_up(which, gpu_device, oracle_mod):
+    """parameters changed after the first forward reach the GPU tables, whichever way they were changed: the cases of
+    tests/test_host_logic.py (in-place updates, the four writes through `.data`, replaced storage -- twice, so that the
+    first address can come back --, a replaced Parameter, load_state_dict, an optimizer step), each decoded and compared
+    with the oracle run on the new values; a decode with nothing changed uploads nothing"""
     import codes
-    from neural_2d_decoder import Neural2DMinSumDecoder
+    from test_host_logic import WEIGHT_CHANGES, weight_change_decoders
     rng = np.random.default_rng(3)
+    T = 6
     code = codes.load_code("small_96_48", 10)
     og = oracle_mod.OracleGraph(code.H)
-    dec = Neural2DMinSumDecoder(code, 2, 6)
+    dec = weight_change_decoders(code, T)[which]()
     llr = awgn(rng, 70, 96, 2.5)
     x = torch.from_numpy(llr).to(gpu_device)
-    def check(beta, alpha):
+    items = lambda d: {k: float(v.item()) for k, v in d.items()}
+
+    def check():
         bits, post, iters = dec(x)
-        ob, op, oi, _ = oracle_mod.neural2d(og, llr, 2, 6, beta, alpha)
+        if which == "neural2d":
+            ob, op, oi, _ = oracle_mod.neural2d(og, llr, 2, T, items(dec.beta_weights), items(dec.alpha_weights))
+        elif which == "wrcq":
+            ob, op, oi, _ = oracle_mod.weighted_rcq(og, llr, 3, QP, 3, T, items(dec.beta_weights), items(dec.alpha_weights))
+        elif which == "offset":
+            ob, op, oi, _ = oracle_mod.neural2d_offset(og, llr, 2, T, items(dec.beta_weights), items(dec.alpha_weights))
+        else:
+            ob, op, oi, _ = oracle_mod.neural_minsum(og, llr, T, items(dec.beta_weights))
         np.testing.assert_array_equal(bits.detach().cpu().numpy(), ob)
         np.testing.assert_array_equal(iters.detach().cpu().numpy(), oi)
-        assert_post(post.detach().cpu().numpy(), op)
+        if which == "wrcq":
+            np.testing.assert_array_equal(post.detach().cpu().numpy(), op)
+        else:
+            assert_post(post.detach().cpu().numpy(), op)
+        return op
+
+    ranges = {"offset": ((0.0, 0.4), (0.0, 0.1))}.get(which, ((0.5, 1.0), (0.8, 1.2)))   # as rand_weights / the offset tests draw them
     for _ in range(2):
-        check(*rand_weights(dec, rng))                                # in-place fill_ (version counter)
-    # the tables are re-flattened only when the parameter fingerprint changes (version counters, identities, storage):
-    # every way of changing a weight must show in it
-    as_dicts = lambda: ({k: float(v.item()) for k, v in dec.beta_weights.items()}, {k: float(v.item()) for k, v in dec.alpha_weights.items()})
+        with torch.no_grad():                                             # in-place fill_ (version counter)
+            for params, (lo, hi) in zip((dec.beta_weights, getattr(dec, "alpha_weights", {})), ranges):
+                for p in params.values():
+                    p.fill_(float(np.float32(rng.uniform(lo, hi))))
+        check()
     k0 = sorted(dec.beta_weights.keys())[0]
-    dec.beta_weights[k0].data = torch.tensor([0.5625])                # storage replaced
-    check(*as_dicts())
-    dec.beta_weights[k0] = torch.nn.Parameter(torch.tensor([0.8125]))  # Parameter replaced under the key
-    check(*as_dicts())
-    sd = {k: torch.full_like(v, 0.6875) for k, v in dec.state_dict().items()}
-    dec.load_state_dict(sd)                                           # the reference's checkpoint path
-    check(*as_dicts())
-    with torch.no_grad():
-        dec.alpha_weights[sorted(dec.alpha_weights.keys())[-1]].mul_(1.25)   # optimizer-style in-place update
-    check(*as_dicts())
-    stamp = dec._stamp
-    check(*as_dicts())                                                # nothing changed: same fingerprint, same results
-    assert dec._stamp == stamp
+    eng = dec._engine
+    uploads = []
+    upload = eng.set_weights
+    eng.set_weights = lambda *a, **kw: (uploads.append(1), upload(*a, **kw))[1]
+    check()
+    assert not uploads
+    for n_changes, (name, change) in enumerate(WEIGHT_CHANGES, 1):
+        change(dec, k0)
+        check()                                                           # the oracle with the new values
+        assert dec._engine is eng and len(uploads) == n_changes, name
+    check()                                                               # nothing changed: no upload, same results
+    assert len(uploads) == len(WEIGHT_CHANGES)
 
 
 def test_packed_bits_and_threads(gpu_device):

@@ -315,42 +315,118 @@ def test_product_never_imports_the_oracle():
         assert "oracle" not in open(os.path.join(PKG, "csrc", fn)).read().lower(), fn
 
 
-def test_parameter_fingerprint_sees_every_kind_of_weight_change():
-    """The degree-shared decoders re-flatten their ParameterDicts only when `_param_stamp()` changes: in-place updates (version
-    counters), replaced storage, a replaced Parameter, load_state_dict and a changed iteration count must all show; reading must not."""
-    import codes
-    from neural_2d_decoder import Neural2DMinSumDecoder
+class _RecordingEngine:
+    """stands in for DecodeEngine where there is no GPU: keeps the tables a decoder's _get_engine hands over"""
+
+    def __init__(self, graph, **kw):
+        self.tables = {k: None if kw.get(k) is None else np.array(kw[k], np.float32) for k in ("beta", "alpha", "oms_alpha")}
+        self.uploads = 0
+
+    def set_weights(self, beta, alpha, oms_alpha=None):
+        self.uploads += 1
+        for k, v in (("beta", beta), ("alpha", alpha), ("oms_alpha", oms_alpha)):
+            if v is not None:
+                self.tables[k] = np.array(v, np.float32)
+
+
+def _tables_from_items(dec):
+    """what the device must hold, read parameter by parameter with .item(): {"beta" | "alpha" | "oms_alpha": [T, slots]}"""
+    T = int(dec.max_iterations)
+    if not hasattr(dec, "alpha_weights"):                                  # one beta per (iteration, edge)
+        g = dec.code.tanner_graph()
+        edges = list(zip(g.check_of_edge.tolist(), g.var_idx.tolist()))
+        return {"beta": np.array([[dec.beta_weights[f"iter_{t}_c{i}_v{j}"].item() for i, j in edges] for t in range(T)], np.float32)}
+    lay = dec._sharing_layout()
+    def table(params, suffixes, default):
+        return np.array([[params[f"iter_{t}_{s}"].item() if s is not None and f"iter_{t}_{s}" in params else default
+                          for s in suffixes] for t in range(T)], np.float32)
+    out = {"beta": table(dec.beta_weights, lay.beta_suffix, dec._beta_default)}
+    out["oms_alpha" if dec._alpha_is_oms else "alpha"] = table(dec.alpha_weights, lay.alpha_suffix, dec._alpha_default)
+    return out
+
+
+# every way of changing a weight: (name, change(dec, key of one beta)).  The four `.data` ones move no version counter, no
+# identity and no address; "storage twice" can bring the first storage's address back (A -> B -> A')
+def _twice(dec, k):
+    dec.beta_weights[k].data = torch.tensor([0.1875])
+    dec.beta_weights[k].data = torch.tensor([0.4375])
+
+
+def _sgd_step(dec, k):
+    opt = torch.optim.SGD(dec.parameters(), lr=0.1)
+    for p_ in dec.parameters():
+        p_.grad = torch.ones_like(p_)
+    opt.step()
+
+
+def _no_grad(f):
+    def run(dec, k):
+        with torch.no_grad():
+            f(dec, k)
+    return run
+
+
+WEIGHT_CHANGES = [
+    ("fill_", _no_grad(lambda dec, k: dec.beta_weights[k].fill_(0.5))),
+    ("mul_ of the last parameter", _no_grad(lambda dec, k: list(dec.parameters())[-1].mul_(1.5))),
+    ("storage replaced", lambda dec, k: setattr(dec.beta_weights[k], "data", torch.tensor([0.25]))),
+    ("storage replaced twice", _twice),
+    ("Parameter replaced", lambda dec, k: dec.beta_weights.__setitem__(k, torch.nn.Parameter(torch.tensor([0.75])))),
+    ("load_state_dict", lambda dec, k: dec.load_state_dict({n: torch.full_like(v, 0.625) for n, v in dec.state_dict().items()})),
+    ("optimizer step", _sgd_step),
+    (".data.fill_", lambda dec, k: dec.beta_weights[k].data.fill_(0.3)),
+    (".data.clamp_", lambda dec, k: dec.beta_weights[k].data.clamp_(max=0.125)),
+    (".data.copy_", lambda dec, k: dec.beta_weights[k].data.copy_(torch.tensor([0.4375]))),
+    (".data.mul_", lambda dec, k: dec.beta_weights[k].data.mul_(1.5)),
+]
+
+
+def weight_change_decoders(code, T):
+    """one decoder of every class that keeps weight tables on the device: name -> constructor"""
+    from neural_2d_decoder import Neural2DMinSumDecoder, Neural2DOffsetMinSumDecoder
+    from neural_minsum_decoder import NeuralMinSumDecoder
     from rcq_decoder import WeightedRCQDecoder
-    code = codes.load_code("small_96_48", 5)
-    for dec in (Neural2DMinSumDecoder(code, 2, 5), WeightedRCQDecoder(code, 3, 8, QP, weight_sharing_type=3, max_iterations=5)):
-        seen = {dec._param_stamp()}
-        def changed():
-            st = dec._param_stamp()
-            new = st not in seen
-            seen.add(st)
-            return new
-        assert not changed()                                              # reading twice: same stamp
-        _ = dec.weight_tables()
-        _ = [float(p.item()) for p in dec.beta_weights.values()]
-        assert not changed()
-        k = sorted(dec.beta_weights.keys())[0]
-        with torch.no_grad():
-            dec.beta_weights[k].fill_(0.5)
-        assert changed()
-        with torch.no_grad():
-            list(dec.parameters())[-1].mul_(1.5)                          # an alpha where the sharing type has any
-        assert changed()
-        dec.beta_weights[k].data = torch.tensor([0.25])
-        assert changed()
-        dec.beta_weights[k] = torch.nn.Parameter(torch.tensor([0.75]))
-        assert changed()
-        dec.load_state_dict({n: torch.full_like(v, 0.625) for n, v in dec.state_dict().items()})
-        assert changed()
-        opt = torch.optim.SGD(dec.parameters(), lr=0.1)
-        for p_ in dec.parameters():
-            p_.grad = torch.ones_like(p_)
-        opt.step()
-        assert changed()
+    return {"neural2d": lambda: Neural2DMinSumDecoder(code, 2, T),
+            "wrcq": lambda: WeightedRCQDecoder(code, 3, 8, QP, weight_sharing_type=3, max_iterations=T),
+            "offset": lambda: Neural2DOffsetMinSumDecoder(code, 2, T),
+            "edge": lambda: NeuralMinSumDecoder(code, T)}
+
+
+@pytest.mark.parametrize("which", ["neural2d", "wrcq", "offset", "edge"])
+def test_parameter_fingerprint_sees_every_kind_of_weight_change(which, monkeypatch):
+    """The decoders with weight tables on the device flatten their ParameterDicts on every call and upload when a value
+    differs from the last upload: in-place updates, writes through `.data` (which move no version counter), replaced
+    storage, a replaced Parameter, load_state_dict, an optimizer step and a changed iteration count must all reach the
+    engine; reading, or decoding again, must upload nothing."""
+    import codes
+    import engine
+    monkeypatch.setattr(engine, "DecodeEngine", _RecordingEngine)
+    monkeypatch.setattr(engine, "_require_gpu", lambda device: torch.device("cuda", 0))
+    torch.manual_seed(11)
+    dec = weight_change_decoders(codes.load_code("small_96_48", 5), 5)[which]()
+
+    def held(eng, after="construction"):
+        want = _tables_from_items(dec)
+        for table, values in want.items():
+            np.testing.assert_array_equal(eng.tables[table], values, err_msg=f"{table} after {after}")
+        return want
+
+    eng = dec._get_engine(None)
+    before = held(eng)
+    _ = [float(p.item()) for p in dec.beta_weights.values()]
+    assert dec._get_engine(None) is eng and eng.uploads == 0                # reading: nothing to upload
+    k = sorted(dec.beta_weights.keys())[0]
+    for n_changes, (name, change) in enumerate(WEIGHT_CHANGES, 1):
+        change(dec, k)
+        assert dec._get_engine(None) is eng, name
+        now = held(eng, name)                                             # the engine holds the new values ...
+        assert any(not np.array_equal(now[t], before[t]) for t in now), f"{name}: the case changes no value"
+        assert eng.uploads == n_changes, name                             # ... through exactly one upload,
+        assert dec._get_engine(None) is eng and eng.uploads == n_changes  # and the next call uploads nothing
+        before = now
+    dec.max_iterations = 4
+    eng4 = dec._get_engine(None)
+    assert eng4 is not eng and held(eng4)["beta"].shape[0] == 4
 
 
 def test_decoder_objects_pickle_without_native_handles():
