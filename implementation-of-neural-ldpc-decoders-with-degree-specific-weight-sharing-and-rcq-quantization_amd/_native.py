@@ -143,7 +143,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_train_joint_ste_workspace_bytes", "ldpc_train_joint_ste",
                    "ldpc_train_joint_layered_workspace_bytes", "ldpc_train_joint_layered",
                    "ldpc_train_joint_layered_ste_workspace_bytes", "ldpc_train_joint_layered_ste",
-                   "ldpc_channel_awgn", "ldpc_sim_count", "ldpc_simulate_workspace_bytes", "ldpc_simulate",
+                   "ldpc_channel_awgn", "ldpc_channel_awgn_mix", "ldpc_sim_count",
+                   "ldpc_simulate_workspace_bytes", "ldpc_simulate",
                    "ldpc_sim_diag_words", "ldpc_sim_count_diag_scratch_bytes", "ldpc_sim_count_diag",
                    "ldpc_simulate_diag_workspace_bytes", "ldpc_simulate_diag")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
@@ -244,6 +245,8 @@ def load():
         u32, u64, f32 = C.c_uint32, C.c_uint64, C.c_float
         lib.ldpc_channel_awgn.restype = C.c_int
         lib.ldpc_channel_awgn.argtypes = [vp, i64, i32, u64, u32, u64, f32, f32, vp, vp]
+        lib.ldpc_channel_awgn_mix.restype = C.c_int
+        lib.ldpc_channel_awgn_mix.argtypes = [vp, i64, i32, u64, u32, u64, vp, vp, i32, vp, vp]
         lib.ldpc_sim_count.restype = C.c_int
         lib.ldpc_sim_count.argtypes = [vp, vp, vp, i64, i32, vp, i64, i64, vp]
         lib.ldpc_simulate_workspace_bytes.restype = C.c_size_t

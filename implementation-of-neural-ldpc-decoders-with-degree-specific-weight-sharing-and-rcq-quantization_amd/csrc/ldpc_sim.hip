@@ -98,6 +98,70 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_awgn(float *__restrict_
     }
 }
 
+// the quad's stores of sim_channel_awgn_mix: the width chosen per lane from the address, as sim_channel_awgn does inline
+__device__ inline void sim_store_quad(float *dst, const float v[4], int cnt)
+{
+    if (cnt == 4) {
+        const uintptr_t a = (uintptr_t)dst;
+        if ((a & 15) == 0) {
+            *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        } else if ((a & 7) == 0) {
+            *reinterpret_cast<float2 *>(dst) = make_float2(v[0], v[1]);
+            *reinterpret_cast<float2 *>(dst + 2) = make_float2(v[2], v[3]);
+        } else {
+            dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+        }
+    } else {
+        for (int k = 0; k < cnt; ++k) dst[k] = v[k];
+    }
+}
+
+// sim_channel_awgn with the SNR point a function of the frame: (scale, shift) = (scale_tab[p], shift_tab[p]), p = f mod K of
+// the absolute frame index f = first_frame + b (ldpc_channel_awgn_mix).  The same lane-per-quad shape, counters, normals and
+// stores; sim_channel_awgn itself is left as it is.  The host passes p0 = first_frame mod K, so that the one 64-bit remainder of
+// a launch is taken there: b <= 2^31 - 1 and p0 < K <= 4096 keep r = b + p0 below 2^32 and the lane's remainder in 32 bits, and
+// that remainder costs no division either: with Kinv = floor((2^32 - 1) / K), also from the host, 2^32 / K - 1 <= Kinv <= 2^32 / K,
+// so umulhi(r, Kinv) is floor(r / K) or one less and r - umulhi(r, Kinv) * K lies in [0, 2K): one conditional subtraction.  The
+// two table reads are issued before the Philox rounds and hidden behind them; a wave covers 256 / Q + 1 rows at most -- one or
+// two on any real code -- so they are nearly wave-uniform, and 2 * 4096 floats stay in cache.
+__global__ __launch_bounds__(kSimBlock) void sim_channel_awgn_mix(float *__restrict__ llr, long long batch, int n, unsigned Q,
+                                                                  uint32_t k0, uint32_t k1, uint32_t stream_id,
+                                                                  unsigned long long first_frame, unsigned p0, unsigned K,
+                                                                  unsigned Kinv,
+                                                                  const float *__restrict__ scale_tab,
+                                                                  const float *__restrict__ shift_tab,
+                                                                  const uint8_t *__restrict__ cw)
+{
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first quad of the workgroup: uniform
+    const unsigned long long b0 = g0 / Q;
+    const unsigned t = (unsigned)(g0 - b0 * Q) + threadIdx.x;                     // < Q + 256 <= 2^29 + 256
+    const unsigned db = t / Q;
+    const long long b = (long long)b0 + db;
+    const unsigned q = t - db * Q;
+    if (b >= batch) return;
+    const unsigned r = (unsigned)b + p0;
+    unsigned p = r - __umulhi(r, Kinv) * K;                                       // in [0, 2K), see above
+    if (p >= K) p -= K;                                                           // (first_frame + b) mod K
+    const float scale = scale_tab[p], shift = shift_tab[p];
+    const unsigned long long f = first_frame + (unsigned long long)b;
+    uint32_t x[4];
+    philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), q, stream_id, k0, k1, x);
+    float z[4];
+    sim_box_muller(x[0], x[1], z[0], z[1]);
+    sim_box_muller(x[2], x[3], z[2], z[3]);
+    const int j0 = (int)(q * 4u);
+    const int cnt = n - j0 < 4 ? n - j0 : 4;
+    unsigned cbits = 0;                                                           // codeword bits j0 .. j0+3
+    if (cw) cbits = (cw[j0 >> 3] >> (j0 & 7)) & 0xfu;                             // j0 % 8 is 0 or 4: one byte holds all four
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float y = fmaf(z[k], scale, shift);
+        v[k] = ((cbits >> k) & 1u) ? -y : y;
+    }
+    sim_store_quad(llr + (size_t)b * (size_t)n + (size_t)j0, v, cnt);
+}
+
 // the raw words of quad i: frame first_frame + i / quads_per_frame, quad i % quads_per_frame (ldpc_debug_philox)
 __global__ __launch_bounds__(kSimBlock) void sim_debug_philox(uint32_t *__restrict__ out, long long count, uint32_t k0,
                                                               uint32_t k1, uint32_t stream_id, unsigned long long first_frame,
@@ -458,6 +522,21 @@ int sim_channel_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, uint
     return LDPC_OK;
 }
 
+int sim_channel_mix_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                           const float *scale_tab, const float *shift_tab, int32_t n_points, const uint8_t *cw, hipStream_t s)
+{
+    const unsigned Q = ((unsigned)n + 3u) / 4u;
+    const unsigned long long quads = (unsigned long long)batch * Q;
+    const unsigned long long blocks = (quads + kSimBlock - 1) / kSimBlock;
+    if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+    const unsigned K = (unsigned)n_points;
+    hipLaunchKernelGGL(sim_channel_awgn_mix, dim3((unsigned)blocks), dim3(kSimBlock), 0, s, llr, (long long)batch, (int)n, Q,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, (unsigned long long)first_frame,
+                       (unsigned)(first_frame % K), K, 0xffffffffu / K, scale_tab, shift_tab, cw);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
 int sim_count_launch(int64_t *state, const uint8_t *packed, const int32_t *iters, int64_t batch, int32_t n,
                      const uint8_t *cw, int64_t max_frames, int64_t max_errors, hipStream_t s)
 {
@@ -623,6 +702,26 @@ int ldpc_channel_awgn(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32
     if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
     return sim_channel_launch((float *)llr, batch, n, seed, stream_id, first_frame, scale, shift, codeword_packed,
                               (hipStream_t)stream);
+}
+
+int ldpc_channel_awgn_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                          const float *scale_tab, const float *shift_tab, int32_t n_points, const uint8_t *codeword_packed,
+                          void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (batch > INT32_MAX) return fail(LDPC_ERR_ARG, "batch > 2^31 - 1");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (n_points < 1 || n_points > 4096) return fail(LDPC_ERR_ARG, "n_points must be in 1 .. 4096");
+    if (batch > 0 && first_frame > (uint64_t)0 - (uint64_t)batch)       // 2^64 - batch: p is not continuous across the wrap
+        return fail(LDPC_ERR_ARG, "first_frame + batch wraps the 64-bit frame index");
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    if (!scale_tab || !shift_tab) return fail(LDPC_ERR_ARG, "NULL scale_tab / shift_tab");
+    if (((uintptr_t)scale_tab % sizeof(float)) != 0 || ((uintptr_t)shift_tab % sizeof(float)) != 0)
+        return fail(LDPC_ERR_ARG, "scale_tab / shift_tab must be 4-byte aligned");
+    return sim_channel_mix_launch((float *)llr, batch, n, seed, stream_id, first_frame, scale_tab, shift_tab, n_points,
+                                  codeword_packed, (hipStream_t)stream);
 }
 
 int ldpc_sim_count(int64_t *state, const uint8_t *packed_bits, const int32_t *iterations, int64_t batch, int32_t n,

@@ -68,6 +68,16 @@ def pack_codeword(codeword, n: int, device) -> torch.Tensor:
     return torch.from_numpy(np.packbits(c.astype(np.uint8), bitorder="little")).to(device)
 
 
+def _channel_codeword(codeword, n: int, dev: torch.device) -> Optional[torch.Tensor]:
+    """the codeword argument of the channel functions -- None, a 0/1 array, or an already packed tensor -- as packed bytes on `dev`"""
+    if codeword is None:
+        return None
+    cw = codeword if isinstance(codeword, torch.Tensor) else pack_codeword(codeword, n, dev)
+    if cw.dtype != torch.uint8 or cw.device != dev or cw.numel() != (n + 7) // 8 or not cw.is_contiguous():
+        raise ValueError(f"packed codeword must be a contiguous uint8 tensor of {(n + 7) // 8} bytes on {dev}")
+    return cw
+
+
 def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, snr_db: Optional[float] = None,
              scale: Optional[float] = None, shift: Optional[float] = None, codeword=None, device=None) -> torch.Tensor:
     """LLRs [batch, n] fp32 of frames first_frame .. first_frame + batch - 1 of the counter-based BI-AWGN stream
@@ -82,11 +92,7 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
     batch, n = int(batch), int(n)
     if batch < 0 or n < 1:
         raise ValueError("batch must be >= 0 and n >= 1")
-    cw = None
-    if codeword is not None:
-        cw = codeword if isinstance(codeword, torch.Tensor) else pack_codeword(codeword, n, dev)
-        if cw.dtype != torch.uint8 or cw.device != dev or cw.numel() != (n + 7) // 8 or not cw.is_contiguous():
-            raise ValueError(f"packed codeword must be a contiguous uint8 tensor of {(n + 7) // 8} bytes on {dev}")
+    cw = _channel_codeword(codeword, n, dev)
     lib = nat.load()
     out = torch.empty((batch, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -95,6 +101,92 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
                                         int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), float(scale),
                                         float(shift), None if cw is None else C.c_void_p(cw.data_ptr()),
                                         C.c_void_p(stream)), "ldpc_channel_awgn")
+    return out
+
+
+MIX_MAX_POINTS = 4096      # ldpc_channel_awgn_mix: n_points <= 4096, batch <= 2^31 - 1 (the point index stays in 32 bits)
+
+
+def snr_grid(snr_range, snr_step: float) -> np.ndarray:
+    """the SNR points lo + k * step, k = 0 .. K - 1, of (lo, hi) = snr_range as float64, K = floor((hi - lo) / step + 1e-9) + 1:
+    (0, 6) with step 0.5 gives 13 points, (3, 3) with any step one"""
+    lo, hi = (float(v) for v in snr_range)
+    step = float(snr_step)
+    if not step > 0:
+        raise ValueError(f"snr_step must be > 0, got {snr_step!r}")
+    if hi < lo:
+        raise ValueError(f"snr_range must be (lo, hi) with hi >= lo, got {snr_range!r}")
+    return lo + step * np.arange(int(np.floor((hi - lo) / step + 1e-9)) + 1, dtype=np.float64)
+
+
+def mix_points(first_frame: int, batch: int, n_points: int, device=None) -> torch.Tensor:
+    """int64 [batch]: the SNR point (first_frame + b) % n_points of each frame of a block of ldpc_channel_awgn_mix.  The
+    remainder of first_frame is taken on Python integers, so frame indices of 2^63 and above are right."""
+    first_frame, batch, n_points = int(first_frame), int(batch), int(n_points)
+    if batch < 0 or n_points < 1 or first_frame < 0:
+        raise ValueError("batch and first_frame must be >= 0 and n_points >= 1")
+    return (first_frame % n_points + torch.arange(batch, dtype=torch.int64, device=device)) % n_points
+
+
+def _mix_table(values, what: str, dev: torch.device) -> torch.Tensor:
+    """a 1-D sequence, or an fp32 tensor already on `dev`, as a contiguous fp32 table on `dev`"""
+    if isinstance(values, torch.Tensor):
+        if values.dtype != torch.float32 or values.device != dev or values.dim() != 1 or not values.is_contiguous():
+            raise ValueError(f"{what} tensor must be a contiguous 1-D float32 tensor on {dev}")
+        return values
+    tab = np.asarray(values, dtype=np.float64)
+    if tab.ndim != 1:
+        raise ValueError(f"{what} must be a 1-D sequence")
+    return torch.from_numpy(tab.astype(np.float32)).to(dev)
+
+
+def awgn_mix_tables(snr_db, llr_convention: str = "decoder", device=None):
+    """(scale_tab, shift_tab): float32 [K] on the device for the K SNR points of snr_db, each through ``awgn_scale_shift`` in
+    double and then cast -- what ``awgn_llr_mix(snr_db=...)`` builds per call, for callers that draw many blocks"""
+    dev = _require_gpu(device)
+    snr = np.asarray(snr_db, dtype=np.float64)
+    if snr.ndim != 1:
+        raise ValueError("snr_db must be a 1-D sequence of SNR points")
+    pairs = [awgn_scale_shift(float(s), llr_convention) for s in snr]
+    return _mix_table([p[0] for p in pairs], "scale", dev), _mix_table([p[1] for p in pairs], "shift", dev)
+
+
+def awgn_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, snr_db=None, scale=None,
+                 shift=None, llr_convention: str = "decoder", codeword=None, device=None) -> torch.Tensor:
+    """``awgn_llr`` with the SNR point a function of the frame (ldpc_channel_awgn_mix): frame f = first_frame + b is drawn at
+    point f % K of a table of K points -- the same noise as ``awgn_llr`` gives frame f, and the same point whatever block the
+    frame is drawn in, so every run of K consecutive frames holds each point once.  Give snr_db, a sequence of K values of
+    Es/N0 (tables through ``awgn_scale_shift(snr, llr_convention)`` per point in double, then fp32), or scale and shift: two
+    1-D sequences, or float32 tensors on the device, of equal length.  codeword as in ``awgn_llr``."""
+    dev = _require_gpu(device)
+    if (snr_db is None) == (scale is None or shift is None):
+        raise ValueError("give either snr_db or both scale and shift")
+    if llr_convention not in ("decoder", "reference"):
+        raise ValueError(f"llr_convention must be 'decoder' or 'reference', got {llr_convention!r}")
+    if snr_db is not None:
+        scale_tab, shift_tab = awgn_mix_tables(snr_db, llr_convention, dev)
+    else:
+        scale_tab, shift_tab = _mix_table(scale, "scale", dev), _mix_table(shift, "shift", dev)
+    n_points = scale_tab.numel()
+    if shift_tab.numel() != n_points:
+        raise ValueError(f"scale and shift must have equal length, got {n_points} and {shift_tab.numel()}")
+    if not 1 <= n_points <= MIX_MAX_POINTS:
+        raise ValueError(f"the number of SNR points must be in 1 .. {MIX_MAX_POINTS}, got {n_points}")
+    batch, n = int(batch), int(n)
+    if batch < 0 or n < 1:
+        raise ValueError("batch must be >= 0 and n >= 1")
+    if batch > 2 ** 31 - 1:
+        raise ValueError("batch must be <= 2^31 - 1")
+    cw = _channel_codeword(codeword, n, dev)
+    lib = nat.load()
+    out = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(lib.ldpc_channel_awgn_mix(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
+                                            int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1),
+                                            C.c_void_p(scale_tab.data_ptr()), C.c_void_p(shift_tab.data_ptr()), n_points,
+                                            None if cw is None else C.c_void_p(cw.data_ptr()), C.c_void_p(stream)),
+                  "ldpc_channel_awgn_mix")
     return out
 
 

@@ -52,6 +52,10 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
                  Device device) -> Tensor llr
      the counter-based BI-AWGN channel (ldpc_channel_awgn): fp32 LLRs [batch, n] of frames first_frame .. of stream
      (seed, stream_id), the same whatever block a frame is drawn in; needs no engine.
+  ldpc::awgn_llr_mix(int batch, int n, int seed, int stream_id, int first_frame, Tensor scale_tab, Tensor shift_tab,
+                     Tensor? codeword_packed, Device device) -> Tensor llr
+     the same stream with the SNR point a function of the frame (ldpc_channel_awgn_mix): frame f is drawn with
+     (scale_tab[p], shift_tab[p]), p = f % K, of two float32 tables of K entries on the device.
 
 ``engine`` is an integer handle of a live ``engine.DecodeEngine`` (``engine_handle(eng)``): operator schemas
 carry tensors and scalars, and the native decoder handle is neither.  There is no CPU implementation: the
@@ -144,6 +148,19 @@ def awgn_llr(batch: int, n: int, seed: int, stream_id: int, first_frame: int, sc
 
 @awgn_llr.register_fake
 def _(batch, n, seed, stream_id, first_frame, scale, shift, codeword_packed, device):
+    return torch.empty((batch, n), dtype=torch.float32, device=device)
+
+
+@torch.library.custom_op("ldpc::awgn_llr_mix", mutates_args=())
+def awgn_llr_mix(batch: int, n: int, seed: int, stream_id: int, first_frame: int, scale_tab: Tensor, shift_tab: Tensor,
+                 codeword_packed: Optional[Tensor], device: torch.device) -> Tensor:
+    import engine
+    return engine.awgn_llr_mix(batch, n, seed=seed, stream_id=stream_id, first_frame=first_frame, scale=scale_tab,
+                               shift=shift_tab, codeword=codeword_packed, device=device)
+
+
+@awgn_llr_mix.register_fake
+def _(batch, n, seed, stream_id, first_frame, scale_tab, shift_tab, codeword_packed, device):
     return torch.empty((batch, n), dtype=torch.float32, device=device)
 
 

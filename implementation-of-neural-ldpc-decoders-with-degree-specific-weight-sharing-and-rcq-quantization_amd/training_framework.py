@@ -26,11 +26,17 @@ does instead: the fixed-T decode with the BCE of EVERY iteration's posterior, ea
 the gradient of that iteration's posterior only (``model.joint_posterior_loss``, include/ldpc_hip.h ldpc_train_joint);
 no per-iteration history is kept, so the memory does not grow with T.  `use_posterior_training` is the reference's
 field and changes nothing.
+
+Addition, stated: `PosteriorJointTrainer.train_stream` is the same loop without a dataset.  The reference trains on one
+fixed set of 1000 host-drawn frames and never reads its own `snr_step`; `train_stream` draws fresh frames every step from
+the counter-based device noise stream, each mini-batch holding every point of the grid snr_range / snr_step in equal share
+(engine.awgn_llr_mix), reproducible bit for bit from (seed, step).
 """
 
 from __future__ import annotations
 
 import logging
+import os
 import time
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -72,8 +78,36 @@ def _grad_norm(model: nn.Module) -> float:
     return float(np.sqrt(sum(sq))) if sq else 0.0
 
 
-def _frames_right(decoded: torch.Tensor, targets: torch.Tensor) -> int:
-    return int((decoded == targets).all(dim=1).sum().item())
+def _frames_ok(decoded: torch.Tensor, targets: Optional[torch.Tensor]) -> torch.Tensor:
+    """bool [B]: every bit of the frame right; targets None is the all-zero codeword, for which no tensor is formed"""
+    return (decoded == (0 if targets is None else targets)).all(dim=1)
+
+
+def stream_first_frame(g: int, batch_size: int, rank: int = 0, world: int = 1) -> int:
+    """first frame of global step g on rank `rank` of `world` in stream training: step g draws the `world` consecutive
+    blocks of batch_size frames that start at frame g * world * batch_size, one per rank, so no frame is drawn twice"""
+    g, batch_size, rank, world = int(g), int(batch_size), int(rank), int(world)
+    if g < 0 or batch_size < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError("need g >= 0, batch_size >= 1 and 0 <= rank < world")
+    return (g * world + rank) * batch_size
+
+
+class _StreamBlocks:
+    """what `_pass` iterates over in stream training: blocks (first_frame, frames) drawn one by one as (llr, None) -- None is
+    the all-zero codeword -- with `drawn()` called after each block"""
+
+    def __init__(self, blocks, draw, drawn=None):
+        self.blocks, self.draw, self.drawn = list(blocks), draw, drawn
+
+    def __len__(self):
+        return len(self.blocks)
+
+    def __iter__(self):
+        for first, frames in self.blocks:
+            llr = self.draw(first, frames)
+            if self.drawn is not None:
+                self.drawn()
+            yield llr, None
 
 
 def _plot_series(panels, figsize, save_path):
@@ -110,6 +144,11 @@ class PosteriorJointTrainer:
         self.gradient_norms: List[float] = []
         self.train_iteration_losses: List[List[float]] = []
         self._pass_iteration_losses: Optional[List[float]] = None
+        self.stream_step = 0                          # train_stream: global steps drawn so far over the trainer's life
+        self.stream_seed: Optional[int] = None        # train_stream: config.seed, or the seed drawn at its first call
+        self.val_losses: List[float] = []
+        self.val_accuracies: List[float] = []
+        self.val_fer_per_point: List[List[float]] = []
         logger.info("trainer ready: %d trainable scalars", sum(p.numel() for p in model.parameters()))
 
     # ---- data ------------------------------------------------------------------------------------------
@@ -138,13 +177,15 @@ class PosteriorJointTrainer:
         return F.binary_cross_entropy_with_logits(posteriors.neg(), targets.to(posteriors.dtype))
 
     # ---- one pass over a loader ----------------------------------------------------------------------------
-    def _pass(self, loader: DataLoader, train: bool) -> Tuple[float, float, float]:
+    def _pass(self, loader, train: bool, frame_errors: Optional[list] = None) -> Tuple[float, float, float]:
+        """`loader`: a sized iterable of (llrs, targets); targets None is the all-zero codeword (stream training).
+        frame_errors: a list that receives each batch's bool [B] frame-error flags, on the device"""
         self.model.train(train)
         loss_sum, right, seen, norms = 0.0, 0, 0, []
         joint = self.config.joint_posterior_loss
         iter_sum = None
         for step, (llrs, targets) in enumerate(loader):
-            llrs, targets = llrs.to(self.device), targets.to(self.device)
+            llrs, targets = llrs.to(self.device), None if targets is None else targets.to(self.device)
             with torch.set_grad_enabled(train):
                 if joint:       # loss on every iteration's posterior, bits of the last one
                     loss, per_iter, decoded, _ = self.model.joint_posterior_loss(llrs, targets)
@@ -152,7 +193,7 @@ class PosteriorJointTrainer:
                     iter_sum = per_iter if iter_sum is None else iter_sum + per_iter
                 else:
                     decoded, posteriors, _ = self.model(llrs)
-                    loss = self.compute_loss(decoded, targets, posteriors)
+                    loss = self.compute_loss(decoded, torch.zeros_like(posteriors) if targets is None else targets, posteriors)
             if train:
                 self.optimizer.zero_grad()
                 loss.backward()                                 # HIP backward sweeps (autograd_bridge.py)
@@ -166,8 +207,11 @@ class PosteriorJointTrainer:
                 if step % 10 == 0:
                     logger.info("step %d: loss %.6f, |grad| %.6f", step, loss.item(), norms[-1])
             loss_sum += float(loss.item())
-            right += _frames_right(decoded, targets)
+            ok = _frames_ok(decoded, targets)
+            right += int(ok.sum().item())
             seen += llrs.shape[0]
+            if frame_errors is not None:
+                frame_errors.append(~ok)
         batches = max(len(loader), 1)
         self._pass_iteration_losses = None if iter_sum is None else (iter_sum / batches).tolist()
         return loss_sum / batches, right / max(seen, 1), (float(np.mean(norms)) if norms else 0.0)
@@ -200,6 +244,80 @@ class PosteriorJointTrainer:
         history = {"train_losses": self.train_losses, "train_accuracies": self.train_accuracies,
                    "gradient_norms": self.gradient_norms}
         if self.config.joint_posterior_loss:
+            history["train_iteration_losses"] = self.train_iteration_losses
+        return history
+
+    def train_stream(self, code: LDPCCode, steps_per_epoch: int, val_frames: int = 0, *, train_stream_id: int = 0,
+                     val_stream_id: int = 1) -> Dict[str, list]:
+        """`train` without a dataset: every step draws config.batch_size fresh frames of the counter-based device noise stream
+        (engine.awgn_llr_mix, seed config.seed), frame f at point f % K of the grid engine.snr_grid(config.snr_range,
+        config.snr_step), so every mini-batch holds each SNR point in equal share, up to one frame.  Global step g -- counted
+        in self.stream_step over the trainer's life, a second call continues the stream -- draws the frames from
+        stream_first_frame(g, batch_size, rank, world) of stream train_stream_id (one block per rank under
+        config.data_parallel with an initialised process group); the transmitted codeword is all zero.  A run is reproducible
+        bit for bit from (seed, step); with config.seed None a seed is drawn once, kept in self.stream_seed and logged.
+        After each epoch frames 0 .. val_frames - 1 of stream val_stream_id are validated, the same frames every epoch.
+        -> the history of `train` plus val_losses, val_accuracies, snr_points (the grid) and val_fer_per_point (per epoch,
+        the frame-error rate of each of the K points; nan for a point no validation frame falls on)."""
+        import engine
+        cfg = self.config
+        bs, steps_per_epoch, val_frames = int(cfg.batch_size), int(steps_per_epoch), int(val_frames)
+        if bs < 1 or steps_per_epoch < 1 or val_frames < 0:
+            raise ValueError("need batch_size >= 1, steps_per_epoch >= 1 and val_frames >= 0")
+        grid = engine.snr_grid(cfg.snr_range, cfg.snr_step)
+        K = len(grid)
+        if self.stream_seed is None:
+            if cfg.seed is None:
+                self.stream_seed = int.from_bytes(os.urandom(8), "little")
+                logger.info("stream training: drew seed %d", self.stream_seed)
+            else:
+                self.stream_seed = int(cfg.seed)
+        world, rank = 1, 0
+        if cfg.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized():
+            world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
+        scale_tab, shift_tab = engine.awgn_mix_tables(grid, cfg.llr_convention, self.device)
+
+        def draw(stream_id):
+            return lambda first, frames: engine.awgn_llr_mix(frames, code.n, seed=self.stream_seed, stream_id=stream_id,
+                                                             first_frame=first, scale=scale_tab, shift=shift_tab,
+                                                             device=scale_tab.device)
+
+        def step_drawn():
+            self.stream_step += 1
+
+        val_blocks = [(first, min(bs, val_frames - first)) for first in range(0, val_frames, bs)]
+        for epoch in range(cfg.num_epochs):
+            t0 = time.time()
+            g0 = self.stream_step
+            blocks = [(stream_first_frame(g0 + k, bs, rank, world), bs) for k in range(steps_per_epoch)]
+            loss, acc, gnorm = self._pass(_StreamBlocks(blocks, draw(train_stream_id), step_drawn), train=True)
+            if cfg.joint_posterior_loss:
+                self.train_iteration_losses.append(self._pass_iteration_losses or [])
+            self.train_losses.append(loss)
+            self.train_accuracies.append(acc)
+            self.gradient_norms.append(gnorm)
+            if val_blocks:
+                wrong: List[torch.Tensor] = []
+                vloss, vacc, _ = self._pass(_StreamBlocks(val_blocks, draw(val_stream_id)), train=False, frame_errors=wrong)
+                wrong = torch.cat(wrong)
+                points = engine.mix_points(0, val_frames, K, device=wrong.device)
+                frames = torch.bincount(points, minlength=K)
+                errors = torch.bincount(points[wrong], minlength=K)
+                self.val_losses.append(vloss)
+                self.val_accuracies.append(vacc)
+                self.val_fer_per_point.append((errors.double() / frames.double()).tolist())     # 0 / 0: nan
+                logger.info("epoch %d/%d: train loss %.6f acc %.4f | val loss %.6f acc %.4f | |grad| %.6f | %.2f s",
+                            epoch + 1, cfg.num_epochs, loss, acc, vloss, vacc, gnorm, time.time() - t0)
+            else:
+                logger.info("epoch %d/%d: train loss %.6f acc %.4f | |grad| %.6f | %.2f s",
+                            epoch + 1, cfg.num_epochs, loss, acc, gnorm, time.time() - t0)
+            if acc > 0.99:                                       # the stop rule of `train`
+                break
+        history = {"train_losses": self.train_losses, "train_accuracies": self.train_accuracies,
+                   "gradient_norms": self.gradient_norms, "val_losses": self.val_losses,
+                   "val_accuracies": self.val_accuracies, "snr_points": grid.tolist(),
+                   "val_fer_per_point": self.val_fer_per_point}
+        if cfg.joint_posterior_loss:
             history["train_iteration_losses"] = self.train_iteration_losses
         return history
 

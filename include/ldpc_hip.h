@@ -344,6 +344,20 @@ int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const v
  *   so a nonzero codeword's LLRs are the exact sign mirror of the all-zero draw.  scale = 2/sigma and shift = 2/sigma^2 are
  *   computed by the caller in double and passed as fp32; the reference's literal channel (bit 0 -> -1) passes -shift.
  *
+ * ldpc_channel_awgn_mix : the same stream with the SNR point a function of the frame (mixed-SNR training batches).  Sample j
+ *   of frame f uses exactly the counter, key, uniforms and Box-Muller above -- the normal z of a frame does not depend on which
+ *   of the two entry points draws it -- and
+ *     llr[b][j] = s_j * fmaf(z, scale_tab[p], shift_tab[p]),  p = f mod n_points,  f = first_frame + b (64-bit, absolute).
+ *   The point is a property of the frame, not of the block: any run of at least n_points consecutive frames holds every point
+ *   in equal share, up to one frame, however the stream is cut into blocks.  n_points == 1 is
+ *   ldpc_channel_awgn(scale_tab[0], shift_tab[0]) bit for bit.  scale_tab / shift_tab: device fp32, 4-byte aligned, n_points
+ *   entries each, read only, computed by the caller in double (negative shifts for the reference's literal channel);
+ *   codeword_packed as above.  LDPC_ERR_ARG, in this order, for batch < 0, batch > 2^31 - 1, n < 1, n_points outside
+ *   1 .. 4096, and a block that would wrap the 64-bit frame index (first_frame > 2^64 - batch: p is not continuous across the
+ *   wrap); then batch == 0 returns LDPC_OK without touching a pointer; then a NULL or misaligned llr, NULL or misaligned
+ *   tables.  The two limits keep the point index of a lane in 32-bit arithmetic.  Asynchronous on `stream`, allocates nothing,
+ *   safe under stream capture, like ldpc_channel_awgn.
+ *
  * ldpc_sim_count : folds one decoded block -- packed_bits[batch][ceil(n/8)] and iterations[batch] as ldpc_decode writes them --
  *   into state[8] (device, int64) = { frames, frame_errors, bit_errors, iterations, done, blocks_seen, 0, 0 }; the caller
  *   zeroes the state to start a point.  Per frame wrong = popcount(packed XOR codeword) over bits < n (pad bits of the last
@@ -393,6 +407,9 @@ typedef struct {
 
 int ldpc_channel_awgn(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
                       float scale, float shift, const uint8_t *codeword_packed, void *stream);
+int ldpc_channel_awgn_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                          const float *scale_tab, const float *shift_tab, int32_t n_points,
+                          const uint8_t *codeword_packed, void *stream);
 int ldpc_sim_count(int64_t *state, const uint8_t *packed_bits, const int32_t *iterations, int64_t batch, int32_t n,
                    const uint8_t *codeword_packed, int64_t max_frames, int64_t max_errors, void *stream);
 size_t ldpc_simulate_workspace_bytes(const ldpc_decoder *d, int64_t block);
