@@ -1239,6 +1239,245 @@ __device__ __forceinline__ void res_dump_c2v(const ResidentPlan &pl, const Resid
     }
 }
 
+// ---- compact kernels: entry and exit of a full block ---------------------------------------------------------
+// A compact plan has n <= n_pos <= kCptRows * kResCptThreads, so the rows of a codeword are ONE trip of kCptRows
+// positions j = tid + k * kResCptThreads per lane.  The fast forms below serve a workgroup whose G codewords all exist
+// (b0 + G <= batch, block-uniform) on a code with n > (kCptRows - 1) * kResCptThreads: rows 0 .. kCptRows-2 are full in
+// every wave and carry no bound at all; the last row is decided per wave on the scalar unit (`jw` = the wave's first j).
+// Everything else -- the padded last block, shorter codes -- keeps the per-element loops of the general kernels.
+constexpr int kCptRows = 4;
+// which of these forms an instantiation takes: the ones whose register allocation they cost scratch keep the general
+// kernels' form of that part (profiles/r18_compiler_report.txt).  The table follows one compiler's spills, not the
+// algorithm: compile the subsets again when the compiler changes (the report says how), and drop a fallback as soon as
+// its instantiation takes the new part without more scratch -- each one is a second form of that part to maintain
+constexpr unsigned kCptEntry = 1u;    // plan words ahead of the LLR loads, unbounded staging of a full block
+constexpr unsigned kCptInit = 2u;     // init scatter on the scalar cell degree
+constexpr unsigned kCptExit = 4u;     // syndrome walk, early inverse-permutation loads, specialised output pass
+constexpr unsigned res_cpt_forms(int form, bool bpc, int nl)
+{
+    if (form == FORM_OMS) return bpc ? kCptEntry | kCptInit : kCptInit;      // the exit (and, per edge, the entry) spill
+    if (form == FORM_RCQ && nl == 4 && !bpc) return kCptEntry | kCptInit;    // the exit spills
+    return kCptEntry | kCptInit | kCptExit;
+}
+static_assert(kCptRows == kResRegVars, "the staging rows are the register rounds");
+
+// element `i` (32-bit index) of a uniform table: global_load / global_store ... v_off, s[base], no 64-bit vector add
+template <typename X>
+__device__ __forceinline__ const X *res_at(const X *base, unsigned i)
+{
+    return reinterpret_cast<const X *>(reinterpret_cast<const char *>(base) + (size_t)(i * (unsigned)sizeof(X)));
+}
+template <typename X>
+__device__ __forceinline__ X *res_at(X *base, unsigned i)
+{
+    return reinterpret_cast<X *>(reinterpret_cast<char *>(base) + (size_t)(i * (unsigned)sizeof(X)));
+}
+
+// a row pointer of the block (uniform), pinned to an SGPR pair: the address of an element stays "scalar base + 32-bit lane
+// offset" instead of being re-associated into 64-bit vector adds shared between the rows.  The pin goes through an integer
+// and comes back as a global-memory pointer (a pointer that passes through inline asm is a flat one to the compiler:
+// flat_load / flat_store behind a 64-bit vector add each)
+template <typename X>
+__device__ __forceinline__ X *res_row(X *base, size_t elems)
+{
+    unsigned long long row = (unsigned long long)(base + elems);
+    asm volatile("" : "+s"(row));
+    return (X *)(__attribute__((address_space(1))) X *)row;
+}
+
+// the fast forms apply (block-uniform).  Opaque on purpose: evaluated at the entry and again at the exit
+template <int G>
+__device__ __forceinline__ bool res_cpt_full_block(const ResidentPlan &pl, const ResidentArgs &a, long long b0)
+{
+    int rows = kCptRows - 1;
+    asm volatile("" : "+s"(rows));
+    return b0 + G <= a.batch && pl.n > rows * kResCptThreads;
+}
+
+// The plan words of the entry, issued ahead of the LLR loads so that all of them return in one round trip: the wave's
+// cell and check words (SGPRs), the lane's slot offsets of its four rounds, the degree of its check and its beta column.
+// No load is conditional (one basic block): an empty cell reads the entries of cell 0, a lane past n_hi / past m the
+// last entry -- values nothing uses (an empty cell is skipped everywhere, the upper offsets are read by degree > 4
+// bodies only, the check phases mask lanes without a check).
+template <int G, bool BPC>
+__device__ __forceinline__ void res_cpt_plan_loads(const ResidentPlan &pl, int tid, unsigned wbase, ResVarState<float, G> &st,
+                                                   unsigned &chk_cells, int &dc_pre, unsigned &bcol)
+{
+    const unsigned lane = (unsigned)tid - wbase;
+    st.cells = pl.vcell[wbase >> 6];
+    chk_cells = pl.ccell[wbase >> 6];
+#pragma unroll
+    for (int r = 0; r < kResRegVars; ++r) {
+        const unsigned qb = ((st.cells >> (8 * r)) & 0xffu) ? wbase + (unsigned)(r * kResCptThreads) : 0u;   // scalar
+        st.plo[r] = *res_at(pl.vslot_lo, qb + lane);               // padded to whole cells
+    }
+    st.phi0 = *res_at(pl.vslot_hi, min((unsigned)tid, (unsigned)max(pl.n_hi, 1) - 1u));
+    const unsigned pc = min((unsigned)tid, (unsigned)pl.m - 1u);
+    dc_pre = *res_at(pl.dc_s, pc);
+    bcol = BPC ? *res_at(pl.bslot_c, pc) : 0u;
+}
+
+// LLR rows of a full block into the staging rows (sorted order), all loads before the first LDS store.  The partial
+// wave of the last row clamps j: its lanes past the row load and store element n-1 once more (same value, same place).
+template <int G>
+__device__ __forceinline__ void res_cpt_stage_llrs(const ResidentPlan &pl, const float *__restrict__ g_llr, long long b0, int tid,
+                                                   unsigned wbase)
+{
+    using P = Pack<float, G>;
+    constexpr int K = kCptRows, NT = kResCptThreads;
+    const unsigned n = (unsigned)pl.n;
+    const float *row[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) row[g] = res_row(g_llr, (size_t)(b0 + g) * n);
+    unsigned ip[K];
+    P v[K];
+#pragma unroll
+    for (int k = 0; k < K - 1; ++k) {
+        const unsigned j = (unsigned)tid + (unsigned)(k * NT);
+        ip[k] = *res_at(pl.inv_perm_v, j);
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[k].x[g] = res_stream_load(res_at(row[g], j));
+    }
+    const bool last = wbase + (unsigned)((K - 1) * NT) < n;         // wave-uniform: some lane of the last row is inside
+    if (last) {
+        const unsigned j = min((unsigned)tid + (unsigned)((K - 1) * NT), n - 1u);
+        ip[K - 1] = *res_at(pl.inv_perm_v, j);
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[K - 1].x[g] = res_stream_load(res_at(row[g], j));
+    }
+#pragma unroll
+    for (int k = 0; k < K - 1; ++k) lds_store<P>(ip[k] * (unsigned)sizeof(P), v[k]);
+    if (last) lds_store<P>(ip[K - 1] * (unsigned)sizeof(P), v[K - 1]);
+}
+
+// init scatter of round R on the wave's scalar cell degree (as res_var_round_cpt dispatches the phases): a uniform cell
+// stores its dv times behind scalar branches, a cell with holes is masked once, only a mixed cell compares per lane and edge
+template <int G, int R>
+__device__ __forceinline__ void res_cpt_init_round(const ResidentPlan &pl, const ResVarState<float, G> &st, int tid, bool zero)
+{
+    using P = Pack<float, G>;
+    const unsigned cd = (st.cells >> (8 * R)) & 0xffu;
+    if (cd == kCellEmpty) return;
+    const uint4 slo = plan_unpack(st.plo[R]), shi = R == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
+    const unsigned off[8] = {slo.x, slo.y, slo.z, slo.w, shi.x, shi.y, shi.z, shi.w};
+    P l = st.l[R];
+    if (zero) {                                                    // T == 0: c2v = 0
+#pragma unroll
+        for (int g = 0; g < G; ++g) l.x[g] = 0.0f;
+    }
+    if (cd == kCellMixed) {
+        const int dv = (int)(pl.vmeta[tid + R * kResCptThreads] & 0xffu);
+#pragma unroll
+        for (int e = 0; e < (R == 0 ? 8 : 4); ++e)
+            if (e < dv) lds_store<P>(off[e], l);
+        return;
+    }
+    if ((cd & kCellHoles) && st.plo[R].y == kResHole) return;       // the empty lanes of the cell
+    const int dv = (int)(cd & 0xfu);                               // wave-uniform: scalar compares and branches
+#pragma unroll
+    for (int e = 0; e < (R == 0 ? 8 : 4); ++e)
+        if (e < dv) lds_store<P>(off[e], l);
+}
+
+// final syndrome of a compact decode: position tid is the lane's only check, its row of decisions sits at immediate
+// offsets k * MS slots from one address; the walk is the check phase's (scalar trip counts from the wave's check word),
+// four slots per group, pairs folded by the three-input xor
+template <int G, int MS>
+__device__ __forceinline__ void res_cpt_syndrome_slots(unsigned cw, int dc, unsigned *sh_unsat, int tid)
+{
+    constexpr unsigned kSlot = sizeof(Pack<float, G>), stride = (unsigned)MS * kSlot;
+    auto body = [&]() {
+        unsigned x = 0;
+        res_walk_edges((unsigned)tid * kSlot, stride, chk_lo(cw), chk_spread(cw), dc, [&](unsigned addr, auto kc) {
+            constexpr int K = decltype(kc)::value;
+            unsigned v[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) v[k] = lds_load<unsigned>(addr + k * stride);
+            if constexpr (K == 1) {
+                x ^= v[0];
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; k += 2) x = __builtin_amdgcn_bitop3_b32(x, v[k], v[k + 1], 0x96);
+            }
+        });
+        if (x) atomicOr(sh_unsat, x);
+    };
+    const int lanes = chk_lanes(cw);
+    if (lanes == 64) body();
+    else if ((tid & 63) < lanes) body();
+}
+
+// output pass of a full block: `ip` = the inverse-permutation entries of the lane's kCptRows positions (loaded by the
+// caller ahead of the exit's barriers; the last row's j clamped as in res_cpt_stage_llrs), posteriors in the staging
+// rows.  What was asked for is tested once per output, outside the rows; the last row's partial wave is masked once.
+template <int G>
+__device__ __forceinline__ void res_cpt_emit(const ResidentPlan &pl, const ResidentArgs &a, long long b0, const unsigned (&ip)[kCptRows],
+                                             int iters, unsigned unsat, int tid, unsigned wbase)
+{
+    using P = Pack<float, G>;
+    constexpr int K = kCptRows, NT = kResCptThreads;
+    const unsigned n = (unsigned)pl.n, jl = (unsigned)tid + (unsigned)((K - 1) * NT), jwl = wbase + (unsigned)((K - 1) * NT);
+    const bool last = jwl < n;                                      // wave-uniform, as in res_cpt_stage_llrs
+    const bool part = jwl + 64u > n;                                // ... and only this wave of the last row is masked
+    if (a.posterior || a.bits || a.packed) {
+        P p[K];
+#pragma unroll
+        for (int k = 0; k < K - 1; ++k) p[k] = lds_load<P>(ip[k] * (unsigned)sizeof(P));
+        if (last) p[K - 1] = lds_load<P>(ip[K - 1] * (unsigned)sizeof(P));
+        if (a.posterior) {
+            float *row[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                row[g] = res_row(a.posterior, (size_t)(b0 + g) * n);
+#pragma unroll
+                for (int k = 0; k < K - 1; ++k) res_stream_store(res_at(row[g], (unsigned)tid + (unsigned)(k * NT)), p[k].x[g]);
+            }
+            if (last && (!part || jl < n)) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) res_stream_store(res_at(row[g], jl), p[K - 1].x[g]);
+            }
+        }
+        if (a.bits) {
+            int *row[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                row[g] = res_row(a.bits, (size_t)(b0 + g) * n);
+#pragma unroll
+                for (int k = 0; k < K - 1; ++k)
+                    res_stream_store(res_at(row[g], (unsigned)tid + (unsigned)(k * NT)), p[k].x[g] < 0.0f ? 1 : 0);
+            }
+            if (last && (!part || jl < n)) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) res_stream_store(res_at(row[g], jl), p[K - 1].x[g] < 0.0f ? 1 : 0);
+            }
+        }
+        if (a.packed) {
+            // a wave's 64 consecutive positions are 8 bytes of the row: ballot, lanes 0..7 store one byte each
+            const unsigned lane = (unsigned)tid - wbase, nb = (n + 7u) >> 3;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                uint8_t *row = res_row(a.packed, (size_t)(b0 + g) * nb);
+#pragma unroll
+                for (int k = 0; k < K - 1; ++k) {
+                    const unsigned long long m = __ballot(p[k].x[g] < 0.0f);
+                    if (lane < 8) *res_at(row, ((wbase + (unsigned)(k * NT)) >> 3) + lane) = (uint8_t)(m >> (8 * lane));
+                }
+                if (last) {
+                    const unsigned long long m = __ballot(jl < n && p[K - 1].x[g] < 0.0f);
+                    if (lane < 8 && jwl + 8 * lane < n) *res_at(row, (jwl >> 3) + lane) = (uint8_t)(m >> (8 * lane));
+                }
+            }
+        }
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (a.iterations) a.iterations[b0 + g] = iters;
+            if (a.success) a.success[b0 + g] = (uint8_t)(((unsat >> g) & 1u) ? 0 : 1);
+        }
+    }
+}
+
 // ES: 0 = fixed-iteration kernel, 1 = early-stop kernel (kept apart so that the fixed-T kernel does not carry
 // the posterior/syndrome/emit code of the stop rule: the extra code cost the hot loop ~4 % when merged)
 constexpr int kResMaxThreads = 1024;   // launch bounds of resident_decode: threads per workgroup, waves per SIMD the
@@ -1262,12 +1501,13 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
     const int n_alpha_lds = a.alpha_in_lds ? a.T * a.n_alpha * (int)(sizeof(T) / 4) : 0;
     // CPT: the LLR rows are staged at offset 0, in the message area the init scatter writes only after they are read
     T *llr_s = reinterpret_cast<T *>(res_smem + (CPT ? 0 : res_off_llr(pl.S, GE)));
-    T *alpha_s = reinterpret_cast<T *>(res_smem + res_off_alpha(pl.S, pl.n, GE));
-    uint8_t *bits_s = res_smem + res_off_bits(pl.S, pl.n, GE, n_alpha_lds);
+    // CPT: no alpha table, decision bytes or parity words in the carve, and nothing that touches them is compiled
+    T *alpha_s = CPT ? nullptr : reinterpret_cast<T *>(res_smem + res_off_alpha(pl.S, pl.n, GE));
+    uint8_t *bits_s = CPT ? nullptr : res_smem + res_off_bits(pl.S, pl.n, GE, n_alpha_lds);
     unsigned *sh_unsat = reinterpret_cast<unsigned *>(res_smem + (CPT ? res_cpt_off_flag(pl.S, GE)
                                                                         : res_off_flag(pl.S, pl.n, GE, n_alpha_lds)));
     ParScatter ps, psf;                                  // per-iteration syndrome (early stop) / final syndrome (fixed T)
-    if (pl.par_words) {
+    if (!CPT && pl.par_words) {
         psf.par_off = (unsigned)res_off_par(pl.S, pl.n, GE, n_alpha_lds);
         psf.shift = (unsigned)pl.par_shift;
         psf.mask = (unsigned)pl.mstride - 1u;
@@ -1286,7 +1526,21 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
     // All loads of a batch of kPro positions are issued before the first LDS store: one HBM round trip per
     // batch instead of one per element (the plain loop waits for every load before it issues the next).
     constexpr int kPro = 4;
-    for (int j0 = tid; j0 < n; j0 += kPro * nt) {
+    // compact kernels: the plan words first (res_cpt_plan_loads), then a full block of a code with a full third row
+    // stages its rows without bounds (`cpt_fast`, block-uniform)
+    ResVarState<T, G> st{};
+    unsigned chk_cells = 0;                              // compact kernels: this wave's check word, in an SGPR
+    int dc_cpt = 0;
+    unsigned bcol_cpt = 0;
+    bool cpt_fast = false;
+    constexpr unsigned EE = CPT ? res_cpt_forms(FORM, BPC, NL) : 0u;
+    if constexpr ((EE & kCptEntry) != 0) {
+        const unsigned wbase = (unsigned)__builtin_amdgcn_readfirstlane(tid) & ~63u;
+        res_cpt_plan_loads<G, BPC>(pl, tid, wbase, st, chk_cells, dc_cpt, bcol_cpt);
+        cpt_fast = res_cpt_full_block<G>(pl, a, b0);
+        if (cpt_fast) res_cpt_stage_llrs<G>(pl, g_llr, b0, tid, wbase);
+    }
+    for (int j0 = tid; j0 < (cpt_fast ? 0 : n); j0 += kPro * nt) {
         unsigned ip[kPro];
         P v[kPro];
 #pragma unroll
@@ -1304,45 +1558,72 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
         for (int k = 0; k < kPro; ++k)
             if (j0 + k * nt < n) reinterpret_cast<P *>(llr_s)[ip[k]] = v[k];
     }
-    for (int k = tid; k < (a.alpha_in_lds ? a.T * a.n_alpha : 0); k += nt) alpha_s[k] = g_alpha[k];
+    if constexpr (!CPT) {
+        for (int k = tid; k < (a.alpha_in_lds ? a.T * a.n_alpha : 0); k += nt) alpha_s[k] = g_alpha[k];
+    }
     if (tid == 0) { sh_unsat[0] = 0; sh_unsat[1] = 0; }
-    for (int k = tid; k < pl.par_words; k += nt) lds_store<unsigned>(psf.par_off + 4u * (unsigned)k, 0u);
+    if constexpr (!CPT) {
+        for (int k = tid; k < pl.par_words; k += nt) lds_store<unsigned>(psf.par_off + 4u * (unsigned)k, 0u);
+    }
+    // first-round check degree (iteration-invariant) and per-check beta of iteration 0, in registers
+    int dc_pre = 0;
+    T b_pre = (T)0;
+    if constexpr ((EE & kCptEntry) != 0) {
+        // the beta of iteration 0 follows its column as soon as that is here: in flight across the barriers of the entry
+        dc_pre = dc_cpt;
+        if (BPC && a.T > 0) b_pre = *res_at(g_beta, bcol_cpt);
+    }
     __syncthreads();
     // "initialise v2c with the channel LLRs" (T == 0: c2v = 0, the loop never runs)
-    ResVarState<T, G> st{};
     if constexpr (CPT) {
-        // the lane's positions q = tid + r*nt of the host's grid: plan entries and LLR pairs into registers once per
-        // launch, the wave's cell word into an SGPR; empty cells load nothing, empty lanes of a cell keep kResHole
-        st.cells = pl.vcell[__builtin_amdgcn_readfirstlane(tid) >> 6];
-        const P *L = reinterpret_cast<const P *>(llr_s);
+        // the lane's positions q = tid + r*nt of the host's grid: LLR pairs (and, in the kernels that do not load them at
+        // the top, the plan entries) into registers once per launch, the wave's cell word into an SGPR
+        if constexpr ((EE & kCptEntry) != 0) {
+            // a position past n_pos reads the last staged row: nothing uses it
 #pragma unroll
-        for (int r = 0; r < kResRegVars; ++r) {
-            const int q = tid + r * nt;
-            if (q < pl.n_pos) st.l[r] = L[q];                     // the staging rows hold positions < n_pos
-            if ((st.cells >> (8 * r)) & 0xffu) {
-                st.plo[r] = pl.vslot_lo[q];                       // padded to whole cells
-                if (r == 0 && q < pl.n_hi) st.phi0 = pl.vslot_hi[q];
+            for (int r = 0; r < kResRegVars; ++r)
+                st.l[r] = lds_load<P>(min((unsigned)tid + (unsigned)(r * kResCptThreads), (unsigned)pl.n_pos - 1u) * (unsigned)sizeof(P));
+        } else {
+            // empty cells load nothing, empty lanes of a cell keep kResHole
+            st.cells = pl.vcell[__builtin_amdgcn_readfirstlane(tid) >> 6];
+            const P *L = reinterpret_cast<const P *>(llr_s);
+#pragma unroll
+            for (int r = 0; r < kResRegVars; ++r) {
+                const int q = tid + r * nt;
+                if (q < pl.n_pos) st.l[r] = L[q];                     // the staging rows hold positions < n_pos
+                if ((st.cells >> (8 * r)) & 0xffu) {
+                    st.plo[r] = pl.vslot_lo[q];                       // padded to whole cells
+                    if (r == 0 && q < pl.n_hi) st.phi0 = pl.vslot_hi[q];
+                }
             }
         }
         __syncthreads();                                   // the init scatter below overwrites the staged LLR rows
+        if constexpr ((EE & kCptInit) != 0) {
+            static_assert(kResRegVars == 4, "four rounds");
+            res_cpt_init_round<G, 0>(pl, st, tid, a.T == 0);
+            res_cpt_init_round<G, 1>(pl, st, tid, a.T == 0);
+            res_cpt_init_round<G, 2>(pl, st, tid, a.T == 0);
+            res_cpt_init_round<G, 3>(pl, st, tid, a.T == 0);
+        } else {
 #pragma unroll
-        for (int r = 0; r < kResRegVars; ++r) {
-            const unsigned cd = (st.cells >> (8 * r)) & 0xffu;
-            if (cd == kCellEmpty) continue;
-            const int q = tid + r * nt;
-            int dv = (int)(cd & 0xfu);
-            if (cd == kCellMixed) dv = (int)(pl.vmeta[q] & 0xffu);
-            else if ((cd & kCellHoles) && st.plo[r].y == kResHole) dv = 0;
-            const uint4 slo = plan_unpack(st.plo[r]), shi = r == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
-            const unsigned off[8] = {slo.x, slo.y, slo.z, slo.w, shi.x, shi.y, shi.z, shi.w};
-            P l = st.l[r];
-            if (a.T == 0) {
+            for (int r = 0; r < kResRegVars; ++r) {
+                const unsigned cd = (st.cells >> (8 * r)) & 0xffu;
+                if (cd == kCellEmpty) continue;
+                const int q = tid + r * nt;
+                int dv = (int)(cd & 0xfu);
+                if (cd == kCellMixed) dv = (int)(pl.vmeta[q] & 0xffu);
+                else if ((cd & kCellHoles) && st.plo[r].y == kResHole) dv = 0;
+                const uint4 slo = plan_unpack(st.plo[r]), shi = r == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
+                const unsigned off[8] = {slo.x, slo.y, slo.z, slo.w, shi.x, shi.y, shi.z, shi.w};
+                P l = st.l[r];
+                if (a.T == 0) {
 #pragma unroll
-                for (int g = 0; g < G; ++g) l.x[g] = (T)0;
+                    for (int g = 0; g < G; ++g) l.x[g] = (T)0;
+                }
+#pragma unroll
+                for (int e = 0; e < (r == 0 ? 8 : 4); ++e)
+                    if (e < dv) lds_store<P>(off[e], l);
             }
-#pragma unroll
-            for (int e = 0; e < (r == 0 ? 8 : 4); ++e)
-                if (e < dv) lds_store<P>(off[e], l);
         }
     } else if constexpr (REG) {
         // the lane's variables q = tid + r*nt: plan entries and LLR pairs into registers, once per launch
@@ -1416,11 +1697,11 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
             }
         }
     }
-    unsigned chk_cells = 0;                              // compact kernels: this wave's check word, in an SGPR
-    if constexpr (CPT) chk_cells = pl.ccell[__builtin_amdgcn_readfirstlane(tid) >> 6];
-    // first-round check degree (iteration-invariant) and per-check beta of iteration 0, in registers
-    const int dc_pre = tid < pl.m ? pl.dc_s[tid] : 0;
-    T b_pre = (BPC && tid < pl.m && a.T > 0) ? g_beta[pl.bslot_c[tid]] : (T)0;
+    if constexpr ((EE & kCptEntry) == 0) {
+        if constexpr (CPT) chk_cells = pl.ccell[__builtin_amdgcn_readfirstlane(tid) >> 6];
+        dc_pre = tid < pl.m ? pl.dc_s[tid] : 0;
+        b_pre = (BPC && tid < pl.m && a.T > 0) ? g_beta[pl.bslot_c[tid]] : (T)0;
+    }
     __syncthreads();
 
     unsigned done = 0;                                   // block-uniform
@@ -1513,6 +1794,38 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
     if (ES) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
     else if (scatter) res_var_phase<G, 1, T, REG>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st, psf);
     else res_var_phase<G, CPT ? 9 : 8, T, REG, CPT>(pl, res_smem, llr_s, bits_s, (const T *)nullptr, (const T *)nullptr, open, tid, nt, st);
+    if constexpr ((EE & kCptExit) != 0) {
+        // a full block's inverse-permutation entries are issued here, ahead of the three barriers below instead of behind them.
+        // The block's form and the wave's base are worked out again (scalar unit) instead of living across the iterations
+        unsigned ip[kCptRows] = {};
+        cpt_fast = res_cpt_full_block<G>(pl, a, b0);
+        const unsigned wbase = (unsigned)__builtin_amdgcn_readfirstlane(tid) & ~63u;
+        if (cpt_fast) {
+#pragma unroll
+            for (int k = 0; k < kCptRows; ++k)
+                ip[k] = *res_at(pl.inv_perm_v, min((unsigned)tid + (unsigned)(k * kResCptThreads), (unsigned)n - 1u));
+        }
+        __syncthreads();
+        res_cpt_syndrome_slots<G, MS>(chk_cells, dc_pre, sh_unsat, tid);
+        __syncthreads();
+        const unsigned unsat = *sh_unsat;
+        // the slots are dead now: the posteriors the last pass kept in registers go to the staging rows (sorted order);
+        // a cell without holes stores unmasked
+#pragma unroll
+        for (int r = 0; r < kResRegVars; ++r) {
+            const unsigned cd = (st.cells >> (8 * r)) & 0xffu;
+            const unsigned q = (unsigned)tid + (unsigned)(r * kResCptThreads);
+            if (cd == kCellEmpty) continue;
+            if (cd != kCellMixed && !(cd & kCellHoles)) lds_store<P>(q * (unsigned)sizeof(P), st.l[r]);
+            else if (q < (unsigned)pl.n_pos) lds_store<P>(q * (unsigned)sizeof(P), st.l[r]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kCptRows; ++k) asm volatile("" : "+v"(ip[k]));   // nothing waits for the entries before this point
+        if (cpt_fast) res_cpt_emit<G>(pl, a, b0, ip, a.T, unsat, tid, wbase);
+        else res_emit<G, T>(pl, a, llr_s, b0, open, a.T, unsat, tid, nt);
+        return;
+    }
     __syncthreads();
     unsigned unsat = kAll;
     if (!ES) {
