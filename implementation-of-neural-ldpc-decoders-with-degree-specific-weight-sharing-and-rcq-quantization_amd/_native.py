@@ -136,13 +136,15 @@ class SimDesc(C.Structure):
 # every symbol include/ldpc_hip.h declares (tests check the library exports them all) ...
 PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info", "ldpc_decoder_create",
                    "ldpc_decoder_set_mode", "ldpc_decoder_info",
-                   "ldpc_decoder_set_weights", "ldpc_decoder_destroy", "ldpc_decoder_workspace_bytes",
+                   "ldpc_decoder_set_weights", "ldpc_decoder_set_quantizers", "ldpc_decoder_destroy", "ldpc_decoder_workspace_bytes",
                    "ldpc_decode", "ldpc_decode_capped", "ldpc_last_error", "ldpc_abi_version", "ldpc_source_hash",
                    "ldpc_train_saved_bytes", "ldpc_train_workspace_bytes", "ldpc_decode_saving", "ldpc_backward",
                    "ldpc_train_joint_workspace_bytes", "ldpc_train_joint",
                    "ldpc_train_joint_ste_workspace_bytes", "ldpc_train_joint_ste",
                    "ldpc_train_joint_layered_workspace_bytes", "ldpc_train_joint_layered",
                    "ldpc_train_joint_layered_ste_workspace_bytes", "ldpc_train_joint_layered_ste",
+                   "ldpc_train_joint_ste_levels_workspace_bytes", "ldpc_train_joint_ste_levels",
+                   "ldpc_train_joint_layered_ste_levels_workspace_bytes", "ldpc_train_joint_layered_ste_levels",
                    "ldpc_channel_awgn", "ldpc_channel_awgn_mix", "ldpc_sim_count",
                    "ldpc_simulate_workspace_bytes", "ldpc_simulate",
                    "ldpc_sim_diag_words", "ldpc_sim_count_diag_scratch_bytes", "ldpc_sim_count_diag",
@@ -192,6 +194,8 @@ def load():
         lib.ldpc_decoder_info.argtypes = [vp, vp]
         lib.ldpc_decoder_set_weights.restype = C.c_int
         lib.ldpc_decoder_set_weights.argtypes = [vp, vp, vp, vp, vp]
+        lib.ldpc_decoder_set_quantizers.restype = C.c_int
+        lib.ldpc_decoder_set_quantizers.argtypes = [vp, vp, vp]
         lib.ldpc_decoder_destroy.restype = None
         lib.ldpc_decoder_destroy.argtypes = [vp]
         lib.ldpc_decoder_workspace_bytes.restype = C.c_size_t
@@ -242,6 +246,11 @@ def load():
         lib.ldpc_train_joint_layered_ste_workspace_bytes.argtypes = [vp, i64]
         lib.ldpc_train_joint_layered_ste.restype = C.c_int
         lib.ldpc_train_joint_layered_ste.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+        for name in ("ldpc_train_joint_ste_levels", "ldpc_train_joint_layered_ste_levels"):
+            getattr(lib, name + "_workspace_bytes").restype = C.c_size_t
+            getattr(lib, name + "_workspace_bytes").argtypes = [vp, i64]
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
         u32, u64, f32 = C.c_uint32, C.c_uint64, C.c_float
         lib.ldpc_channel_awgn.restype = C.c_int
         lib.ldpc_channel_awgn.argtypes = [vp, i64, i32, u64, u32, u64, f32, f32, vp, vp]

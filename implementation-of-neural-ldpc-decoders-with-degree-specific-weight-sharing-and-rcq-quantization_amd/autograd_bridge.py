@@ -120,16 +120,20 @@ def check_layered_gradient(value, schedule="layered"):
 
 
 def joint_loss_ste(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets,
-                   iteration_weights, layered: bool = False):
+                   iteration_weights, layered: bool = False, thresholds=None):
     """joint_loss() of the quantised WeightedRCQDecoder through ``torch.ops.ldpc.rcq_joint_loss``: the same loss on the
     decoder's own fixed-T decode, differentiable with the straight-through rule of include/ldpc_hip.h
     (ldpc_train_joint_ste) -> (loss, loss_per_iteration, bits, posterior).  ``layered``: the engine runs the paper's
-    layered schedule -- ``torch.ops.ldpc.rcq_layered_joint_loss`` (ldpc_train_joint_layered_ste)."""
-    return joint_loss(beta_table, alpha_table, engine, llr, targets, iteration_weights, False, quantised=True, layered=layered)
+    layered schedule -- ``torch.ops.ldpc.rcq_layered_joint_loss`` (ldpc_train_joint_layered_ste).
+    ``thresholds`` [Q, L] (a learned quantiser, rcq_decoder.WeightedRCQDecoder.thresholds_tensor): the call goes through
+    ``torch.ops.ldpc.rcq_joint_loss_levels`` / ``rcq_layered_joint_loss_levels``, which decode with that table and whose
+    backward sums the level gradients [T, L] per quantiser (the engine's q_of_iter) into d loss / d thresholds."""
+    return joint_loss(beta_table, alpha_table, engine, llr, targets, iteration_weights, False, quantised=True, layered=layered,
+                      thresholds=thresholds)
 
 
 def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr: torch.Tensor, targets, iteration_weights,
-               alpha_is_oms: bool, quantised: bool = False, layered: bool = False):
+               alpha_is_oms: bool, quantised: bool = False, layered: bool = False, thresholds=None):
     """posterior joint training through ``torch.ops.ldpc.minsum_joint_loss`` (torch_ops.py) -> (loss, loss_per_iteration,
     bits, posterior): loss = sum_t w_t * mean BCEWithLogits(-posterior_t, targets) over the T iterations of the fixed-T
     decode, differentiable in the tables (and in `llr` when it requires grad) with the posterior-local gradient of the
@@ -157,8 +161,15 @@ def joint_loss(beta_table: torch.Tensor, alpha_table: torch.Tensor, engine, llr:
     op, form = ((torch.ops.ldpc.rcq_layered_joint_loss if layered else torch.ops.ldpc.rcq_joint_loss, ())
                 if quantised else                                               # the quantised operators have no alpha_is_oms
                 (torch.ops.ldpc.minsum_layered_joint_loss if layered else torch.ops.ldpc.minsum_joint_loss, (bool(alpha_is_oms),)))
-    loss, lpi, post, bits, _gb, _ga, _gl = op(xd.contiguous(), y, beta_table, alpha_table, w, torch_ops.engine_handle(engine),
-                                              *form, bool(want_grads), bool(want_llr))
+    if thresholds is not None:
+        if not quantised:
+            raise ValueError("thresholds belong to the quantised decoders")
+        op = torch.ops.ldpc.rcq_layered_joint_loss_levels if layered else torch.ops.ldpc.rcq_joint_loss_levels
+        loss, lpi, post, bits = op(xd.contiguous(), y, beta_table, alpha_table, thresholds, w, torch_ops.engine_handle(engine),
+                                   bool(want_grads), bool(want_llr))[:4]
+    else:
+        loss, lpi, post, bits, _gb, _ga, _gl = op(xd.contiguous(), y, beta_table, alpha_table, w,
+                                                  torch_ops.engine_handle(engine), *form, bool(want_grads), bool(want_llr))
     out_dev = llr.device
     if single:
         bits, post = bits[0], post[0]

@@ -94,6 +94,9 @@ struct ldpc_decoder {
     float *lut = nullptr;          // device [Q][2L] signed reconstruction values
     std::vector<int> q_of_iter;    // host
     int *q_of_iter_dev = nullptr;  // device copy (frozen codewords look their quantiser up)
+    std::vector<float> lut_host;   // what `lut` was uploaded from (ldpc_decoder_set_quantizers enqueues the copy)
+    int *level_iota = nullptr;     // device 0 .. n_levels: the identity slot map the level gradient is reduced with
+    bool resc_per_check = false;   // the compact plan has one beta slot per (sub-)check: its check words follow rcq_zero0
     size_t elem() const { return dtype == LDPC_F64 ? 8 : 4; }
     // LDS-resident engine (ldpc_resident.hip): built at creation when the code qualifies
     int schedule = 0;              // LDPC_SCHED_*
@@ -788,8 +791,84 @@ int decode_dispatch(const ldpc_decoder *d, const void *llr, int64_t batch, bool 
 }
 
 
-// alpha table identically 1.0f / every quantiser's tau_0 == 0: exact shortcuts in the resident kernel
-void resident_table_flags(ldpc_decoder *d, const void *alpha_host, const float *thr_host)
+// Everything the decoder derives from the VALUES of its quantiser tables, in one place: ldpc_decoder_create and
+// ldpc_decoder_set_quantizers both go through quantizer_flags / apply_quantizer_flags, so a decoder whose thresholds were
+// replaced picks the kernels a freshly created one would.
+struct QuantizerFlags {
+    bool pair_ok = false;       // code-pair form: thresholds 1.. of every quantiser positive and non-decreasing
+    bool key_float4 = false;    // ... 4 levels, every one of them in [2^-50, 2^50]: the float form of the key
+    bool rcq_zero0 = false;     // every tau_0 == 0: the resident kernel quantises per check (and the compact plan's check words)
+    bool lay_zero0 = false;     // layered plans: magnitude 0 reconstructs to 0 under every quantiser
+    bool lay_sorted = false;    // layered plans: tau_1 <= tau_2 <= ... under every quantiser
+};
+
+QuantizerFlags quantizer_flags(const ldpc_decoder *d, const float *thr)
+{
+    QuantizerFlags f;
+    const int L = d->n_levels, Q = d->n_quant;
+    const ldpc_graph *g = d->g;
+    if (d->dtype == LDPC_F32 && d->schedule == LDPC_SCHED_FLOODING && g->E > 0 && d->beta_per_check && L <= 62) {
+        // code-pair form: level(|beta * x|) must be non-decreasing in x, i.e. thresholds 1.. of every quantiser sorted, and
+        // positive (level(0) = 0; the magnitude compares run on the bit patterns)
+        // (threshold 0 never decides a level, rcq_decoder.py:79-85)
+        bool sorted = true;
+        for (int q = 0; q < Q && sorted; ++q)
+            for (int k = 1; k < L; ++k) {
+                const float t = thr[(size_t)q * L + k];
+                if (!(t > 0.0f) || (k > 1 && t < thr[(size_t)q * L + k - 1])) { sorted = false; break; }
+            }
+        f.pair_ok = sorted;
+        bool in_range = sorted && L == 4;
+        for (int q = 0; q < Q && in_range; ++q)
+            for (int k = 1; k < L; ++k) {
+                const float t = thr[(size_t)q * L + k];
+                if (!(t >= 0x1p-50f && t <= 0x1p50f)) in_range = false;
+            }
+        f.key_float4 = in_range;
+    }
+    f.rcq_zero0 = true;
+    for (int q = 0; q < Q; ++q) f.rcq_zero0 = f.rcq_zero0 && thr[(size_t)q * L] == 0.0f;
+    // magnitude 0 reconstructs to 0 under every quantiser (rcq_decoder.py:79-85, :107-119): tau_0 == 0 and no later
+    // threshold <= 0 -- true for the reference's C * (j / (2^(bc-1) - 1))^gamma with gamma > 0
+    f.lay_zero0 = true;
+    for (int q = 0; q < Q; ++q) {
+        float rec = thr[(size_t)q * L];
+        for (int k = 1; k < L; ++k)
+            if (0.0f >= thr[(size_t)q * L + k]) rec = thr[(size_t)q * L + k];
+        f.lay_zero0 = f.lay_zero0 && rec == 0.0f;
+    }
+    f.lay_sorted = true;                                              // tau_1 <= tau_2 <= ... under every quantiser
+    for (int q = 0; q < Q; ++q)
+        for (int k = 2; k < L; ++k) f.lay_sorted = f.lay_sorted && thr[(size_t)q * L + k - 1] <= thr[(size_t)q * L + k];
+    return f;
+}
+
+// the flags into the decoder and into the plans already built from earlier ones (creation: none yet, the plan builders
+// read d->rcq_zero0 and call quantizer_flags themselves)
+void apply_quantizer_flags(ldpc_decoder *d, const QuantizerFlags &f)
+{
+    d->pair_ok = f.pair_ok; d->key_float4 = f.key_float4; d->rcq_zero0 = f.rcq_zero0;
+    if (d->resc_ok) {                                 // compact plan: which waves run the scalar-counted check phase
+        std::vector<ResVCheck> vc;
+        if (resident_checks(d->g, vc)) cpt_check_words(vc, d->resc_per_check && f.rcq_zero0, d->resc.ccell);
+    }
+    if (d->lay_ok) { d->lay.zero0 = f.lay_zero0 ? 1 : 0; d->lay.sorted = f.lay_sorted ? 1 : 0; }
+}
+
+// signed reconstruction LUT: value of code c = (1 - 2*sign_bit) * tau[c mod L]  (rcq_decoder.py:107-119)
+void fill_quantizer_lut(ldpc_decoder *d, const float *thr)
+{
+    const size_t L = d->n_levels, Q = d->n_quant;
+    d->lut_host.resize(Q * 2 * L);
+    for (size_t q = 0; q < Q; ++q)
+        for (size_t c = 0; c < 2 * L; ++c) {
+            const float sb = c >= L ? 1.0f : 0.0f;
+            d->lut_host[q * 2 * L + c] = (1.0f - 2.0f * sb) * thr[q * L + (c % L)];
+        }
+}
+
+// alpha table identically 1.0f: an exact shortcut in the resident kernel (the quantiser's flags: quantizer_flags)
+void resident_table_flags(ldpc_decoder *d, const void *alpha_host)
 {
     if (alpha_host) {
         const size_t cnt = (size_t)std::max(d->T, 0) * d->n_alpha;
@@ -802,11 +881,6 @@ void resident_table_flags(ldpc_decoder *d, const void *alpha_host, const float *
             for (size_t k = 0; k < cnt; ++k) unit = unit && a[k] == 1.0;
         }
         d->unit_alpha = unit;
-    }
-    if (thr_host) {
-        bool z = true;
-        for (int q = 0; q < d->n_quant; ++q) z = z && thr_host[(size_t)q * d->n_levels] == 0.0f;
-        d->rcq_zero0 = z;
     }
 }
 
@@ -883,6 +957,7 @@ int build_resident_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
     if (int rc = upload_plan(d, c.resc, d->resc)) return rc;
     d->resc_layout = std::move(c.resc_layout);
     d->resc_lds = c.resc_lds;
+    d->resc_per_check = c.resc.per_check;
     d->resc_ok = true;
     return LDPC_OK;
 }
@@ -1122,21 +1197,11 @@ int build_layered_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
             off[(size_t)i * lw + t] = o | (dc == 1 ? kLayDeg1Bit : 0u);
         }
     }
-    // magnitude 0 reconstructs to 0 under every quantiser (rcq_decoder.py:79-85, :107-119): tau_0 == 0 and no later
-    // threshold <= 0 -- true for the reference's C * (j / (2^(bc-1) - 1))^gamma with gamma > 0
-    bool zero0 = true;
-    for (int q = 0; q < (minsum ? 0 : d->n_quant); ++q) {
-        float rec = desc->thresholds[(size_t)q * d->n_levels];
-        for (int k = 1; k < d->n_levels; ++k)
-            if (0.0f >= desc->thresholds[(size_t)q * d->n_levels + k]) rec = desc->thresholds[(size_t)q * d->n_levels + k];
-        zero0 = zero0 && rec == 0.0f;
-    }
+    // what the kernels may assume of the quantiser tables (quantizer_flags; both hold trivially for the min-sum forms)
+    const QuantizerFlags qf = minsum ? QuantizerFlags{} : quantizer_flags(d, desc->thresholds);
+    const bool zero0 = minsum || qf.lay_zero0, sorted = minsum || qf.lay_sorted;
     int rc = upload(&d->lay_off, off.data(), off.size());
     if (rc) return rc;
-    bool sorted = true;                                               // tau_1 <= tau_2 <= ... under every quantiser
-    for (int q = 0; q < (minsum ? 0 : d->n_quant); ++q)
-        for (int k = 2; k < d->n_levels; ++k)
-            sorted = sorted && desc->thresholds[(size_t)q * d->n_levels + k - 1] <= desc->thresholds[(size_t)q * d->n_levels + k];
     // A power-of-two region per codeword (address = offset | row bits, one v_and_or_b32) was measured and dropped: 4 x 8192 bytes
     // leave room for only four workgroups per CU instead of five and put the four rows of a wave on the same LDS banks
     // ((1998,1512): 11.2 vs 9.6 ms, profiles/r03_layered_variants.txt).  The kernel keeps the template flag for A/B builds.
@@ -1446,15 +1511,12 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
         if (d->q_of_iter.empty()) d->q_of_iter.push_back(0);
         const size_t L = d->n_levels, Q = d->n_quant;
         rc = upload(&d->thresholds, desc->thresholds, Q * L);
-        // signed reconstruction LUT: value of code c = (1 - 2*sign_bit) * tau[c mod L]  (rcq_decoder.py:107-119)
-        std::vector<float> lut(Q * 2 * L);
-        for (size_t q = 0; q < Q; ++q)
-            for (size_t c = 0; c < 2 * L; ++c) {
-                const float sb = c >= L ? 1.0f : 0.0f;
-                lut[q * 2 * L + c] = (1.0f - 2.0f * sb) * desc->thresholds[q * L + (c % L)];
-            }
-        if (!rc) rc = upload(&d->lut, lut.data(), lut.size());
+        fill_quantizer_lut(d, desc->thresholds);
+        if (!rc) rc = upload(&d->lut, d->lut_host.data(), d->lut_host.size());
         if (!rc) rc = upload(&d->q_of_iter_dev, d->q_of_iter.data(), d->q_of_iter.size());
+        std::vector<int> iota(L + 1);
+        for (size_t k = 0; k <= L; ++k) iota[k] = (int)k;
+        if (!rc) rc = upload(&d->level_iota, iota.data(), iota.size());
         if (!rc && Q * 2 * L * sizeof(float) > 64 * 1024) rc = fail(LDPC_ERR_UNSUPPORTED, "quantiser LUTs exceed 64 KiB of LDS");
     }
     if (!rc && d->form == LDPC_C2V_OMS && desc->oms_alpha && d->T > 0) {
@@ -1500,27 +1562,8 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
         if (!rc) rc = upload(&d->gat_nbr, nbr.data(), nbr.size());
         d->gat_ok = !rc;
     }
-    if (!rc && d->form == LDPC_C2V_RCQ && d->dtype == LDPC_F32 && d->schedule == LDPC_SCHED_FLOODING && g->E > 0 &&
-        d->beta_per_check && d->n_levels <= 62) {
-        // code-pair form: level(|beta * x|) must be non-decreasing in x, i.e. thresholds 1.. of every quantiser sorted, and
-        // positive (level(0) = 0; the magnitude compares run on the bit patterns)
-        // (threshold 0 never decides a level, rcq_decoder.py:79-85)
-        bool sorted = true;
-        for (int q = 0; q < d->n_quant && sorted; ++q)
-            for (int k = 1; k < d->n_levels; ++k) {
-                const float t = desc->thresholds[(size_t)q * d->n_levels + k];
-                if (!(t > 0.0f) || (k > 1 && t < desc->thresholds[(size_t)q * d->n_levels + k - 1])) { sorted = false; break; }
-            }
-        d->pair_ok = sorted;
-        bool in_range = sorted && d->n_levels == 4;
-        for (int q = 0; q < d->n_quant && in_range; ++q)
-            for (int k = 1; k < d->n_levels; ++k) {
-                const float t = desc->thresholds[(size_t)q * d->n_levels + k];
-                if (!(t >= 0x1p-50f && t <= 0x1p50f)) in_range = false;
-            }
-        d->key_float4 = in_range;
-    }
-    resident_table_flags(d, desc->alpha, d->form == LDPC_C2V_RCQ ? desc->thresholds : nullptr);
+    if (!rc && d->form == LDPC_C2V_RCQ) apply_quantizer_flags(d, quantizer_flags(d, desc->thresholds));   // before the plans
+    resident_table_flags(d, desc->alpha);
     beta_table_flags(d, desc->beta);
     if (!rc && d->schedule == LDPC_SCHED_FLOODING) rc = build_resident_plan(d, desc);
     if (!rc) rc = build_layered_plan(d, desc);
@@ -1580,7 +1623,7 @@ int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alph
     }
     if (alpha) {
         HIP_TRY(hipMemcpyAsync(d->alpha, alpha, rows * d->n_alpha * es, hipMemcpyHostToDevice, s));
-        resident_table_flags(d, alpha, nullptr);
+        resident_table_flags(d, alpha);
     }
     if (oms_alpha) {
         if (!d->oms_alpha) return fail(LDPC_ERR_ARG, "decoder was created without oms_alpha");
@@ -1590,13 +1633,38 @@ int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alph
     return LDPC_OK;
 }
 
+static int set_quantizers_impl(ldpc_decoder *d, const float *thresholds, void *stream)
+{
+    if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
+    if (d->form != LDPC_C2V_RCQ) return fail(LDPC_ERR_UNSUPPORTED, "ldpc_decoder_set_quantizers: the decoder has no quantiser (LDPC_C2V_RCQ only)");
+    if (!thresholds) return fail(LDPC_ERR_ARG, "NULL thresholds");
+    const QuantizerFlags f = quantizer_flags(d, thresholds);
+    // a forced form the new table does not admit: refuse before anything is touched (ldpc_decoder_set_mode's message)
+    if (d->mode == LDPC_MODE_PAIR && !f.pair_ok)
+        return fail(LDPC_ERR_UNSUPPORTED, "the code-pair form needs an fp32 flooding RCQ decoder with one beta per check, "
+                                          "sorted thresholds and at most 62 levels");
+    DeviceGuard guard(d->g->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t L = d->n_levels, Q = d->n_quant;
+    HIP_TRY(hipMemcpyAsync(d->thresholds, thresholds, Q * L * sizeof(float), hipMemcpyHostToDevice, s));
+    fill_quantizer_lut(d, thresholds);
+    HIP_TRY(hipMemcpyAsync(d->lut, d->lut_host.data(), d->lut_host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    apply_quantizer_flags(d, f);
+    return LDPC_OK;
+}
+
+int ldpc_decoder_set_quantizers(ldpc_decoder *d, const float *thresholds, void *stream)
+{
+    LDPC_NOTHROW(set_quantizers_impl(d, thresholds, stream))
+}
+
 void ldpc_decoder_destroy(ldpc_decoder *d)
 {
     if (!d) return;
     DeviceGuard guard(d->g->device);
     (void)hipFree(d->beta); (void)hipFree(d->alpha); (void)hipFree(d->oms_alpha);
     (void)hipFree(d->beta_slot); (void)hipFree(d->alpha_slot); (void)hipFree(d->oms_alpha_slot);
-    (void)hipFree(d->thresholds); (void)hipFree(d->lut); (void)hipFree(d->q_of_iter_dev);
+    (void)hipFree(d->thresholds); (void)hipFree(d->lut); (void)hipFree(d->q_of_iter_dev); (void)hipFree(d->level_iota);
     for (void *p : d->res_bufs) (void)hipFree(p);
     (void)hipFree(d->gat_meta); (void)hipFree(d->gat_nbr); (void)hipFree(d->lay_off);
     (void)hipFree(d->lay_slot); (void)hipFree(d->lay_beta); (void)hipFree(d->lay_oms_slot); (void)hipFree(d->lay_oms);

@@ -533,4 +533,101 @@ __global__ __launch_bounds__(kBlock) void reduce_tiles(const float *__restrict__
     item_sum[x] = a;
 }
 
+// ------------------------------------------------------------------------------------------
+// Level gradient of the quantised joint loss (ldpc_train_joint_ste_levels, ldpc_train_joint_layered_ste_levels): the
+// posterior of iteration t is l_t[v] = llr_v + sum over the edges e at v of deq_t(code_t[e]) and the reconstruction value
+// of level l is tau_l, so
+//   d J_t / d tau_l = sum over b < batch and e of [code_t[b][e] mod L == l] * s(code_t[b][e]) * g_t[b][var(e)],
+// s = +1 for code < L, -1 otherwise, g_t the seed joint_loss_grad wrote.  The codes are read, nothing is compared again.
+//
+// Tile layout of the other gradient kernels: one wave covers the W = 64 * VEC codewords of one tile and takes one chunk of
+// kLgChunk consecutive CSR edges; per edge it reads the wave-uniform var_idx[e], one code row (W bytes: a dword per lane
+// at VEC = 4) and the seed row of var(e).  Each lane keeps one fp32 accumulator per level, which sums the at most
+// kLgChunk * VEC terms of this chunk and nothing else:
+//   NREG = 4 / 8 (L <= 4 / L <= 8): in registers, updated by a compare-and-select per level (no indexed register file on
+//       this target: a run-time index into a register array would go through scratch).  No LDS; 256-thread workgroups.
+//   NREG = 0 (L = 16 .. 128): in LDS at acc[level][lane] -- lane-private words, read-add-write in program order, no
+//       atomics and no barrier; a wave's 64 lanes hit 64 consecutive words, so there is no bank conflict.  L * 256 bytes per
+//       wave (32 KiB at L = 128), hence one-wave workgroups: five fit a CU at L = 128, sixteen at L = 32.
+// The accumulators are then widened: the 64 lanes are summed in fp64 by the fixed butterfly, and part[tile][chunk][l] is
+// written for every level (a wave of padding codewords writes zeros), so the scratch needs no clearing.  Codewords
+// b >= batch are skipped on the lane's index, whatever their code and seed rows hold, and a byte that is no code of this
+// quantiser (level >= L) is skipped rather than used as an index.
+// ------------------------------------------------------------------------------------------
+constexpr int kLgChunk = 64;                   // CSR edges per wave: an fp32 accumulator sums at most 64 * VEC terms
+
+template <int VEC, int NREG>
+__global__ __launch_bounds__(NREG ? kBlock : kWave) void level_grad(GraphDev g, const uint8_t *__restrict__ codes,
+                                                                    const float *__restrict__ seed, long long batch,
+                                                                    int n_levels, int chunks, int waves,
+                                                                    double *__restrict__ part)
+{
+    constexpr int W = kWave * VEC;
+    extern __shared__ float level_acc_s[];         // NREG == 0: [n_levels][kWave]
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wv = uni((int)blockIdx.x * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6));
+    if (wv >= waves) return;
+    const int tile = uni(wv / chunks), chunk = uni(wv % chunks);
+    const int e_lo = chunk * kLgChunk, e_hi = e_lo + kLgChunk < g.E ? e_lo + kLgChunk : g.E;
+    bool real[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) real[c] = (long long)tile * W + (long long)lane * VEC + c < batch;
+    const uint8_t *crow = codes + ((size_t)tile * g.E + e_lo) * W + (size_t)lane * VEC;
+    const float *gbase = seed + (size_t)tile * g.n * W + (size_t)lane * VEC;
+    constexpr int NR = NREG ? NREG : 1;
+    float acc[NR];
+#pragma unroll
+    for (int l = 0; l < NR; ++l) acc[l] = 0.0f;
+    if constexpr (NREG == 0)
+        for (int l = 0; l < n_levels; ++l) level_acc_s[l * kWave + lane] = 0.0f;
+#pragma unroll 4
+    for (int e = e_lo; e < e_hi; ++e) {
+        const int v = uni(g.var_idx[e]);
+        const Pack<uint8_t, VEC> cq = ld<uint8_t, VEC>(crow + (size_t)(e - e_lo) * W);
+        const Pack<float, VEC> gv = ld<float, VEC>(gbase + (size_t)v * W);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+            const int q = cq.x[c];
+            const bool neg = q >= n_levels;
+            const int lvl = neg ? q - n_levels : q;
+            const bool use = real[c] && lvl < n_levels;
+            const float term = use ? (neg ? -gv.x[c] : gv.x[c]) : 0.0f;
+            if constexpr (NREG != 0) {
+#pragma unroll
+                for (int l = 0; l < NR; ++l) acc[l] += lvl == l ? term : 0.0f;
+            } else {
+                if (use) level_acc_s[lvl * kWave + lane] += term;
+            }
+        }
+    }
+    double *out = part + ((size_t)tile * chunks + chunk) * n_levels;
+    if constexpr (NREG != 0) {
+#pragma unroll
+        for (int l = 0; l < NR; ++l) {
+            const double d = wave_sum_d((double)acc[l]);
+            if (lane == 0 && l < n_levels) out[l] = d;
+        }
+    } else {
+        for (int l = 0; l < n_levels; ++l) {
+            const double d = wave_sum_d((double)level_acc_s[l * kWave + lane]);
+            if (lane == 0) out[l] = d;
+        }
+    }
+}
+
+// part[tile][chunk][l] -> tile_sum[tile][l]: one thread per (tile, level) adds the tile's waves in chunk order, fp64.
+// reduce_table_grads<double> (tiles = the tiles, count = L, the identity slot map) then adds the tiles in order and rounds.
+__global__ __launch_bounds__(kBlock) void level_grad_waves(const double *__restrict__ part, int tiles, int chunks,
+                                                           int n_levels, double *__restrict__ tile_sum)
+{
+    const int x = blockIdx.x * kBlock + threadIdx.x;
+    if (x >= tiles * n_levels) return;
+    const int tile = x / n_levels, l = x % n_levels;
+    const double *p = part + (size_t)tile * chunks * n_levels + l;
+    double a = 0.0;
+#pragma unroll 8
+    for (int c = 0; c < chunks; ++c) a += p[(size_t)c * n_levels];
+    tile_sum[x] = a;
+}
+
 }  // namespace ldpc

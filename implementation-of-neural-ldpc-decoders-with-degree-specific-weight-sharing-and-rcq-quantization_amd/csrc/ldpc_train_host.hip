@@ -1,6 +1,7 @@
 // ldpc_train_host.hip -- host side of the gradient (training) path over the kernels in ldpc_train.hip: the saving decode and
 // its backward sweeps (ldpc_decode_saving / ldpc_backward), and posterior joint training (ldpc_train_joint,
-// ldpc_train_joint_ste, ldpc_train_joint_layered, ldpc_train_joint_layered_ste: one workspace carver and one loop for the four).
+// ldpc_train_joint_ste, ldpc_train_joint_layered, ldpc_train_joint_layered_ste: one workspace carver and one loop for the four,
+// and for the two ..._levels forms of the quantised ones, which add the level gradient of the learned quantisers).
 //
 // Not a unit of its own: ldpc_hip.hip includes it after the decode entry points and it uses that file's Workspace, carve,
 // pick_vec, launch_cn, launch_vn, decode_dispatch, saved_layout, fail, HIP_TRY and DeviceGuard.
@@ -131,7 +132,8 @@ int backward_impl(const ldpc_decoder *d, const char *saved, const float *llr, in
 //                  (one row set: iteration t reads and rewrites the code of every edge), and cn_backward<..., FORM_RCQ, LOCAL>
 //                  differentiates the check update with v2c_t := u and the straight-through mask read from the codes the walk
 //                  just wrote.  E rows: U and d J/d u in fp32, the codes as bytes;  n rows as kJointLayered.
-// Every kind adds per-tile partials of the table gradients and of the loss.
+// Every kind adds per-tile partials of the table gradients and of the loss.  The ..._levels entry points of the two quantised
+// kinds add, behind everything else, the partials of level_grad (d J_t / d the reconstruction value of every level).
 enum { kJointMinsum = 0, kJointSte = 1, kJointLayered = 2, kJointLayeredSte = 3 };
 
 int joint_supported(const ldpc_decoder *d, int kind)
@@ -188,9 +190,12 @@ struct JointWs {
     // layered: the posterior copy g_l is formed on, R (kJointLayeredSte: 1-byte codes in its place), U
     float *glT = nullptr, *msgs = nullptr, *urows = nullptr;
     uint8_t *codes = nullptr;
+    // the level-gradient entry points: level_grad's partials [tile][chunk][L] and their per-tile sums [tile][L]
+    int lvl_chunks = 0;
+    double *lvl_part = nullptr, *lvl_tile = nullptr;
     size_t total = 0;
 };
-JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, int kind)
+JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, int kind, bool levels = false)
 {
     JointWs w;
     const bool layered = kind == kJointLayered || kind == kJointLayeredSte;
@@ -224,6 +229,12 @@ JointWs carve_joint(const ldpc_decoder *d, int64_t batch, void *base, int kind)
     take(w.loss_part, tiles * vb * sizeof(double));
     // item_sum: the longest row of partials reduced -- per edge, and per variable where the variable-side alpha has a gradient
     take(w.item_sum, (layered ? E : std::max(n, E)) * sizeof(double));
+    if (levels) {                                     // after everything else: the other rows lie where they lie without it
+        const size_t L = (size_t)std::max(d->n_levels, 1);
+        w.lvl_chunks = (int)((E + kLgChunk - 1) / kLgChunk);
+        take(w.lvl_part, tiles * w.lvl_chunks * L * sizeof(double));
+        take(w.lvl_tile, tiles * L * sizeof(double));
+    }
     w.total = off;
     return w;
 }
@@ -265,7 +276,7 @@ void joint_forward_layered(const ldpc_decoder *d, const JointWs &w, int t, uint6
 template <int VEC>
 int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, int64_t batch, const float *weights,
                float *loss_per_iter, int32_t *bits, float *posterior, float *grad_beta, float *grad_alpha,
-               float *grad_oms_alpha, float *grad_llr, const JointWs &w, int kind, hipStream_t s)
+               float *grad_oms_alpha, float *grad_llr, float *grad_levels, const JointWs &w, int kind, hipStream_t s)
 {
     constexpr int W = 64 * VEC;
     constexpr int JT = transpose_vars<float>();
@@ -273,7 +284,8 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
     const int T = d->T, tiles = w.tiles, vc = (g.n + JT - 1) / JT;
     const dim3 tgrid((unsigned)((size_t)tiles * VEC * vc)), blk(kBlock);
     const bool layered = kind == kJointLayered || kind == kJointLayeredSte, oms = d->form == LDPC_C2V_OMS, rcq = d->form == LDPC_C2V_RCQ;
-    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
+    const bool want_tables = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
+    const bool want = want_tables || grad_levels;     // the seed g_t is formed for either
     const bool oa_grad = grad_oms_alpha && oms && d->oms_alpha;
     const size_t nrow_bytes = (size_t)tiles * W * g.n * sizeof(float);
     // flooding: the LLR rows stay; layered: P = llr, R = +0 ("no message yet"; the RCQ walk reads no code in iteration 0),
@@ -330,6 +342,27 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
                            loss_per_iter + t);
         HIP_TRY(hipGetLastError());
         if (!want) continue;
+        if (grad_levels) {
+            // d J_t/d tau: the seed against the codes of iteration t (flooding: this iteration's check sweep; layered: after
+            // the walk every code in the rows is this iteration's), into row t
+            const uint8_t *lcodes = layered ? (const uint8_t *)w.codes : (const uint8_t *)w.c2v[t & 1];
+            const int L = d->n_levels, waves = tiles * w.lvl_chunks;
+#define LDPC_LVG(NREG_, BLOCK_, LDS_)                                                                                  \
+    hipLaunchKernelGGL((level_grad<VEC, NREG_>), dim3((unsigned)((waves + (BLOCK_) / kWave - 1) / ((BLOCK_) / kWave))),    \
+                       dim3(BLOCK_), (size_t)(LDS_), s, g, lcodes, (const float *)seed, (long long)batch, L, w.lvl_chunks, \
+                       waves, w.lvl_part)
+            if (L <= 4) LDPC_LVG(4, kBlock, 0);
+            else if (L <= 8) LDPC_LVG(8, kBlock, 0);
+            else LDPC_LVG(0, kWave, (size_t)L * kWave * sizeof(float));
+#undef LDPC_LVG
+            hipLaunchKernelGGL(level_grad_waves, dim3((unsigned)((tiles * L + kBlock - 1) / kBlock)), blk, 0, s,
+                               (const double *)w.lvl_part, tiles, w.lvl_chunks, L, w.lvl_tile);
+            hipLaunchKernelGGL(reduce_table_grads<double>, dim3((unsigned)L), dim3(kWave), 0, s, (const double *)w.lvl_tile,
+                               tiles, L, (const int *)d->level_iota, (const int *)d->level_iota, L,
+                               grad_levels + (size_t)t * L);
+            HIP_TRY(hipGetLastError());
+        }
+        if (!want_tables) continue;
         // posterior-local backward of iteration t: check side (beta_t, offset alpha_t, d J/d v2c_t or d J/d u), then the
         // alpha_t-1 partial of the flooding normalised / RCQ forms and the LLR gradient
         const bool alpha_step = !layered && !oms && t >= 1 && grad_alpha;
@@ -382,17 +415,18 @@ int joint_impl(const ldpc_decoder *d, const float *llr, const float *targets, in
     return LDPC_OK;
 }
 
-size_t joint_workspace_bytes(const ldpc_decoder *d, int64_t batch, int kind)
+size_t joint_workspace_bytes(const ldpc_decoder *d, int64_t batch, int kind, bool levels = false)
 {
     if (!d || batch < 0) return 0;
-    return carve_joint(d, batch, nullptr, kind).total;
+    if (levels && d->form != LDPC_C2V_RCQ) return 0;      // no levels: the entry point refuses such a decoder
+    return carve_joint(d, batch, nullptr, kind, levels).total;
 }
 
 // ldpc_train_joint, ldpc_train_joint_ste, ldpc_train_joint_layered and ldpc_train_joint_layered_ste: the same argument rules
 int train_joint_entry(const ldpc_decoder *d, int kind, const void *llr, const void *targets, int64_t batch,
                       const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
                       void *grad_beta, void *grad_alpha, void *grad_oms_alpha, void *grad_llr, void *workspace,
-                      size_t workspace_bytes, void *stream)
+                      size_t workspace_bytes, void *stream, bool levels = false, void *grad_levels = nullptr)
 {
     const bool ste = kind == kJointSte, layered = kind == kJointLayered || kind == kJointLayeredSte;
     if (int rc = joint_supported(d, kind)) return rc;
@@ -401,7 +435,7 @@ int train_joint_entry(const ldpc_decoder *d, int kind, const void *llr, const vo
     if (!d->beta_inv_ptr || (!layered && !d->alpha_inv_ptr)) return fail(LDPC_ERR_UNSUPPORTED, "internal: the decoder has no inverse slot maps");
     if (ste && d->n_levels > kVnbLutMax / 2) return fail(LDPC_ERR_UNSUPPORTED, "more than %d quantiser levels", kVnbLutMax / 2);
     if (!loss_per_iter) return fail(LDPC_ERR_ARG, "NULL loss_per_iter");
-    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr;
+    const bool want = grad_beta || grad_alpha || grad_oms_alpha || grad_llr || grad_levels;
     if (want && !iteration_weights) return fail(LDPC_ERR_ARG, "NULL iteration_weights");
     DeviceGuard guard(d->g->device);
     hipStream_t s = (hipStream_t)stream;
@@ -410,18 +444,19 @@ int train_joint_entry(const ldpc_decoder *d, int kind, const void *llr, const vo
         if (grad_beta) HIP_TRY(hipMemsetAsync(grad_beta, 0, (size_t)d->T * d->n_beta * 4, s));
         if (grad_alpha) HIP_TRY(hipMemsetAsync(grad_alpha, 0, (size_t)d->T * d->n_alpha * 4, s));
         if (grad_oms_alpha && d->n_oms_alpha > 0) HIP_TRY(hipMemsetAsync(grad_oms_alpha, 0, (size_t)d->T * d->n_oms_alpha * 4, s));
+        if (grad_levels) HIP_TRY(hipMemsetAsync(grad_levels, 0, (size_t)d->T * d->n_levels * 4, s));
         return LDPC_OK;
     }
     if (d->g->n == 0 || d->g->E == 0) return fail(LDPC_ERR_UNSUPPORTED, "the joint loss needs a graph with edges");
     if (!llr || !workspace) return fail(LDPC_ERR_ARG, "NULL llr/workspace");
     if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
-    const JointWs w = carve_joint(d, batch, workspace, kind);
+    const JointWs w = carve_joint(d, batch, workspace, kind, levels);
     if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.total);
     if ((size_t)w.tiles * ((d->g->n + 3) / 4) > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
 #define LDPC_JOINT(V_)                                                                                                 \
     joint_impl<V_>(d, (const float *)llr, (const float *)targets, batch, (const float *)iteration_weights,             \
                    (float *)loss_per_iter, bits, (float *)posterior, (float *)grad_beta, (float *)grad_alpha,          \
-                   (float *)grad_oms_alpha, (float *)grad_llr, w, kind, s)
+                   (float *)grad_oms_alpha, (float *)grad_llr, (float *)grad_levels, w, kind, s)
     if (w.vec == 1) return LDPC_JOINT(1);
     return LDPC_JOINT(4);
 #undef LDPC_JOINT
@@ -552,6 +587,34 @@ int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const v
 {
     return train_joint_entry(d, kJointLayeredSte, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior,
                              grad_beta, grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream);
+}
+
+size_t ldpc_train_joint_ste_levels_workspace_bytes(const ldpc_decoder *d, int64_t batch)
+{
+    return joint_workspace_bytes(d, batch, kJointSte, true);
+}
+
+int ldpc_train_joint_ste_levels(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                                const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                                void *grad_beta, void *grad_alpha, void *grad_llr, void *grad_levels, void *workspace,
+                                size_t workspace_bytes, void *stream)
+{
+    return train_joint_entry(d, kJointSte, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior, grad_beta,
+                             grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream, true, grad_levels);
+}
+
+size_t ldpc_train_joint_layered_ste_levels_workspace_bytes(const ldpc_decoder *d, int64_t batch)
+{
+    return joint_workspace_bytes(d, batch, kJointLayeredSte, true);
+}
+
+int ldpc_train_joint_layered_ste_levels(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                                        const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                                        void *grad_beta, void *grad_alpha, void *grad_llr, void *grad_levels,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    return train_joint_entry(d, kJointLayeredSte, llr, targets, batch, iteration_weights, loss_per_iter, bits, posterior,
+                             grad_beta, grad_alpha, nullptr, grad_llr, workspace, workspace_bytes, stream, true, grad_levels);
 }
 
 }  // extern "C"

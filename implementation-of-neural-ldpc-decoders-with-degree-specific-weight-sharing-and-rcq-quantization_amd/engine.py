@@ -307,6 +307,8 @@ class DecodeEngine:
             desc.n_quantizers, desc.n_levels = thresholds.shape
             desc.thresholds, desc.q_of_iter = nat.ptr(thresholds), nat.ptr(q_of_iter)
             keep += [thresholds, q_of_iter]
+            self._thresholds = thresholds.copy()   # what the device holds (set_quantizers replaces it)
+            self.q_of_iter = q_of_iter[:max(self.iters, 1)].copy()
         if self.c2v_form == nat.C2V_OMS and oms_alpha is not None:
             oms_alpha = np.ascontiguousarray(oms_alpha, dtype=self.np_dtype).reshape(rows, -1)
             oms_alpha_slot = np.ascontiguousarray(oms_alpha_slot, dtype=np.int32)
@@ -427,6 +429,32 @@ class DecodeEngine:
             self._tables[1] = alpha.copy()
         if oms_alpha is not None:
             self._tables[2] = oms_alpha.copy()
+
+    def set_quantizers(self, thresholds: np.ndarray):
+        """Replace the quantiser tables of an RCQ engine (ldpc_decoder_set_quantizers): float32 [n_quantizers, n_levels], the
+        shape it was created with.  Everything the native decoder derives from the threshold values is derived again, so
+        the engine decodes and trains exactly as one created with this table; the handle, the plans and the weights stay.
+        NotImplementedError on an engine without a quantiser, and when the mode is forced to 'pair' and the table does not
+        admit that form (the engine then keeps its old table)."""
+        if self.c2v_form != nat.C2V_RCQ:
+            raise NotImplementedError("set_quantizers: the engine has no quantiser (RCQ decoders only)")
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+        if thr.shape != self._thresholds.shape:
+            raise ValueError(f"thresholds must have shape {self._thresholds.shape}, got {thr.shape}")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            nat.check(self._lib.ldpc_decoder_set_quantizers(self.handle, nat.ptr(thr), C.c_void_p(stream.cuda_stream)),
+                      "ldpc_decoder_set_quantizers")
+            stream.synchronize()     # pageable host array: make the upload complete before it dies
+        self._thresholds = thr.copy()
+        with self._ws_lock:          # the streaming form, and with it the workspace layout, may have changed
+            self._ws.clear()
+        return self
+
+    def current_thresholds(self) -> Optional[np.ndarray]:
+        """numpy copy of the quantiser table [n_quantizers, n_levels] the device holds (None: no quantiser)"""
+        thr = getattr(self, "_thresholds", None)
+        return None if thr is None else thr.copy()
 
     def current_tables(self):
         """(beta [T, Sb], alpha [T, Sa], oms_alpha [T, So] | None) numpy copies of the tables the device holds"""
@@ -754,14 +782,16 @@ class DecodeEngine:
 
     def train_joint_layered_ste(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                                 iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
-                                want_grad_llr: bool = False) -> dict:
+                                want_grad_llr: bool = False, want_levels: bool = False) -> dict:
         """train_joint() of the quantised decoder under the paper's layered schedule (ldpc_train_joint_layered_ste): the
         fixed-T layered W-RCQ decode, unchanged, one iteration per launch, with the layered posterior-local gradients of J
         formed through the straight-through rule of include/ldpc_hip.h (iteration t's loss reaches beta_t and the LLRs
         through the check update that wrote each message; gradient 1 through the quantiser below its top level, 0 where
         the code saturated).  Same arguments and the same dict as train_joint_ste; "grad_alpha" (the table the schedule
-        does not use) is all zero.  NotImplementedError for every other decoder."""
-        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="layered_ste")
+        does not use) is all zero.  ``want_levels``: as in train_joint_ste (ldpc_train_joint_layered_ste_levels).
+        NotImplementedError for every other decoder."""
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr,
+                                 kind="layered_ste_levels" if want_levels else "layered_ste")
 
     def train_joint_layered(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                             iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
@@ -775,12 +805,16 @@ class DecodeEngine:
 
     def train_joint_ste(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                         iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
-                        want_grad_llr: bool = False) -> dict:
+                        want_grad_llr: bool = False, want_levels: bool = False) -> dict:
         """train_joint() of the quantised decoder (ldpc_train_joint_ste): the fp32 RCQ flooding decode, unchanged, with
         the posterior-local gradients of J formed through the straight-through rule of include/ldpc_hip.h (gradient 1
         through the quantiser below its top level, 0 where the code saturated).  Same arguments and the same dict as
-        train_joint ("grad_oms_alpha" is always None); NotImplementedError for every other decoder."""
-        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr, kind="ste")
+        train_joint ("grad_oms_alpha" is always None); NotImplementedError for every other decoder.
+        ``want_levels``: the call goes through ldpc_train_joint_ste_levels and the dict gains "grad_levels" [T, n_levels]:
+        d J_t / d (reconstruction value of level l) in row t, the signed per-level sum of the seed over the codes the
+        forward stored (include/ldpc_hip.h); every other entry is bit-identical to the call without it."""
+        return self._train_joint(llr, targets, iteration_weights, want_grads, want_grad_llr,
+                                 kind="ste_levels" if want_levels else "ste")
 
     def train_joint(self, llr: torch.Tensor, targets: Optional[torch.Tensor] = None,
                     iteration_weights: Optional[torch.Tensor] = None, want_grads: bool = True,
@@ -798,10 +832,14 @@ class DecodeEngine:
     _JOINT_ENTRY = {"minsum": ("ldpc_train_joint", "ldpc_train_joint_workspace_bytes", True),
                     "ste": ("ldpc_train_joint_ste", "ldpc_train_joint_ste_workspace_bytes", False),
                     "layered": ("ldpc_train_joint_layered", "ldpc_train_joint_layered_workspace_bytes", True),
-                    "layered_ste": ("ldpc_train_joint_layered_ste", "ldpc_train_joint_layered_ste_workspace_bytes", False)}
+                    "layered_ste": ("ldpc_train_joint_layered_ste", "ldpc_train_joint_layered_ste_workspace_bytes", False),
+                    "ste_levels": ("ldpc_train_joint_ste_levels", "ldpc_train_joint_ste_levels_workspace_bytes", False),
+                    "layered_ste_levels": ("ldpc_train_joint_layered_ste_levels",
+                                           "ldpc_train_joint_layered_ste_levels_workspace_bytes", False)}
 
     def _train_joint(self, llr, targets, iteration_weights, want_grads, want_grad_llr, kind: str) -> dict:
         entry, ws_bytes, has_goa = self._JOINT_ENTRY[kind]
+        want_levels = kind.endswith("_levels")      # those entry points take grad_levels after grad_llr
         llr = self._check_llr(llr)
         B, n = llr.shape
         dev = self.device
@@ -824,6 +862,11 @@ class DecodeEngine:
         goa = (torch.empty(self._table_shapes[2], dtype=torch.float32, device=dev)
                if want_grads and has_goa and self._table_shapes[2] is not None else None)
         gl = torch.empty((B, n), dtype=torch.float32, device=dev) if want_grad_llr else None
+        glv = None
+        if want_levels:
+            if self.c2v_form != nat.C2V_RCQ:
+                raise NotImplementedError("want_levels: the engine has no quantiser (RCQ decoders only)")
+            glv = torch.empty((T, self._thresholds.shape[1]), dtype=torch.float32, device=dev)
         ws = None
         if B > 0:
             need = int(getattr(self._lib, ws_bytes)(self.handle, B))
@@ -835,10 +878,13 @@ class DecodeEngine:
             stream = torch.cuda.current_stream(dev).cuda_stream
             p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
             grads = (p(gb), p(ga), p(goa), p(gl)) if has_goa else (p(gb), p(ga), p(gl))
+            if want_levels:
+                grads += (p(glv),)
             nat.check(getattr(self._lib, entry)(self.handle, p(llr), p(targets), B, p(w), p(lpi), p(bits), p(post), *grads,
                                                 p(ws), 0 if ws is None else ws.numel(), C.c_void_p(stream)), entry)
         return {"loss": (w[:T] * lpi).sum(), "loss_per_iter": lpi, "bits": bits, "posterior": post,
-                "grad_beta": gb, "grad_alpha": ga, "grad_oms_alpha": goa, "grad_llr": gl}
+                "grad_beta": gb, "grad_alpha": ga, "grad_oms_alpha": goa, "grad_llr": gl,
+                **({"grad_levels": glv} if want_levels else {})}
 
     def debug_sweep(self, batch: int, which: int, it: int):
         """Launch one CN (which=0) or VN (which=1) sweep on the state a previous

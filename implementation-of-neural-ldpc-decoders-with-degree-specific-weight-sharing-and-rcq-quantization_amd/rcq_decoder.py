@@ -59,6 +59,23 @@ loss reaches beta_t and the LLRs through the one check update that wrote each me
 u = llr_v + a constant, d Q^-1(Q(m)) / d m by the rule above on the code the update stored -- nothing earlier and nothing
 through another check of the same iteration; alpha, which the schedule does not use, gets a zero gradient
 (include/ldpc_hip.h ldpc_train_joint_layered_ste).  ``layered_gradient`` on a flooding W-RCQ decoder is a ValueError.
+
+Learned quantisers: ``WeightedRCQDecoder(..., learn_quantizer=True)`` (keyword only) makes the ``(C, gamma)`` pairs
+parameters -- ``quantizer_C`` and ``quantizer_gamma``, float64 ``[n_quantizers]``, initialised from ``quantizer_params`` --
+and ``joint_posterior_loss`` gives them a gradient on both schedules.  The value path stays the reference's:
+``self.quantizers`` is the list of ``NonUniformQuantizer(bc, float(C), float(gamma))`` of the current parameter values (rebuilt
+when they change, writes through ``.data`` included), so at its initial parameters the decoder is bit-identical to the plain
+one, and a plain decoder built from the learned pairs decodes as the trained one does.  The gradient: iteration t's
+posterior is llr + the reconstructed messages at the variable and level l reconstructs to tau_l, so d J_t / d tau_l is the
+signed per-level sum of the loss seed over the codes the forward stored (ldpc_train_joint_ste_levels; level 0 and the top
+level like any other -- a saturated message, which passes nothing to beta, still moves the top level); the thresholds as
+decision boundaries pass no gradient (straight-through), and with x_j = j / (L - 1)
+    d tau_j / d C = x_j^gamma,      d tau_j / d gamma = C x_j^gamma ln x_j  (1 <= j <= L - 2;  := 0 at j = 0 and j = L - 1)
+in float64 on the host (``quantizer_param_grads``).  A change of ``(C, gamma)`` re-uploads the tables into the SAME native
+decoder (``DecodeEngine.set_quantizers``): the engine object and its handle survive optimiser steps.  Non-finite ``C`` or
+``gamma``, or ``gamma < 0``, raise a ValueError naming the parameter at the next decode or loss; ``bc < 2`` cannot be learned
+(one level, and the reference's constructor divides by zero).  No constraint keeps the learned table positive and sorted:
+one that is not decodes through the generic kernel forms, as a freshly created decoder with it would.
 """
 
 from __future__ import annotations
@@ -144,6 +161,42 @@ def _threshold_table(quantizers) -> np.ndarray:
     return np.stack([q.thresholds_f32() for q in quantizers]).astype(np.float32)
 
 
+def quantizer_param_grads(C, gamma, grad_table):
+    """Chain rule from d J / d tau [Q, L] to the parameters of tau_j = C * x_j^gamma, x_j = j / (L - 1), in float64:
+    d tau_j / d C = x_j^gamma (0^0 = 1, as the value path has it);  d tau_j / d gamma = C * x_j^gamma * ln x_j for
+    1 <= j <= L - 2 and := 0 at j = 0 (the limit for gamma > 0; at gamma = 0 the derivative does not exist) and at
+    j = L - 1 (ln 1).  -> (d J / d C [Q], d J / d gamma [Q]), torch float64 on the device of grad_table."""
+    as64 = lambda v: v.detach().to(torch.float64) if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v, dtype=np.float64))
+    g = as64(grad_table)
+    C, gamma = as64(C).to(g.device).reshape(-1, 1), as64(gamma).to(g.device).reshape(-1, 1)
+    L = g.shape[1]
+    if L < 2:
+        raise ValueError("a quantiser with one level has no (C, gamma) parametrisation")
+    x = (torch.arange(L, dtype=torch.float64, device=g.device) / (L - 1)).reshape(1, -1)
+    xg = x ** gamma
+    lnx = torch.zeros_like(x)
+    lnx[:, 1:L - 1] = torch.log(x[:, 1:L - 1])
+    # j = 0 and j = L - 1 carry no gamma term: a `where`, not a product with 0 (x_0^gamma * ln x_0 is 0 * -inf)
+    dgamma = torch.where(lnx != 0, C * xg * lnx, torch.zeros_like(xg))
+    return (g * xg).sum(dim=1), (g * dgamma).sum(dim=1)
+
+
+class _ThresholdTable(torch.autograd.Function):
+    """(C [Q], gamma [Q], table [Q, L]) -> table: the VALUES are the reference's (float32 of Python-float arithmetic, handed
+    in), the derivative is quantizer_param_grads"""
+
+    @staticmethod
+    def forward(ctx, C, gamma, table):
+        ctx.save_for_backward(C, gamma)
+        return table.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        C, gamma = ctx.saved_tensors
+        gC, gg = quantizer_param_grads(C, gamma, g)
+        return gC.to(device=C.device, dtype=C.dtype), gg.to(device=gamma.device, dtype=gamma.dtype), None
+
+
 class RCQMinSumDecoder:
     """RCQ MinSum decoder with non-uniform quantisation (flooding schedule)."""
 
@@ -210,7 +263,7 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
 
     def __init__(self, code: LDPCCode, bc: int, bv: int, quantizer_params: List[Tuple[float, float]],
                  weight_sharing_type: int = 2, max_iterations: int = 50, layered: bool = False, *,
-                 quantizer_gradient=None, layered_gradient=None):
+                 quantizer_gradient=None, layered_gradient=None, learn_quantizer: bool = False):
         super().__init__()
         import autograd_bridge as ab
         self.bc = bc
@@ -220,13 +273,72 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
         self.quantizer_gradient = ab.check_quantizer_gradient(quantizer_gradient)
         # how joint_posterior_loss differentiates the layered schedule (layered="paper" only): None (it refuses) or "posterior_local"
         self.layered_gradient = ab.check_layered_gradient(layered_gradient, self._schedule_name())
-        self.quantizers = [NonUniformQuantizer(bc, C, gamma) for C, gamma in quantizer_params]
+        self.learn_quantizer = bool(learn_quantizer)
+        if self.learn_quantizer:
+            if bc < 2:
+                raise ValueError(f"learn_quantizer=True needs bc >= 2 (bc = {bc} has one level and no (C, gamma) to learn)")
+            self._quantizers, self._quantizer_key = None, None     # built from the parameter VALUES on demand
+        else:
+            self.quantizers = [NonUniformQuantizer(bc, C, gamma) for C, gamma in quantizer_params]
         self._init_sharing(code, weight_sharing_type, max_iterations)
+        if self.learn_quantizer:                      # after the weights: their order in parameters() / state_dict stays
+            self.quantizer_C = torch.nn.Parameter(torch.tensor([float(C) for C, _ in quantizer_params], dtype=torch.float64))
+            self.quantizer_gamma = torch.nn.Parameter(torch.tensor([float(g) for _, g in quantizer_params], dtype=torch.float64))
         logger.info(f"Initialized Weighted RCQ decoder: bc={bc}, bv={bv}, "
                     f"weight_type={weight_sharing_type}, layered={layered}")
 
+    @property
+    def quantizers(self) -> List[NonUniformQuantizer]:
+        """the quantisers of the decoder; with learn_quantizer the list built from the CURRENT values of quantizer_C /
+        quantizer_gamma -- compared by value on every access, as _get_engine compares the weight tables (`p.data` writes
+        leave no other trace)"""
+        if not self.__dict__.get("learn_quantizer", False):
+            return self.__dict__["_quantizers"]
+        C = self.quantizer_C.detach().to("cpu", torch.float64).numpy()
+        gamma = self.quantizer_gamma.detach().to("cpu", torch.float64).numpy()
+        key = (C.tobytes(), gamma.tobytes())
+        if self._quantizers is None or self._quantizer_key != key:
+            for name, v in (("quantizer_C", C), ("quantizer_gamma", gamma)):
+                if not np.all(np.isfinite(v)):
+                    raise ValueError(f"{name} holds a non-finite value: {v.tolist()}")
+            if np.any(gamma < 0):
+                raise ValueError(f"quantizer_gamma holds a negative value ({gamma.tolist()}): tau_0 = C * 0^gamma would "
+                                 "divide by zero")
+            self._quantizers = [NonUniformQuantizer(self.bc, float(c), float(g)) for c, g in zip(C, gamma)]
+            self._quantizer_key = key
+        return self._quantizers
+
+    @quantizers.setter
+    def quantizers(self, value):
+        if self.__dict__.get("learn_quantizer", False):
+            raise AttributeError("the quantisers of a learn_quantizer decoder follow quantizer_C / quantizer_gamma")
+        self.__dict__["_quantizers"] = value
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        if self.learn_quantizer:
+            state.update(_quantizers=None, _quantizer_key=None)
+        return state
+
     def _get_quantizer(self, iteration: int) -> NonUniformQuantizer:
-        return self.quantizers[_quantizer_index(len(self.quantizers), self.max_iterations, iteration)]
+        quantizers = self.quantizers
+        return quantizers[_quantizer_index(len(quantizers), self.max_iterations, iteration)]
+
+    def _get_engine(self, device):
+        """the weights' engine cache; a learn_quantizer decoder also brings the engine's quantiser table up to the current
+        parameter values -- into the same native decoder (DecodeEngine.set_quantizers), never a rebuild"""
+        if not self.learn_quantizer:
+            return super()._get_engine(device)
+        thr = _threshold_table(self.quantizers)          # validates (C, gamma) before any device work
+        eng = super()._get_engine(device)
+        if not np.array_equal(eng.current_thresholds(), thr):
+            eng.set_quantizers(thr)
+        return eng
+
+    def thresholds_tensor(self) -> torch.Tensor:
+        """[Q, L] float64: the float32 table the engine decodes with, differentiable in quantizer_C / quantizer_gamma"""
+        table = torch.from_numpy(_threshold_table(self.quantizers).astype(np.float64))
+        return _ThresholdTable.apply(self.quantizer_C, self.quantizer_gamma, table)
 
     def _schedule(self) -> int:
         """message schedule of the engine: the paper's layered one for layered="paper", else flooding (the reference
@@ -239,6 +351,9 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
         return "layered" if isinstance(self.layered, str) and self.layered == "paper" else "flooding"
 
     def _extra_key(self):
+        # learned thresholds are no part of the engine's identity: they reach it through set_quantizers
+        if self.learn_quantizer:
+            return (len(self.quantizer_C), self.bc, self._schedule())
         return (_threshold_table(self.quantizers).tobytes(), self._schedule())
 
     def _engine_kwargs(self, layout, beta, alpha):
@@ -275,7 +390,8 @@ class WeightedRCQDecoder(_DegreeSharedDecoder):
         eng = self._get_engine(llr.device if llr.is_cuda else device)
         bt, at = self._sharing_layout().tables_torch(self.beta_weights, self.alpha_weights, int(self.max_iterations),
                                                      self._beta_default, self._alpha_default)
-        return ab.joint_loss_ste(bt, at, eng, llr, targets, iteration_weights, layered=paper)
+        thr = self.thresholds_tensor() if self.learn_quantizer else None
+        return ab.joint_loss_ste(bt, at, eng, llr, targets, iteration_weights, layered=paper, thresholds=thr)
 
     def forward(self, llr: torch.Tensor, early_stop: bool = True, device=None):
         """

@@ -104,6 +104,8 @@ def all_reduce_gradients(parameters, group: Optional[dist.ProcessGroup] = None, 
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return sum(p.numel() for p in params)
     dev, dt = params[0].device, params[0].dtype
+    for p in params:                                  # the widest dtype: a float64 parameter is not reduced in float32
+        dt = torch.promote_types(dt, p.dtype)
     flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).to(device=dev, dtype=dt)
                       for p in params])
     dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)

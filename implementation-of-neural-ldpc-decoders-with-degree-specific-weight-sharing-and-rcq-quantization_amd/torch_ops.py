@@ -48,6 +48,17 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
      bit for bit; the gradients are layered posterior-local with the straight-through rule on the code each check update wrote.
      alpha is not used by the schedule: its gradient is all zero.
 
+  ldpc::rcq_joint_loss_levels(Tensor llr, Tensor? targets, Tensor beta, Tensor alpha, Tensor thresholds,
+                              Tensor iteration_weights, int engine, bool want_grads=True, bool want_grad_llr=False)
+        -> the seven outputs of rcq_joint_loss and Tensor grad_levels
+  ldpc::rcq_layered_joint_loss_levels(... the same arguments ...) -> the same eight outputs
+     rcq_joint_loss / rcq_layered_joint_loss with the quantiser as an input (ldpc_train_joint_ste_levels,
+     ldpc_train_joint_layered_ste_levels): `thresholds` [Q, L] is the table the decode runs with (the engine's own is put back
+     afterwards when it differs) and is differentiable -- grad_levels [T, L] fp32 holds d loss / d (reconstruction value of
+     level l) of iteration t, the signed per-level sum of the loss seed over the codes the forward stored, and the backward
+     sums its rows per quantiser (the engine's q_of_iter) into d loss / d thresholds.  The thresholds as decision boundaries
+     pass no gradient (straight-through).  The first seven outputs equal the base operator's bit for bit.
+
   ldpc::awgn_llr(int batch, int n, int seed, int stream_id, int first_frame, float scale, float shift, Tensor? codeword_packed,
                  Device device) -> Tensor llr
      the counter-based BI-AWGN channel (ldpc_channel_awgn): fp32 LLRs [batch, n] of frames first_frame .. of stream
@@ -258,16 +269,34 @@ minsum_decode_train.register_autograd(_train_backward, setup_context=_train_setu
 
 
 # ------------------------------------------------------------------------------------------ posterior joint training
-def _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, method):
-    """the four joint-loss operators; `method`: the engine's train_joint | train_joint_ste | train_joint_layered |
-    train_joint_layered_ste"""
+def _with_thresholds(eng, thresholds: np.ndarray):
+    """_with_tables for the quantiser table of an RCQ engine"""
+    held = eng.current_thresholds()
+    if held is None:
+        raise NotImplementedError("ldpc ops: the engine has no quantiser (RCQ decoders only)")
+    if np.array_equal(held, thresholds):
+        return lambda: None
+    eng.set_quantizers(thresholds)
+    return lambda: eng.set_quantizers(held)
+
+
+def _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, want_grads, want_grad_llr, method,
+           thresholds=None):
+    """the joint-loss operators; `method`: the engine's train_joint | train_joint_ste | train_joint_layered |
+    train_joint_layered_ste.  `thresholds` (the two ..._levels operators): the quantiser table of the call; the result
+    gains grad_levels [T, L] -- formed whenever the table is given, it is what the operator exists for"""
     eng = _engine(engine)
-    restore = _with_tables(eng, _np_table(beta), _np_table(alpha), alpha_is_oms)
+    restore_q = (lambda: None) if thresholds is None else _with_thresholds(eng, _np_table(thresholds))
     try:
-        r = getattr(eng, method)(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
-                                 want_grads=want_grads, want_grad_llr=want_grad_llr)
+        restore = _with_tables(eng, _np_table(beta), _np_table(alpha), alpha_is_oms)
+        try:
+            extra = {} if thresholds is None else {"want_levels": True}
+            r = getattr(eng, method)(llr.detach(), None if targets is None else targets.detach(), iteration_weights.detach(),
+                                     want_grads=want_grads, want_grad_llr=want_grad_llr, **extra)
+        finally:
+            restore()
     finally:
-        restore()
+        restore_q()
     dev = llr.device
     if want_grads:
         gb = r["grad_beta"].to(device=beta.device, dtype=beta.dtype)
@@ -277,6 +306,8 @@ def _joint(llr, targets, beta, alpha, iteration_weights, engine, alpha_is_oms, w
     else:
         gb, ga = torch.empty((0,), dtype=beta.dtype, device=beta.device), torch.empty((0,), dtype=alpha.dtype, device=alpha.device)
     gl = r["grad_llr"] if want_grad_llr else torch.empty((0,), dtype=torch.float32, device=dev)
+    if thresholds is not None:
+        return r["loss"], r["loss_per_iter"], r["posterior"], r["bits"], gb, ga, gl, r["grad_levels"]
     return r["loss"], r["loss_per_iter"], r["posterior"], r["bits"], gb, ga, gl
 
 
@@ -370,3 +401,64 @@ def _joint_backward(ctx, g_loss, *_unused):
 
 for _op in (minsum_joint_loss, minsum_layered_joint_loss, rcq_joint_loss, rcq_layered_joint_loss):
     _op.register_autograd(_joint_backward, setup_context=_joint_setup)
+
+
+# ------------------------------------------------------------------------------------------ learned quantisers
+@torch.library.custom_op("ldpc::rcq_joint_loss_levels", mutates_args=())
+def rcq_joint_loss_levels(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, thresholds: Tensor,
+                          iteration_weights: Tensor, engine: int, want_grads: bool = True,
+                          want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """rcq_joint_loss run with the quantiser table `thresholds` [Q, L] (ldpc_train_joint_ste_levels): its seven outputs and
+    grad_levels [T, L], d loss / d (reconstruction value of level l) of iteration t"""
+    return _joint(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr, "train_joint_ste",
+                  thresholds=thresholds)
+
+
+@torch.library.custom_op("ldpc::rcq_layered_joint_loss_levels", mutates_args=())
+def rcq_layered_joint_loss_levels(llr: Tensor, targets: Optional[Tensor], beta: Tensor, alpha: Tensor, thresholds: Tensor,
+                                  iteration_weights: Tensor, engine: int, want_grads: bool = True,
+                                  want_grad_llr: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """rcq_joint_loss_levels under the paper's layered schedule (ldpc_train_joint_layered_ste_levels)"""
+    return _joint(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr,
+                  "train_joint_layered_ste", thresholds=thresholds)
+
+
+@rcq_layered_joint_loss_levels.register_fake
+@rcq_joint_loss_levels.register_fake
+def _(llr, targets, beta, alpha, thresholds, iteration_weights, engine, want_grads=True, want_grad_llr=False):
+    T, L = iteration_weights.shape[0], thresholds.shape[1]
+    return _joint_fake(llr, targets, beta, alpha, iteration_weights, engine, False, want_grads, want_grad_llr) + (
+        torch.empty((T, L), dtype=torch.float32, device=llr.device),)
+
+
+def _levels_setup(ctx, inputs, output):
+    ctx.want_grads, ctx.want_grad_llr = inputs[-2:]
+    thresholds, engine = inputs[4], inputs[6]
+    _loss, lpi, post, bits, gb, ga, gl, glv = output
+    # row t of grad_levels belongs to the quantiser of iteration t
+    ctx.q_of_iter = [int(q) for q in _engine(engine).q_of_iter[:glv.shape[0]]]
+    ctx.thr_meta = (tuple(thresholds.shape), thresholds.dtype, thresholds.device)
+    ctx.save_for_backward(lpi, gb, ga, gl, glv)
+    ctx.mark_non_differentiable(lpi, post, bits, gb, ga, gl, glv)
+    ctx.set_materialize_grads(False)
+
+
+def _levels_backward(ctx, g_loss, *_unused):
+    lpi, gb, ga, gl, glv = ctx.saved_tensors
+    if g_loss is None:
+        return (None,) * 9
+    g_beta = gb * g_loss.to(gb.device) if ctx.want_grads and ctx.needs_input_grad[2] else None
+    g_alpha = ga * g_loss.to(ga.device) if ctx.want_grads and ctx.needs_input_grad[3] else None
+    g_llr = gl * g_loss if ctx.want_grad_llr and ctx.needs_input_grad[0] else None
+    g_thr = None
+    if ctx.needs_input_grad[4]:
+        shape, dtype, dev = ctx.thr_meta
+        rows = (glv * g_loss.to(glv.device)).to(device=dev, dtype=dtype)
+        g_thr = torch.zeros(shape, dtype=dtype, device=dev).index_add(
+            0, torch.tensor(ctx.q_of_iter, dtype=torch.long, device=dev), rows)     # [T, L] -> [Q, L], rows in order
+    g_w = lpi * g_loss if ctx.needs_input_grad[5] else None
+    return g_llr, None, g_beta, g_alpha, g_thr, g_w, None, None, None
+
+
+for _op in (rcq_joint_loss_levels, rcq_layered_joint_loss_levels):
+    _op.register_autograd(_levels_backward, setup_context=_levels_setup)

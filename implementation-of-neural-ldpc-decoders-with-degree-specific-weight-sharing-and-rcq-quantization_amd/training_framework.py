@@ -149,6 +149,9 @@ class PosteriorJointTrainer:
         self.val_losses: List[float] = []
         self.val_accuracies: List[float] = []
         self.val_fer_per_point: List[List[float]] = []
+        # a decoder with learn_quantizer: its (C, gamma) pairs after each epoch (the float64 pair trains with the rest of
+        # model.parameters(): Adam keeps its state per parameter in that parameter's dtype)
+        self.quantizer_params: List[List[Tuple[float, float]]] = []
         logger.info("trainer ready: %d trainable scalars", sum(p.numel() for p in model.parameters()))
 
     # ---- data ------------------------------------------------------------------------------------------
@@ -216,6 +219,16 @@ class PosteriorJointTrainer:
         self._pass_iteration_losses = None if iter_sum is None else (iter_sum / batches).tolist()
         return loss_sum / batches, right / max(seen, 1), (float(np.mean(norms)) if norms else 0.0)
 
+    def _record_quantizer(self, history: Optional[dict] = None):
+        """after an epoch: append the learned (C, gamma) pairs; with `history`: put the series into it as quantizer_params"""
+        if not getattr(self.model, "learn_quantizer", False):
+            return
+        if history is not None:
+            history["quantizer_params"] = self.quantizer_params
+            return
+        self.quantizer_params.append([(float(c), float(g)) for c, g in zip(self.model.quantizer_C.detach().cpu().tolist(),
+                                                                          self.model.quantizer_gamma.detach().cpu().tolist())])
+
     def train_epoch(self, train_loader: DataLoader) -> Tuple[float, float, float]:
         """-> (mean loss, frame accuracy, mean gradient norm)"""
         return self._pass(train_loader, train=True)
@@ -231,6 +244,7 @@ class PosteriorJointTrainer:
         for epoch in range(self.config.num_epochs):
             t0 = time.time()
             loss, acc, gnorm = self.train_epoch(train_loader)
+            self._record_quantizer()
             if self.config.joint_posterior_loss:
                 self.train_iteration_losses.append(self._pass_iteration_losses or [])
             vloss, vacc, _ = self.validate(val_loader)
@@ -245,6 +259,7 @@ class PosteriorJointTrainer:
                    "gradient_norms": self.gradient_norms}
         if self.config.joint_posterior_loss:
             history["train_iteration_losses"] = self.train_iteration_losses
+        self._record_quantizer(history)
         return history
 
     def train_stream(self, code: LDPCCode, steps_per_epoch: int, val_frames: int = 0, *, train_stream_id: int = 0,
@@ -291,6 +306,7 @@ class PosteriorJointTrainer:
             g0 = self.stream_step
             blocks = [(stream_first_frame(g0 + k, bs, rank, world), bs) for k in range(steps_per_epoch)]
             loss, acc, gnorm = self._pass(_StreamBlocks(blocks, draw(train_stream_id), step_drawn), train=True)
+            self._record_quantizer()
             if cfg.joint_posterior_loss:
                 self.train_iteration_losses.append(self._pass_iteration_losses or [])
             self.train_losses.append(loss)
@@ -319,6 +335,7 @@ class PosteriorJointTrainer:
                    "val_fer_per_point": self.val_fer_per_point}
         if cfg.joint_posterior_loss:
             history["train_iteration_losses"] = self.train_iteration_losses
+        self._record_quantizer(history)
         return history
 
     def plot_training_history(self, save_path: Optional[str] = None):

@@ -155,6 +155,16 @@ int ldpc_decoder_info(const ldpc_decoder *d, int32_t out4[4]);
  * enqueued on `stream`, host arrays must stay valid until it has run. */
 int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alpha,
                              const void *oms_alpha, void *stream);
+/* replace the quantiser tables of an LDPC_C2V_RCQ decoder: thresholds is host [n_quantizers][n_levels] fp32, the shapes the
+ * decoder was created with (LDPC_ERR_UNSUPPORTED for a decoder of another form).  Contract of ldpc_decoder_set_weights:
+ * the uploads (threshold table, signed reconstruction LUT) are enqueued on `stream`, `thresholds` must stay valid until it has
+ * run, and the next call must not be made before.  Everything ldpc_decoder_create derives from the threshold VALUES is
+ * derived again -- which streaming form applies (code pair / its float key), the resident kernels' tau_0 == 0 shortcut and
+ * the compact plan's check words, the layered kernels' lean instantiation -- so every decode and training call afterwards
+ * equals that of a decoder created with these tables, bit for bit; nothing of the graph, the plans' layout or the weights
+ * is rebuilt.  When the mode was forced to LDPC_MODE_PAIR and the new table does not admit that form (thresholds 1.. not
+ * positive and sorted) the call returns LDPC_ERR_UNSUPPORTED and leaves the decoder exactly as it was. */
+int ldpc_decoder_set_quantizers(ldpc_decoder *d, const float *thresholds, void *stream);
 void ldpc_decoder_destroy(ldpc_decoder *d);
 
 /* bytes of device scratch ldpc_decode needs for a batch of `batch` codewords */
@@ -324,6 +334,34 @@ int ldpc_train_joint_layered_ste(const ldpc_decoder *d, const void *llr, const v
                                  const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
                                  void *grad_beta, void *grad_alpha, void *grad_llr,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- level gradients of the quantised joint losses (learned quantisers) -----------------------------
+ * ldpc_train_joint_ste and ldpc_train_joint_layered_ste with one more output: the gradient of J with respect to the
+ * RECONSTRUCTION values of the quantiser.  Argument lists, rules, refusals and error messages of the entry point each
+ * extends; every other output is bit-identical to that entry point's; scratch from the ..._levels_workspace_bytes function
+ * of its own (the base layout followed by the per-wave partials).  L = n_levels.
+ *   grad_levels[T][L] fp32 (device, overwritten, may be NULL: then exactly the launches of the base entry point):
+ *       grad_levels[t][l] = sum over b < batch and the edges e of [code_t[b][e] mod L == l] * s(code_t[b][e]) * g_t[b][var(e)]
+ *   with code_t the byte the forward stored for the edge in iteration t, s = +1 for code < L and -1 otherwise, and
+ *   g_t = w_t * (y - sigmoid(-l_t)) / (B n) the seed of J_t.  It is d J_t / d tau_l under the rule both entry points use:
+ *   l_t[v] = llr_v + sum over the edges at v of deq_t(code_t[e]) (layered: P_t[v] = llr_v + sum of r_t,e), deq of level l is
+ *   +-tau_l, the thresholds as decision boundaries get no gradient (straight-through: the codes are what the forward
+ *   stored) and the leave-one-out sums of the next variable update stay constants.  Level 0 and the top level get a
+ *   gradient like any other; a saturated message, which passes nothing to beta, still moves tau_L-1.  Row t belongs to the
+ *   quantiser q_of_iter[t]; summing rows per quantiser and the chain rule to whatever parametrises tau are the caller's.
+ *   Codewords b >= batch of the last tile contribute nothing whatever the scratch held; batch == 0 gives zeros.
+ *   Summation: fp32 within one wave's chunk of 64 edges, fp64 above (lanes, waves, tiles in a fixed order), rounded once.
+ * Deterministic: no atomics. */
+size_t ldpc_train_joint_ste_levels_workspace_bytes(const ldpc_decoder *d, int64_t batch);
+int ldpc_train_joint_ste_levels(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                                const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                                void *grad_beta, void *grad_alpha, void *grad_llr, void *grad_levels,
+                                void *workspace, size_t workspace_bytes, void *stream);
+size_t ldpc_train_joint_layered_ste_levels_workspace_bytes(const ldpc_decoder *d, int64_t batch);
+int ldpc_train_joint_layered_ste_levels(const ldpc_decoder *d, const void *llr, const void *targets, int64_t batch,
+                                        const void *iteration_weights, void *loss_per_iter, int32_t *bits, void *posterior,
+                                        void *grad_beta, void *grad_alpha, void *grad_llr, void *grad_levels,
+                                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- on-device Monte-Carlo (BI-AWGN) ---------------------------------------------------------
  * The reference's deliverable is FER / BER curves (simulation_framework.py:85-139: draw, decode, count, stop at max_frames

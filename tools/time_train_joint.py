@@ -22,7 +22,13 @@ copy and loss 16n, check backward 12E (u, gathered g_l, write d/du) -- 40E + 16n
 layered_gradient="posterior_local") (type 2, bc = 3, three quantisers) on the same workloads, with `forward_share` as for
 --decoder layered (engine.train_joint_layered_ste(want_grads=False)).  Algorithmic bytes: walk 14E (the held form: one read
 of P and of the 1-byte codes, writing P, codes and u), posterior copy and loss 16n, check backward 13E (u, codes, gathered
-g_l, write d/du) -- 27E + 16n."""
+g_l, write d/du) -- 27E + 16n.
+--learn-quantizer (with --decoder wrcq or wrcq_layered) adds the same step of the decoder built with learn_quantizer=True --
+the level gradient (kernel level_grad: E code bytes and 4E gathered seed bytes per codeword and iteration on top of the
+step's bytes), the chain rule to (C, gamma), Adam on the float64 pair and the re-upload of the moved thresholds into the same
+native decoder (DecodeEngine.set_quantizers) -- as `levels_ms_per_step`, and the engine call alone with and without
+grad_levels (engine.train_joint_ste(want_levels=...), no autograd, no optimiser) as `engine_ms` / `engine_levels_ms`;
+`levels_bytes_ratio` is 5E over the step's algorithmic bytes, the overhead the added traffic alone would cost."""
 import argparse, json, os, sys
 os.environ.setdefault("LDPC_TRAIN_MAX_SAVED_BYTES", str(64 << 30))     # let the BPTT step run where the HBM holds it
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -51,7 +57,7 @@ def time_steps(step, steps):
 WRCQ_QUANTIZERS = [(3.0, 1.3), (5.0, 1.3), (7.0, 1.3)]
 
 
-def run(name, T, B, steps, snr_db, dev, decoder="neural2d"):
+def run(name, T, B, steps, snr_db, dev, decoder="neural2d", learn_quantizer=False):
     import autograd_bridge as ab
     import codes
     from neural_2d_decoder import Neural2DMinSumDecoder
@@ -104,6 +110,34 @@ def run(name, T, B, steps, snr_db, dev, decoder="neural2d"):
             return forward(llr, want_grads=False)["loss"]
         ms_f, _ = time_steps(forward_only, steps)
         out.update({"forward_ms_per_step": ms_f, "forward_share": ms_f / ms})
+    if learn_quantizer and (wrcq or wrcq_lay):
+        call = eng.train_joint_ste if wrcq else eng.train_joint_layered_ste
+        ms_e, _ = time_steps(lambda: call(llr, want_grad_llr=False)["loss"], steps)
+        ms_l, _ = time_steps(lambda: call(llr, want_grad_llr=False, want_levels=True)["loss"], steps)
+        how = dict(quantizer_gradient="straight_through", learn_quantizer=True)
+        if wrcq_lay:
+            how.update(layered="paper", layered_gradient="posterior_local")
+        learn = WeightedRCQDecoder(code, 3, 8, WRCQ_QUANTIZERS, 2, T, **how)
+        learn.load_state_dict(model.state_dict(), strict=False)
+        opt_l = torch.optim.Adam(learn.parameters(), lr=1e-3)
+
+        def pjt_levels():
+            opt_l.zero_grad()
+            loss = learn.joint_posterior_loss(llr)[0]
+            loss.backward()
+            opt_l.step()
+            return loss
+
+        ms_s, loss_s = time_steps(pjt_levels, steps)
+        eng_l = learn._get_engine(dev)
+        ws_l = int(getattr(eng_l._lib, "ldpc_train_joint_ste_levels_workspace_bytes" if wrcq
+                           else "ldpc_train_joint_layered_ste_levels_workspace_bytes")(eng_l.handle, B))
+        out.update({"engine_ms": ms_e, "engine_levels_ms": ms_l, "engine_levels_overhead": ms_l / ms_e - 1.0,
+                    "levels_ms_per_step": ms_s, "levels_step_overhead": ms_s / ms - 1.0, "levels_loss": loss_s,
+                    "levels_bytes_ratio": 5 * g.E / ((28 if wrcq else 27) * g.E + 16 * g.n),
+                    "levels_workspace_bytes_per_codeword": ws_l / B,
+                    "learned": [[float(c), float(gm)] for c, gm in zip(learn.quantizer_C.tolist(), learn.quantizer_gamma.tolist())]})
+        del learn, opt_l, eng_l
     if wrcq or layered or wrcq_lay:                        # no saved-history path exists for these decoders
         del model, opt, eng
         torch.cuda.empty_cache()
@@ -128,12 +162,16 @@ def main():
     ap.add_argument("--snr-db", type=float, default=3.0)
     ap.add_argument("--workload", type=int, default=None, help="run only WORKLOADS[i]")
     ap.add_argument("--decoder", choices=("neural2d", "wrcq", "layered", "wrcq_layered"), default="neural2d")
+    ap.add_argument("--learn-quantizer", action="store_true", help="also time the step with the level gradient (wrcq, wrcq_layered)")
     a = ap.parse_args()
+    if a.learn_quantizer and a.decoder not in ("wrcq", "wrcq_layered"):
+        ap.error("--learn-quantizer needs --decoder wrcq or wrcq_layered")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     todo = WORKLOADS if a.workload is None else WORKLOADS[a.workload:a.workload + 1]
-    res = [run(name, T, B, a.steps, a.snr_db, dev, a.decoder) for name, T, B in todo]
-    print(json.dumps({"tool": "time_train_joint", "decoder": a.decoder, "steps": a.steps, "results": res}))
+    res = [run(name, T, B, a.steps, a.snr_db, dev, a.decoder, a.learn_quantizer) for name, T, B in todo]
+    print(json.dumps({"tool": "time_train_joint", "decoder": a.decoder, "learn_quantizer": a.learn_quantizer, "steps": a.steps,
+                      "results": res}))
 
 
 if __name__ == "__main__":
