@@ -551,6 +551,44 @@ SavedLayout saved_layout(const ldpc_decoder *d, int tiles, int W)
     return sl;
 }
 
+// vector forms of the layout changes: the caller side moves the widest of 16 / 8 / 4 bytes per lane that divides the row
+// length in bytes and that both pointers are aligned to (NULL counts as aligned), never less than one element.  0: the
+// scalar kernels -- an fp64 decoder whose `bits` sit at 4 mod 8 (a legal int32_t*), or a pointer below its element's alignment
+int vec_bytes(size_t elem, int n, const void *a, const void *b)
+{
+    for (int vb = 16; vb >= (int)elem; vb >>= 1)
+        if (((size_t)n * elem) % vb == 0 && ((uintptr_t)a & (vb - 1)) == 0 && ((uintptr_t)b & (vb - 1)) == 0) return vb;
+    return 0;
+}
+
+// The kernels that move a streaming decode's rows between the caller's layout and the tiles, chosen from the tile width,
+// the row length and the addresses of the caller's pointers (compared, never dereferenced).  decode_impl launches by this
+// and ldpc_debug_boundary_kernels reports it.
+enum { kOutNone = 0, kOutLayout = 1, kOutLastRows = 2 };
+struct BoundaryKernels {
+    int vec = 0;
+    int in_bytes = 0;        // caller-side bytes per access of the entrance pass (transpose_in_v / transpose_in_q4); 0: transpose_in
+    bool fused_in = false;   // code-pair form on 256-codeword tiles: the entrance pass also codes the LLRs (transpose_in_q4)
+    int out_path = kOutNone; // kOutLayout: transpose_out_v / transpose_out; kOutLastRows: vn_last_rows stores the caller's rows
+    int out_bytes = 0;       // caller-side bytes per access on the way out (vn_last_rows: 4 * QV); 0: transpose_out
+};
+BoundaryKernels boundary_kernels(const ldpc_decoder *d, int vec, int T_it, bool saving, const void *llr,
+                                 const void *posterior, const int32_t *bits)
+{
+    const size_t elem = d->elem();
+    // fp32 flooding decode on 256-codeword tiles outside the training forward: the fused passes at either end may run
+    const bool rows4 = elem == 4 && vec == 4 && d->schedule == LDPC_SCHED_FLOODING && !saving && T_it > 0;
+    BoundaryKernels k;
+    k.vec = vec;
+    k.in_bytes = vec_bytes(elem, d->g->n, llr, nullptr);
+    k.fused_in = rows4 && use_pair(d) && pair_q4<4>(d) && k.in_bytes == 16;
+    if (bits || posterior) {
+        k.out_bytes = vec_bytes(elem, d->g->n, posterior, bits);
+        k.out_path = rows4 && k.out_bytes >= 4 ? kOutLastRows : kOutLayout;
+    }
+    return k;
+}
+
 template <typename T, int VEC>
 int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool early_stop, int32_t *bits,
                 void *posterior, int32_t *iterations, uint8_t *success, uint8_t *packed,
@@ -563,16 +601,10 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
     const bool need_post = bits || posterior;          // packed decisions / iterations only: the last pass stores no posterior rows
     const int vc = (g.n + JT - 1) / JT;
     const dim3 tgrid((unsigned)((size_t)w.tiles * VEC * vc));       // transposes: one block per (tile, 64-codeword run, chunk)
+    const BoundaryKernels bk = boundary_kernels(d, VEC, T_it, saved != nullptr, llr, posterior, bits);
 
-    // vector forms of the layout changes: the caller side moves the widest of 16 / 8 / 4 bytes per lane that the row length
-    // and the buffers' alignment admit (0: not even element-aligned -- cannot happen for tensors, kept as the scalar kernels)
-    auto vec_bytes = [&](const void *a, const void *b) {
-        for (int vb = 16; vb >= (int)sizeof(T); vb >>= 1)
-            if (((size_t)g.n * sizeof(T)) % vb == 0 && ((uintptr_t)a & (vb - 1)) == 0 && ((uintptr_t)b & (vb - 1)) == 0) return vb;
-        return 0;
-    };
     auto layout_in = [&]() {
-        switch (vec_bytes(llr, nullptr)) {
+        switch (bk.in_bytes) {
         case 16: hipLaunchKernelGGL((transpose_in_v<T, VEC, 16>), tgrid, dim3(kBlock), 0, s, (const T *)llr, (T *)w.llrT, (long long)batch, g.n, vc); break;
         case 8: hipLaunchKernelGGL((transpose_in_v<T, VEC, 8>), tgrid, dim3(kBlock), 0, s, (const T *)llr, (T *)w.llrT, (long long)batch, g.n, vc); break;
         case 4:
@@ -585,7 +617,7 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
         }
     };
     auto layout_out = [&](const T *srcT) {
-        switch (vec_bytes(posterior, bits)) {
+        switch (bk.out_bytes) {
         case 16: hipLaunchKernelGGL((transpose_out_v<T, VEC, 16>), tgrid, dim3(kBlock), 0, s, srcT, w.bitsT, (T *)posterior, bits, (long long)batch, g.n, vc); break;
         case 8: hipLaunchKernelGGL((transpose_out_v<T, VEC, 8>), tgrid, dim3(kBlock), 0, s, srcT, w.bitsT, (T *)posterior, bits, (long long)batch, g.n, vc); break;
         case 4:
@@ -598,9 +630,9 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
         }
     };
     // code-pair form on 256-codeword tiles: the layout change also codes the LLRs for iteration 0 (transpose_in_q4)
-    bool fused_init = false;
+    const bool fused_init = bk.fused_in;
     if constexpr (sizeof(T) == 4 && VEC == 4) {
-        if (use_pair(d) && !saved && pair_q4<VEC>(d) && T_it > 0 && d->schedule == LDPC_SCHED_FLOODING && vec_bytes(llr, nullptr) == 16) {
+        if (fused_init) {
             const int vb = (g.n + kRowsVars - 1) / kRowsVars;
             const float *beta0 = (const float *)d->beta;
             const float *thr0 = d->thresholds + (size_t)d->q_of_iter[0] * d->n_levels;
@@ -614,7 +646,6 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
     } while (0)
             if (d->key_float4) LDPC_TIQ(kKeyFloat4); else if (d->n_levels == 4) LDPC_TIQ(4); else LDPC_TIQ(0);
 #undef LDPC_TIQ
-            fused_init = true;
         }
     }
     if (!fused_init) layout_in();
@@ -665,14 +696,14 @@ int decode_impl(const ldpc_decoder *d, const void *llr, int64_t batch, bool earl
             return fail(LDPC_ERR_UNSUPPORTED, "layered schedule is fp32 only");
         }
     }
-    // fp32, 256-codeword tiles, 16-byte-aligned caller rows: the last variable pass writes posterior / decisions into the
-    // caller's rows itself (vn_last_rows) -- no tile-major posterior array, no transpose_out pass
+    // fp32, 256-codeword tiles: the last variable pass writes posterior / decisions into the caller's rows itself
+    // (vn_last_rows, 4 / 2 / 1 floats per store) -- no tile-major posterior array, no transpose_out pass
     RowsOut rows_out;
     const RowsOut *rows = nullptr;
     if constexpr (sizeof(T) == 4 && VEC == 4) {
-        if (!saved && T_it > 0 && (bits || posterior) && vec_bytes(posterior, bits) >= 4) {
+        if (bk.out_path == kOutLastRows) {
             rows_out.posterior = (float *)posterior; rows_out.bits = bits; rows_out.batch = (long long)batch;
-            rows_out.qv = vec_bytes(posterior, bits) / 4;
+            rows_out.qv = bk.out_bytes / 4;
             rows = &rows_out;
         }
     }
@@ -1874,6 +1905,22 @@ int ldpc_debug_resident_kernel(const ldpc_decoder *d, int32_t early_stop, int32_
                              k.bpc, k.nl, k.ms, pl.mstride, k.split, d->unit_alpha, d->rcq_zero0,
                              d->form == LDPC_C2V_OMS && d->oms_alpha != nullptr, k.alpha_in_lds};
     std::copy(out, out + 12, out12);
+    return LDPC_OK;
+}
+
+int ldpc_debug_boundary_kernels(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int32_t saving,
+                                const void *llr, const void *posterior, const int32_t *bits, int32_t out5[5])
+{
+    if (!d || !out5) return fail(LDPC_ERR_ARG, "NULL argument");
+    if (batch <= 0) return fail(LDPC_ERR_ARG, "batch must be >= 1");
+    if (saving) {
+        if (int rc = train_supported(d)) return rc;                   // ldpc_decode_saving streams whatever the mode
+    } else if (use_resident(d) || use_layered_lds(d))
+        return fail(LDPC_ERR_UNSUPPORTED, "the LDS-resident kernels read and write the caller's rows element by element");
+    IterCap cap(max_iterations > 0 ? max_iterations : INT_MAX);      // as ldpc_decode_capped; <= 0: the decoder's T
+    const BoundaryKernels k = boundary_kernels(d, pick_vec(d, batch), capped_T(d), saving != 0, llr, posterior, bits);
+    const int32_t out[5] = {k.vec, k.in_bytes, k.fused_in, k.out_path, k.out_bytes};
+    std::copy(out, out + 5, out5);
     return LDPC_OK;
 }
 

@@ -407,6 +407,19 @@ class DecodeEngine:
                 "unit_alpha": bool(o[8]), "rcq_zero0": bool(o[9]), "oms_alpha": bool(o[10]),
                 "alpha_in_lds": bool(o[11])}
 
+    def boundary_kernels(self, batch: int, *, llr: int = 0, posterior: int = 0, bits: int = 0,
+                         max_iters: Optional[int] = None, saving: bool = False) -> dict:
+        """which kernels move the rows of a streaming decode between the caller's layout and the tiles
+        (ldpc_debug_boundary_kernels; host only).  llr / posterior / bits are ADDRESSES (tensor.data_ptr(); 0: NULL).
+        NotImplementedError when the decode runs an LDS-resident kernel."""
+        o = np.zeros(5, dtype=np.int32)
+        a = lambda v: C.c_void_p(int(v)) if v else None
+        nat.check(self._lib.ldpc_debug_boundary_kernels(self.handle, int(batch), int(max_iters or 0), int(bool(saving)),
+                                                        a(llr), a(posterior), a(bits), nat.ptr(o)),
+                  "ldpc_debug_boundary_kernels")
+        return {"vec": int(o[0]), "in_bytes": int(o[1]), "fused_in": bool(o[2]),
+                "out_path": ("none", "layout", "last-rows")[int(o[3])], "out_bytes": int(o[4])}
+
     # ------------------------------------------------------------------ weights
     def set_weights(self, beta: Optional[np.ndarray], alpha: Optional[np.ndarray],
                     oms_alpha: Optional[np.ndarray] = None):

@@ -179,7 +179,12 @@ size_t ldpc_decoder_workspace_bytes(const ldpc_decoder *d, int64_t batch);
  *   bits[batch][n] int32 (posterior < 0), posterior[batch][n] dtype,
  *   iterations[batch] int32, success[batch] uint8,
  *   packed_bits[batch][ceil(n/8)] uint8, bit j of a codeword at byte j/8, bit j%8
- *   (wire format of the multi-GPU all-gather). */
+ *   (wire format of the multi-GPU all-gather).
+ * Rows: any n >= 1, rows packed (row b starts n elements after row b - 1).  llr, posterior and bits each need only
+ * the alignment of their element type -- 4 bytes for llr / posterior of an fp32 decoder and for bits, 8 bytes for
+ * llr / posterior of an fp64 decoder -- and are independent of one another: wider alignment (up to 16 bytes, of the
+ * pointer and of the row length in bytes) is used where present and never required, and no result depends on it
+ * (tests/test_gpu_row_alignment.py).  The same holds for ldpc_decode_capped and ldpc_decode_saving. */
 int ldpc_decode(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop,
                 int32_t *bits, void *posterior, int32_t *iterations, uint8_t *success,
                 uint8_t *packed_bits, void *workspace, size_t workspace_bytes, void *stream);

@@ -5,7 +5,8 @@
  * reference interface corresponds to it.  bench.py uses ldpc_debug_sweep to time one sweep kernel
  * with HIP events; the parity tests use the two state dumps to compare per-edge check-to-variable
  * messages (for RCQ: the 3-bit quantiser codes the reference emits, rcq_decoder.py:244-246) on BOTH
- * engines; ldpc_debug_resident_kernel lets a test assert WHICH resident kernel and table flags a decode runs.
+ * engines; ldpc_debug_resident_kernel lets a test assert WHICH resident kernel and table flags a decode runs,
+ * ldpc_debug_boundary_kernels which layout kernels a streaming decode takes for given caller pointers.
  */
 #ifndef LDPC_HIP_DEBUG_H
 #define LDPC_HIP_DEBUG_H
@@ -48,6 +49,20 @@ int ldpc_debug_resident_c2v(const ldpc_decoder *d, const void *llr, int64_t batc
  * resident_kernel).  G is the kernel's (1 for fp64: one codeword in the slots of a float pair).  LDPC_ERR_UNSUPPORTED when the
  * decoder's mode does not put it on the resident engine or its schedule is layered (those never launch resident_decode). */
 int ldpc_debug_resident_kernel(const ldpc_decoder *d, int32_t early_stop, int32_t out12[12]);
+
+/* The kernels that move a streaming decode's rows between the caller's layout and the tiles (host only, no device is
+ * touched; llr, posterior and bits are compared, never dereferenced, and may be NULL as in ldpc_decode).  For a decode of
+ * `batch` codewords running at most max_iterations of the decoder's iterations (<= 0: its T), through ldpc_decode /
+ * ldpc_decode_capped or (saving != 0) ldpc_decode_saving: out5 = { VEC, input bytes, fused entrance, output path, output
+ * bytes }.  VEC: codewords per lane of a tile (64 * VEC codewords wide).  Input bytes: what one lane moves per access on the
+ * caller's side of the entrance pass, 16 / 8 / 4 (transpose_in_v), 0 the scalar transpose_in.  Fused entrance: 1 when the
+ * code-pair form's transpose_in_q4 runs instead (16-byte rows only).  Output path: 0 none (neither bits nor posterior), 1
+ * the layout pass (transpose_out_v, or the scalar transpose_out when output bytes is 0), 2 the last variable pass stores the
+ * caller's rows itself (vn_last_rows, output bytes / 4 floats per store).  The launcher and this hook read one selection
+ * (csrc/ldpc_hip.hip, boundary_kernels).  LDPC_ERR_UNSUPPORTED when the decode runs an LDS-resident kernel (those read and
+ * write the caller's rows element by element) or, with saving != 0, the decoder has no gradient path. */
+int ldpc_debug_boundary_kernels(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int32_t saving,
+                                const void *llr, const void *posterior, const int32_t *bits, int32_t out5[5]);
 
 /* Compact fixed-T plan of the LDS-resident engine (host only, no device is touched).  The kernel runs the variable at
  * position q = r*512 + w*64 + lane in round r (< 4) of wave w (< 8); cells[w*4 + r] describes cell (w, r): 0 empty,

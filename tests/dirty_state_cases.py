@@ -24,7 +24,7 @@ from test_gpu_layered_weighted import restate as layered_wrcq_restate
 from test_gpu_parity import QP, oracle_capped, wide_check_code
 
 F32, F64 = np.float32, np.float64
-CODES = {"small": "small_96_48", "ira": "ira_1998_1512", "wide": None}
+CODES = {"small": "small_96_48", "ira": "ira_1998_1512", "wide": wide_check_code}     # a shipped code's name, or what builds the code
 T_OF = {"small": 10, "ira": 10, "wide": 8}
 # (precision, B): fp32 1 | 64 (VEC = 1, a full tile) | 65 (VEC = 4, 191 padding codewords) | 257 (the second tile holds one
 # live codeword); fp64 129 (VEC = 2).  The layered schedules run VEC = 1 at every B: 65 and 257 end in a tile of one codeword
@@ -68,10 +68,17 @@ def seed_of(*parts):
     return zlib.crc32("/".join(str(p) for p in parts).encode())
 
 
+def register_code(name, make, T, snr):
+    """another code for the case lists built on this module (tests/row_alignment_cases.py): make() -> LDPCCode, the
+    decoders' T, and the (low, high) SNR of its batches"""
+    assert name not in CODES
+    CODES[name], T_OF[name], SNR[name] = make, T, snr
+
+
 @functools.lru_cache(maxsize=None)
 def load_code(name):
     import codes
-    return wide_check_code() if name == "wide" else codes.load_code(CODES[name], T_OF[name])
+    return CODES[name]() if callable(CODES[name]) else codes.load_code(CODES[name], T_OF[name])
 
 
 def oracle_graph(oracle_mod, code):
