@@ -236,7 +236,9 @@ int launch_cn(const ldpc_decoder *d, const Workspace &w, int it, bool use_done, 
     if (cb == 0 || g.E == 0) return LDPC_OK;
     const dim3 grid((unsigned)((size_t)w.tiles * cb)), block(kBlock);
     const bool first = it == 0;
-    const int n_wide = d->g->n_wide;                 // > 0: the sweep below skips them, cn_sweep_wide follows
+    // > 0: the sweep below skips them, cn_sweep_wide follows.  The sum-product recursion is sequential along a check:
+    // cn_sweep keeps checks of every degree, one wave each
+    const int n_wide = d->form == LDPC_C2V_SPA ? 0 : d->g->n_wide;
     const T *src = first ? (const T *)w.llrT : (const T *)w.v2c;
     const T *beta_row = (const T *)d->beta + (size_t)it * d->n_beta;
     if constexpr (sizeof(T) == 4 && VEC == 4) {
@@ -276,6 +278,8 @@ int launch_cn(const ldpc_decoder *d, const Workspace &w, int it, bool use_done, 
         else { if (first) LDPC_CN(FORM_NMS, true); else LDPC_CN(FORM_NMS, false); }
     } else if (d->form == LDPC_C2V_OMS) {
         if (first) LDPC_CN(FORM_OMS, true); else LDPC_CN(FORM_OMS, false);
+    } else if (d->form == LDPC_C2V_SPA) {
+        if (first) LDPC_CN(FORM_SPA, true); else LDPC_CN(FORM_SPA, false);
     } else {
         if constexpr (sizeof(T) == 4) {
             if (d->n_levels == 4) {                      // bc = 3: compare chain with a compile-time length
@@ -1474,7 +1478,7 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
     *out = nullptr;
     if (!g || !desc) return fail(LDPC_ERR_ARG, "NULL argument");
     if (desc->dtype != LDPC_F32 && desc->dtype != LDPC_F64) return fail(LDPC_ERR_ARG, "bad dtype");
-    if (desc->c2v_form < LDPC_C2V_NMS || desc->c2v_form > LDPC_C2V_OMS) return fail(LDPC_ERR_ARG, "bad c2v_form");
+    if (desc->c2v_form < LDPC_C2V_NMS || desc->c2v_form > LDPC_C2V_SPA) return fail(LDPC_ERR_ARG, "bad c2v_form");
     if (desc->iters < 0) return fail(LDPC_ERR_ARG, "iters < 0");
     if (desc->n_beta_slots < 1 || desc->n_alpha_slots < 1 || !desc->beta || !desc->alpha ||
         (g->E > 0 && !desc->beta_slot) || (g->n > 0 && !desc->alpha_slot))
@@ -1487,6 +1491,15 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
     if (desc->dtype == LDPC_F32 && g->max_dv > 575) return fail(LDPC_ERR_UNSUPPORTED, "variable degree %d > 575 (fp32 sum order)", g->max_dv);
     if (desc->dtype == LDPC_F64 && g->max_dv > 128) return fail(LDPC_ERR_UNSUPPORTED, "variable degree %d > 128 (fp64 sum order)", g->max_dv);
     if (desc->schedule < LDPC_SCHED_FLOODING || desc->schedule > LDPC_SCHED_LAYERED) return fail(LDPC_ERR_ARG, "bad schedule");
+    if (desc->c2v_form == LDPC_C2V_SPA) {
+        if (desc->schedule != LDPC_SCHED_FLOODING)
+            return fail(LDPC_ERR_UNSUPPORTED, "the sum-product form (LDPC_C2V_SPA) decodes under LDPC_SCHED_FLOODING only: layered "
+                                              "belief propagation is not implemented");
+        for (int i = 0; i < g->m; ++i)
+            if (g->h_check_ptr[i + 1] - g->h_check_ptr[i] == 1)
+                return fail(LDPC_ERR_UNSUPPORTED, "check %d has degree 1: its sum-product message is the empty product, an infinite "
+                                                  "LLR (LDPC_C2V_SPA needs every check of degree 0 or >= 2)", i);
+    }
     if (desc->schedule != LDPC_SCHED_FLOODING) {
         if (desc->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "layered schedule is fp32 only");
         if (desc->c2v_form != LDPC_C2V_RCQ && desc->schedule == LDPC_SCHED_LAYERED_REF)
@@ -1596,7 +1609,8 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
     if (!rc && d->form == LDPC_C2V_RCQ) apply_quantizer_flags(d, quantizer_flags(d, desc->thresholds));   // before the plans
     resident_table_flags(d, desc->alpha);
     beta_table_flags(d, desc->beta);
-    if (!rc && d->schedule == LDPC_SCHED_FLOODING) rc = build_resident_plan(d, desc);
+    // the sum-product form has the two-sweep streaming engine only: no LDS-resident plan is built for it
+    if (!rc && d->schedule == LDPC_SCHED_FLOODING && d->form != LDPC_C2V_SPA) rc = build_resident_plan(d, desc);
     if (!rc) rc = build_layered_plan(d, desc);
     if (rc) {
         ldpc_decoder_destroy(d);
@@ -1615,6 +1629,9 @@ int ldpc_decoder_set_mode(ldpc_decoder *d, int32_t mode)
 {
     if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
     if (mode < LDPC_MODE_AUTO || mode > LDPC_MODE_PAIR) return fail(LDPC_ERR_ARG, "bad mode");
+    if (d->form == LDPC_C2V_SPA && (mode == LDPC_MODE_RESIDENT || mode == LDPC_MODE_GATHER || mode == LDPC_MODE_PAIR))
+        return fail(LDPC_ERR_UNSUPPORTED, "the sum-product form (LDPC_C2V_SPA) has the two-sweep streaming engine only "
+                                          "(LDPC_MODE_AUTO / STREAM / SWEEPS): no LDS-resident, fused or code-pair form");
     if (mode == LDPC_MODE_GATHER && !d->gat_ok)
         return fail(LDPC_ERR_UNSUPPORTED, "the fused RCQ iteration needs an fp32 flooding RCQ decoder with variable degree <= 8");
     if (mode == LDPC_MODE_PAIR && !d->pair_ok)

@@ -24,9 +24,9 @@ namespace ldpc {
 constexpr int kWave = 64;
 constexpr int kBlock = 256;                 // 4 waves: 4 consecutive nodes of one tile
 constexpr int kWavesPerBlock = kBlock / kWave;
-constexpr int kWideCheck = 32;              // checks of higher degree go to cn_sweep_wide (one check per block)
+constexpr int kWideCheck = 32;              // checks of higher degree go to cn_sweep_wide (one check per block; not FORM_SPA)
 
-enum { FORM_NMS = 0, FORM_RCQ = 1, FORM_OMS = 2 };
+enum { FORM_NMS = 0, FORM_RCQ = 1, FORM_OMS = 2, FORM_SPA = 3 };
 
 struct GraphDev {
     int n, m, E;
@@ -137,6 +137,29 @@ __device__ __forceinline__ void store_masked(T *p, const Pack<T, VEC> &v, const 
     }
 }
 
+// Sum-product check update (FORM_SPA): a [+] b = 2 atanh(tanh(a/2) tanh(b/2)) in the Jacobian form
+//   a [+] b = sign(a) sign(b) min(|a|, |b|) + (g(|a + b|) - g(|a - b|)),   g(x) = log1p(exp(-x)),
+// accurate exp / log1p (DESIGN.md "Sum-product").  The correction is formed as ONE difference that is then added, so the
+// operation is exactly odd in either argument (negating a swaps |a + b| and |a - b|) and exactly commutative; a zero argument
+// gives g(|b|) - g(|b|) = 0 exactly; |a + b| = inf gives g = 0, so finite inputs of any magnitude stay finite.
+__device__ __forceinline__ float spa_g(float x) { return log1pf(expf(-x)); }
+__device__ __forceinline__ double spa_g(double x) { return log1p(exp(-x)); }
+template <typename T>
+__device__ __forceinline__ T spa_boxplus(T a, T b)
+{
+    const T aa = abs_of<T>(a), ab = abs_of<T>(b);
+    const T sm = flip_sign<T>(aa < ab ? aa : ab, signbit_of<T>(a) ^ signbit_of<T>(b));
+    return sm + (spa_g(abs_of<T>(a + b)) - spa_g(abs_of<T>(a - b)));
+}
+template <typename T, int VEC>
+__device__ __forceinline__ Pack<T, VEC> spa_boxplus(const Pack<T, VEC> &a, const Pack<T, VEC> &b)
+{
+    Pack<T, VEC> r;
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) r.x[c] = spa_boxplus<T>(a.x[c], b.x[c]);
+    return r;
+}
+
 // Training forward (ldpc_decode_saving): every iteration writes its own slice, so a stopped codeword's latched
 // values are carried forward from the previous iteration's slice instead of being left in place.
 template <typename T, int VEC>
@@ -211,6 +234,39 @@ __global__ __launch_bounds__(kBlock) void cn_sweep(GraphDev g, const T *__restri
     }
     const T *in_base = FIRST ? src + (size_t)tile * g.n * W + lane_off
                              : src + ((size_t)tile * g.E + e0) * W + lane_off;
+
+    if constexpr (FORM == FORM_SPA) {
+        // Sum-product: c2v_k = beta * (f_{k-1} [+] b_{k+1}) with the prefixes f_k = x_0 [+] .. [+] x_k and the suffixes
+        // b_k = x_k [+] .. [+] x_{dc-1}.  O(1) registers per lane at any degree: pass 1 walks forward and parks f_{k-1} in
+        // the check's OUTPUT row k, pass 2 walks backward with the running suffix, reads the parked prefix and overwrites the
+        // row with the message.  Every store is the masked one: a frozen codeword keeps its latched rows, what it reads back
+        // as a "prefix" is its latched message and the value formed from it is never stored.  Degree 1 has no message (the
+        // empty product is an infinite one): ldpc_decoder_create refuses such a graph.
+        if (dc < 2) continue;
+        T *out_base = reinterpret_cast<T *>(c2v_out) + ((size_t)tile * g.E + e0) * W + lane_off;
+        auto row_of = [&](int t) { return FIRST ? in_base + (size_t)g.var_idx[e0 + t] * W : in_base + (size_t)t * W; };
+        Pack<T, VEC> f = ld<T, VEC>(row_of(0));
+        for (int t = 1; t + 1 < dc; ++t) {             // rows 1 .. dc-2: the last edge takes its prefix from the register
+            store_masked<T, VEC>(out_base + (size_t)t * W, f, fz);
+            f = spa_boxplus<T, VEC>(f, ld<T, VEC>(row_of(t)));
+        }
+        Pack<T, VEC> b = f;                            // overwritten at t = dc - 1 before its first use
+        for (int t = dc - 1; t >= 0; --t) {
+            const T w = beta_row[beta_slot[e0 + t]];
+            Pack<T, VEC> msg;
+            if (t == dc - 1) msg = f;                  // f_{dc-2}
+            else if (t == 0) msg = b;                  // b_1
+            else msg = spa_boxplus<T, VEC>(ld<T, VEC>(out_base + (size_t)t * W), b);
+            if (t > 0) {
+                const Pack<T, VEC> x = ld<T, VEC>(row_of(t));
+                b = (t == dc - 1) ? x : spa_boxplus<T, VEC>(x, b);
+            }
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) msg.x[c] = w * msg.x[c];
+            store_masked<T, VEC>(out_base + (size_t)t * W, msg, fz);
+        }
+        continue;
+    }
 
     T m1[VEC], m2[VEC];
     int idx[VEC];

@@ -8,9 +8,17 @@
 #include <type_traits>
 
 namespace {
+// the sum-product form is a decode-only baseline: every gradient entry point refuses it with this message
+int spa_no_gradient()
+{
+    return fail(LDPC_ERR_UNSUPPORTED, "the sum-product form (LDPC_C2V_SPA) has no gradient path: ldpc_decode_saving, ldpc_backward "
+                                      "and the ldpc_train_joint* entry points exist for the min-sum and RCQ forms");
+}
+
 int train_supported(const ldpc_decoder *d)
 {
     if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
+    if (d->form == LDPC_C2V_SPA) return spa_no_gradient();
     if (d->schedule != LDPC_SCHED_FLOODING && d->form != LDPC_C2V_RCQ)
         return fail(LDPC_ERR_UNSUPPORTED, "the layered schedule (LDPC_SCHED_LAYERED) has no gradient path: gradients exist for "
                                           "the fp32 normalised / offset min-sum decoders under LDPC_SCHED_FLOODING");
@@ -140,7 +148,8 @@ int joint_supported(const ldpc_decoder *d, int kind)
 {
     if (kind == kJointMinsum) return train_supported(d);
     if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
-    if (kind == kJointSte) {     // the quantised decoder, differentiated with the straight-through rule
+    if (d->form == LDPC_C2V_SPA) return spa_no_gradient();
+    if (kind == kJointSte) {    // the quantised decoder, differentiated with the straight-through rule
         if (d->dtype != LDPC_F32 || d->form != LDPC_C2V_RCQ || d->schedule != LDPC_SCHED_FLOODING)
             return fail(LDPC_ERR_UNSUPPORTED, "the straight-through joint loss exists for the fp32 RCQ flooding decoders "
                                               "(ldpc_train_joint has the min-sum forms; the RCQ decoder under LDPC_SCHED_LAYERED takes "

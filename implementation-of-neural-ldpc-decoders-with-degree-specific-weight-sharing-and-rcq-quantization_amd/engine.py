@@ -390,7 +390,8 @@ class DecodeEngine:
         kernels = None
         if resident and self.schedule == nat.SCHED_FLOODING:
             kernels = {"fixed_T": self._resident_kernel(False), "early_stop": self._resident_kernel(True)}
-        return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel,
+        form = {nat.C2V_NMS: "NMS", nat.C2V_RCQ: "RCQ", nat.C2V_OMS: "OMS", nat.C2V_SPA: "SPA"}[self.c2v_form]
+        return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel, "form": form,
                 "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
                 "codewords_per_workgroup": int(out[1]),
                 "threads_per_workgroup": threads, "lds_bytes": lds, "workgroups_per_cu": per_cu,

@@ -20,6 +20,10 @@ row-wise map of the single-codeword call; keyword ``early_stop=False`` runs exac
 iterations.  Arithmetic type follows the input: float64 in -> fp64 kernels with
 np.sum's association order (results identical to the reference), float32 in -> fp32.
 
+``SumProductDecoder(code, scale=1.0)`` (no reference counterpart) is the belief-propagation baseline of these decoders on
+the same engine: the check update ``scale * 2 atanh(prod tanh(x / 2))`` of ``LDPC_C2V_SPA`` (include/ldpc_hip.h), everything
+else -- call shapes, return types, stop rule -- as ``BasicMinSumDecoder``, with which it shares ``decode``.
+
 ``schedule="layered"`` (keyword only; also on the neural min-sum decoders of neural_2d_decoder.py and
 neural_minsum_decoder.py) runs the layered schedule in place of flooding: checks are walked in order on running
 posteriors, each check first takes its previous message off (``u = P - R``), forms the min-sum message of the decoder's
@@ -113,14 +117,14 @@ def check_schedule(schedule) -> str:
     return schedule
 
 
-class BasicMinSumDecoder:
-    """Basic (normalised) MinSum LDPC decoder; flooding schedule, ``schedule="layered"``: the layered one (fp32 only)."""
+class _ScaledCheckDecoder:
+    """What BasicMinSumDecoder and SumProductDecoder share: ONE scale on every check-to-variable message, unit alpha, the
+    engine cache and the decode body.  A subclass names the check rule (``_c2v_form``, a ``_native.C2V_*`` name), the
+    attribute holding the scale (``_scale_attr``) and its schedule."""
 
-    def __init__(self, code: LDPCCode, factor: float = 0.7, *, schedule: str = "flooding"):
-        self.code = code
-        self.factor = factor
-        self.schedule = check_schedule(schedule)
-        self._engines = {}
+    _c2v_form = None
+    _scale_attr = None
+    schedule = "flooding"
 
     def _engine(self, torch_dtype, device):
         import torch
@@ -129,14 +133,15 @@ class BasicMinSumDecoder:
         dev = _require_gpu(device)
         g = self.code.tanner_graph()
         T = int(self.code.max_iterations)
-        key = (torch_dtype, dev.index, id(g), T, float(self.factor), self.schedule)
+        scale = float(getattr(self, self._scale_attr))
+        key = (torch_dtype, dev.index, id(g), T, scale, self.schedule)
         eng = self._engines.get(key)
         if eng is None:
             np_dt = np.float32 if torch_dtype == torch.float32 else np.float64
             rows = max(T, 1)
             extra = {"schedule": nat.SCHED_LAYERED} if self.schedule == "layered" else {}
-            eng = DecodeEngine(g, dtype=torch_dtype, c2v_form=nat.C2V_NMS, iters=T,
-                               beta=np.full((rows, 1), self.factor, dtype=np_dt),     # factor * min * prod(signs)
+            eng = DecodeEngine(g, dtype=torch_dtype, c2v_form=getattr(nat, self._c2v_form), iters=T,
+                               beta=np.full((rows, 1), scale, dtype=np_dt),           # scale * check-rule(others)
                                beta_slot=np.zeros(g.E, np.int32),
                                alpha=np.ones((rows, 1), dtype=np_dt),                 # llr + 1 * sum(others)
                                alpha_slot=np.zeros(g.n, np.int32), device=dev, **extra)
@@ -145,7 +150,7 @@ class BasicMinSumDecoder:
 
     def decode(self, llr, early_stop: bool = True, device=None):
         """
-        Decode using the MinSum algorithm.
+        Decode with the decoder's check rule (MinSum / sum-product).
 
         Args:
             llr: log-likelihood ratios from the channel, ``[n]`` (reference) or ``[B, n]``
@@ -185,6 +190,41 @@ class BasicMinSumDecoder:
         if single:
             return bits[0], bool(succ[0]), int(its[0])
         return bits, succ, its
+
+
+class BasicMinSumDecoder(_ScaledCheckDecoder):
+    """Basic (normalised) MinSum LDPC decoder; flooding schedule, ``schedule="layered"``: the layered one (fp32 only)."""
+
+    _c2v_form = "C2V_NMS"
+    _scale_attr = "factor"                # factor * min * prod(signs)
+
+    def __init__(self, code: LDPCCode, factor: float = 0.7, *, schedule: str = "flooding"):
+        self.code = code
+        self.factor = factor
+        self.schedule = check_schedule(schedule)
+        self._engines = {}
+
+
+class SumProductDecoder(_ScaledCheckDecoder):
+    """Sum-product (belief propagation) decoder, the baseline the min-sum family is measured against; no reference
+    counterpart.  Flooding schedule, check update ``scale * 2 atanh(prod tanh(x / 2))`` over a check's other edges
+    (``LDPC_C2V_SPA`` of include/ldpc_hip.h); ``scale=1.0`` is plain BP.  ``decode`` is ``BasicMinSumDecoder.decode``:
+    ``[n]`` or ``[B, n]``, numpy or torch, float64 numpy in -> the fp64 engine.  Decode only: the engine refuses
+    gradients, the joint losses, the layered schedules and the LDS-resident mode with ``NotImplementedError``, and a code
+    with a degree-1 check (its message would be infinite) when the engine is created."""
+
+    _c2v_form = "C2V_SPA"
+    _scale_attr = "scale"
+
+    def __init__(self, code: LDPCCode, scale: float = 1.0):
+        self.code = code
+        self.scale = scale
+        self._engines = {}
+
+    def _get_engine(self, device):
+        """the fp32 engine (what LDPSimulator, replay_errors and sharding.decode_sharded ask a decoder for)"""
+        import torch
+        return self._engine(torch.float32, device)
 
 
 def create_test_ldpc_code() -> LDPCCode:

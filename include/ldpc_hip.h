@@ -58,8 +58,28 @@ enum { LDPC_F32 = 0, LDPC_F64 = 1 };
 enum {
     LDPC_C2V_NMS = 0,  /* c2v = (beta * min) * s             ldpc_decoder.py:118-120, neural_2d_decoder.py:189-191 */
     LDPC_C2V_RCQ = 1,  /* c2v = deq(quant((beta * s) * min)) rcq_decoder.py:242-246, 559-563 (1-byte codes in HBM) */
-    LDPC_C2V_OMS = 2   /* c2v = s * (relu(min - beta) - a_c) neural_2d_decoder.py:400-401                          */
+    LDPC_C2V_OMS = 2,  /* c2v = s * (relu(min - beta) - a_c) neural_2d_decoder.py:400-401                          */
+    LDPC_C2V_SPA = 3   /* c2v = beta * 2 atanh(prod over the OTHER edges of tanh(x / 2)): sum-product / belief propagation */
 };
+/* LDPC_C2V_SPA is the baseline the min-sum family is measured against ("95-98 % of BP performance"); the reference has no
+ * such decoder, the yardstick is a CPU restatement (tests/spa_reference.py).  Flooding schedule only.  x_e is the
+ * variable-to-check message on edge e (the LLR of its variable in iteration 0) and, on the edges e of check c,
+ *     c2v_e = beta_t[beta_slot[e]] * 2 atanh( prod_{e' in c, e' != e} tanh(x_e' / 2) )
+ * formed by forward / backward box-plus recursions: with g(x) = log1p(exp(-x)),
+ *     a [+] b = sign(a) sign(b) min(|a|, |b|) + (g(|a + b|) - g(|a - b|)),
+ *     f_k = f_k-1 [+] x_k,   b_k = x_k [+] b_k+1,   c2v_k = beta * (f_k-1 [+] b_k+1)   (c2v_1 = beta * b_2, c2v_dc = beta * f_dc-1).
+ * beta all 1.0 is plain BP; the tables are applied as LDPC_C2V_NMS applies them ("neural BP" weights work in the forward pass).
+ * Variable update, alpha, posterior, decision (posterior < 0), syndrome, early stop, ldpc_decode_capped and packed bits are
+ * those of LDPC_C2V_NMS, through the same kernels; thresholds and oms_alpha are ignored.
+ *   - LLRs must be finite; finite inputs of any magnitude give finite messages.
+ *   - A zero on another edge of the check gives exactly 0 (either sign).
+ *   - The update is odd: negating an input negates, bit for bit, exactly the messages it feeds with odd multiplicity.
+ *   - Checks of degree 0 are skipped; a graph with a check of degree 1 is refused by ldpc_decoder_create
+ *     (LDPC_ERR_UNSUPPORTED: the empty product would be an infinite message).
+ * fp32 and fp64; ldpc_decode, ldpc_decode_capped and (fp32) ldpc_simulate / ldpc_simulate_diag.  The engine is the two-sweep
+ * streaming form: LDPC_MODE_AUTO, STREAM and SWEEPS all select it and ldpc_decoder_info reports { LDPC_MODE_SWEEPS, 0, 0, 0 };
+ * RESIDENT, GATHER and PAIR are refused, as are both layered schedules, ldpc_decode_saving, ldpc_backward and every
+ * ldpc_train_joint* entry point (LDPC_ERR_UNSUPPORTED). */
 
 /* message schedule.  LAYERED_REF is RCQMinSumDecoder(layered=True) exactly as the reference runs it
  * (rcq_decoder.py:281-350): checks processed in order on running posteriors whose "previous
