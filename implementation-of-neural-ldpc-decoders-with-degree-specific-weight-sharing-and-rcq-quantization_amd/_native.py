@@ -133,6 +133,12 @@ class SimDesc(C.Structure):
                 ("max_frames", C.c_int64), ("max_errors", C.c_int64), ("block", C.c_int64), ("poll_blocks", C.c_int32)]
 
 
+class RateMatch(C.Structure):
+    """ldpc_rate_match of include/ldpc_hip.h: the masks of a rate-matching profile (device pointers, NULL = none / all)"""
+    _fields_ = [("punctured_packed", C.c_void_p), ("shortened_packed", C.c_void_p), ("count_packed", C.c_void_p),
+                ("short_llr", C.c_float)]
+
+
 # every symbol include/ldpc_hip.h declares (tests check the library exports them all) ...
 PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info", "ldpc_decoder_create",
                    "ldpc_decoder_set_mode", "ldpc_decoder_info",
@@ -148,7 +154,9 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_channel_awgn", "ldpc_channel_awgn_mix", "ldpc_sim_count",
                    "ldpc_simulate_workspace_bytes", "ldpc_simulate",
                    "ldpc_sim_diag_words", "ldpc_sim_count_diag_scratch_bytes", "ldpc_sim_count_diag",
-                   "ldpc_simulate_diag_workspace_bytes", "ldpc_simulate_diag")
+                   "ldpc_simulate_diag_workspace_bytes", "ldpc_simulate_diag",
+                   "ldpc_channel_awgn_rm", "ldpc_channel_awgn_mix_rm", "ldpc_sim_count_rm", "ldpc_sim_count_diag_rm",
+                   "ldpc_simulate_rm", "ldpc_simulate_diag_rm")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -274,6 +282,19 @@ def load():
         lib.ldpc_simulate_diag_workspace_bytes.argtypes = [vp, i64, i64]
         lib.ldpc_simulate_diag.restype = C.c_int
         lib.ldpc_simulate_diag.argtypes = [vp, C.POINTER(SimDesc), i64, vp, vp, vp, C.c_size_t, vp]
+        rm = C.POINTER(RateMatch)
+        lib.ldpc_channel_awgn_rm.restype = C.c_int
+        lib.ldpc_channel_awgn_rm.argtypes = [vp, i64, i32, u64, u32, u64, f32, f32, vp, rm, vp]
+        lib.ldpc_channel_awgn_mix_rm.restype = C.c_int
+        lib.ldpc_channel_awgn_mix_rm.argtypes = [vp, i64, i32, u64, u32, u64, vp, vp, i32, vp, rm, vp]
+        lib.ldpc_sim_count_rm.restype = C.c_int
+        lib.ldpc_sim_count_rm.argtypes = [vp, vp, vp, i64, i32, vp, i64, i64, rm, vp]
+        lib.ldpc_sim_count_diag_rm.restype = C.c_int
+        lib.ldpc_sim_count_diag_rm.argtypes = [vp, vp, i32, i64, vp, vp, vp, i64, i32, vp, u64, i64, i64, vp, C.c_size_t, rm, vp]
+        lib.ldpc_simulate_rm.restype = C.c_int
+        lib.ldpc_simulate_rm.argtypes = [vp, C.POINTER(SimDesc), rm, vp, vp, C.c_size_t, vp]
+        lib.ldpc_simulate_diag_rm.restype = C.c_int
+        lib.ldpc_simulate_diag_rm.argtypes = [vp, C.POINTER(SimDesc), rm, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p

@@ -196,6 +196,30 @@ def load_code(name: str, max_iterations: int = 50):
     return LDPCCode.from_graph(g, k=g.n - g.m, max_iterations=max_iterations)
 
 
+def staircase_encode(graph: TannerGraph, info_bits) -> np.ndarray:
+    """Systematic encoding on a graph whose last m columns are the IRA staircase (parity column p on checks p and p + 1, the
+    last one on check m - 1 only): p_i = p_{i-1} + (H_info u)_i over GF(2).  info_bits: 0/1, [k] or [B, k] with k = n - m
+    -> uint8 codewords [n] or [B, n] with H c = 0.  numpy, on the host.  ValueError when the last m columns are not that
+    staircase."""
+    n, m = graph.n, graph.m
+    k = n - m
+    rows, cols = np.asarray(graph.check_of_edge, dtype=np.int64), np.asarray(graph.var_idx, dtype=np.int64)
+    par = cols >= k
+    have = np.unique(rows[par] * m + (cols[par] - k))                                 # (check, parity column) pairs, sorted
+    p = np.arange(m, dtype=np.int64)
+    want = np.unique(np.concatenate([p * m + p, (p[:-1] + 1) * m + p[:-1]]))
+    if k < 1 or int(par.sum()) != want.size or not np.array_equal(have, want):
+        raise ValueError("the last m columns of the graph are not the IRA staircase")
+    u = np.asarray(info_bits)
+    if u.shape[-1:] != (k,) or u.ndim not in (1, 2) or not np.isin(u, (0, 1)).all():
+        raise ValueError(f"info_bits must be 0/1 of shape [{k}] or [B, {k}]")
+    u2 = np.atleast_2d(u).astype(np.uint8)
+    s = np.zeros((u2.shape[0], m), dtype=np.uint8)                                    # (H_info u)_i
+    np.bitwise_xor.at(s, (slice(None), rows[~par]), u2[:, cols[~par]])
+    c = np.concatenate([u2, np.bitwise_xor.accumulate(s, axis=1)], axis=1)
+    return c[0] if u.ndim == 1 else c
+
+
 if __name__ == "__main__":  # regenerate + verify the committed edge lists
     os.makedirs(_DATA_DIR, exist_ok=True)
     for name, spec in _SPECS.items():

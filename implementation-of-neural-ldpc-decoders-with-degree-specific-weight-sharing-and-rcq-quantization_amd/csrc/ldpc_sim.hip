@@ -162,6 +162,103 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_awgn_mix(float *__restr
     sim_store_quad(llr + (size_t)b * (size_t)n + (size_t)j0, v, cnt);
 }
 
+// ------------------------------------------------------------------------------------------ rate matching
+// ldpc_channel_awgn_rm / _mix_rm: the stream above with a punctured mask (the bit was not sent: LLR +0.0f, an erasure to the
+// min-sum kernels) and a shortened mask (the bit is known: s_j * short_llr).  The Philox counter stays on the VARIABLE index
+// j -- quad q of frame f draws the words it draws in sim_channel_awgn -- so every transmitted position holds the plain draw
+// bit for bit and the profiles of a rate-compatible family see common noise.  The same lane-per-quad shape and stores as the
+// plain kernels, which are left as they are.  A quad's four mask bits sit in one byte, as its codeword bits do (j0 % 8 is 0
+// or 4); the three byte loads are issued before the Philox rounds.  A quad none of whose bits below n is transmitted skips
+// the rounds and both Box-Muller pairs: a lane-level branch, so a contiguous punctured block of 64 quads or more frees whole
+// waves and a scattered profile frees next to nothing.
+
+// mask nibbles of quad j0 / 4: (codeword, punctured and not shortened, shortened), each four bits
+__device__ inline void sim_rm_nibbles(int j0, const uint8_t *__restrict__ cw, const uint8_t *__restrict__ punct,
+                                      const uint8_t *__restrict__ shrt, unsigned &cbits, unsigned &pbits, unsigned &sbits)
+{
+    const int byte = j0 >> 3, sh = j0 & 7;
+    cbits = cw ? (cw[byte] >> sh) & 0xfu : 0u;
+    sbits = shrt ? (shrt[byte] >> sh) & 0xfu : 0u;
+    pbits = punct ? (punct[byte] >> sh) & 0xfu & ~sbits : 0u;                     // a bit in both masks is shortened
+}
+
+// the quad's four LLRs: the plain draw where the bit is transmitted.  `live` has bit k set for j0 + k < n, so the pad bits of a
+// mask's last byte never keep a tail quad from being skipped (and are never stored)
+__device__ inline void sim_rm_quad(unsigned long long f, unsigned q, uint32_t k0, uint32_t k1, uint32_t stream_id, float scale,
+                                   float shift, float short_llr, unsigned cbits, unsigned pbits, unsigned sbits, unsigned live,
+                                   float v[4])
+{
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (((pbits | sbits) & live) != live) {                                       // a transmitted bit in the quad
+        uint32_t x[4];
+        philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), q, stream_id, k0, k1, x);
+        sim_box_muller(x[0], x[1], z[0], z[1]);
+        sim_box_muller(x[2], x[3], z[2], z[3]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float y = fmaf(z[k], scale, shift);
+        if ((sbits >> k) & 1u) y = short_llr;
+        y = ((cbits >> k) & 1u) ? -y : y;
+        v[k] = ((pbits >> k) & 1u) ? 0.0f : y;                                    // +0.0f whatever the codeword bit is
+    }
+}
+
+__global__ __launch_bounds__(kSimBlock) void sim_channel_awgn_rm(float *__restrict__ llr, long long batch, int n, unsigned Q,
+                                                                 uint32_t k0, uint32_t k1, uint32_t stream_id,
+                                                                 unsigned long long first_frame, float scale, float shift,
+                                                                 const uint8_t *__restrict__ cw,
+                                                                 const uint8_t *__restrict__ punct,
+                                                                 const uint8_t *__restrict__ shrt, float short_llr)
+{
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first quad of the workgroup: uniform
+    const unsigned long long b0 = g0 / Q;
+    const unsigned t = (unsigned)(g0 - b0 * Q) + threadIdx.x;                     // < Q + 256 <= 2^29 + 256
+    const unsigned db = t / Q;
+    const long long b = (long long)b0 + db;
+    const unsigned q = t - db * Q;
+    if (b >= batch) return;
+    const int j0 = (int)(q * 4u);
+    const int cnt = n - j0 < 4 ? n - j0 : 4;
+    unsigned cbits, pbits, sbits;
+    sim_rm_nibbles(j0, cw, punct, shrt, cbits, pbits, sbits);
+    float v[4];
+    sim_rm_quad(first_frame + (unsigned long long)b, q, k0, k1, stream_id, scale, shift, short_llr, cbits, pbits, sbits,
+                (1u << cnt) - 1u, v);
+    sim_store_quad(llr + (size_t)b * (size_t)n + (size_t)j0, v, cnt);
+}
+
+__global__ __launch_bounds__(kSimBlock) void sim_channel_awgn_mix_rm(float *__restrict__ llr, long long batch, int n, unsigned Q,
+                                                                     uint32_t k0, uint32_t k1, uint32_t stream_id,
+                                                                     unsigned long long first_frame, unsigned p0, unsigned K,
+                                                                     unsigned Kinv,
+                                                                     const float *__restrict__ scale_tab,
+                                                                     const float *__restrict__ shift_tab,
+                                                                     const uint8_t *__restrict__ cw,
+                                                                     const uint8_t *__restrict__ punct,
+                                                                     const uint8_t *__restrict__ shrt, float short_llr)
+{
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first quad of the workgroup: uniform
+    const unsigned long long b0 = g0 / Q;
+    const unsigned t = (unsigned)(g0 - b0 * Q) + threadIdx.x;                     // < Q + 256 <= 2^29 + 256
+    const unsigned db = t / Q;
+    const long long b = (long long)b0 + db;
+    const unsigned q = t - db * Q;
+    if (b >= batch) return;
+    const unsigned r = (unsigned)b + p0;
+    unsigned p = r - __umulhi(r, Kinv) * K;                                       // in [0, 2K), as in sim_channel_awgn_mix
+    if (p >= K) p -= K;                                                           // (first_frame + b) mod K
+    const float scale = scale_tab[p], shift = shift_tab[p];
+    const int j0 = (int)(q * 4u);
+    const int cnt = n - j0 < 4 ? n - j0 : 4;
+    unsigned cbits, pbits, sbits;
+    sim_rm_nibbles(j0, cw, punct, shrt, cbits, pbits, sbits);
+    float v[4];
+    sim_rm_quad(first_frame + (unsigned long long)b, q, k0, k1, stream_id, scale, shift, short_llr, cbits, pbits, sbits,
+                (1u << cnt) - 1u, v);
+    sim_store_quad(llr + (size_t)b * (size_t)n + (size_t)j0, v, cnt);
+}
+
 // the raw words of quad i: frame first_frame + i / quads_per_frame, quad i % quads_per_frame (ldpc_debug_philox)
 __global__ __launch_bounds__(kSimBlock) void sim_debug_philox(uint32_t *__restrict__ out, long long count, uint32_t k0,
                                                               uint32_t k1, uint32_t stream_id, unsigned long long first_frame,
@@ -505,6 +602,187 @@ __global__ __launch_bounds__(kSimFoldBlock) void sim_diag_fold(long long *state,
     }
 }
 
+// ------------------------------------------------------------------------------------------ masked counters
+// ldpc_sim_count_rm / _diag_rm with a count mask: wrong = popcount((packed XOR codeword) AND mask) over bits < n, and that
+// number in the place of `wrong` everywhere -- frame errors, the stop rule, undetected errors, the records.  The kernels that
+// read packed rows are restated with the mask; sim_diag_fold reads the per-frame words only and serves both.  Without a mask
+// the entry points launch the plain kernels above, which are left as they are.
+
+__device__ inline int sim_row_wrong_rm(const uint8_t *__restrict__ row, const uint8_t *__restrict__ cw,
+                                       const uint8_t *__restrict__ mask, int rb, int n, int lane)
+{
+    int cnt = 0;
+    for (int off = lane * 4; off < rb; off += 256) {
+        uint32_t w = sim_row_word(row, rb, off);
+        if (cw) w ^= sim_row_word(cw, rb, off);
+        w &= sim_row_word(mask, rb, off);
+        const long long nb = (long long)n - 8ll * off;                 // >= 1: off < rb = ceil(n / 8)
+        if (nb < 32) w &= (1u << nb) - 1u;
+        cnt += __popc(w);
+    }
+    return sim_wave_sum(cnt);
+}
+
+__global__ __launch_bounds__(kSimBlock) void sim_count_frames_rm(long long *state, const uint8_t *__restrict__ packed,
+                                                                 const int *__restrict__ iters, long long B, int n, int rb,
+                                                                 const uint8_t *__restrict__ cw,
+                                                                 const uint8_t *__restrict__ mask, long long max_frames,
+                                                                 long long max_errors)
+{
+    const long long take0 = sim_take0(state, B, max_frames, max_errors);
+    const int lane = threadIdx.x & 63;
+    const long long wave = (long long)blockIdx.x * (kSimBlock / 64) + (threadIdx.x >> 6);
+    const long long stride = (long long)gridDim.x * (kSimBlock / 64) * 64;
+    long long s_ferr = 0, s_wrong = 0, s_it = 0;                       // wave-uniform
+    for (long long base = wave * 64; base < take0; base += stride) {
+        const int rows = take0 - base < 64 ? (int)(take0 - base) : 64;
+        s_it += sim_wave_sum(lane < rows ? iters[base + lane] : 0);
+        for (int k = 0; k < rows; ++k) {
+            const int w = sim_row_wrong_rm(packed + (size_t)(base + k) * (size_t)rb, cw, mask, rb, n, lane);
+            s_wrong += w;
+            s_ferr += w > 0;
+        }
+    }
+    if (lane == 0) {
+        unsigned long long *st = reinterpret_cast<unsigned long long *>(state);
+        if (s_it) atomicAdd(&st[3], (unsigned long long)s_it);
+        if (s_ferr) atomicAdd(&st[6], (unsigned long long)s_ferr);
+        if (s_wrong) atomicAdd(&st[7], (unsigned long long)s_wrong);
+    }
+}
+
+__global__ __launch_bounds__(kSimFoldBlock) void sim_count_fold_rm(long long *state, const uint8_t *__restrict__ packed,
+                                                                   const int *__restrict__ iters, long long B, int n, int rb,
+                                                                   const uint8_t *__restrict__ cw,
+                                                                   const uint8_t *__restrict__ mask, long long max_frames,
+                                                                   long long max_errors)
+{
+    constexpr int kWaves = kSimFoldBlock / 64;
+    __shared__ int sh_cnt[kWaves];
+    __shared__ long long sh_sum[kWaves][4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long long frames0 = state[0], errors0 = state[1], done0 = state[4];
+    const long long take0 = sim_take0(state, B, max_frames, max_errors);
+    const long long e = state[6], w = state[7];
+    long long take = take0, d_ferr = e, d_wrong = w, d_it = 0;
+    if (take0 > 0 && errors0 + e >= max_errors) {        // the error limit falls inside this block: uniform branch
+        const long long need = max_errors - errors0;     // >= 1 (take0 > 0)
+        long long cum = 0;                               // frame errors before this step
+        long long acc[4] = {0, 0, 0, 0};                 // per thread: frames kept; frame errors, wrong bits, iterations taken back
+        for (long long tile = 0; tile < take0; tile += kSimFoldBlock) {
+            const long long wbase = tile + (long long)wv * 64;
+            const int rows = take0 - wbase < 64 ? (take0 - wbase > 0 ? (int)(take0 - wbase) : 0) : 64;
+            int mine = 0;                                // masked wrong bits of frame tile + tid
+            for (int k = 0; k < rows; ++k) {
+                const int c = sim_row_wrong_rm(packed + (size_t)(wbase + k) * (size_t)rb, cw, mask, rb, n, lane);
+                if (lane == k) mine = c;
+            }
+            const bool valid = lane < rows;
+            const int ferr = valid && mine > 0;
+            const unsigned long long bal = __ballot(ferr);
+            const int incl = __popcll(bal & ((2ull << lane) - 1ull));
+            if (lane == 0) sh_cnt[wv] = __popcll(bal);
+            __syncthreads();
+            int before = 0, total = 0;
+            for (int k = 0; k < kWaves; ++k) {
+                before += k < wv ? sh_cnt[k] : 0;
+                total += sh_cnt[k];
+            }
+            __syncthreads();
+            if (valid) {
+                if (cum + before + incl - ferr < need) {  // fewer than `need` frame errors before this frame: it is consumed
+                    acc[0] += 1;
+                } else {
+                    acc[1] += ferr;
+                    acc[2] += mine;
+                    acc[3] += iters[wbase + lane];
+                }
+            }
+            cum += total;
+        }
+        for (int k = 0; k < 4; ++k) {
+            long long v = acc[k];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) sh_sum[wv][k] = v;
+        }
+        __syncthreads();
+        long long tot[4] = {0, 0, 0, 0};
+        for (int k = 0; k < kWaves; ++k)
+            for (int c = 0; c < 4; ++c) tot[c] += sh_sum[k][c];
+        take = tot[0];
+        d_ferr = e - tot[1];
+        d_wrong = w - tot[2];
+        d_it = -tot[3];
+    }
+    __syncthreads();                                     // every thread has read the state
+    if (tid == 0) {
+        const long long frames = frames0 + take, fe = errors0 + d_ferr;
+        state[0] = frames;
+        state[1] = fe;
+        state[2] += d_wrong;
+        state[3] += d_it;
+        state[4] = (done0 != 0 || frames >= max_frames || fe >= max_errors) ? 1 : 0;
+        state[5] += 1;
+        state[6] = 0;
+        state[7] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kSimBlock) void sim_diag_frames_rm(long long *state, long long *diag, int T, int lds_bins,
+                                                                uint32_t *__restrict__ words,
+                                                                const uint8_t *__restrict__ packed,
+                                                                const int *__restrict__ iters,
+                                                                const uint8_t *__restrict__ success, long long B, int n, int rb,
+                                                                const uint8_t *__restrict__ cw,
+                                                                const uint8_t *__restrict__ mask, long long max_frames,
+                                                                long long max_errors)
+{
+    extern __shared__ unsigned sim_hist[];      // lds_bins counters (T + 1, or none)
+    unsigned long long *hist = reinterpret_cast<unsigned long long *>(diag) + 4;
+    for (int t = threadIdx.x; t < lds_bins; t += kSimBlock) sim_hist[t] = 0;
+    __syncthreads();
+    const long long take0 = sim_take0(state, B, max_frames, max_errors);
+    const int lane = threadIdx.x & 63;
+    const long long wave = (long long)blockIdx.x * (kSimBlock / 64) + (threadIdx.x >> 6);
+    const long long stride = (long long)gridDim.x * (kSimBlock / 64) * 64;
+    long long s_ferr = 0, s_wrong = 0, s_und = 0, s_it = 0;      // wave-uniform
+    for (long long base = wave * 64; base < take0; base += stride) {
+        const int rows = take0 - base < 64 ? (int)(take0 - base) : 64;
+        int mine = 0;                           // masked wrong bits of frame base + lane
+        for (int k = 0; k < rows; ++k) {
+            const int w = sim_row_wrong_rm(packed + (size_t)(base + k) * (size_t)rb, cw, mask, rb, n, lane);
+            s_wrong += w;
+            s_ferr += w > 0;
+            if (lane == k) mine = w;
+        }
+        int my_it = 0, und = 0;
+        if (lane < rows) {
+            my_it = iters[base + lane];
+            const unsigned ok = success[base + lane] != 0;
+            und = mine > 0 && ok;
+            words[base + lane] = (uint32_t)mine | (ok << 31);
+            const int bin = sim_clamp_bin(my_it, T);
+            if (lds_bins) atomicAdd(&sim_hist[bin], 1u);
+            else atomicAdd(&hist[bin], 1ull);
+        }
+        s_it += sim_wave_sum(my_it);
+        s_und += __popcll(__ballot(und));
+    }
+    if (lane == 0) {
+        unsigned long long *st = reinterpret_cast<unsigned long long *>(state);
+        if (s_it) atomicAdd(&st[3], (unsigned long long)s_it);
+        if (s_ferr) atomicAdd(&st[6], (unsigned long long)s_ferr);
+        if (s_wrong) atomicAdd(&st[7], (unsigned long long)s_wrong);
+        if (s_und) atomicAdd(reinterpret_cast<unsigned long long *>(diag) + 2, (unsigned long long)s_und);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < lds_bins; t += kSimBlock) {
+        const unsigned c = sim_hist[t];
+        if (c) atomicAdd(&hist[t], (unsigned long long)c);
+    }
+}
+
 }  // namespace ldpc
 
 namespace {
@@ -537,19 +815,69 @@ int sim_channel_mix_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, 
     return LDPC_OK;
 }
 
+// a rate-matching profile is usable: short_llr finite and > 0 wherever something is shortened (NULL: no rate matching)
+int sim_rm_check(const ldpc_rate_match *rm)
+{
+    if (rm && rm->shortened_packed && !(std::isfinite(rm->short_llr) && rm->short_llr > 0.0f))
+        return fail(LDPC_ERR_ARG, "short_llr must be finite and > 0 when shortened_packed is given");
+    return LDPC_OK;
+}
+
+int sim_channel_rm_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                          float scale, float shift, const uint8_t *cw, const ldpc_rate_match *rm, hipStream_t s)
+{
+    if (!rm) return sim_channel_launch(llr, batch, n, seed, stream_id, first_frame, scale, shift, cw, s);
+    const unsigned Q = ((unsigned)n + 3u) / 4u;
+    const unsigned long long quads = (unsigned long long)batch * Q;
+    const unsigned long long blocks = (quads + kSimBlock - 1) / kSimBlock;
+    if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+    hipLaunchKernelGGL(sim_channel_awgn_rm, dim3((unsigned)blocks), dim3(kSimBlock), 0, s, llr, (long long)batch, (int)n, Q,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, (unsigned long long)first_frame, scale, shift, cw,
+                       rm->punctured_packed, rm->shortened_packed, rm->shortened_packed ? rm->short_llr : 0.0f);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+int sim_channel_mix_rm_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                              const float *scale_tab, const float *shift_tab, int32_t n_points, const uint8_t *cw,
+                              const ldpc_rate_match *rm, hipStream_t s)
+{
+    if (!rm) return sim_channel_mix_launch(llr, batch, n, seed, stream_id, first_frame, scale_tab, shift_tab, n_points, cw, s);
+    const unsigned Q = ((unsigned)n + 3u) / 4u;
+    const unsigned long long quads = (unsigned long long)batch * Q;
+    const unsigned long long blocks = (quads + kSimBlock - 1) / kSimBlock;
+    if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+    const unsigned K = (unsigned)n_points;
+    hipLaunchKernelGGL(sim_channel_awgn_mix_rm, dim3((unsigned)blocks), dim3(kSimBlock), 0, s, llr, (long long)batch, (int)n, Q,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, (unsigned long long)first_frame,
+                       (unsigned)(first_frame % K), K, 0xffffffffu / K, scale_tab, shift_tab, cw, rm->punctured_packed,
+                       rm->shortened_packed, rm->shortened_packed ? rm->short_llr : 0.0f);
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+// mask: the count mask of a rate-matching profile, or NULL for the plain kernels
 int sim_count_launch(int64_t *state, const uint8_t *packed, const int32_t *iters, int64_t batch, int32_t n,
-                     const uint8_t *cw, int64_t max_frames, int64_t max_errors, hipStream_t s)
+                     const uint8_t *cw, int64_t max_frames, int64_t max_errors, hipStream_t s, const uint8_t *mask = nullptr)
 {
     const int rb = (int)(((int64_t)n + 7) / 8);
-    if (batch > 0) {
-        const long long groups = (batch + kSimBlock - 1) / kSimBlock;        // 64 frames per wave and pass
-        hipLaunchKernelGGL(sim_count_frames, dim3((unsigned)std::min<long long>(groups, 2048)), dim3(kSimBlock), 0, s,
-                           (long long *)state, packed, iters, (long long)batch, (int)n, rb, cw, (long long)max_frames,
-                           (long long)max_errors);
+    const long long groups = (batch + kSimBlock - 1) / kSimBlock;            // 64 frames per wave and pass
+    const dim3 grid((unsigned)std::min<long long>(groups, 2048));
+    if (batch > 0 && mask) {
+        hipLaunchKernelGGL(sim_count_frames_rm, grid, dim3(kSimBlock), 0, s, (long long *)state, packed, iters,
+                           (long long)batch, (int)n, rb, cw, mask, (long long)max_frames, (long long)max_errors);
+        HIP_TRY(hipGetLastError());
+    } else if (batch > 0) {
+        hipLaunchKernelGGL(sim_count_frames, grid, dim3(kSimBlock), 0, s, (long long *)state, packed, iters,
+                           (long long)batch, (int)n, rb, cw, (long long)max_frames, (long long)max_errors);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(sim_count_fold, dim3(1), dim3(kSimFoldBlock), 0, s, (long long *)state, packed, iters, (long long)batch,
-                       (int)n, rb, cw, (long long)max_frames, (long long)max_errors);
+    if (batch > 0 && mask)
+        hipLaunchKernelGGL(sim_count_fold_rm, dim3(1), dim3(kSimFoldBlock), 0, s, (long long *)state, packed, iters,
+                           (long long)batch, (int)n, rb, cw, mask, (long long)max_frames, (long long)max_errors);
+    else                                                 // an empty block reads no row: the plain fold latches `done`
+        hipLaunchKernelGGL(sim_count_fold, dim3(1), dim3(kSimFoldBlock), 0, s, (long long *)state, packed, iters,
+                           (long long)batch, (int)n, rb, cw, (long long)max_frames, (long long)max_errors);
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
@@ -564,16 +892,23 @@ size_t sim_diag_scratch_bytes(int64_t batch) { return batch > 0 ? align_up((size
 
 int sim_count_diag_launch(int64_t *state, int64_t *diag, int32_t T, int64_t capture, const uint8_t *packed, const int32_t *iters,
                           const uint8_t *success, int64_t batch, int32_t n, const uint8_t *cw, uint64_t first_frame,
-                          int64_t max_frames, int64_t max_errors, uint32_t *words, hipStream_t s)
+                          int64_t max_frames, int64_t max_errors, uint32_t *words, hipStream_t s,
+                          const uint8_t *mask = nullptr)
 {
     if (batch == 0)                                      // nothing to bin or record: the plain fold moves the state alone
         return sim_count_launch(state, packed, iters, 0, n, cw, max_frames, max_errors, s);
     const int rb = (int)(((int64_t)n + 7) / 8);
     const int lds_bins = (int64_t)T + 1 <= kSimDiagLdsBins ? T + 1 : 0;
     const long long groups = (batch + kSimBlock - 1) / kSimBlock;            // 64 frames per wave and pass
-    hipLaunchKernelGGL(sim_diag_frames, dim3((unsigned)std::min<long long>(groups, 2048)), dim3(kSimBlock),
-                       (size_t)lds_bins * sizeof(unsigned), s, (long long *)state, (long long *)diag, (int)T, lds_bins, words,
-                       packed, iters, success, (long long)batch, (int)n, rb, cw, (long long)max_frames, (long long)max_errors);
+    const dim3 grid((unsigned)std::min<long long>(groups, 2048));
+    if (mask)
+        hipLaunchKernelGGL(sim_diag_frames_rm, grid, dim3(kSimBlock), (size_t)lds_bins * sizeof(unsigned), s, (long long *)state,
+                           (long long *)diag, (int)T, lds_bins, words, packed, iters, success, (long long)batch, (int)n, rb, cw,
+                           mask, (long long)max_frames, (long long)max_errors);
+    else
+        hipLaunchKernelGGL(sim_diag_frames, grid, dim3(kSimBlock), (size_t)lds_bins * sizeof(unsigned), s, (long long *)state,
+                           (long long *)diag, (int)T, lds_bins, words, packed, iters, success, (long long)batch, (int)n, rb, cw,
+                           (long long)max_frames, (long long)max_errors);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sim_diag_fold, dim3(1), dim3(kSimFoldBlock), 0, s, (long long *)state, (long long *)diag, (int)T,
                        (long long)capture, (const uint32_t *)words, iters, (long long)batch, (unsigned long long)first_frame,
@@ -623,14 +958,17 @@ struct PinnedState {
     }
 };
 
-// the host loop of ldpc_simulate (capture < 0, out_diag unused) and of ldpc_simulate_diag (capture >= 0)
-int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t capture, int64_t out_state[8], int64_t *out_diag,
-                  void *workspace, size_t workspace_bytes, void *stream)
+// the host loop of ldpc_simulate (capture < 0, out_diag unused) and of ldpc_simulate_diag (capture >= 0); rm: the profile of
+// the _rm forms, NULL for the plain ones -- which then launch exactly what they launched before the profile existed
+int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_rate_match *rm, int64_t capture,
+                  int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream)
 {
     const bool diagnostics = capture >= 0;
     if (!d || !desc || !out_state) return fail(LDPC_ERR_ARG, "NULL decoder / descriptor / out_state");
     if (diagnostics && !out_diag) return fail(LDPC_ERR_ARG, "NULL out_diag");
     if (diagnostics && sim_diag_words(d->T, capture) == 0) return fail(LDPC_ERR_ARG, "capture too large");
+    if (int rc = sim_rm_check(rm)) return rc;
+    const uint8_t *mask = rm ? rm->count_packed : nullptr;
     if (desc->block < 1) return fail(LDPC_ERR_ARG, "block < 1");
     if (desc->poll_blocks < 1) return fail(LDPC_ERR_ARG, "poll_blocks < 1");
     if (d->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "ldpc_simulate draws fp32 LLRs: float64 decoders are not supported");
@@ -657,16 +995,18 @@ int simulate_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t capt
     auto count = [&](int64_t frames, int64_t first) {    // fold one decoded block (frames = 0: latch `done`)
         if (diagnostics)
             return sim_count_diag_launch(state, diag, d->T, capture, packed, iters, success, frames, n, desc->codeword_packed,
-                                         desc->first_frame + (uint64_t)first, desc->max_frames, desc->max_errors, words, s);
-        return sim_count_launch(state, packed, iters, frames, n, desc->codeword_packed, desc->max_frames, desc->max_errors, s);
+                                         desc->first_frame + (uint64_t)first, desc->max_frames, desc->max_errors, words, s,
+                                         mask);
+        return sim_count_launch(state, packed, iters, frames, n, desc->codeword_packed, desc->max_frames, desc->max_errors, s,
+                                mask);
     };
     int64_t drawn = 0;                                   // frames drawn so far: block k starts at first_frame + k * block
     for (;;) {
         int queued = 0;
         for (int p = 0; p < desc->poll_blocks && drawn < desc->max_frames; ++p, ++queued) {
             const int64_t frames = std::min<int64_t>(desc->block, desc->max_frames - drawn);
-            if (int rc = sim_channel_launch(llr, frames, n, desc->seed, desc->stream_id, desc->first_frame + (uint64_t)drawn,
-                                            desc->scale, desc->shift, desc->codeword_packed, s))
+            if (int rc = sim_channel_rm_launch(llr, frames, n, desc->seed, desc->stream_id, desc->first_frame + (uint64_t)drawn,
+                                               desc->scale, desc->shift, desc->codeword_packed, rm, s))
                 return rc;
             if (int rc = ldpc_decode(d, llr, frames, 1, nullptr, nullptr, iters, success, packed, base + w.o_dec, w.dec_bytes, s))
                 return rc;
@@ -745,7 +1085,7 @@ size_t ldpc_simulate_workspace_bytes(const ldpc_decoder *d, int64_t block)
 int ldpc_simulate(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t out_state[8], void *workspace,
                   size_t workspace_bytes, void *stream)
 {
-    LDPC_NOTHROW(simulate_impl(d, desc, -1, out_state, nullptr, workspace, workspace_bytes, stream))
+    LDPC_NOTHROW(simulate_impl(d, desc, nullptr, -1, out_state, nullptr, workspace, workspace_bytes, stream))
 }
 
 size_t ldpc_sim_diag_words(int32_t T, int64_t capture) { return sim_diag_words(T, capture); }
@@ -784,7 +1124,93 @@ int ldpc_simulate_diag(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t
                        int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (capture < 0) return fail(LDPC_ERR_ARG, "capture < 0");
-    LDPC_NOTHROW(simulate_impl(d, desc, capture, out_state, out_diag, workspace, workspace_bytes, stream))
+    LDPC_NOTHROW(simulate_impl(d, desc, nullptr, capture, out_state, out_diag, workspace, workspace_bytes, stream))
+}
+
+// ---- rate matching: each entry point above with a profile (NULL: the plain call, the very same kernels)
+int ldpc_channel_awgn_rm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         float scale, float shift, const uint8_t *codeword_packed, const ldpc_rate_match *rm, void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = sim_rm_check(rm)) return rc;
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    return sim_channel_rm_launch((float *)llr, batch, n, seed, stream_id, first_frame, scale, shift, codeword_packed, rm,
+                                 (hipStream_t)stream);
+}
+
+int ldpc_channel_awgn_mix_rm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                             const float *scale_tab, const float *shift_tab, int32_t n_points, const uint8_t *codeword_packed,
+                             const ldpc_rate_match *rm, void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (batch > INT32_MAX) return fail(LDPC_ERR_ARG, "batch > 2^31 - 1");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (n_points < 1 || n_points > 4096) return fail(LDPC_ERR_ARG, "n_points must be in 1 .. 4096");
+    if (batch > 0 && first_frame > (uint64_t)0 - (uint64_t)batch)       // 2^64 - batch: p is not continuous across the wrap
+        return fail(LDPC_ERR_ARG, "first_frame + batch wraps the 64-bit frame index");
+    if (int rc = sim_rm_check(rm)) return rc;
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    if (!scale_tab || !shift_tab) return fail(LDPC_ERR_ARG, "NULL scale_tab / shift_tab");
+    if (((uintptr_t)scale_tab % sizeof(float)) != 0 || ((uintptr_t)shift_tab % sizeof(float)) != 0)
+        return fail(LDPC_ERR_ARG, "scale_tab / shift_tab must be 4-byte aligned");
+    return sim_channel_mix_rm_launch((float *)llr, batch, n, seed, stream_id, first_frame, scale_tab, shift_tab, n_points,
+                                     codeword_packed, rm, (hipStream_t)stream);
+}
+
+int ldpc_sim_count_rm(int64_t *state, const uint8_t *packed_bits, const int32_t *iterations, int64_t batch, int32_t n,
+                      const uint8_t *codeword_packed, int64_t max_frames, int64_t max_errors, const ldpc_rate_match *rm,
+                      void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = sim_rm_check(rm)) return rc;
+    if (!state) return fail(LDPC_ERR_ARG, "NULL state");
+    if (((uintptr_t)state % sizeof(int64_t)) != 0) return fail(LDPC_ERR_ARG, "state must be 8-byte aligned");
+    if (batch > 0 && (!packed_bits || !iterations)) return fail(LDPC_ERR_ARG, "NULL packed_bits / iterations");
+    return sim_count_launch(state, packed_bits, iterations, batch, n, codeword_packed, max_frames, max_errors,
+                            (hipStream_t)stream, rm ? rm->count_packed : nullptr);
+}
+
+int ldpc_sim_count_diag_rm(int64_t *state, int64_t *diag, int32_t T, int64_t capture, const uint8_t *packed_bits,
+                           const int32_t *iterations, const uint8_t *success, int64_t batch, int32_t n,
+                           const uint8_t *codeword_packed, uint64_t block_first_frame, int64_t max_frames, int64_t max_errors,
+                           void *scratch, size_t scratch_bytes, const ldpc_rate_match *rm, void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (T < 0) return fail(LDPC_ERR_ARG, "T < 0");
+    if (capture < 0) return fail(LDPC_ERR_ARG, "capture < 0");
+    if (sim_diag_words(T, capture) == 0) return fail(LDPC_ERR_ARG, "capture too large");
+    if (int rc = sim_rm_check(rm)) return rc;
+    if (!state) return fail(LDPC_ERR_ARG, "NULL state");
+    if (((uintptr_t)state % sizeof(int64_t)) != 0) return fail(LDPC_ERR_ARG, "state must be 8-byte aligned");
+    if (((uintptr_t)diag % sizeof(int64_t)) != 0) return fail(LDPC_ERR_ARG, "diag must be 8-byte aligned");
+    if (batch > 0 && (!packed_bits || !iterations || !success)) return fail(LDPC_ERR_ARG, "NULL packed_bits / iterations / success");
+    if (batch > 0 && (!diag || !scratch)) return fail(LDPC_ERR_ARG, "NULL diag / scratch");
+    if (((uintptr_t)scratch % sizeof(uint32_t)) != 0) return fail(LDPC_ERR_ARG, "scratch must be 4-byte aligned");
+    if (scratch_bytes < sim_diag_scratch_bytes(batch))
+        return fail(LDPC_ERR_WORKSPACE, "scratch %zu < required %zu", scratch_bytes, sim_diag_scratch_bytes(batch));
+    return sim_count_diag_launch(state, diag, T, capture, packed_bits, iterations, success, batch, n, codeword_packed,
+                                 block_first_frame, max_frames, max_errors, (uint32_t *)scratch, (hipStream_t)stream,
+                                 rm ? rm->count_packed : nullptr);
+}
+
+int ldpc_simulate_rm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_rate_match *rm, int64_t out_state[8],
+                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    LDPC_NOTHROW(simulate_impl(d, desc, rm, -1, out_state, nullptr, workspace, workspace_bytes, stream))
+}
+
+int ldpc_simulate_diag_rm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_rate_match *rm, int64_t capture,
+                          int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (capture < 0) return fail(LDPC_ERR_ARG, "capture < 0");
+    LDPC_NOTHROW(simulate_impl(d, desc, rm, capture, out_state, out_diag, workspace, workspace_bytes, stream))
 }
 
 int ldpc_debug_philox(uint32_t *out4, int64_t count, uint64_t seed, uint32_t stream_id, uint64_t first_frame,

@@ -78,12 +78,27 @@ def _channel_codeword(codeword, n: int, dev: torch.device) -> Optional[torch.Ten
     return cw
 
 
+def _profile(rate_matching, n: int, dev: torch.device):
+    """(struct, ctypes argument) of a RateMatching for the _rm entry points on `dev`; (None, None) without one.  The struct
+    is returned so that it outlives the call."""
+    if rate_matching is None:
+        return None, None
+    from rate_matching import RateMatching
+    if not isinstance(rate_matching, RateMatching) or rate_matching.n != n:
+        raise ValueError(f"rate_matching must be a RateMatching of n = {n}")
+    rm = rate_matching.native(dev)
+    return rm, C.byref(rm)
+
+
 def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, snr_db: Optional[float] = None,
-             scale: Optional[float] = None, shift: Optional[float] = None, codeword=None, device=None) -> torch.Tensor:
+             scale: Optional[float] = None, shift: Optional[float] = None, codeword=None, device=None,
+             rate_matching=None) -> torch.Tensor:
     """LLRs [batch, n] fp32 of frames first_frame .. first_frame + batch - 1 of the counter-based BI-AWGN stream
     (ldpc_channel_awgn; the stream is defined in include/ldpc_hip.h and INTEGRATION.md): frame f gets the same noise whatever
     block it is drawn in.  Give snr_db (Es/N0, positive-mean LLRs for the all-zero codeword) or (scale, shift) = (2/sigma,
-    2/sigma^2).  codeword: 0/1 array of length n, or an already packed uint8 tensor on the device; None: all zero."""
+    2/sigma^2).  codeword: 0/1 array of length n, or an already packed uint8 tensor on the device; None: all zero.
+    rate_matching: a RateMatching of this n (ldpc_channel_awgn_rm): +0.0 at its punctured bits, +-short_llr at its shortened
+    bits, the plain draw bit for bit everywhere else."""
     dev = _require_gpu(device)
     if (snr_db is None) == (scale is None or shift is None):
         raise ValueError("give either snr_db or both scale and shift")
@@ -93,14 +108,17 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
     if batch < 0 or n < 1:
         raise ValueError("batch must be >= 0 and n >= 1")
     cw = _channel_codeword(codeword, n, dev)
+    rm, rm_arg = _profile(rate_matching, n, dev)
     lib = nat.load()
     out = torch.empty((batch, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(lib.ldpc_channel_awgn(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
-                                        int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), float(scale),
-                                        float(shift), None if cw is None else C.c_void_p(cw.data_ptr()),
-                                        C.c_void_p(stream)), "ldpc_channel_awgn")
+        args = (C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
+                int(first_frame) & (2 ** 64 - 1), float(scale), float(shift), None if cw is None else C.c_void_p(cw.data_ptr()))
+        if rm is None:
+            nat.check(lib.ldpc_channel_awgn(*args, C.c_void_p(stream)), "ldpc_channel_awgn")
+        else:
+            nat.check(lib.ldpc_channel_awgn_rm(*args, rm_arg, C.c_void_p(stream)), "ldpc_channel_awgn_rm")
     return out
 
 
@@ -152,12 +170,14 @@ def awgn_mix_tables(snr_db, llr_convention: str = "decoder", device=None):
 
 
 def awgn_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, snr_db=None, scale=None,
-                 shift=None, llr_convention: str = "decoder", codeword=None, device=None) -> torch.Tensor:
+                 shift=None, llr_convention: str = "decoder", codeword=None, device=None,
+                 rate_matching=None) -> torch.Tensor:
     """``awgn_llr`` with the SNR point a function of the frame (ldpc_channel_awgn_mix): frame f = first_frame + b is drawn at
     point f % K of a table of K points -- the same noise as ``awgn_llr`` gives frame f, and the same point whatever block the
     frame is drawn in, so every run of K consecutive frames holds each point once.  Give snr_db, a sequence of K values of
     Es/N0 (tables through ``awgn_scale_shift(snr, llr_convention)`` per point in double, then fp32), or scale and shift: two
-    1-D sequences, or float32 tensors on the device, of equal length.  codeword as in ``awgn_llr``."""
+    1-D sequences, or float32 tensors on the device, of equal length.  codeword and rate_matching as in ``awgn_llr``
+    (ldpc_channel_awgn_mix_rm with a profile)."""
     dev = _require_gpu(device)
     if (snr_db is None) == (scale is None or shift is None):
         raise ValueError("give either snr_db or both scale and shift")
@@ -178,15 +198,18 @@ def awgn_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_fra
     if batch > 2 ** 31 - 1:
         raise ValueError("batch must be <= 2^31 - 1")
     cw = _channel_codeword(codeword, n, dev)
+    rm, rm_arg = _profile(rate_matching, n, dev)
     lib = nat.load()
     out = torch.empty((batch, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(lib.ldpc_channel_awgn_mix(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
-                                            int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1),
-                                            C.c_void_p(scale_tab.data_ptr()), C.c_void_p(shift_tab.data_ptr()), n_points,
-                                            None if cw is None else C.c_void_p(cw.data_ptr()), C.c_void_p(stream)),
-                  "ldpc_channel_awgn_mix")
+        args = (C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
+                int(first_frame) & (2 ** 64 - 1), C.c_void_p(scale_tab.data_ptr()), C.c_void_p(shift_tab.data_ptr()), n_points,
+                None if cw is None else C.c_void_p(cw.data_ptr()))
+        if rm is None:
+            nat.check(lib.ldpc_channel_awgn_mix(*args, C.c_void_p(stream)), "ldpc_channel_awgn_mix")
+        else:
+            nat.check(lib.ldpc_channel_awgn_mix_rm(*args, rm_arg, C.c_void_p(stream)), "ldpc_channel_awgn_mix_rm")
     return out
 
 
@@ -541,14 +564,17 @@ class DecodeEngine:
 
     def sim_count(self, state: torch.Tensor, packed_bits: torch.Tensor, iterations: torch.Tensor, *, max_frames: int,
                   max_errors: int, codeword=None, success: Optional[torch.Tensor] = None,
-                  diag: Optional[torch.Tensor] = None, first_frame: int = 0, capture: int = 0) -> torch.Tensor:
+                  diag: Optional[torch.Tensor] = None, first_frame: int = 0, capture: int = 0,
+                  rate_matching=None) -> torch.Tensor:
         """Fold one decoded block into `state` (int64 [8] on this engine's GPU, zeroed by the caller to start a point:
         frames, frame_errors, bit_errors, iterations, done, blocks_seen, 0, 0) with the reference's in-order stop rule
         (ldpc_sim_count).  packed_bits uint8 [B, ceil(n/8)] and iterations int32 [B] as decode(want_packed=True) returns
         them.  With `diag` (sim_diag_buffer(capture), kept over the blocks of a point) the diagnostics of the consumed frames
         are kept too (ldpc_sim_count_diag; parse_sim_diag unpacks them): `success` [B] as decode returns it, `first_frame` the
-        stream index of the block's first frame.  Asynchronous; returns `state`."""
+        stream index of the block's first frame.  With rate_matching the counters look at its count mask only
+        (ldpc_sim_count_rm / _diag_rm).  Asynchronous; returns `state`."""
         n = self.graph.n
+        rm, rm_arg = _profile(rate_matching, n, self.device)
         if state.dtype != torch.int64 or state.shape != (8,) or state.device != self.device or not state.is_contiguous():
             raise ValueError("state must be a contiguous int64 tensor of 8 words on the engine's device")
         B = int(packed_bits.shape[0]) if packed_bits.dim() == 2 else -1
@@ -564,8 +590,11 @@ class DecodeEngine:
                 raise ValueError("success and capture belong to the diagnostic counters: give diag (sim_diag_buffer)")
             with torch.cuda.device(self.device):
                 stream = torch.cuda.current_stream(self.device).cuda_stream
-                nat.check(self._lib.ldpc_sim_count(p(state), p(packed_bits), p(iterations), B, n, p(cw), int(max_frames),
-                                                   int(max_errors), C.c_void_p(stream)), "ldpc_sim_count")
+                args = (p(state), p(packed_bits), p(iterations), B, n, p(cw), int(max_frames), int(max_errors))
+                if rm is None:
+                    nat.check(self._lib.ldpc_sim_count(*args, C.c_void_p(stream)), "ldpc_sim_count")
+                else:
+                    nat.check(self._lib.ldpc_sim_count_rm(*args, rm_arg, C.c_void_p(stream)), "ldpc_sim_count_rm")
             return state
         capture = int(capture)
         if capture < 0:
@@ -581,28 +610,32 @@ class DecodeEngine:
         with torch.cuda.device(self.device):
             scratch = torch.empty(max(need, 4), dtype=torch.uint8, device=self.device)   # stream-ordered by the allocator
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(self._lib.ldpc_sim_count_diag(p(state), p(diag), int(self.iters), capture, p(packed_bits), p(iterations),
-                                                    p(success), B, n, p(cw), int(first_frame) & (2 ** 64 - 1), int(max_frames),
-                                                    int(max_errors), p(scratch), scratch.numel(), C.c_void_p(stream)),
-                      "ldpc_sim_count_diag")
+            args = (p(state), p(diag), int(self.iters), capture, p(packed_bits), p(iterations), p(success), B, n, p(cw),
+                    int(first_frame) & (2 ** 64 - 1), int(max_frames), int(max_errors), p(scratch), scratch.numel())
+            if rm is None:
+                nat.check(self._lib.ldpc_sim_count_diag(*args, C.c_void_p(stream)), "ldpc_sim_count_diag")
+            else:
+                nat.check(self._lib.ldpc_sim_count_diag_rm(*args, rm_arg, C.c_void_p(stream)), "ldpc_sim_count_diag_rm")
         return state
 
     def simulate(self, *, seed: int, max_frames: int, max_errors: int, stream_id: int = 0, first_frame: int = 0,
                  snr_db: Optional[float] = None, scale: Optional[float] = None, shift: Optional[float] = None,
                  codeword=None, block: int = 65536, poll_blocks: int = 4, diagnostics: bool = False,
-                 capture: int = 0) -> dict:
+                 capture: int = 0, rate_matching=None) -> dict:
         """One SNR point on the device (ldpc_simulate): blocks of `block` frames of the counter-based AWGN stream, early-stop
         decode, in-order error counters, one host round trip every `poll_blocks` blocks.  -> {frames, frame_errors,
         bit_errors, iterations, done, blocks_seen}; all but blocks_seen are independent of block and poll_blocks.
         With diagnostics (ldpc_simulate_diag) also undetected_errors (the decisions satisfy H and are not the codeword),
         detected_errors, iteration_histogram (np.int64 [T + 1] over the consumed frames), captured and error_frames: the
         first `capture` frame errors as a structured array (frame, wrong_bits, iterations, undetected) -- awgn_llr(1, n,
-        first_frame=frame, ...) draws such a frame again.  Synchronous."""
+        first_frame=frame, ...) draws such a frame again.  rate_matching: the profile on the channel and the counters
+        (ldpc_simulate_rm / _diag_rm).  Synchronous."""
         if (snr_db is None) == (scale is None or shift is None):
             raise ValueError("give either snr_db or both scale and shift")
         if snr_db is not None:
             scale, shift = awgn_scale_shift(snr_db)
         cw = self._packed_codeword(codeword)
+        rm, rm_arg = _profile(rate_matching, self.graph.n, self.device)
         desc = nat.SimDesc()
         desc.seed, desc.stream_id = int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1)
         desc.first_frame = int(first_frame) & (2 ** 64 - 1)
@@ -625,7 +658,13 @@ class DecodeEngine:
             self._sim_ws = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            if diagnostics:
+            tail = (C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream))
+            if rm is not None and diagnostics:
+                nat.check(self._lib.ldpc_simulate_diag_rm(self.handle, C.byref(desc), rm_arg, capture, nat.ptr(out),
+                                                          nat.ptr(words), *tail), "ldpc_simulate_diag_rm")
+            elif rm is not None:
+                nat.check(self._lib.ldpc_simulate_rm(self.handle, C.byref(desc), rm_arg, nat.ptr(out), *tail), "ldpc_simulate_rm")
+            elif diagnostics:
                 nat.check(self._lib.ldpc_simulate_diag(self.handle, C.byref(desc), capture, nat.ptr(out), nat.ptr(words),
                                                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)),
                           "ldpc_simulate_diag")

@@ -30,6 +30,8 @@ Channel (``SimulationConfig.channel``):
             bin the stop iterations and record the stream index of the first ``capture_errors`` frame errors of every point
             (``SimulationResult.undetected_errors`` / ``iteration_histograms`` / ``error_frames``);
             ``LDPSimulator.replay_errors`` draws and decodes recorded frames again.
+            ``SimulationConfig.rate_matching`` (this channel only) punctures and shortens bits on the channel and restricts
+            the error counters to its count mask; the bit error rate is then per counted bit.
 """
 
 from __future__ import annotations
@@ -39,6 +41,7 @@ import logging
 import os
 import threading
 import time
+import warnings
 from concurrent.futures import ThreadPoolExecutor, as_completed
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Tuple, Union
@@ -49,6 +52,7 @@ import torch
 from ldpc_decoder import BasicMinSumDecoder, LDPCCode
 from neural_2d_decoder import Neural2DMinSumDecoder, Neural2DOffsetMinSumDecoder
 from neural_minsum_decoder import NeuralMinSumDecoder, NeuralOffsetMinSumDecoder
+from rate_matching import RateMatching
 from rcq_decoder import RCQMinSumDecoder, WeightedRCQDecoder
 
 logger = logging.getLogger(__name__)
@@ -77,8 +81,14 @@ class SimulationConfig:
     poll_blocks: int = 4                    # channel="device", resident engine: blocks between two looks at the counters
     diagnostics: bool = False               # channel="device": undetected errors, stop-iteration histogram, failing frames
     capture_errors: int = 0                 # ... record the first so many frame errors of every point (implies diagnostics)
+    rate_matching: Optional[RateMatching] = None   # channel="device": punctured / shortened bits and the counters' mask
 
     def __post_init__(self):
+        if self.rate_matching is not None:
+            if not isinstance(self.rate_matching, RateMatching):
+                raise ValueError("rate_matching must be a rate_matching.RateMatching")
+            if self.channel != "device":
+                raise ValueError("rate_matching needs channel='device'")
         if self.channel not in ("torch", "device"):
             raise ValueError(f"channel must be 'torch' or 'device', got {self.channel!r}")
         if self.codeword is not None and self.channel != "device":
@@ -237,6 +247,7 @@ class LDPSimulator:
         self.config = config
         self.results: Dict[str, SimulationResult] = {}
         self._last = threading.local()          # diagnostics of the calling thread's last point (simulate_decoder collects them)
+        self._warned_punctured_zero = False     # the all-zero-codeword warning is issued once per simulator
         if config.save_results:
             os.makedirs(config.results_dir, exist_ok=True)
 
@@ -259,12 +270,21 @@ class LDPSimulator:
         eng = _engine_of(decoder, device)
         self._last.diagnostics = None
         if self.config.channel == "device":
+            rm = self.config.rate_matching
+            if rm is not None and rm.n != code.n:
+                raise ValueError(f"rate_matching is a profile of n = {rm.n}, the code has n = {code.n}")
+            if rm is not None and rm.n_punctured and self.config.codeword is None and not self._warned_punctured_zero:
+                self._warned_punctured_zero = True
+                warnings.warn("punctured bits with the all-zero codeword: a punctured bit that is never recovered keeps posterior "
+                              "0, decides 0 and counts as correct -- send a nonzero codeword (SimulationConfig.codeword, e.g. "
+                              "codes.staircase_encode)", UserWarning, stacklevel=2)
             c = self._simulate_device(eng, code.n, float(snr_db), int(max_frames), int(max_errors))
             if "iteration_histogram" in c:
                 self._last.diagnostics = c
             frames = c["frames"]
+            counted = code.n if rm is None else rm.n_counted
             return (c["frame_errors"] / frames if frames > 0 else 0.0,
-                    c["bit_errors"] / (frames * code.n) if frames > 0 else 0.0,
+                    c["bit_errors"] / (frames * counted) if frames > 0 and counted > 0 else 0.0,
                     c["iterations"] / frames if frames > 0 else 0.0, time.time() - start_time, frames, c["frame_errors"])
         gen = torch.Generator(device=device)
         gen.manual_seed(int(self.config.seed) * 1_000_003 + int(round(snr_db * 1000)))
@@ -301,24 +321,27 @@ class LDPSimulator:
         stream_id = int(round(snr_db * 1000)) % (1 << 32)
         block = max(1, int(cfg.batch_frames))
         cw = None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, n, eng.device)
+        rm = cfg.rate_matching
         if eng.info()["engine"] == "resident":
             return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, scale=scale, shift=shift, codeword=cw,
                                 max_frames=max_frames, max_errors=max_errors, block=block,
-                                poll_blocks=max(1, int(cfg.poll_blocks)), diagnostics=diagnostics, capture=capture)
+                                poll_blocks=max(1, int(cfg.poll_blocks)), diagnostics=diagnostics, capture=capture,
+                                rate_matching=rm)
         state = torch.zeros(8, dtype=torch.int64, device=eng.device)
         diag = eng.sim_diag_buffer(capture) if diagnostics else None
         drawn, cap, host = 0, None, [0] * 8
         while drawn < max_frames and not host[4]:
             frames = min(block, max_frames - drawn)
             llr = _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn, scale=scale,
-                                   shift=shift, codeword=cw, device=eng.device)
+                                   shift=shift, codeword=cw, device=eng.device, rate_matching=rm)
             if diagnostics:
                 packed, iters, success = _decode_block_flags(eng, llr, cap)
                 eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw,
-                              success=success, diag=diag, first_frame=drawn, capture=capture)
+                              success=success, diag=diag, first_frame=drawn, capture=capture, rate_matching=rm)
             else:
                 packed, iters = _decode_block(eng, llr, cap)
-                eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw)
+                eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw,
+                              rate_matching=rm)
             cap = _next_cap(eng, iters, int(cfg.stage_min_block)) if cfg.staged_early_stop else None
             host = state.tolist()                                               # the one read of the block
             drawn += frames
@@ -330,7 +353,7 @@ class LDPSimulator:
 
     def replay_errors(self, decoder, code: LDPCCode, snr_db: float, frames) -> dict:
         """Draw the listed frames of the point at `snr_db` again -- stream indices, e.g. error_frames["frame"] of a run with
-        this configuration (same seed, convention and codeword; channel="device") -- and decode them with early stop.
+        this configuration (same seed, convention, codeword and rate_matching; channel="device") -- and decode them with early stop.
         -> {frames, llr [F, n], bits int32 [F, n], posterior [F, n], iterations int32 [F], success bool [F]} on the device.
         A frame has the same noise whatever block it was drawn in, so this reproduces the recorded failure exactly."""
         import engine as _engine
@@ -343,7 +366,7 @@ class LDPSimulator:
         cw = None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, code.n, eng.device)
         frames = [int(f) for f in np.asarray(frames).reshape(-1)]
         rows = [_engine.awgn_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, scale=scale, shift=shift,
-                                 codeword=cw, device=eng.device) for f in frames]
+                                 codeword=cw, device=eng.device, rate_matching=cfg.rate_matching) for f in frames]
         llr = torch.cat(rows, dim=0) if rows else torch.empty((0, code.n), dtype=torch.float32, device=eng.device)
         with torch.no_grad():
             res = eng.decode(llr, early_stop=True)

@@ -132,10 +132,17 @@ def _plot_series(panels, figsize, save_path):
 class PosteriorJointTrainer:
     """Adam on the BCE of the posterior the decoder returns (default), or -- config.joint_posterior_loss -- on the
     weighted sum of every iteration's posterior BCE with the paper's posterior-local gradient; then the history also
-    holds each epoch's per-iteration training losses (`train_iteration_losses`, one [T] list per epoch)."""
+    holds each epoch's per-iteration training losses (`train_iteration_losses`, one [T] list per epoch).
+    rate_matching (keyword only, a rate_matching.RateMatching): the profile `train_stream` draws its training and validation
+    frames through -- punctured bits enter the decoder as +0.0, shortened ones as +short_llr; `train` does not use it."""
 
-    def __init__(self, model: nn.Module, config: TrainingConfig):
+    def __init__(self, model: nn.Module, config: TrainingConfig, *, rate_matching=None):
         self.model, self.config = model, config
+        if rate_matching is not None:
+            from rate_matching import RateMatching
+            if not isinstance(rate_matching, RateMatching):
+                raise ValueError("rate_matching must be a rate_matching.RateMatching")
+        self.rate_matching = rate_matching
         self.device = torch.device(config.device)
         self.model.to(self.device)
         self.optimizer = optim.Adam(self.model.parameters(), lr=config.learning_rate)
@@ -269,7 +276,8 @@ class PosteriorJointTrainer:
         config.snr_step), so every mini-batch holds each SNR point in equal share, up to one frame.  Global step g -- counted
         in self.stream_step over the trainer's life, a second call continues the stream -- draws the frames from
         stream_first_frame(g, batch_size, rank, world) of stream train_stream_id (one block per rank under
-        config.data_parallel with an initialised process group); the transmitted codeword is all zero.  A run is reproducible
+        config.data_parallel with an initialised process group); the transmitted codeword is all zero; with the trainer's
+        rate_matching the draw is engine.awgn_llr_mix(..., rate_matching=...), the same frames with the profile applied.  A run is reproducible
         bit for bit from (seed, step); with config.seed None a seed is drawn once, kept in self.stream_seed and logged.
         After each epoch frames 0 .. val_frames - 1 of stream val_stream_id are validated, the same frames every epoch.
         -> the history of `train` plus val_losses, val_accuracies, snr_points (the grid) and val_fer_per_point (per epoch,
@@ -295,7 +303,7 @@ class PosteriorJointTrainer:
         def draw(stream_id):
             return lambda first, frames: engine.awgn_llr_mix(frames, code.n, seed=self.stream_seed, stream_id=stream_id,
                                                              first_frame=first, scale=scale_tab, shift=shift_tab,
-                                                             device=scale_tab.device)
+                                                             device=scale_tab.device, rate_matching=self.rate_matching)
 
         def step_drawn():
             self.stream_step += 1

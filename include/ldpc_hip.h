@@ -491,6 +491,55 @@ int ldpc_simulate_diag(const ldpc_decoder *d, const ldpc_sim_desc *desc, int64_t
                        int64_t *out_diag /* host, ldpc_sim_diag_words(T of d, capture) */,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- rate matching: punctured and shortened bits on the channel, a count mask on the counters ----
+ * A profile says which of the n variable nodes were not sent (punctured), which are known to the receiver (shortened) and
+ * which bits the error counters look at.  Each _rm entry point is the entry point above with `const ldpc_rate_match *rm`
+ * inserted before `stream` (after `desc` for the two simulate forms); rm == NULL is the plain call and launches the very same
+ * kernels.  The struct lives on the host, its masks on the device; ldpc_sim_desc and the workspace sizes are unchanged.
+ *
+ * Channel.  Sample j of frame f draws exactly the normal z that ldpc_channel_awgn defines -- the Philox counter is on the
+ * VARIABLE index j, not on the transmit position -- so a rate-matched draw equals the plain draw on every transmitted
+ * position, bit for bit, and the profiles of a rate-compatible family are compared on common noise.  Then
+ *     punctured bit      llr = +0.0f (positive zero whatever the codeword bit is: an erasure, sign(0) = 0 in the min-sum kernels)
+ *     shortened bit      llr = s_j * short_llr
+ *     bit in both masks  shortened
+ * Bits at and beyond n in a mask's last byte are ignored.  LDPC_ERR_ARG when shortened_packed is given and short_llr is not
+ * finite and > 0; that check comes after the scalar argument checks of the plain call and before batch == 0 returns LDPC_OK
+ * without touching a device pointer; the pointer checks follow in the order of the plain call.
+ *
+ * Counters.  wrong = popcount((packed XOR codeword) AND count_packed) over bits < n takes the place of `wrong` everywhere: a
+ * frame error is wrong > 0, the stop rule runs on it, "undetected" is wrong > 0 with success != 0, the records hold it.  state,
+ * diag, done and blocks_seen are those of the plain counters; count_packed == NULL gives the plain counters' words exactly.
+ * Only count_packed is read by the two counter calls.
+ *
+ * ldpc_simulate_rm / ldpc_simulate_diag_rm run the host loop of ldpc_simulate / _diag with the profile on the channel and
+ * the counters; the decode is untouched. */
+typedef struct {
+    const uint8_t *punctured_packed;  /* device, ceil(n/8) bytes, bit j at byte j/8 bit j%8 (as codeword_packed); NULL = none */
+    const uint8_t *shortened_packed;  /* device, same format; NULL = none */
+    const uint8_t *count_packed;      /* device, same format: bits that the error counters look at; NULL = all n bits */
+    float short_llr;                  /* magnitude of a shortened bit's LLR; read only when shortened_packed != NULL */
+} ldpc_rate_match;
+
+int ldpc_channel_awgn_rm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         float scale, float shift, const uint8_t *codeword_packed, const ldpc_rate_match *rm, void *stream);
+int ldpc_channel_awgn_mix_rm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                             const float *scale_tab, const float *shift_tab, int32_t n_points,
+                             const uint8_t *codeword_packed, const ldpc_rate_match *rm, void *stream);
+int ldpc_sim_count_rm(int64_t *state, const uint8_t *packed_bits, const int32_t *iterations, int64_t batch, int32_t n,
+                      const uint8_t *codeword_packed, int64_t max_frames, int64_t max_errors, const ldpc_rate_match *rm,
+                      void *stream);
+int ldpc_sim_count_diag_rm(int64_t *state, int64_t *diag, int32_t T, int64_t capture,
+                           const uint8_t *packed_bits, const int32_t *iterations, const uint8_t *success,
+                           int64_t batch, int32_t n, const uint8_t *codeword_packed, uint64_t block_first_frame,
+                           int64_t max_frames, int64_t max_errors, void *scratch, size_t scratch_bytes,
+                           const ldpc_rate_match *rm, void *stream);
+int ldpc_simulate_rm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_rate_match *rm, int64_t out_state[8],
+                     void *workspace, size_t workspace_bytes, void *stream);
+int ldpc_simulate_diag_rm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_rate_match *rm, int64_t capture,
+                          int64_t out_state[8], int64_t *out_diag /* host, ldpc_sim_diag_words(T of d, capture) */,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
 /* sha256 (hex) over the sources and the compile recipe this library was built from, embedded at build time
