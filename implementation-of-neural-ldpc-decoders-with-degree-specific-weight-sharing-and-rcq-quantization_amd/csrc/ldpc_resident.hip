@@ -830,6 +830,10 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
 // MODE 9: MODE 8 with the posterior of the `emask` components kept in *lreg (compact kernels: no llr_s, the slots are
 //         still being read by other lanes)
 // `lreg`: the variable's LLR pair held in registers (ResVarState), or null to read it from llr_s
+// The compact kernels run MODE 0 / 2 / 9 of this body from res_cpt_gather + res_cpt_scatter (offsets extracted from the
+// packed plan words at their use): a change to the sums, their order or the v2c expression here is to be made there too
+// (a mixed cell of the same kernels runs this body; tests/test_gpu_var_rounds.py compares every cell kind with the
+// streaming engine bit for bit)
 template <int G, int DV, int MODE, typename T>
 __device__ __forceinline__ void res_var_body(unsigned char *smem, T *__restrict__ llr_s,
                                              uint8_t *__restrict__ bits_s, int q, const uint4 &slo, const uint4 &shi,
@@ -939,29 +943,138 @@ struct ResVarState {
     unsigned cells;               // compact kernels: this wave's word of ResidentPlan::vcell (wave-uniform, SGPR)
 };
 
-// one round of the compact variable phase: a uniform cell branches on its scalar degree straight into the body
-// (rounds 1-3 hold degree <= 4 only); the alpha column and a mixed cell's degrees come from vmeta, which the rare
-// users load instead of keeping four registers of it per lane
+// element `i` (32-bit index) of a uniform table: global_load / global_store ... v_off, s[base], no 64-bit vector add
+template <typename X>
+__device__ __forceinline__ const X *res_at(const X *base, unsigned i)
+{
+    return reinterpret_cast<const X *>(reinterpret_cast<const char *>(base) + (size_t)(i * (unsigned)sizeof(X)));
+}
+template <typename X>
+__device__ __forceinline__ X *res_at(X *base, unsigned i)
+{
+    return reinterpret_cast<X *>(reinterpret_cast<char *>(base) + (size_t)(i * (unsigned)sizeof(X)));
+}
+
+// ---- compact variable phase ---------------------------------------------------------------------
+// What lives across the iteration loop is the packed plan words and the LLR pairs, nothing else.  Everything a rare path
+// needs is formed where it is used, behind something the compiler cannot see through, so that it is not hoisted out of
+// the loop into registers of its own (the four vmeta lane addresses, the bslot_c one and the constants of the mixed
+// cell's per-lane switch took 14 VGPRs that way, and one of the addresses was reloaded from scratch every iteration).
+
+// Offset k of a variable (an LDS byte offset: one 16-bit half of a packed plan word), extracted at its use.  The
+// instruction is written out: to the compiler the result is not loop-invariant, so the up to 20 unpacked offsets of a
+// lane stay out of the loop's registers, and the packed word is only read -- redefining the packed words once per phase
+// through an empty asm, as res_var_phase_reg does, cost a second copy of five of them and a v_mov each per iteration.
+template <int K>
+__device__ __forceinline__ unsigned plan_offset(const uint2 &lo, const uint2 &hi)
+{
+    const unsigned w = K < 2 ? lo.x : K < 4 ? lo.y : K < 6 ? hi.x : hi.y;
+    unsigned o;
+    if constexpr ((K & 1) == 0) asm volatile("v_and_b32_e32 %0, 0xffff, %1" : "=v"(o) : "v"(w));
+    else asm volatile("v_lshrrev_b32_e32 %0, 16, %1" : "=v"(o) : "v"(w));
+    return o;
+}
+
+// an empty lane of a cell with holes (vslot_lo.y == kResHole; 0xffff is no variable's offset: they are multiples of 8).
+// Tested on the extracted half, so that the compare stays in the loop too
+__device__ __forceinline__ bool plan_is_hole(const uint2 &lo) { return plan_offset<3>(lo, lo) == 0xffffu; }
+
+// vmeta of the lane's round-R position, "scalar base + 32-bit lane offset" with an opaque offset.  Read by a mixed cell
+// (degree) and by a decoder with alpha columns (MODE 0); never by Basic or RCQ on a code without mixed cells
+template <int R>
+__device__ __forceinline__ unsigned res_cpt_vmeta(const ResidentPlan &pl, int tid)
+{
+    unsigned q = (unsigned)tid + (unsigned)(R * kResCptThreads);
+    asm volatile("" : "+v"(q));
+    return *res_at(pl.vmeta, q);
+}
+
+// the gather half of a uniform cell's body: DV offsets extracted (kept for the stores), DV reads, nothing waits for them here
+template <int G, int DV, int NX>
+__device__ __forceinline__ void res_cpt_gather(const uint2 &lo, const uint2 &hi, unsigned (&off)[NX], Pack<float, G> (&x)[NX])
+{
+    using P = Pack<float, G>;
+    static_assert(DV >= 1 && DV <= NX && NX <= 8, "degree");
+#define LDPC_CPT_LD(K) \
+    if constexpr (DV > K) { off[K] = plan_offset<K>(lo, hi); x[K] = lds_load<P>(off[K]); }
+    LDPC_CPT_LD(0) LDPC_CPT_LD(1) LDPC_CPT_LD(2) LDPC_CPT_LD(3) LDPC_CPT_LD(4) LDPC_CPT_LD(5) LDPC_CPT_LD(6) LDPC_CPT_LD(7)
+#undef LDPC_CPT_LD
+}
+
+// the other half: res_var_body's sums (same sum_ct expressions, same order) from the gathered values.  MODE 0 / 2: v2c
+// back in place; MODE 9: the decisions into the variable's slots and the posterior of the `emask` codewords into `l`
+template <int G, int DV, int MODE, int NX>
+__device__ __forceinline__ void res_cpt_scatter(const unsigned (&off)[NX], const Pack<float, G> (&x)[NX],
+                                                Pack<float, G> &l, float a, unsigned emask)
+{
+    using P = Pack<float, G>;
+    static_assert(MODE == 0 || MODE == 2 || MODE == 9, "compact: fixed-T register-state modes");
+    P out[DV];
+    unsigned byte = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float xs[DV];
+#pragma unroll
+        for (int k = 0; k < DV; ++k) xs[k] = x[k].x[g];
+        if constexpr (MODE == 9) {
+            const float post = l.x[g] + sum_ct<DV, -1, 0, float>(xs);
+            byte |= (post < 0.0f ? 1u : 0u) << g;
+            if ((emask >> g) & 1u) l.x[g] = post;
+        } else {
+            auto v2c = [&](float llr, float sum) { return MODE == 2 ? llr + sum : llr + a * sum; };
+            if constexpr (DV >= 1) out[0].x[g] = v2c(l.x[g], sum_ct<DV - 1, 0, 0, float>(xs));
+            if constexpr (DV >= 2) out[1].x[g] = v2c(l.x[g], sum_ct<DV - 1, 1, 0, float>(xs));
+            if constexpr (DV >= 3) out[2].x[g] = v2c(l.x[g], sum_ct<DV - 1, 2, 0, float>(xs));
+            if constexpr (DV >= 4) out[3].x[g] = v2c(l.x[g], sum_ct<DV - 1, 3, 0, float>(xs));
+            if constexpr (DV >= 5) out[4].x[g] = v2c(l.x[g], sum_ct<DV - 1, 4, 0, float>(xs));
+            if constexpr (DV >= 6) out[5].x[g] = v2c(l.x[g], sum_ct<DV - 1, 5, 0, float>(xs));
+            if constexpr (DV >= 7) out[6].x[g] = v2c(l.x[g], sum_ct<DV - 1, 6, 0, float>(xs));
+            if constexpr (DV >= 8) out[7].x[g] = v2c(l.x[g], sum_ct<DV - 1, 7, 0, float>(xs));
+        }
+    }
+#define LDPC_CPT_ST(K) \
+    if constexpr (DV > K) { \
+        if constexpr (MODE == 9) lds_store<unsigned>(off[K], byte); \
+        else lds_store<P>(off[K], out[K]); \
+    }
+    LDPC_CPT_ST(0) LDPC_CPT_ST(1) LDPC_CPT_ST(2) LDPC_CPT_ST(3) LDPC_CPT_ST(4) LDPC_CPT_ST(5) LDPC_CPT_ST(6) LDPC_CPT_ST(7)
+#undef LDPC_CPT_ST
+}
+
+// one round of the compact variable phase on the wave's scalar cell word: an empty cell is skipped, a uniform cell
+// branches on its scalar degree straight into the body (rounds 1-3 hold degree <= 4 only), a cell with holes masks its
+// empty lanes once, only a mixed cell runs the per-lane switch, its degrees from vmeta
 template <int G, int MODE, typename T, int R>
 __device__ __forceinline__ void res_var_round_cpt(const ResidentPlan &pl, unsigned char *smem, const T *__restrict__ alpha_glb,
-                                                  unsigned emask, int tid, int nt, ResVarState<T, G> &st)
+                                                  unsigned emask, int tid, unsigned cells, ResVarState<T, G> &st)
 {
+    using P = Pack<T, G>;
     constexpr int DMAX = R == 0 ? 8 : 4;
-    const unsigned cd = (st.cells >> (8 * R)) & 0xffu;
+    const unsigned cd = (cells >> (8 * R)) & 0xffu;
     if (cd == kCellEmpty) return;
-    const int q = tid + R * nt;
-    const uint4 slo = plan_unpack(st.plo[R]), shi = R == 0 ? plan_unpack(st.phi0) : make_uint4(0, 0, 0, 0);
-    T a = (T)0;
-    if (MODE == 0) a = alpha_glb[pl.vmeta[q] >> 8];
-    const ParScatter ps{};
+    const uint2 lo = st.plo[R], hi = st.phi0;
     if (cd == kCellMixed) {
-        res_var_dispatch<G, MODE, T, DMAX>(smem, nullptr, nullptr, q, (int)(pl.vmeta[q] & 0xffu), slo, shi, a, emask, ps,
+        const unsigned meta = res_cpt_vmeta<R>(pl, tid);
+        int dv = (int)(meta & 0xffu);
+        asm volatile("" : "+v"(dv));       // plain compares against inline constants (an SDWA byte compare keeps its constants in VGPRs)
+        const uint4 slo = make_uint4(plan_offset<0>(lo, hi), plan_offset<1>(lo, hi), plan_offset<2>(lo, hi), plan_offset<3>(lo, hi));
+        uint4 shi = make_uint4(0, 0, 0, 0);
+        if constexpr (R == 0) shi = make_uint4(plan_offset<4>(lo, hi), plan_offset<5>(lo, hi), plan_offset<6>(lo, hi), plan_offset<7>(lo, hi));
+        T a = (T)0;
+        if (MODE == 0) a = alpha_glb[meta >> 8];
+        res_var_dispatch<G, MODE, T, DMAX>(smem, nullptr, nullptr, tid + R * kResCptThreads, dv, slo, shi, a, emask, ParScatter{},
                                            &st.l[R]);
         return;
     }
-    if ((cd & kCellHoles) && st.plo[R].y == kResHole) return;       // the empty lanes of the cell
+    T a = (T)0;
+    if (MODE == 0) a = alpha_glb[res_cpt_vmeta<R>(pl, tid) >> 8];
+    if ((cd & kCellHoles) && plan_is_hole(lo)) return;               // the empty lanes of the cell
+    P x[DMAX];
+    unsigned off[DMAX];
 #define LDPC_RVU(D) \
-    case D: if constexpr (D <= DMAX) res_var_body<G, D, MODE, T>(smem, nullptr, nullptr, q, slo, shi, a, emask, ps, &st.l[R]); break;
+    case D: \
+        if constexpr (D <= DMAX) { res_cpt_gather<G, D>(lo, hi, off, x); res_cpt_scatter<G, D, MODE>(off, x, st.l[R], a, emask); } \
+        break;
     switch (cd & 0xfu) {                                           // wave-uniform: scalar compares and branches
         LDPC_RVU(1) LDPC_RVU(2) LDPC_RVU(3) LDPC_RVU(4) LDPC_RVU(5) LDPC_RVU(6) LDPC_RVU(7) LDPC_RVU(8)
     default: break;
@@ -971,16 +1084,17 @@ __device__ __forceinline__ void res_var_round_cpt(const ResidentPlan &pl, unsign
 
 template <int G, int MODE, typename T>
 __device__ __forceinline__ void res_var_phase_cpt(const ResidentPlan &pl, unsigned char *smem, const T *__restrict__ alpha_glb,
-                                                  unsigned emask, int tid, int nt, ResVarState<T, G> &st)
+                                                  unsigned emask, int tid, ResVarState<T, G> &st)
 {
-#pragma unroll
-    for (int r = 0; r < kResRegVars; ++r) asm volatile("" : "+v"(st.plo[r].x), "+v"(st.plo[r].y));
-    asm volatile("" : "+v"(st.phi0.x), "+v"(st.phi0.y));
-    static_assert(kResRegVars == 4, "four rounds");
-    res_var_round_cpt<G, MODE, T, 0>(pl, smem, alpha_glb, emask, tid, nt, st);
-    res_var_round_cpt<G, MODE, T, 1>(pl, smem, alpha_glb, emask, tid, nt, st);
-    res_var_round_cpt<G, MODE, T, 2>(pl, smem, alpha_glb, emask, tid, nt, st);
-    res_var_round_cpt<G, MODE, T, 3>(pl, smem, alpha_glb, emask, tid, nt, st);
+    static_assert(kResRegVars == 4 && std::is_same<T, float>::value, "four rounds, fp32");
+    // the wave's cell word, opaque once per phase: every test of a cell's kind or degree is a scalar compare and branch at its
+    // place in the loop (hoisted, the tests became lane masks in SGPR pairs -- more than there are, spilled to VGPR lanes)
+    unsigned cells = st.cells;
+    asm volatile("" : "+s"(cells));
+    res_var_round_cpt<G, MODE, T, 0>(pl, smem, alpha_glb, emask, tid, cells, st);
+    res_var_round_cpt<G, MODE, T, 1>(pl, smem, alpha_glb, emask, tid, cells, st);
+    res_var_round_cpt<G, MODE, T, 2>(pl, smem, alpha_glb, emask, tid, cells, st);
+    res_var_round_cpt<G, MODE, T, 3>(pl, smem, alpha_glb, emask, tid, cells, st);
 }
 
 template <int G, int MODE, typename T>
@@ -1024,7 +1138,7 @@ __device__ __forceinline__ void res_var_phase(const ResidentPlan &pl, unsigned c
 {
     if constexpr (CPT) {
         static_assert(REG && (MODE == 0 || MODE == 2 || MODE == 9), "compact: fixed-T register-state modes");
-        res_var_phase_cpt<G, MODE, T>(pl, smem, alpha_glb, emask, tid, nt, st);
+        res_var_phase_cpt<G, MODE, T>(pl, smem, alpha_glb, emask, tid, st);
         return;
     } else if constexpr (REG) {
         res_var_phase_reg<G, MODE, T>(pl, smem, llr_s, bits_s, alpha_lds, alpha_glb, emask, tid, nt, st, ps);
@@ -1260,18 +1374,6 @@ constexpr unsigned res_cpt_forms(int form, bool bpc, int nl)
     return kCptEntry | kCptInit | kCptExit;
 }
 static_assert(kCptRows == kResRegVars, "the staging rows are the register rounds");
-
-// element `i` (32-bit index) of a uniform table: global_load / global_store ... v_off, s[base], no 64-bit vector add
-template <typename X>
-__device__ __forceinline__ const X *res_at(const X *base, unsigned i)
-{
-    return reinterpret_cast<const X *>(reinterpret_cast<const char *>(base) + (size_t)(i * (unsigned)sizeof(X)));
-}
-template <typename X>
-__device__ __forceinline__ X *res_at(X *base, unsigned i)
-{
-    return reinterpret_cast<X *>(reinterpret_cast<char *>(base) + (size_t)(i * (unsigned)sizeof(X)));
-}
 
 // a row pointer of the block (uniform), pinned to an SGPR pair: the address of an element stays "scalar base + 32-bit lane
 // offset" instead of being re-associated into 64-bit vector adds shared between the rows.  The pin goes through an integer
@@ -1717,8 +1819,17 @@ void resident_decode(ResidentPlan pl, ResidentArgs a)
         const T *alpha_glb = g_alpha + (size_t)it * a.n_alpha;
         res_check_phase<G, FORM, BPC, NL, MS, T, SPLIT, CPT>(pl, res_smem, beta_row, oa_row, thr, a.n_levels,
                                                              a.rcq_zero0 != 0, dc_pre, b_pre, tid, nt, chk_cells);
-        if (BPC && tid < pl.m && it + 1 < a.T)           // next iteration's beta: in flight across the phases below
-            b_pre = g_beta[(size_t)(it + 1) * a.n_beta + pl.bslot_c[tid]];
+        if (BPC && tid < pl.m && it + 1 < a.T) {         // next iteration's beta: in flight across the phases below
+            if constexpr (CPT) {
+                // the column's address is formed here from the scalar base and an opaque lane offset: hoisted out of the
+                // loop it was a 64-bit lane address, spilled and reloaded every iteration
+                unsigned p = (unsigned)tid;
+                asm volatile("" : "+v"(p));
+                b_pre = *res_at(g_beta + (size_t)(it + 1) * a.n_beta, (unsigned)*res_at(pl.bslot_c, p));
+            } else {
+                b_pre = g_beta[(size_t)(it + 1) * a.n_beta + pl.bslot_c[tid]];
+            }
+        }
         __syncthreads();
         if (ES && !a.posterior) {
             // reference stop rule without a second gather pass: the variable phase also yields this iteration's
