@@ -50,7 +50,11 @@ enum {
     LDPC_ERR_WORKSPACE = -4     /* workspace too small                           */
 };
 
-/* arithmetic type of messages, weights, LLRs and posteriors */
+/* arithmetic type of messages, weights, LLRs and posteriors.  LDPC_F64 takes any
+ * LDPC_C2V_NMS / LDPC_C2V_OMS / LDPC_C2V_SPA table set under LDPC_SCHED_FLOODING (many
+ * beta slots, per-variable alpha slots, oms_alpha) on the streaming engine; the
+ * LDS-resident engine runs those of them that are LDPC_C2V_NMS with one beta slot per
+ * check (any alpha table) on a code it admits, the others stream. */
 enum { LDPC_F32 = 0, LDPC_F64 = 1 };
 
 /* check-to-variable rule; `min` is min1 (min2 on the arg-min edge), `s` the
