@@ -42,7 +42,7 @@ class NativeEngineError(RuntimeError):
 
 # the one compiled unit first, then everything it includes
 SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
-           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
+           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_encode.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
 
 
 def _source_files():
@@ -156,7 +156,9 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_sim_diag_words", "ldpc_sim_count_diag_scratch_bytes", "ldpc_sim_count_diag",
                    "ldpc_simulate_diag_workspace_bytes", "ldpc_simulate_diag",
                    "ldpc_channel_awgn_rm", "ldpc_channel_awgn_mix_rm", "ldpc_sim_count_rm", "ldpc_sim_count_diag_rm",
-                   "ldpc_simulate_rm", "ldpc_simulate_diag_rm")
+                   "ldpc_simulate_rm", "ldpc_simulate_diag_rm",
+                   "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode", "ldpc_encode_random",
+                   "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -295,6 +297,20 @@ def load():
         lib.ldpc_simulate_rm.argtypes = [vp, C.POINTER(SimDesc), rm, vp, vp, C.c_size_t, vp]
         lib.ldpc_simulate_diag_rm.restype = C.c_int
         lib.ldpc_simulate_diag_rm.argtypes = [vp, C.POINTER(SimDesc), rm, i64, vp, vp, vp, C.c_size_t, vp]
+        lib.ldpc_encoder_create.restype = C.c_int
+        lib.ldpc_encoder_create.argtypes = [C.POINTER(vp), i32, i32, vp, vp, vp, vp, i32]
+        lib.ldpc_encoder_destroy.restype = None
+        lib.ldpc_encoder_destroy.argtypes = [vp]
+        lib.ldpc_encode.restype = C.c_int
+        lib.ldpc_encode.argtypes = [vp, vp, i64, vp, vp]
+        lib.ldpc_encode_random.restype = C.c_int
+        lib.ldpc_encode_random.argtypes = [vp, i64, u64, u32, u64, vp, vp, vp]
+        lib.ldpc_channel_awgn_cw.restype = C.c_int
+        lib.ldpc_channel_awgn_cw.argtypes = [vp, i64, i32, u64, u32, u64, f32, f32, vp, rm, vp]
+        lib.ldpc_simulate_enc_workspace_bytes.restype = C.c_size_t
+        lib.ldpc_simulate_enc_workspace_bytes.argtypes = [vp, i64, i64]
+        lib.ldpc_simulate_enc.restype = C.c_int
+        lib.ldpc_simulate_enc.argtypes = [vp, C.POINTER(SimDesc), vp, rm, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p

@@ -220,6 +220,122 @@ def staircase_encode(graph: TannerGraph, info_bits) -> np.ndarray:
     return c[0] if u.ndim == 1 else c
 
 
+def _is_staircase(graph: TannerGraph) -> bool:
+    """the test of ``staircase_encode``: the last m columns are the IRA staircase and there is at least one information bit"""
+    n, m = graph.n, graph.m
+    k = n - m
+    if k < 1 or m < 1:
+        return False
+    rows, cols = np.asarray(graph.check_of_edge, dtype=np.int64), np.asarray(graph.var_idx, dtype=np.int64)
+    par = cols >= k
+    have = np.unique(rows[par] * m + (cols[par] - k))
+    p = np.arange(m, dtype=np.int64)
+    want = np.unique(np.concatenate([p * m + p, (p[:-1] + 1) * m + p[:-1]]))
+    return int(par.sum()) == want.size and np.array_equal(have, want)
+
+
+class Encoder:
+    """Systematic encoder of a binary linear code in the one format the device encoder reads (ldpc_encoder_create):
+
+        p_r = XOR_{i in row r} u_i   (and, with ``accumulate`` and r > 0, XOR p_{r-1})
+        c[info_pos[i]] = u_i,  c[parity_pos[r]] = p_r
+
+    with ``row_ptr`` / ``info_idx`` a CSR over information-bit indices 0 .. k - 1, ``info_pos`` [k] and ``parity_pos``
+    [n - k] ascending and together a permutation of 0 .. n - 1, and k = n - rank(H).  ``systematic``: the information bits
+    are the first k code bits.  Build one with ``Encoder.from_graph``."""
+
+    MAX_ENTRIES = 1 << 27
+
+    def __init__(self, n: int, k: int, info_pos, parity_pos, row_ptr, info_idx, accumulate: bool):
+        self.n, self.k = int(n), int(k)
+        self.info_pos = np.ascontiguousarray(info_pos, dtype=np.int32)
+        self.parity_pos = np.ascontiguousarray(parity_pos, dtype=np.int32)
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        self.info_idx = np.ascontiguousarray(info_idx, dtype=np.int32)
+        self.accumulate = bool(accumulate)
+        m = self.n - self.k
+        if self.info_pos.shape != (self.k,) or self.parity_pos.shape != (m,) or self.row_ptr.shape != (m + 1,):
+            raise ValueError("info_pos, parity_pos and row_ptr must have k, n - k and n - k + 1 entries")
+        if not np.array_equal(np.sort(np.concatenate([self.info_pos, self.parity_pos])), np.arange(self.n)):
+            raise ValueError("info_pos and parity_pos must together be a permutation of 0 .. n - 1")
+        if (np.diff(self.info_pos) <= 0).any() or (np.diff(self.parity_pos) <= 0).any():
+            raise ValueError("info_pos and parity_pos must be ascending")
+        if self.row_ptr[0] != 0 or (np.diff(self.row_ptr) < 0).any() or int(self.row_ptr[-1]) != self.info_idx.size:
+            raise ValueError("row_ptr must be monotone from 0 to len(info_idx)")
+        if self.info_idx.size and (self.info_idx.min() < 0 or self.info_idx.max() >= self.k):
+            raise ValueError("info_idx must hold information-bit indices 0 .. k - 1")
+        self.systematic = bool(np.array_equal(self.info_pos, np.arange(self.k)))
+
+    @classmethod
+    def from_graph(cls, graph: TannerGraph, method: str = "auto") -> "Encoder":
+        """method "auto": the sparse staircase form (rows = the information part of H, accumulate) when the last m columns
+        are the IRA staircase -- the test of ``staircase_encode`` -- else "eliminate": Gauss-Jordan over GF(2) on the dense H,
+        pivot columns searched from the highest column index down, for each column the first row at or below the current pivot
+        row that has a 1; redundant rows drop out.  The pivot columns are the parity positions, the free columns the
+        information positions, row r the free columns set in the reduced row of the r-th parity position.  ValueError when the
+        CSR would exceed 2^27 entries (a large non-staircase code needs another encoder)."""
+        if method not in ("auto", "eliminate"):
+            raise ValueError(f"method must be 'auto' or 'eliminate', got {method!r}")
+        n, m = graph.n, graph.m
+        if method == "auto" and _is_staircase(graph):
+            k = n - m
+            rows, cols = np.asarray(graph.check_of_edge, dtype=np.int64), np.asarray(graph.var_idx, dtype=np.int64)
+            info = cols < k
+            order = np.lexsort((cols[info], rows[info]))
+            row_ptr = np.zeros(m + 1, dtype=np.int64)
+            np.cumsum(np.bincount(rows[info], minlength=m), out=row_ptr[1:])
+            return cls(n, k, np.arange(k), np.arange(k, n), row_ptr, cols[info][order], True)
+        A = graph.to_dense(np.uint8)
+        r, pivots = 0, []
+        for c in range(n - 1, -1, -1):
+            if r == m:
+                break
+            hit = np.flatnonzero(A[r:, c])
+            if hit.size == 0:
+                continue
+            p = r + int(hit[0])
+            if p != r:
+                A[[r, p]] = A[[p, r]]
+            others = np.flatnonzero(A[:, c])
+            others = others[others != r]
+            A[others] ^= A[r]
+            pivots.append(c)
+            r += 1
+        parity_pos = np.array(sorted(pivots), dtype=np.int64)
+        is_par = np.zeros(n, dtype=bool)
+        is_par[parity_pos] = True
+        info_pos = np.flatnonzero(~is_par)
+        k = n - r
+        row_of_pivot = np.empty(n, dtype=np.int64)
+        row_of_pivot[np.array(pivots, dtype=np.int64)] = np.arange(r)
+        R = A[row_of_pivot[parity_pos]][:, info_pos] if r else np.zeros((0, k), dtype=np.uint8)
+        entries = int(R.sum(dtype=np.int64))
+        if entries > cls.MAX_ENTRIES:
+            raise ValueError(f"the eliminated encoder has {entries} entries, more than 2^27: a large non-staircase code needs "
+                             f"another encoder")
+        row_ptr = np.zeros(r + 1, dtype=np.int64)
+        np.cumsum(R.sum(axis=1, dtype=np.int64), out=row_ptr[1:])
+        return cls(n, k, info_pos, parity_pos, row_ptr, np.nonzero(R)[1], False)
+
+    def encode(self, info_bits) -> np.ndarray:
+        """info_bits: 0/1, [k] or [B, k] -> uint8 codewords [n] or [B, n].  numpy, on the host: the yardstick of the device
+        encoder; on a staircase graph it equals ``staircase_encode``."""
+        u = np.asarray(info_bits)
+        if u.shape[-1:] != (self.k,) or u.ndim not in (1, 2) or not np.isin(u, (0, 1)).all():
+            raise ValueError(f"info_bits must be 0/1 of shape [{self.k}] or [B, {self.k}]")
+        u2 = np.atleast_2d(u).astype(np.uint8)
+        m = self.n - self.k
+        p = np.zeros((u2.shape[0], m), dtype=np.uint8)
+        row_of_entry = np.repeat(np.arange(m, dtype=np.int64), np.diff(self.row_ptr))
+        np.bitwise_xor.at(p, (slice(None), row_of_entry), u2[:, self.info_idx])
+        if self.accumulate:
+            p = np.bitwise_xor.accumulate(p, axis=1)
+        c = np.empty((u2.shape[0], self.n), dtype=np.uint8)
+        c[:, self.info_pos] = u2
+        c[:, self.parity_pos] = p
+        return c[0] if u.ndim == 1 else c
+
+
 if __name__ == "__main__":  # regenerate + verify the committed edge lists
     os.makedirs(_DATA_DIR, exist_ok=True)
     for name, spec in _SPECS.items():

@@ -1770,6 +1770,9 @@ int ldpc_decode_capped(const ldpc_decoder *d, const void *llr, int64_t batch, in
 // ---- on-device Monte-Carlo: AWGN channel, error counters, one SNR point (ldpc_channel_awgn / ldpc_sim_count / ldpc_simulate)
 #include "ldpc_sim.hip"
 
+// ---- random codewords: device encoder, per-frame channel, one SNR point on them (ldpc_encode* / ldpc_channel_awgn_cw / ldpc_simulate_enc)
+#include "ldpc_encode.hip"
+
 extern "C" {
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

@@ -72,6 +72,8 @@ def _channel_codeword(codeword, n: int, dev: torch.device) -> Optional[torch.Ten
     """the codeword argument of the channel functions -- None, a 0/1 array, or an already packed tensor -- as packed bytes on `dev`"""
     if codeword is None:
         return None
+    if isinstance(codeword, str):
+        raise ValueError(f"codeword must be None, a 0/1 array or a packed uint8 tensor, got {codeword!r}")
     cw = codeword if isinstance(codeword, torch.Tensor) else pack_codeword(codeword, n, dev)
     if cw.dtype != torch.uint8 or cw.device != dev or cw.numel() != (n + 7) // 8 or not cw.is_contiguous():
         raise ValueError(f"packed codeword must be a contiguous uint8 tensor of {(n + 7) // 8} bytes on {dev}")
@@ -90,6 +92,14 @@ def _profile(rate_matching, n: int, dev: torch.device):
     return rm, C.byref(rm)
 
 
+def _codeword_rows(codeword: torch.Tensor, batch: int, n: int, dev: torch.device) -> torch.Tensor:
+    """one packed codeword per frame: a contiguous uint8 tensor [batch, ceil(n/8)] on `dev`"""
+    if (codeword.dtype != torch.uint8 or codeword.device != dev or tuple(codeword.shape) != (batch, (n + 7) // 8)
+            or not codeword.is_contiguous()):
+        raise ValueError(f"codeword rows must be a contiguous uint8 tensor [{batch}, {(n + 7) // 8}] on {dev}")
+    return codeword
+
+
 def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, snr_db: Optional[float] = None,
              scale: Optional[float] = None, shift: Optional[float] = None, codeword=None, device=None,
              rate_matching=None) -> torch.Tensor:
@@ -98,7 +108,8 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
     block it is drawn in.  Give snr_db (Es/N0, positive-mean LLRs for the all-zero codeword) or (scale, shift) = (2/sigma,
     2/sigma^2).  codeword: 0/1 array of length n, or an already packed uint8 tensor on the device; None: all zero.
     rate_matching: a RateMatching of this n (ldpc_channel_awgn_rm): +0.0 at its punctured bits, +-short_llr at its shortened
-    bits, the plain draw bit for bit everywhere else."""
+    bits, the plain draw bit for bit everywhere else.  A 2-D uint8 tensor [batch, ceil(n/8)] is one packed codeword per frame,
+    as ``encode_random`` returns them (ldpc_channel_awgn_cw): frame b is the one-codeword draw of that frame with row b."""
     dev = _require_gpu(device)
     if (snr_db is None) == (scale is None or shift is None):
         raise ValueError("give either snr_db or both scale and shift")
@@ -107,7 +118,8 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
     batch, n = int(batch), int(n)
     if batch < 0 or n < 1:
         raise ValueError("batch must be >= 0 and n >= 1")
-    cw = _channel_codeword(codeword, n, dev)
+    rows = isinstance(codeword, torch.Tensor) and codeword.dim() == 2
+    cw = _codeword_rows(codeword, batch, n, dev) if rows else _channel_codeword(codeword, n, dev)
     rm, rm_arg = _profile(rate_matching, n, dev)
     lib = nat.load()
     out = torch.empty((batch, n), dtype=torch.float32, device=dev)
@@ -115,7 +127,9 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
         stream = torch.cuda.current_stream(dev).cuda_stream
         args = (C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
                 int(first_frame) & (2 ** 64 - 1), float(scale), float(shift), None if cw is None else C.c_void_p(cw.data_ptr()))
-        if rm is None:
+        if rows:
+            nat.check(lib.ldpc_channel_awgn_cw(*args, rm_arg, C.c_void_p(stream)), "ldpc_channel_awgn_cw")
+        elif rm is None:
             nat.check(lib.ldpc_channel_awgn(*args, C.c_void_p(stream)), "ldpc_channel_awgn")
         else:
             nat.check(lib.ldpc_channel_awgn_rm(*args, rm_arg, C.c_void_p(stream)), "ldpc_channel_awgn_rm")
@@ -288,6 +302,95 @@ class _NativeGraph:
             cls._cache[key] = (weakref.ref(graph), ng)
             weakref.finalize(graph, cls._evict, key)
             return ng
+
+
+class _NativeEncoder:
+    """ldpc_encoder* for (codes.Encoder, device), cached as _NativeGraph caches graphs: weakly on the host object"""
+    _cache = {}
+    _lock = threading.Lock()
+
+    def __init__(self, encoder, device: torch.device):
+        lib = nat.load()
+        self.handle = C.c_void_p()
+        with torch.cuda.device(device):
+            nat.check(lib.ldpc_encoder_create(C.byref(self.handle), encoder.n, encoder.k, nat.ptr(encoder.info_pos),
+                                              nat.ptr(encoder.parity_pos), nat.ptr(encoder.row_ptr), nat.ptr(encoder.info_idx),
+                                              int(encoder.accumulate)), "ldpc_encoder_create")
+        self._lib = lib
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) is not None and self.handle.value:
+                self._lib.ldpc_encoder_destroy(self.handle)
+                self.handle = C.c_void_p()
+        except Exception:
+            pass
+
+    @classmethod
+    def _evict(cls, key):
+        with cls._lock:
+            cls._cache.pop(key, None)
+
+    @classmethod
+    def get(cls, encoder, device: torch.device) -> "_NativeEncoder":
+        key = (id(encoder), device.index)
+        with cls._lock:
+            hit = cls._cache.get(key)
+            if hit is not None and hit[0]() is encoder:
+                return hit[1]
+            ne = cls(encoder, device)
+            cls._cache[key] = (weakref.ref(encoder), ne)
+            weakref.finalize(encoder, cls._evict, key)
+            return ne
+
+
+def _check_encoder(encoder):
+    from codes import Encoder
+    if not isinstance(encoder, Encoder):
+        raise ValueError("encoder must be a codes.Encoder")
+    return encoder
+
+
+def encode_random(encoder, batch: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, device=None,
+                  want_info: bool = False):
+    """Codewords of frames first_frame .. first_frame + batch - 1 of the information-bit stream (ldpc_encode_random; the
+    stream is defined in include/ldpc_hip.h and INTEGRATION.md): uint8 [batch, ceil(n/8)] on the device, bit j at byte j/8,
+    bit j%8 -- what ``awgn_llr(codeword=...)`` and ``DecodeEngine.sim_count(codeword=...)`` take.  The codeword of a frame does
+    not depend on the block it is drawn in.  want_info: -> (codewords, information rows uint8 [batch, ceil(k/8)])."""
+    enc = _check_encoder(encoder)
+    dev = _require_gpu(device)
+    batch = int(batch)
+    if batch < 0:
+        raise ValueError("batch must be >= 0")
+    ne = _NativeEncoder.get(enc, dev)
+    cw = torch.empty((batch, (enc.n + 7) // 8), dtype=torch.uint8, device=dev)
+    info = torch.empty((batch, (enc.k + 7) // 8), dtype=torch.uint8, device=dev) if want_info else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(ne._lib.ldpc_encode_random(ne.handle, batch, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
+                                             int(first_frame) & (2 ** 64 - 1), C.c_void_p(cw.data_ptr()),
+                                             None if info is None else C.c_void_p(info.data_ptr()), C.c_void_p(stream)),
+                  "ldpc_encode_random")
+    return (cw, info) if want_info else cw
+
+
+def encode(encoder, info_packed: torch.Tensor) -> torch.Tensor:
+    """Codewords uint8 [B, ceil(n/8)] of the information rows info_packed, uint8 [B, ceil(k/8)] on a GPU in the packed format
+    (ldpc_encode); bits at and beyond k in a row's last byte are ignored."""
+    enc = _check_encoder(encoder)
+    if not isinstance(info_packed, torch.Tensor) or info_packed.dtype != torch.uint8 or info_packed.dim() != 2 \
+            or info_packed.shape[1] != (enc.k + 7) // 8:
+        raise ValueError(f"info_packed must be a uint8 tensor [B, {(enc.k + 7) // 8}]")
+    dev = _require_gpu(info_packed.device)
+    info_packed = info_packed.contiguous()
+    batch = int(info_packed.shape[0])
+    ne = _NativeEncoder.get(enc, dev)
+    cw = torch.empty((batch, (enc.n + 7) // 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(ne._lib.ldpc_encode(ne.handle, C.c_void_p(info_packed.data_ptr()), batch, C.c_void_p(cw.data_ptr()),
+                                      C.c_void_p(stream)), "ldpc_encode")
+    return cw
 
 
 class DecodeEngine:
@@ -556,7 +659,17 @@ class DecodeEngine:
     def _packed_codeword(self, codeword) -> Optional[torch.Tensor]:
         if codeword is None or isinstance(codeword, torch.Tensor):
             return codeword
+        if isinstance(codeword, str):
+            raise ValueError(f"codeword must be None, a 0/1 array, a packed uint8 tensor or (simulate) 'random', got {codeword!r}")
         return pack_codeword(codeword, self.graph.n, self.device)
+
+    def encoder(self):
+        """the codes.Encoder of this engine's graph (Encoder.from_graph, built once): what simulate(codeword="random") draws with"""
+        enc = getattr(self, "_encoder", None)
+        if enc is None:
+            from codes import Encoder
+            enc = self._encoder = Encoder.from_graph(self.graph)
+        return enc
 
     def sim_diag_buffer(self, capture: int = 0) -> torch.Tensor:
         """a zeroed diag buffer for sim_count(diag=...) with room for `capture` frame-error records (int64 on this engine's GPU)"""
@@ -572,7 +685,8 @@ class DecodeEngine:
         them.  With `diag` (sim_diag_buffer(capture), kept over the blocks of a point) the diagnostics of the consumed frames
         are kept too (ldpc_sim_count_diag; parse_sim_diag unpacks them): `success` [B] as decode returns it, `first_frame` the
         stream index of the block's first frame.  With rate_matching the counters look at its count mask only
-        (ldpc_sim_count_rm / _diag_rm).  Asynchronous; returns `state`."""
+        (ldpc_sim_count_rm / _diag_rm).  codeword: None, one codeword for every frame, or a 2-D uint8 tensor [B, ceil(n/8)] of
+        one packed codeword per frame (``encode_random``).  Asynchronous; returns `state`."""
         n = self.graph.n
         rm, rm_arg = _profile(rate_matching, n, self.device)
         if state.dtype != torch.int64 or state.shape != (8,) or state.device != self.device or not state.is_contiguous():
@@ -583,6 +697,11 @@ class DecodeEngine:
         if iterations.dtype != torch.int32 or iterations.shape != (B,) or iterations.device != self.device:
             raise ValueError("iterations must be int32 [B] on the engine's device")
         packed_bits, iterations = packed_bits.contiguous(), iterations.contiguous()
+        if isinstance(codeword, torch.Tensor) and codeword.dim() == 2:
+            # one codeword per frame: the code is linear, so the decisions XORed with the rows are counted against the
+            # all-zero word (out of place: the caller's packed_bits stay as they are)
+            packed_bits = torch.bitwise_xor(packed_bits, _codeword_rows(codeword, B, n, self.device))
+            codeword = None
         cw = self._packed_codeword(codeword)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         if diag is None:
@@ -629,12 +748,18 @@ class DecodeEngine:
         detected_errors, iteration_histogram (np.int64 [T + 1] over the consumed frames), captured and error_frames: the
         first `capture` frame errors as a structured array (frame, wrong_bits, iterations, undetected) -- awgn_llr(1, n,
         first_frame=frame, ...) draws such a frame again.  rate_matching: the profile on the channel and the counters
-        (ldpc_simulate_rm / _diag_rm).  Synchronous."""
+        (ldpc_simulate_rm / _diag_rm).  codeword="random": a fresh codeword per frame, drawn on the device from the point's
+        seed, stream_id and frame index with the encoder of this engine's graph (ldpc_simulate_enc); a recorded frame's
+        codeword is ``encode_random(self.encoder(), 1, first_frame=frame, ...)``.  Synchronous."""
         if (snr_db is None) == (scale is None or shift is None):
             raise ValueError("give either snr_db or both scale and shift")
         if snr_db is not None:
             scale, shift = awgn_scale_shift(snr_db)
-        cw = self._packed_codeword(codeword)
+        random = isinstance(codeword, str)
+        if random and codeword != "random":
+            raise ValueError(f"codeword must be None, a 0/1 array, a packed uint8 tensor or 'random', got {codeword!r}")
+        ne = _NativeEncoder.get(self.encoder(), self.device) if random else None
+        cw = None if random else self._packed_codeword(codeword)
         rm, rm_arg = _profile(rate_matching, self.graph.n, self.device)
         desc = nat.SimDesc()
         desc.seed, desc.stream_id = int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1)
@@ -647,9 +772,11 @@ class DecodeEngine:
         capture = int(capture)
         if capture < 0 or (capture and not diagnostics):
             raise ValueError("capture must be >= 0 and needs diagnostics=True")
-        if diagnostics:
+        words = np.zeros(sim_diag_words(self.iters, capture), dtype=np.int64) if diagnostics else None
+        if random:
+            need = int(self._lib.ldpc_simulate_enc_workspace_bytes(self.handle, max(int(block), 1), capture if diagnostics else -1))
+        elif diagnostics:
             need = int(self._lib.ldpc_simulate_diag_workspace_bytes(self.handle, max(int(block), 1), capture))
-            words = np.zeros(sim_diag_words(self.iters, capture), dtype=np.int64)
         else:
             need = int(self._lib.ldpc_simulate_workspace_bytes(self.handle, max(int(block), 1)))
         ws = getattr(self, "_sim_ws", None)
@@ -659,7 +786,10 @@ class DecodeEngine:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             tail = (C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream))
-            if rm is not None and diagnostics:
+            if random:
+                nat.check(self._lib.ldpc_simulate_enc(self.handle, C.byref(desc), ne.handle, rm_arg, capture if diagnostics else -1,
+                                                      nat.ptr(out), nat.ptr(words), *tail), "ldpc_simulate_enc")
+            elif rm is not None and diagnostics:
                 nat.check(self._lib.ldpc_simulate_diag_rm(self.handle, C.byref(desc), rm_arg, capture, nat.ptr(out),
                                                           nat.ptr(words), *tail), "ldpc_simulate_diag_rm")
             elif rm is not None:

@@ -25,7 +25,9 @@ Channel (``SimulationConfig.channel``):
   "device"  the native Monte-Carlo path: the counter-based AWGN stream of ``engine.awgn_llr`` (seed = ``config.seed``,
             stream_id = round(snr_db * 1000) mod 2^32, frame f the same noise whatever ``batch_frames`` is), the device-side
             counters of ``DecodeEngine.sim_count``, and on the LDS-resident engine the whole point in one native call
-            (``DecodeEngine.simulate``).  ``SimulationConfig.codeword`` sends a codeword other than all-zero.
+            (``DecodeEngine.simulate``).  ``SimulationConfig.codeword`` sends a codeword other than all-zero: a 0/1 array for
+            every frame, or ``"random"`` for a fresh codeword per frame, encoded on the device from the point's seed, stream
+            and frame index (``engine.encode_random`` with ``codes.Encoder.from_graph`` of the decoder's graph).
             ``SimulationConfig.diagnostics`` / ``capture_errors`` (this channel only) also count the undetected frame errors,
             bin the stop iterations and record the stream index of the first ``capture_errors`` frame errors of every point
             (``SimulationResult.undetected_errors`` / ``iteration_histograms`` / ``error_frames``);
@@ -77,7 +79,8 @@ class SimulationConfig:
     staged_early_stop: bool = True          # streaming engine: cap the block's first stage, finish stragglers as a small batch
     stage_min_block: int = 1024             # ... only for blocks of at least this many frames
     channel: str = "torch"                  # "torch": torch.randn draw, host stop rule; "device": the native Monte-Carlo path
-    codeword: Optional[np.ndarray] = None   # 0/1 array of length n sent instead of the all-zero codeword (channel="device" only)
+    codeword: Optional[np.ndarray] = None   # 0/1 array of length n sent instead of the all-zero codeword, or "random": a fresh
+    #                                         codeword per frame from the device encoder (channel="device" only)
     poll_blocks: int = 4                    # channel="device", resident engine: blocks between two looks at the counters
     diagnostics: bool = False               # channel="device": undetected errors, stop-iteration histogram, failing frames
     capture_errors: int = 0                 # ... record the first so many frame errors of every point (implies diagnostics)
@@ -91,6 +94,8 @@ class SimulationConfig:
                 raise ValueError("rate_matching needs channel='device'")
         if self.channel not in ("torch", "device"):
             raise ValueError(f"channel must be 'torch' or 'device', got {self.channel!r}")
+        if isinstance(self.codeword, str) and self.codeword != "random":
+            raise ValueError(f"codeword must be None, a 0/1 array or 'random', got {self.codeword!r}")
         if self.codeword is not None and self.channel != "device":
             raise ValueError("a codeword other than all-zero needs channel='device'")
         if int(self.capture_errors) < 0:
@@ -276,8 +281,8 @@ class LDPSimulator:
             if rm is not None and rm.n_punctured and self.config.codeword is None and not self._warned_punctured_zero:
                 self._warned_punctured_zero = True
                 warnings.warn("punctured bits with the all-zero codeword: a punctured bit that is never recovered keeps posterior "
-                              "0, decides 0 and counts as correct -- send a nonzero codeword (SimulationConfig.codeword, e.g. "
-                              "codes.staircase_encode)", UserWarning, stacklevel=2)
+                              "0, decides 0 and counts as correct -- send random codewords (SimulationConfig.codeword = 'random') or a "
+                              "nonzero one (e.g. codes.staircase_encode)", UserWarning, stacklevel=2)
             c = self._simulate_device(eng, code.n, float(snr_db), int(max_frames), int(max_errors))
             if "iteration_histogram" in c:
                 self._last.diagnostics = c
@@ -320,7 +325,8 @@ class LDPSimulator:
         scale, shift = _engine.awgn_scale_shift(snr_db, cfg.llr_convention)
         stream_id = int(round(snr_db * 1000)) % (1 << 32)
         block = max(1, int(cfg.batch_frames))
-        cw = None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, n, eng.device)
+        random = isinstance(cfg.codeword, str)            # "random": a fresh codeword per frame
+        cw = "random" if random else None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, n, eng.device)
         rm = cfg.rate_matching
         if eng.info()["engine"] == "resident":
             return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, scale=scale, shift=shift, codeword=cw,
@@ -332,6 +338,9 @@ class LDPSimulator:
         drawn, cap, host = 0, None, [0] * 8
         while drawn < max_frames and not host[4]:
             frames = min(block, max_frames - drawn)
+            if random:                                                          # the block's codeword rows
+                cw = _engine.encode_random(eng.encoder(), frames, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn,
+                                           device=eng.device)
             llr = _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn, scale=scale,
                                    shift=shift, codeword=cw, device=eng.device, rate_matching=rm)
             if diagnostics:
@@ -355,7 +364,8 @@ class LDPSimulator:
         """Draw the listed frames of the point at `snr_db` again -- stream indices, e.g. error_frames["frame"] of a run with
         this configuration (same seed, convention, codeword and rate_matching; channel="device") -- and decode them with early stop.
         -> {frames, llr [F, n], bits int32 [F, n], posterior [F, n], iterations int32 [F], success bool [F]} on the device.
-        A frame has the same noise whatever block it was drawn in, so this reproduces the recorded failure exactly."""
+        A frame has the same noise whatever block it was drawn in, so this reproduces the recorded failure exactly.  Under
+        codeword="random" each frame's codeword is drawn again too and the dict has `codewords`: uint8 [F, ceil(n/8)], packed."""
         import engine as _engine
         cfg = self.config
         if cfg.channel != "device":
@@ -363,15 +373,22 @@ class LDPSimulator:
         eng = _engine_of(decoder, _engine._require_gpu(cfg.device))
         scale, shift = _engine.awgn_scale_shift(float(snr_db), cfg.llr_convention)
         stream_id = int(round(float(snr_db) * 1000)) % (1 << 32)
-        cw = None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, code.n, eng.device)
+        random = isinstance(cfg.codeword, str)
+        cw = None if random or cfg.codeword is None else _engine.pack_codeword(cfg.codeword, code.n, eng.device)
         frames = [int(f) for f in np.asarray(frames).reshape(-1)]
+        words = [_engine.encode_random(eng.encoder(), 1, seed=int(cfg.seed), stream_id=stream_id, first_frame=f,
+                                       device=eng.device) for f in frames] if random else [cw] * len(frames)
         rows = [_engine.awgn_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, scale=scale, shift=shift,
-                                 codeword=cw, device=eng.device, rate_matching=cfg.rate_matching) for f in frames]
+                                 codeword=c, device=eng.device, rate_matching=cfg.rate_matching) for f, c in zip(frames, words)]
         llr = torch.cat(rows, dim=0) if rows else torch.empty((0, code.n), dtype=torch.float32, device=eng.device)
         with torch.no_grad():
             res = eng.decode(llr, early_stop=True)
-        return {"frames": frames, "llr": llr, "bits": res.bits, "posterior": res.posterior, "iterations": res.iterations,
-                "success": res.success}
+        out = {"frames": frames, "llr": llr, "bits": res.bits, "posterior": res.posterior, "iterations": res.iterations,
+               "success": res.success}
+        if random:
+            out["codewords"] = (torch.cat(words, dim=0) if words else
+                                torch.empty((0, (code.n + 7) // 8), dtype=torch.uint8, device=eng.device))
+        return out
 
     # ------------------------------------------------------------------------------ sweeps
     def simulate_decoder(self, decoder: Union[Callable, torch.nn.Module], code: LDPCCode,

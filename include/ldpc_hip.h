@@ -544,6 +544,64 @@ int ldpc_simulate_diag_rm(const ldpc_decoder *d, const ldpc_sim_desc *desc, cons
                           int64_t out_state[8], int64_t *out_diag /* host, ldpc_sim_diag_words(T of d, capture) */,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- random codewords: a device encoder and a channel that reads one codeword per frame --------
+ * With one codeword for every frame of a point -- all-zero by default -- a punctured bit that is never recovered keeps
+ * posterior 0, decides 0 and counts as correct, and sign-asymmetric decoder rules are never exercised.  These entry points
+ * draw a fresh codeword per frame from the counter-based stream.  Everything above is unchanged.
+ *
+ * Encoder.  A systematic encoder of a binary linear code in one format for sparse and dense codes (host arrays, copied to
+ * the device of the calling thread):
+ *     p_r = XOR of u_i over i in info_idx[row_ptr[r] .. row_ptr[r+1])   and, with accumulate != 0 and r > 0, XOR p_{r-1}
+ *     c[info_pos[i]] = u_i  (i < k),   c[parity_pos[r]] = p_r  (r < n - k)
+ * ldpc_encoder_create returns LDPC_ERR_ARG unless n >= 1, 0 <= k <= n, info_pos[k] and parity_pos[n-k] are together a
+ * permutation of 0 .. n-1, row_ptr[n-k+1] starts at 0 and is monotone and every info_idx is in 0 .. k-1 (all checked before a
+ * device is touched), and LDPC_ERR_UNSUPPORTED when a frame does not fit the kernel's LDS (n above roughly 130000).
+ *
+ * Rows are in the decoders' packed format -- bit j at byte j/8, bit j%8 -- and rows are packed: codewords_packed[batch]
+ * [ceil(n/8)], info_packed[batch][ceil(k/8)] (device, any alignment; the stride is 250 bytes for n = 1998).  Bits at and
+ * beyond n (k) in a row's last byte are written 0 (ignored on input).
+ *
+ * ldpc_encode : codewords of the given information rows.
+ * ldpc_encode_random : codewords of frames first_frame .. first_frame + batch - 1 of the information-bit stream, and the
+ *   information rows themselves when info_packed != NULL.  Information bit i of frame f is bit i % 32 of word x[(i / 32) % 4] of
+ *     (x0, x1, x2, x3) = Philox4x32-10(counter = (f & 0xffffffff, f >> 32, 0x80000000 | (i / 128), stream_id),
+ *                                      key = (seed & 0xffffffff, seed >> 32))
+ *   -- the rounds of the noise stream above.  That stream's third counter word is a quad index below 2^29 + 256, so the set
+ *   top bit keeps the two disjoint under one (seed, stream_id).  The codeword of frame f does not depend on the block it is
+ *   drawn in.
+ * Both: LDPC_ERR_ARG for batch < 0; then batch == 0 returns LDPC_OK without touching a pointer or a device; then LDPC_ERR_ARG
+ * for a NULL encoder or a NULL row pointer (info_packed of ldpc_encode_random may be NULL).  Asynchronous on `stream`,
+ * allocate nothing, safe under stream capture.
+ *
+ * ldpc_channel_awgn_cw : ldpc_channel_awgn_rm with the codeword bits of frame b read from row b of codewords_packed[batch]
+ *   [ceil(n/8)] (rm == NULL: ldpc_channel_awgn).  Frame b equals the one-codeword call of that one frame with that row, bit
+ *   for bit.  Argument checks as ldpc_channel_awgn_rm; codewords_packed must not be NULL when batch > 0.
+ *
+ * ldpc_simulate_enc : ldpc_simulate (capture < 0, out_diag unused) or ldpc_simulate_diag (capture >= 0), with rm as the _rm
+ *   forms take it (NULL: none), on a fresh codeword per frame.  Per block: ldpc_encode_random with the point's seed, stream_id
+ *   and frame indices, ldpc_channel_awgn_cw, ldpc_decode, the packed decisions XORed with the codeword rows, and the counters
+ *   above against the all-zero word -- the code is linear, so popcount((d ^ c) & mask) is the error count and d satisfies H
+ *   exactly when d ^ c does; `success` comes from the decoder.  Records, replay and the independence of block and poll_blocks
+ *   are those of ldpc_simulate_diag; a recorded frame is drawn again by ldpc_encode_random(batch = 1, first_frame = record[0])
+ *   and ldpc_channel_awgn_cw of that row.  desc->codeword_packed must be NULL, the encoder's n the decoder's and both on one
+ *   device (LDPC_ERR_ARG); float64 decoders: LDPC_ERR_UNSUPPORTED.  workspace: ldpc_simulate_enc_workspace_bytes(d, block,
+ *   capture) -- the plain workspace plus the block's codeword rows; the existing sizes do not change.  Synchronous, as
+ *   ldpc_simulate. */
+typedef struct ldpc_encoder ldpc_encoder;
+
+int ldpc_encoder_create(ldpc_encoder **out, int32_t n, int32_t k, const int32_t *info_pos, const int32_t *parity_pos,
+                        const int32_t *row_ptr, const int32_t *info_idx, int32_t accumulate);
+void ldpc_encoder_destroy(ldpc_encoder *e);
+int ldpc_encode(const ldpc_encoder *e, const uint8_t *info_packed, int64_t batch, uint8_t *codewords_packed, void *stream);
+int ldpc_encode_random(const ldpc_encoder *e, int64_t batch, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                       uint8_t *codewords_packed, uint8_t *info_packed /* or NULL */, void *stream);
+int ldpc_channel_awgn_cw(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         float scale, float shift, const uint8_t *codewords_packed, const ldpc_rate_match *rm, void *stream);
+size_t ldpc_simulate_enc_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture);
+int ldpc_simulate_enc(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_rate_match *rm,
+                      int64_t capture, int64_t out_state[8], int64_t *out_diag /* host, or NULL when capture < 0 */,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
 /* sha256 (hex) over the sources and the compile recipe this library was built from, embedded at build time
