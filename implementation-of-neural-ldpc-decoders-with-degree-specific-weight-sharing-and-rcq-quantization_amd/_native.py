@@ -162,7 +162,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
-                 "ldpc_debug_resident_kernel", "ldpc_debug_boundary_kernels", "ldpc_debug_min2", "ldpc_debug_philox")
+                 "ldpc_debug_resident_kernel", "ldpc_debug_boundary_kernels", "ldpc_debug_launch_geometry", "ldpc_debug_min2",
+                 "ldpc_debug_philox")
 EXPORTS = PRODUCT_EXPORTS + DEBUG_EXPORTS
 
 _lib = None
@@ -234,6 +235,8 @@ def load():
         lib.ldpc_debug_resident_kernel.argtypes = [vp, i32, vp]
         lib.ldpc_debug_boundary_kernels.restype = C.c_int
         lib.ldpc_debug_boundary_kernels.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp]
+        lib.ldpc_debug_launch_geometry.restype = C.c_int
+        lib.ldpc_debug_launch_geometry.argtypes = [vp, i64, vp]
         lib.ldpc_train_saved_bytes.restype = C.c_size_t
         lib.ldpc_train_saved_bytes.argtypes = [vp, i64]
         lib.ldpc_train_workspace_bytes.restype = C.c_size_t

@@ -210,14 +210,42 @@ Workspace carve(const ldpc_decoder *d, int64_t batch, void *base)
     return w;
 }
 
+// ---- launch geometry: the two rules that depend on the tile count -----------------------------
+// launch_syndrome / launch_gather launch by them and ldpc_debug_launch_geometry reports them.
+// Blocks per tile of the syndrome + latch pass over m checks; 1: the one-block syndrome_latch.
+int syndrome_chunks(int m, int tiles)
+{
+    const int max_chunks = (m + kBlock - 1) / kBlock;
+    // 64 tiles or more keep the one-block form (measured equal there: 173 vs 182 us at 128 tiles of the (16200,7200) code)
+    return tiles >= 64 ? 1 : std::min(max_chunks, std::max(1, 256 / std::max(tiles, 1)));
+}
+
+// Tile mapping of cn_gather on tiles of W codewords: xcd_tiles > 0 the XCD-affine mapping (then == tiles), on a grid padded
+// to a multiple of 8 tiles.
+struct GatherTiles {
+    int xcd_tiles = 0;
+    size_t padded = 0;
+};
+GatherTiles gather_tiles(int n, int E, int tiles, int W)
+{
+    GatherTiles t;
+    // XCD-affine tile mapping when the rows one tile touches (LLRs + both code buffers) fit an XCD's 4 MiB L2: the re-reads
+    // then hit there instead of going through the fabric.  At W = 256 that is 4n + 2E <= 16384: neither benchmark code
+    // qualifies ((1998,1512): 4n + 2E = 21166; (16200,7200): 29 MB per tile); small_96_48 does, from 16 tiles on.  The
+    // figures once quoted here -- (1998,1512) RCQ 6.28 -> 5.85 ms per decode, (16200,7200) 3 % slower -- are those of
+    // profiles/r02_ab_timings.json, builds xcd0_vec4 / xcd1_vec4: an A/B build with the mapping forced on for every code,
+    // not this condition, under which the (1998,1512) code keeps the tile-major mapping.  No measurement exists under it.
+    t.xcd_tiles = (tiles >= 16 && ((size_t)4 * n + 2 * (size_t)E) * W <= (4u << 20)) ? tiles : 0;
+    t.padded = t.xcd_tiles ? (size_t)((tiles + 7) / 8) * 8 : (size_t)tiles;
+    return t;
+}
+
 // ---- launch helpers, one per kernel family ------------------------------------------------
 // syndrome + latch: one block per tile when there are many tiles, else `chunks` blocks per tile (syndrome_latch_chunks)
 template <int VEC>
 void launch_syndrome(const GraphDev &g, const Workspace &w, int it_plus_1, int latch, hipStream_t s)
 {
-    const int max_chunks = (g.m + kBlock - 1) / kBlock;
-    // 64 tiles or more keep the one-block form (measured equal there: 173 vs 182 us at 128 tiles of the (16200,7200) code)
-    const int chunks = w.tiles >= 64 ? 1 : std::min(max_chunks, std::max(1, 256 / std::max(w.tiles, 1)));
+    const int chunks = syndrome_chunks(g.m, w.tiles);
     if (chunks <= 1)
         hipLaunchKernelGGL((syndrome_latch<VEC>), dim3(w.tiles), dim3(kBlock), 0, s, g, w.bitsT, w.done, w.iters, it_plus_1, latch);
     else
@@ -503,13 +531,9 @@ int launch_gather(const ldpc_decoder *d, const Workspace &w, int it, bool use_do
     const int per_block = kWavesPerBlock * cpw;
     const int cb = (g.m + per_block - 1) / per_block;
     if (cb == 0 || g.E == 0) return LDPC_OK;
-    // XCD-affine tile mapping when the rows one tile touches (LLRs + both code buffers) fit an XCD's 4 MiB L2: the re-reads
-    // then hit there instead of going through the fabric (measured, (1998,1512) RCQ: 6.28 -> 5.85 ms per decode; on the
-    // (16200,7200) code, 29 MB per tile, it costs 3 %)
-    constexpr int W = 64 * VEC;
-    const int xcd_tiles = (w.tiles >= 16 && ((size_t)4 * g.n + 2 * (size_t)g.E) * W <= (4u << 20)) ? w.tiles : 0;
-    const size_t tiles_padded = xcd_tiles ? (size_t)((w.tiles + 7) / 8) * 8 : (size_t)w.tiles;
-    const dim3 grid((unsigned)(tiles_padded * cb)), block(kBlock);
+    const GatherTiles gt = gather_tiles(g.n, g.E, w.tiles, 64 * VEC);       // XCD-affine mapping or tile-major
+    const int xcd_tiles = gt.xcd_tiles;
+    const dim3 grid((unsigned)(gt.padded * cb)), block(kBlock);
     const float *beta_row = (const float *)d->beta + (size_t)it * d->n_beta;
     const float *alpha_prev = (const float *)d->alpha + (size_t)(it - 1) * d->n_alpha;
     const float *thr = d->thresholds + (size_t)d->q_of_iter[it] * d->n_levels;
@@ -1941,6 +1965,21 @@ int ldpc_debug_boundary_kernels(const ldpc_decoder *d, int64_t batch, int32_t ma
     const BoundaryKernels k = boundary_kernels(d, pick_vec(d, batch), capped_T(d), saving != 0, llr, posterior, bits);
     const int32_t out[5] = {k.vec, k.in_bytes, k.fused_in, k.out_path, k.out_bytes};
     std::copy(out, out + 5, out5);
+    return LDPC_OK;
+}
+
+int ldpc_debug_launch_geometry(const ldpc_decoder *d, int64_t batch, int64_t out8[8])
+{
+    if (!d || !out8) return fail(LDPC_ERR_ARG, "NULL argument");
+    if (batch <= 0) return fail(LDPC_ERR_ARG, "batch must be >= 1");
+    if (use_resident(d) || use_layered_lds(d))
+        return fail(LDPC_ERR_UNSUPPORTED, "the LDS-resident kernels have no tiles: launch geometry exists only on the streaming engine");
+    const Workspace w = carve(d, batch, nullptr);
+    const bool flooding = d->schedule == LDPC_SCHED_FLOODING;      // the layered kernels check the syndrome themselves
+    const bool gather = flooding && d->dtype == LDPC_F32 && use_gather(d);
+    const GatherTiles gt = gather ? gather_tiles(d->g->n, d->g->E, w.tiles, 64 * w.vec) : GatherTiles{0, (size_t)w.tiles};
+    const int64_t out[8] = {w.vec, w.tiles, flooding ? syndrome_chunks(d->g->m, w.tiles) : 0, gt.xcd_tiles, (int64_t)gt.padded, 0, 0, 0};
+    std::copy(out, out + 8, out8);
     return LDPC_OK;
 }
 

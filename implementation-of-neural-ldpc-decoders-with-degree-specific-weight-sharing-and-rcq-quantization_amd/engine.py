@@ -547,6 +547,16 @@ class DecodeEngine:
         return {"vec": int(o[0]), "in_bytes": int(o[1]), "fused_in": bool(o[2]),
                 "out_path": ("none", "layout", "last-rows")[int(o[3])], "out_bytes": int(o[4])}
 
+    def launch_geometry(self, batch: int) -> dict:
+        """the tile-count rules of a streaming decode of `batch` codewords (ldpc_debug_launch_geometry; host only): tile
+        width and count, blocks per tile of the syndrome pass (1: the one-block kernel, 0: a layered schedule launches none),
+        and cn_gather's XCD-affine tile count (0: tile-major) and padded grid.  NotImplementedError on an LDS-resident engine."""
+        o = np.zeros(8, dtype=np.int64)
+        nat.check(self._lib.ldpc_debug_launch_geometry(self.handle, int(batch), nat.ptr(o)), "ldpc_debug_launch_geometry")
+        assert not o[5:].any()
+        return {"vec": int(o[0]), "tiles": int(o[1]), "syndrome_chunks": int(o[2]), "gather_xcd_tiles": int(o[3]),
+                "gather_tiles_padded": int(o[4])}
+
     # ------------------------------------------------------------------ weights
     def set_weights(self, beta: Optional[np.ndarray], alpha: Optional[np.ndarray],
                     oms_alpha: Optional[np.ndarray] = None):

@@ -6,7 +6,8 @@
  * with HIP events; the parity tests use the two state dumps to compare per-edge check-to-variable
  * messages (for RCQ: the 3-bit quantiser codes the reference emits, rcq_decoder.py:244-246) on BOTH
  * engines; ldpc_debug_resident_kernel lets a test assert WHICH resident kernel and table flags a decode runs,
- * ldpc_debug_boundary_kernels which layout kernels a streaming decode takes for given caller pointers.
+ * ldpc_debug_boundary_kernels which layout kernels a streaming decode takes for given caller pointers,
+ * ldpc_debug_launch_geometry which syndrome kernel and which cn_gather tile mapping a batch's tile count selects.
  */
 #ifndef LDPC_HIP_DEBUG_H
 #define LDPC_HIP_DEBUG_H
@@ -63,6 +64,19 @@ int ldpc_debug_resident_kernel(const ldpc_decoder *d, int32_t early_stop, int32_
  * write the caller's rows element by element) or, with saving != 0, the decoder has no gradient path. */
 int ldpc_debug_boundary_kernels(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int32_t saving,
                                 const void *llr, const void *posterior, const int32_t *bits, int32_t out5[5]);
+
+/* The launch rules of a streaming decode that depend on how many tiles the batch is cut into (host only, no device is
+ * touched): out8 = { VEC, tiles, syndrome chunks, gather XCD tiles, gather padded tiles, 0, 0, 0 }.  VEC and tiles as
+ * ldpc_debug_workspace_layout.  Syndrome chunks: the blocks per tile of the syndrome + latch pass; 2 or more is
+ * syndrome_latch_chunks (per-tile ticket and OR word in the workspace, both zero between launches), 1 the one-block
+ * syndrome_latch, 0 a layered schedule (its kernels check the syndrome themselves).  Gather XCD tiles: the tile count
+ * handed to cn_gather when it runs the XCD-affine tile mapping (workgroup b works on tile 8 * (b / 8 / check blocks) + b % 8),
+ * 0 for the tile-major mapping or a decoder that does not launch cn_gather (any form but the fused RCQ iteration);
+ * gather padded tiles: the tiles its grid covers -- under the XCD mapping the next multiple of 8, whose surplus workgroups
+ * exit at once -- else `tiles`.  The last three words are spare and zero.  The launchers and this hook read one pair of
+ * functions (csrc/ldpc_hip.hip, syndrome_chunks and gather_tiles).  LDPC_ERR_UNSUPPORTED when the decode runs an
+ * LDS-resident kernel: those have no tiles. */
+int ldpc_debug_launch_geometry(const ldpc_decoder *d, int64_t batch, int64_t out8[8]);
 
 /* Compact fixed-T plan of the LDS-resident engine (host only, no device is touched).  The kernel runs the variable at
  * position q = r*512 + w*64 + lane in round r (< 4) of wave w (< 8); cells[w*4 + r] describes cell (w, r): 0 empty,
