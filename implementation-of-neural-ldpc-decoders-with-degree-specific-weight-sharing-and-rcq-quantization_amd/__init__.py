@@ -31,6 +31,7 @@ from engine import DecodeEngine, DecodeResult  # noqa: E402,F401
 from _native import NativeEngineError, build_native  # noqa: E402,F401
 import codes  # noqa: E402,F401
 from rate_matching import RateMatching  # noqa: E402,F401
+from modulation import Modulation  # noqa: E402,F401
 from simulation_framework import (SimulationConfig, SimulationResult, LDPSimulator,  # noqa: E402,F401
                                   create_test_decoders)
 

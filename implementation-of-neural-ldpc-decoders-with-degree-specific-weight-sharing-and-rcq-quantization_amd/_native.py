@@ -42,7 +42,7 @@ class NativeEngineError(RuntimeError):
 
 # the one compiled unit first, then everything it includes
 SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
-           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_encode.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
+           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_encode.hip", "ldpc_modulation.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
 
 
 def _source_files():
@@ -139,6 +139,11 @@ class RateMatch(C.Structure):
                 ("short_llr", C.c_float)]
 
 
+class ModulationDesc(C.Structure):
+    """ldpc_modulation of include/ldpc_hip.h: bits per symbol, fading, amp and the interleaver (device pointer, NULL = identity)"""
+    _fields_ = [("bits_per_symbol", C.c_int32), ("fading", C.c_int32), ("amp", C.c_float), ("position", C.c_void_p)]
+
+
 # every symbol include/ldpc_hip.h declares (tests check the library exports them all) ...
 PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info", "ldpc_decoder_create",
                    "ldpc_decoder_set_mode", "ldpc_decoder_info",
@@ -158,7 +163,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_channel_awgn_rm", "ldpc_channel_awgn_mix_rm", "ldpc_sim_count_rm", "ldpc_sim_count_diag_rm",
                    "ldpc_simulate_rm", "ldpc_simulate_diag_rm",
                    "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode", "ldpc_encode_random",
-                   "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc")
+                   "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc",
+                   "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -314,6 +320,13 @@ def load():
         lib.ldpc_simulate_enc_workspace_bytes.argtypes = [vp, i64, i64]
         lib.ldpc_simulate_enc.restype = C.c_int
         lib.ldpc_simulate_enc.argtypes = [vp, C.POINTER(SimDesc), vp, rm, i64, vp, vp, vp, C.c_size_t, vp]
+        mod = C.POINTER(ModulationDesc)
+        lib.ldpc_channel_sym.restype = C.c_int
+        lib.ldpc_channel_sym.argtypes = [vp, i64, i32, u64, u32, u64, mod, vp, i64, vp, vp]
+        lib.ldpc_simulate_sym_workspace_bytes.restype = C.c_size_t
+        lib.ldpc_simulate_sym_workspace_bytes.argtypes = [vp, i64, i64]
+        lib.ldpc_simulate_sym.restype = C.c_int
+        lib.ldpc_simulate_sym.argtypes = [vp, C.POINTER(SimDesc), vp, mod, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p

@@ -1797,6 +1797,9 @@ int ldpc_decode_capped(const ldpc_decoder *d, const void *llr, int64_t batch, in
 // ---- random codewords: device encoder, per-frame channel, one SNR point on them (ldpc_encode* / ldpc_channel_awgn_cw / ldpc_simulate_enc)
 #include "ldpc_encode.hip"
 
+// ---- symbol channel: Gray-mapped QAM, Rayleigh fading, max-log demapper, one SNR point on it (ldpc_channel_sym / ldpc_simulate_sym)
+#include "ldpc_modulation.hip"
+
 extern "C" {
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

@@ -1,0 +1,350 @@
+// ldpc_modulation.hip -- a symbol channel for the on-device Monte-Carlo path: Gray-mapped BPSK / QPSK / 16- / 64- / 256-QAM over
+// AWGN or per-symbol Rayleigh fading with a max-log demapper (ldpc_channel_sym) and the host loop of one SNR point on it
+// (ldpc_simulate_sym) of include/ldpc_hip.h.
+//
+// Included by ldpc_hip.hip below ldpc_encode.hip (it uses ldpc_sim.hip's Philox rounds, uniforms, Box-Muller, counters and
+// workspace carving and ldpc_encode.hip's encoder launch and row XOR): still the one compiled unit.
+//
+// Definition (include/ldpc_hip.h; tests/modulation_reference.py restates it in numpy).  m bits per symbol,
+// S = ceil(n / m) symbols per frame, transmit index t = s * m + k is bit k of symbol s and carries the codeword bit of variable
+// pos[t] (identity when pos is NULL); transmit indices >= n are pad bits, sent as 0 and never stored.  The first h = m / 2 bits
+// label the I axis, the next h the Q axis (m = 1: an I axis with h = 1 only).  An axis is Gray-labelled 2^h-PAM: level index
+// i = running XOR of b_0 .. b_{h-1} (b_0 the most significant bit), integer amplitude a = (2^h - 1) - 2 i.
+//   (x0, x1, x2, x3) = Philox4x32-10(counter = (f lo, f hi, 0x40000000 | s, stream_id), key = seed)
+//   (zI, zQ) = sim_box_muller(x0, x1);  g = 1.0f, or sqrtf(-logf(u(x2))) under Rayleigh fading;  e = g * amp
+//   per axis: v = e * (float)a + z;  D(a') = (v - e * (float)a')^2;  llr_k = 0.5f * (min_{b_k = 1} D - min_{b_k = 0} D)
+// Every multiply and add is rounded on its own: no fmaf is written here and the unit is built with -ffp-contract=off.
+
+namespace ldpc {
+
+constexpr uint32_t kSymCounterTag = 0x40000000u;    // third counter word: disjoint from the noise quads (< 2^29 + 256) and the information words (top bit)
+constexpr unsigned kSymMaxSymbols = 1u << 29;
+
+// the run of M floats of one symbol at dst, whose address is PH floats past a 16-byte boundary: 16-byte stores where the
+// address allows them, then 8-byte ones, else single floats.  Everything is resolved at compile time, so v stays in registers.
+template <int M, int PH, int P = 0>
+__device__ inline void sym_store_run(float *dst, const float (&v)[M])
+{
+    if constexpr (P < M) {
+        constexpr int ph = (PH + P) & 3;
+        if constexpr (ph == 0 && M - P >= 4) {
+            *reinterpret_cast<float4 *>(dst + P) = make_float4(v[P], v[P + 1], v[P + 2], v[P + 3]);
+            sym_store_run<M, PH, P + 4>(dst, v);
+        } else if constexpr ((ph & 1) == 0 && M - P >= 2) {
+            *reinterpret_cast<float2 *>(dst + P) = make_float2(v[P], v[P + 1]);
+            sym_store_run<M, PH, P + 2>(dst, v);
+        } else {
+            dst[P] = v[P];
+            sym_store_run<M, PH, P + 1>(dst, v);
+        }
+    }
+}
+
+// a lane's M consecutive LLRs: the widest stores its address allows (a row starts at byte 4 * b * n and a symbol M floats on, so
+// every alignment occurs); the last symbol of a row stores its cnt < M live values one by one
+template <int M>
+__device__ inline void sym_store(float *dst, const float (&v)[M], int cnt)
+{
+    if (cnt == M) {
+        if constexpr (M == 1) {
+            dst[0] = v[0];
+        } else {
+            switch ((unsigned)((uintptr_t)dst >> 2) & 3u) {
+            case 0: sym_store_run<M, 0>(dst, v); break;
+            case 1: sym_store_run<M, 1>(dst, v); break;
+            case 2: sym_store_run<M, 2>(dst, v); break;
+            default: sym_store_run<M, 3>(dst, v); break;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < M; ++k)
+            if (k < cnt) dst[k] = v[k];
+    }
+}
+
+// one axis of H bits: `bits` holds b_k at bit k (b_0, the most significant label bit, at bit 0).  Sends the labelled amplitude
+// through v = e * a + z, forms the 2^H squared distances once and takes the H masked minima out of them.
+template <int H>
+__device__ inline float sym_axis(unsigned bits, float e, float z, float *llr)
+{
+    constexpr int L = 1 << H;
+    unsigned i = 0, run = 0;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        run ^= (bits >> k) & 1u;
+        i = (i << 1) | run;
+    }
+    const int a = (L - 1) - 2 * (int)i;
+    const float ea = e * (float)a;
+    const float v = ea + z;
+    float D[L];
+#pragma unroll
+    for (int c = 0; c < L; ++c) {
+        const float ec = e * (float)((L - 1) - 2 * c);
+        const float t = v - ec;
+        D[c] = t * t;
+    }
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        float m0 = INFINITY, m1 = INFINITY;
+#pragma unroll
+        for (int c = 0; c < L; ++c) {
+            const int gray = c ^ (c >> 1);                                        // label of level c, b_0 at bit H - 1
+            if ((gray >> (H - 1 - k)) & 1) m1 = fminf(m1, D[c]);
+            else m0 = fminf(m0, D[c]);
+        }
+        const float d = m1 - m0;
+        llr[k] = 0.5f * d;
+    }
+    return v;
+}
+
+// One lane per symbol; consecutive lanes hold consecutive symbols of the [batch][S] block, the lane-to-(frame, symbol)
+// arithmetic of sim_channel_awgn.  256-thread workgroups, no LDS.  Identity path (PERM false): the lane owns floats
+// s * M .. s * M + M - 1 of row b.  Permuted path: bit k of the symbol is the codeword bit of variable pos[s * M + k], and its
+// LLR goes there with a 4-byte store.  cw_stride 0: one codeword for every frame; cw NULL: the all-zero word.
+template <int M, bool FADING, bool PERM>
+__global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__ llr, long long batch, int n, unsigned S,
+                                                             uint32_t k0, uint32_t k1, uint32_t stream_id,
+                                                             unsigned long long first_frame, float amp,
+                                                             const int *__restrict__ pos, const uint8_t *__restrict__ cw,
+                                                             long long cw_stride, float4 *__restrict__ received)
+{
+    constexpr int H = M == 1 ? 1 : M / 2;
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
+    const unsigned long long b0 = g0 / S;
+    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
+    const unsigned db = t / S;
+    const long long b = (long long)b0 + db;
+    const unsigned s = t - db * S;
+    if (b >= batch) return;
+    const int j0 = (int)s * M;                                                    // < n <= 2^31 - 1
+    const int cnt = n - j0 < M ? n - j0 : M;
+    const int rb = (n + 7) >> 3;
+    const uint8_t *row = cw ? cw + (size_t)b * (size_t)cw_stride : nullptr;
+    int p[M];                                                                     // permuted path: the symbol's variables
+    (void)p; (void)rb;
+    unsigned bits = 0;                                                           // bit k of the symbol at bit k; pad bits 0
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k) {
+            p[k] = k < cnt ? pos[j0 + k] : 0;
+            if (row && k < cnt) bits |= ((unsigned)(row[p[k] >> 3] >> (p[k] & 7)) & 1u) << k;
+        }
+    } else if (row) {
+        const int byte = j0 >> 3, sh = j0 & 7;
+        unsigned w = row[byte];
+        if (M == 6 && byte + 1 < rb) w |= (unsigned)row[byte + 1] << 8;           // six bits from bit 4 or 6 on reach into the next byte
+        bits = (w >> sh) & ((1u << cnt) - 1u);
+    }
+    const unsigned long long f = first_frame + (unsigned long long)b;
+    uint32_t x[4];
+    philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), kSymCounterTag | s, stream_id, k0, k1, x);
+    float zI, zQ;
+    sim_box_muller(x[0], x[1], zI, zQ);
+    float g = 1.0f;
+    if (FADING) g = sqrtf(-logf(sim_uniform(x[2])));
+    const float e = g * amp;
+    float v[M];
+    const float vI = sym_axis<H>(bits & ((1u << H) - 1u), e, zI, v);
+    float vQ = 0.0f;
+    if constexpr (M > 1) vQ = sym_axis<H>(bits >> H, e, zQ, v + H);
+    if (received) received[(size_t)b * S + s] = make_float4(vI, vQ, e, 0.0f);
+    float *dst = llr + (size_t)b * (size_t)n;
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k)
+            if (k < cnt) dst[p[k]] = v[k];
+    } else {
+        sym_store<M>(dst + j0, v, cnt);
+    }
+}
+
+}  // namespace ldpc
+
+namespace {
+
+// the scalar part of a modulation descriptor (the position table is a device pointer: the caller vouches for it)
+int sym_mod_check(const ldpc_modulation *mod, int32_t n)
+{
+    if (!mod) return fail(LDPC_ERR_ARG, "NULL mod");
+    const int32_t m = mod->bits_per_symbol;
+    if (m != 1 && m != 2 && m != 4 && m != 6 && m != 8)
+        return fail(LDPC_ERR_ARG, "bits_per_symbol must be 1, 2, 4, 6 or 8 (BPSK, QPSK, 16- / 64- / 256-QAM), got %d", m);
+    if (mod->fading != 0 && mod->fading != 1) return fail(LDPC_ERR_ARG, "fading must be 0 (none) or 1 (Rayleigh per symbol), got %d", mod->fading);
+    if (!(std::isfinite(mod->amp) && mod->amp >= 0.0f)) return fail(LDPC_ERR_ARG, "amp must be finite and >= 0");
+    if (((int64_t)n + m - 1) / m >= (int64_t)kSymMaxSymbols)
+        return fail(LDPC_ERR_UNSUPPORTED, "a frame of %lld symbols: the symbol index must stay below 2^29", (long long)(((int64_t)n + m - 1) / m));
+    return LDPC_OK;
+}
+
+template <int M, bool FADING>
+void sym_launch_perm(bool perm, dim3 grid, hipStream_t s, float *llr, long long batch, int n, unsigned S, uint32_t k0, uint32_t k1,
+                     uint32_t stream_id, unsigned long long first_frame, float amp, const int *pos, const uint8_t *cw,
+                     long long cw_stride, float4 *received)
+{
+    if (perm)
+        hipLaunchKernelGGL((sim_channel_sym<M, FADING, true>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, k0, k1, stream_id,
+                           first_frame, amp, pos, cw, cw_stride, received);
+    else
+        hipLaunchKernelGGL((sim_channel_sym<M, FADING, false>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, k0, k1, stream_id,
+                           first_frame, amp, pos, cw, cw_stride, received);
+}
+
+// one launch of sim_channel_sym; mod has passed sym_mod_check
+int sim_channel_sym_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                           const ldpc_modulation *mod, const uint8_t *cw, int64_t cw_stride, void *received, hipStream_t s)
+{
+    const int m = mod->bits_per_symbol;
+    const unsigned S = (unsigned)(((int64_t)n + m - 1) / m);
+    const unsigned long long syms = (unsigned long long)batch * S;
+    const unsigned long long blocks = (syms + kSimBlock - 1) / kSimBlock;
+    if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+    const dim3 grid((unsigned)blocks);
+    const bool perm = mod->position != nullptr, fading = mod->fading != 0;
+#define LDPC_SYM_CASE(M)                                                                                                          \
+    case M:                                                                                                                       \
+        if (fading)                                                                                                               \
+            sym_launch_perm<M, true>(perm, grid, s, llr, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32),      \
+                                     stream_id, (unsigned long long)first_frame, mod->amp, (const int *)mod->position, cw,        \
+                                     (long long)cw_stride, (float4 *)received);                                                   \
+        else                                                                                                                      \
+            sym_launch_perm<M, false>(perm, grid, s, llr, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32),     \
+                                      stream_id, (unsigned long long)first_frame, mod->amp, (const int *)mod->position, cw,       \
+                                      (long long)cw_stride, (float4 *)received);                                                  \
+        break;
+    switch (m) {
+        LDPC_SYM_CASE(1)
+        LDPC_SYM_CASE(2)
+        LDPC_SYM_CASE(4)
+        LDPC_SYM_CASE(6)
+        LDPC_SYM_CASE(8)
+    default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+    }
+#undef LDPC_SYM_CASE
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+// simulate_enc_impl's loop with the symbol channel: encode_random (or the descriptor's one codeword), sim_channel_sym,
+// ldpc_decode, the decisions XORed with the codeword rows (one codeword: the counters compare against it themselves), the
+// existing counters.
+int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
+                      int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    const bool diagnostics = capture >= 0;
+    if (!d || !desc || !out_state) return fail(LDPC_ERR_ARG, "NULL decoder / descriptor / out_state");
+    if (diagnostics && !out_diag) return fail(LDPC_ERR_ARG, "NULL out_diag");
+    if (diagnostics && sim_diag_words(d->T, capture) == 0) return fail(LDPC_ERR_ARG, "capture too large");
+    if (e && desc->codeword_packed) return fail(LDPC_ERR_ARG, "codeword_packed must be NULL with an encoder: the codewords are drawn per frame");
+    if (desc->block < 1) return fail(LDPC_ERR_ARG, "block < 1");
+    if (desc->poll_blocks < 1) return fail(LDPC_ERR_ARG, "poll_blocks < 1");
+    if (d->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "ldpc_simulate_sym draws fp32 LLRs: float64 decoders are not supported");
+    if (d->g->n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = sym_mod_check(mod, d->g->n)) return rc;
+    if (e && e->g.n != d->g->n) return fail(LDPC_ERR_ARG, "the encoder has n = %d, the decoder n = %d", e->g.n, d->g->n);
+    if (e && e->device != d->g->device) return fail(LDPC_ERR_ARG, "encoder and decoder live on different devices");
+    if (!workspace) return fail(LDPC_ERR_ARG, "NULL workspace");
+    if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
+    const SimWorkspace w = sim_carve(d, desc->block, capture);
+    const size_t total = sim_enc_total(d, desc->block, capture);
+    if (total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, total);
+    DeviceGuard guard(d->g->device);
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)workspace;
+    float *llr = (float *)(base + w.o_llr);
+    uint8_t *packed = (uint8_t *)(base + w.o_packed);
+    int32_t *iters = (int32_t *)(base + w.o_iters);
+    int64_t *state = (int64_t *)(base + w.o_state);
+    uint8_t *success = diagnostics ? (uint8_t *)(base + w.o_success) : nullptr;
+    uint32_t *words = diagnostics ? (uint32_t *)(base + w.o_words) : nullptr;
+    int64_t *diag = diagnostics ? (int64_t *)(base + w.o_diag) : nullptr;
+    uint8_t *cw = (uint8_t *)(base + sim_enc_cw_offset(d, desc->block, capture));
+    const int32_t n = d->g->n;
+    const long long rb = ((long long)n + 7) / 8;
+    const uint8_t *one = e ? nullptr : desc->codeword_packed;       // the counters' codeword: rows are XORed away instead
+    PinnedState host;
+    HIP_TRY(hipHostMalloc((void **)&host.p, 8 * sizeof(int64_t), hipHostMallocDefault));
+    HIP_TRY(hipMemsetAsync(state, 0, 8 * sizeof(int64_t), s));
+    if (diagnostics) HIP_TRY(hipMemsetAsync(diag, 0, w.diag_words * sizeof(int64_t), s));
+    auto count = [&](int64_t frames, int64_t first) {    // fold one block (frames = 0: latch `done`)
+        if (diagnostics)
+            return sim_count_diag_launch(state, diag, d->T, capture, packed, iters, success, frames, n, one,
+                                         desc->first_frame + (uint64_t)first, desc->max_frames, desc->max_errors, words, s);
+        return sim_count_launch(state, packed, iters, frames, n, one, desc->max_frames, desc->max_errors, s);
+    };
+    int64_t drawn = 0;                                   // frames drawn so far: block k starts at first_frame + k * block
+    for (;;) {
+        int queued = 0;
+        for (int p = 0; p < desc->poll_blocks && drawn < desc->max_frames; ++p, ++queued) {
+            const int64_t frames = std::min<int64_t>(desc->block, desc->max_frames - drawn);
+            const uint64_t first = desc->first_frame + (uint64_t)drawn;
+            if (e)
+                if (int rc = enc_launch(e, frames, 1, desc->seed, desc->stream_id, first, nullptr, cw, nullptr, s)) return rc;
+            if (int rc = sim_channel_sym_launch(llr, frames, n, desc->seed, desc->stream_id, first, mod, e ? cw : one, e ? rb : 0,
+                                                nullptr, s))
+                return rc;
+            if (int rc = ldpc_decode(d, llr, frames, 1, nullptr, nullptr, iters, success, packed, base + w.o_dec, w.dec_bytes, s))
+                return rc;
+            if (e) {
+                const long long bytes = (long long)frames * rb, xblocks = ((bytes >> 2) + kSimBlock - 1) / kSimBlock;
+                hipLaunchKernelGGL(enc_xor_rows, dim3((unsigned)std::max<long long>(xblocks, 1)), dim3(kSimBlock), 0, s, packed,
+                                   (const uint8_t *)cw, bytes);
+                HIP_TRY(hipGetLastError());
+            }
+            if (int rc = count(frames, drawn)) return rc;
+            drawn += frames;
+        }
+        if (queued == 0)                                 // max_frames <= 0, or every frame drawn: an empty block latches `done`
+            if (int rc = count(0, drawn)) return rc;
+        HIP_TRY(hipMemcpyAsync(host.p, state, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (host.p[4] != 0) break;
+        if (queued == 0) return fail(LDPC_ERR_HIP, "internal error: every frame counted and the point is not done");
+    }
+    if (diagnostics) {
+        HIP_TRY(hipMemcpyAsync(out_diag, diag, w.diag_words * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (int k = 0; k < 8; ++k) out_state[k] = host.p[k];
+    return LDPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                     const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride, void *received,
+                     void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = sym_mod_check(mod, n)) return rc;
+    if (codeword_stride != 0 && codeword_stride != ((int64_t)n + 7) / 8)
+        return fail(LDPC_ERR_ARG, "codeword_stride must be 0 (one codeword) or ceil(n / 8) = %lld (one packed row per frame)",
+                    (long long)(((int64_t)n + 7) / 8));
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    if (received && ((uintptr_t)received % 16) != 0) return fail(LDPC_ERR_ARG, "received must be 16-byte aligned");
+    return sim_channel_sym_launch((float *)llr, batch, n, seed, stream_id, first_frame, mod, codewords_packed, codeword_stride,
+                                  received, (hipStream_t)stream);
+}
+
+size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture)
+{
+    return ldpc_simulate_enc_workspace_bytes(d, block, capture);
+}
+
+int ldpc_simulate_sym(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
+                      int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    LDPC_NOTHROW(simulate_sym_impl(d, desc, e, mod, capture < 0 ? -1 : capture, out_state, out_diag, workspace, workspace_bytes,
+                                   stream))
+}
+
+}  // extern "C"

@@ -136,7 +136,51 @@ def awgn_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: 
     return out
 
 
-MIX_MAX_POINTS = 4096      # ldpc_channel_awgn_mix: n_points <= 4096, batch <= 2^31 - 1 (the point index stays in 32 bits)
+def _check_modulation(modulation):
+    from modulation import Modulation
+    if not isinstance(modulation, Modulation):
+        raise ValueError("modulation must be a modulation.Modulation")
+    return modulation
+
+
+def _symbol_amp(modulation, snr_db, amp) -> float:
+    if (snr_db is None) == (amp is None):
+        raise ValueError("with a modulation give either snr_db or amp")
+    return modulation.amp(snr_db) if amp is None else float(amp)
+
+
+def sym_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, modulation, snr_db: Optional[float] = None,
+            amp: Optional[float] = None, codeword=None, device=None, want_received: bool = False):
+    """Max-log LLRs [batch, n] fp32 of frames first_frame .. first_frame + batch - 1 sent as Gray-mapped symbols of `modulation`
+    (a modulation.Modulation) over AWGN or per-symbol Rayleigh fading (ldpc_channel_sym; defined in include/ldpc_hip.h and
+    INTEGRATION.md 6f): frame f gets the same noise and fading whatever block it is drawn in.  Give snr_db (Es/N0) or amp, the
+    constellation's half-spacing over the per-dimension noise standard deviation.  codeword: None (all zero), a 0/1 array of
+    length n, a packed uint8 tensor, or a 2-D uint8 tensor [batch, ceil(n/8)] of one packed codeword per frame, as
+    ``encode_random`` returns them.  want_received: -> (llr, received), received fp32 [batch, S, 4] = (vI, vQ, e, 0) per
+    symbol, e the fading gain times amp (vQ = 0 for BPSK) -- for a constellation plot or a demapper of your own."""
+    dev = _require_gpu(device)
+    mod = _check_modulation(modulation)
+    amp = _symbol_amp(mod, snr_db, amp)
+    batch, n = int(batch), int(n)
+    if batch < 0 or n < 1:
+        raise ValueError("batch must be >= 0 and n >= 1")
+    rows = isinstance(codeword, torch.Tensor) and codeword.dim() == 2
+    cw = _codeword_rows(codeword, batch, n, dev) if rows else _channel_codeword(codeword, n, dev)
+    desc, _keep = mod.native(amp, n, dev)
+    lib = nat.load()
+    out = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    rec = torch.empty((batch, mod.symbols(n), 4), dtype=torch.float32, device=dev) if want_received else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(lib.ldpc_channel_sym(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
+                                       int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), C.byref(desc),
+                                       None if cw is None else C.c_void_p(cw.data_ptr()), (n + 7) // 8 if rows else 0,
+                                       None if rec is None else C.c_void_p(rec.data_ptr()), C.c_void_p(stream)),
+                  "ldpc_channel_sym")
+    return (out, rec) if want_received else out
+
+
+MIX_MAX_POINTS = 4096     # ldpc_channel_awgn_mix: n_points <= 4096, batch <= 2^31 - 1 (the point index stays in 32 bits)
 
 
 def snr_grid(snr_range, snr_step: float) -> np.ndarray:
@@ -750,7 +794,7 @@ class DecodeEngine:
     def simulate(self, *, seed: int, max_frames: int, max_errors: int, stream_id: int = 0, first_frame: int = 0,
                  snr_db: Optional[float] = None, scale: Optional[float] = None, shift: Optional[float] = None,
                  codeword=None, block: int = 65536, poll_blocks: int = 4, diagnostics: bool = False,
-                 capture: int = 0, rate_matching=None) -> dict:
+                 capture: int = 0, rate_matching=None, modulation=None, amp: Optional[float] = None) -> dict:
         """One SNR point on the device (ldpc_simulate): blocks of `block` frames of the counter-based AWGN stream, early-stop
         decode, in-order error counters, one host round trip every `poll_blocks` blocks.  -> {frames, frame_errors,
         bit_errors, iterations, done, blocks_seen}; all but blocks_seen are independent of block and poll_blocks.
@@ -760,7 +804,16 @@ class DecodeEngine:
         first_frame=frame, ...) draws such a frame again.  rate_matching: the profile on the channel and the counters
         (ldpc_simulate_rm / _diag_rm).  codeword="random": a fresh codeword per frame, drawn on the device from the point's
         seed, stream_id and frame index with the encoder of this engine's graph (ldpc_simulate_enc); a recorded frame's
-        codeword is ``encode_random(self.encoder(), 1, first_frame=frame, ...)``.  Synchronous."""
+        codeword is ``encode_random(self.encoder(), 1, first_frame=frame, ...)``.  modulation: a modulation.Modulation -- the
+        point runs on the symbol channel of ``sym_llr`` (ldpc_simulate_sym) at snr_db or `amp`; scale / shift and
+        rate_matching do not apply to it.  Synchronous."""
+        if modulation is not None:
+            return self._simulate_sym(_check_modulation(modulation), seed=seed, max_frames=max_frames, max_errors=max_errors,
+                                      stream_id=stream_id, first_frame=first_frame, snr_db=snr_db, amp=amp, scale=scale,
+                                      shift=shift, codeword=codeword, block=block, poll_blocks=poll_blocks,
+                                      diagnostics=diagnostics, capture=capture, rate_matching=rate_matching)
+        if amp is not None:
+            raise ValueError("amp belongs to a modulation: give snr_db or (scale, shift)")
         if (snr_db is None) == (scale is None or shift is None):
             raise ValueError("give either snr_db or both scale and shift")
         if snr_db is not None:
@@ -811,6 +864,48 @@ class DecodeEngine:
             else:
                 nat.check(self._lib.ldpc_simulate(self.handle, C.byref(desc), nat.ptr(out), C.c_void_p(ws.data_ptr()),
                                                   ws.numel(), C.c_void_p(stream)), "ldpc_simulate")
+        res = {k: int(v) for k, v in zip(SIM_COUNTERS, out)}
+        if diagnostics:
+            res.update(parse_sim_diag(words, self.iters, capture))
+            res["detected_errors"] = res["frame_errors"] - res["undetected_errors"]
+        return res
+
+    def _simulate_sym(self, mod, *, seed, max_frames, max_errors, stream_id, first_frame, snr_db, amp, scale, shift, codeword,
+                      block, poll_blocks, diagnostics, capture, rate_matching) -> dict:
+        """simulate(modulation=mod): one native call of ldpc_simulate_sym"""
+        if rate_matching is not None:
+            raise ValueError("rate matching together with a modulation is not provided")
+        if scale is not None or shift is not None:
+            raise ValueError("scale and shift belong to the BI-AWGN channel: with a modulation give snr_db or amp")
+        amp = _symbol_amp(mod, snr_db, amp)
+        random = isinstance(codeword, str)                     # (a float64 engine is refused by the native call)
+        if random and codeword != "random":
+            raise ValueError(f"codeword must be None, a 0/1 array, a packed uint8 tensor or 'random', got {codeword!r}")
+        ne = _NativeEncoder.get(self.encoder(), self.device) if random else None
+        cw = None if random else _channel_codeword(codeword, self.graph.n, self.device)
+        mdesc, _keep = mod.native(amp, self.graph.n, self.device)
+        desc = nat.SimDesc()
+        desc.seed, desc.stream_id = int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1)
+        desc.first_frame = int(first_frame) & (2 ** 64 - 1)
+        desc.scale, desc.shift = 0.0, 0.0
+        desc.codeword_packed = None if cw is None else cw.data_ptr()
+        desc.max_frames, desc.max_errors = int(max_frames), int(max_errors)
+        desc.block, desc.poll_blocks = int(block), int(poll_blocks)
+        out = np.zeros(8, dtype=np.int64)
+        capture = int(capture)
+        if capture < 0 or (capture and not diagnostics):
+            raise ValueError("capture must be >= 0 and needs diagnostics=True")
+        words = np.zeros(sim_diag_words(self.iters, capture), dtype=np.int64) if diagnostics else None
+        need = int(self._lib.ldpc_simulate_sym_workspace_bytes(self.handle, max(int(block), 1), capture if diagnostics else -1))
+        ws = getattr(self, "_sim_ws", None)
+        if ws is None or ws.numel() < need:
+            self._sim_ws = None
+            self._sim_ws = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            nat.check(self._lib.ldpc_simulate_sym(self.handle, C.byref(desc), None if ne is None else ne.handle, C.byref(mdesc),
+                                                  capture if diagnostics else -1, nat.ptr(out), nat.ptr(words),
+                                                  C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)), "ldpc_simulate_sym")
         res = {k: int(v) for k, v in zip(SIM_COUNTERS, out)}
         if diagnostics:
             res.update(parse_sim_diag(words, self.iters, capture))

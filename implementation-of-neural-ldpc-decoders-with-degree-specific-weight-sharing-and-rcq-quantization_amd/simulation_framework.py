@@ -34,6 +34,10 @@ Channel (``SimulationConfig.channel``):
             ``LDPSimulator.replay_errors`` draws and decodes recorded frames again.
             ``SimulationConfig.rate_matching`` (this channel only) punctures and shortens bits on the channel and restricts
             the error counters to its count mask; the bit error rate is then per counted bit.
+            ``SimulationConfig.modulation`` (this channel only; a ``modulation.Modulation``) sends the bits as Gray-mapped BPSK /
+            QPSK / 16- / 64- / 256-QAM symbols over AWGN or per-symbol Rayleigh fading and demaps them with the max-log rule
+            (``engine.sym_llr``); ``snr_db`` is then Es/N0 of the symbol.  Not together with
+            ``rate_matching``; from 16-QAM up it needs ``codeword="random"`` (or a codeword).
 """
 
 from __future__ import annotations
@@ -45,7 +49,7 @@ import threading
 import time
 import warnings
 from concurrent.futures import ThreadPoolExecutor, as_completed
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -54,6 +58,7 @@ import torch
 from ldpc_decoder import BasicMinSumDecoder, LDPCCode
 from neural_2d_decoder import Neural2DMinSumDecoder, Neural2DOffsetMinSumDecoder
 from neural_minsum_decoder import NeuralMinSumDecoder, NeuralOffsetMinSumDecoder
+from modulation import Modulation
 from rate_matching import RateMatching
 from rcq_decoder import RCQMinSumDecoder, WeightedRCQDecoder
 
@@ -85,8 +90,24 @@ class SimulationConfig:
     diagnostics: bool = False               # channel="device": undetected errors, stop-iteration histogram, failing frames
     capture_errors: int = 0                 # ... record the first so many frame errors of every point (implies diagnostics)
     rate_matching: Optional[RateMatching] = None   # channel="device": punctured / shortened bits and the counters' mask
+    # channel="device": Gray-mapped symbols over AWGN or Rayleigh fading, max-log demapper.  An init-only argument kept as a
+    # plain attribute: the dataclass fields (and with them repr, ==, the reference's field list) stay the twenty above
+    modulation: InitVar[Optional[Modulation]] = None
 
-    def __post_init__(self):
+    def __post_init__(self, modulation=None):
+        self.modulation = modulation
+        if self.modulation is not None:
+            if not isinstance(self.modulation, Modulation):
+                raise ValueError("modulation must be a modulation.Modulation")
+            if self.channel != "device":
+                raise ValueError("modulation needs channel='device'")
+            if self.rate_matching is not None:
+                raise ValueError("rate_matching together with modulation is not provided (DESIGN.md section 3j)")
+            if self.llr_convention != "decoder":
+                raise ValueError("modulation maps bit 0 to the positive half: llr_convention must be 'decoder'")
+            if self.modulation.bits_per_symbol >= 4 and self.codeword is None:
+                raise ValueError(f"{self.modulation.scheme} with the all-zero codeword sends one corner point only and its bit "
+                                 f"channels are not output-symmetric: set codeword=\"random\" (or give a codeword)")
         if self.rate_matching is not None:
             if not isinstance(self.rate_matching, RateMatching):
                 raise ValueError("rate_matching must be a rate_matching.RateMatching")
@@ -328,7 +349,20 @@ class LDPSimulator:
         random = isinstance(cfg.codeword, str)            # "random": a fresh codeword per frame
         cw = "random" if random else None if cfg.codeword is None else _engine.pack_codeword(cfg.codeword, n, eng.device)
         rm = cfg.rate_matching
+        mod = cfg.modulation
+
+        def draw(frames, first, cw):                       # the block's LLRs: the symbol channel under a modulation
+            if mod is not None:
+                return _engine.sym_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=first, modulation=mod,
+                                       snr_db=snr_db, codeword=cw, device=eng.device)
+            return _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=first, scale=scale,
+                                    shift=shift, codeword=cw, device=eng.device, rate_matching=rm)
+
         if eng.info()["engine"] == "resident":
+            if mod is not None:
+                return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, snr_db=snr_db, modulation=mod, codeword=cw,
+                                    max_frames=max_frames, max_errors=max_errors, block=block,
+                                    poll_blocks=max(1, int(cfg.poll_blocks)), diagnostics=diagnostics, capture=capture)
             return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, scale=scale, shift=shift, codeword=cw,
                                 max_frames=max_frames, max_errors=max_errors, block=block,
                                 poll_blocks=max(1, int(cfg.poll_blocks)), diagnostics=diagnostics, capture=capture,
@@ -341,8 +375,7 @@ class LDPSimulator:
             if random:                                                          # the block's codeword rows
                 cw = _engine.encode_random(eng.encoder(), frames, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn,
                                            device=eng.device)
-            llr = _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn, scale=scale,
-                                   shift=shift, codeword=cw, device=eng.device, rate_matching=rm)
+            llr = draw(frames, drawn, cw)
             if diagnostics:
                 packed, iters, success = _decode_block_flags(eng, llr, cap)
                 eng.sim_count(state, packed, iters, max_frames=max_frames, max_errors=max_errors, codeword=cw,
@@ -378,8 +411,13 @@ class LDPSimulator:
         frames = [int(f) for f in np.asarray(frames).reshape(-1)]
         words = [_engine.encode_random(eng.encoder(), 1, seed=int(cfg.seed), stream_id=stream_id, first_frame=f,
                                        device=eng.device) for f in frames] if random else [cw] * len(frames)
-        rows = [_engine.awgn_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, scale=scale, shift=shift,
-                                 codeword=c, device=eng.device, rate_matching=cfg.rate_matching) for f, c in zip(frames, words)]
+        if cfg.modulation is not None:                     # the symbol channel draws a frame again just the same
+            rows = [_engine.sym_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, modulation=cfg.modulation,
+                                    snr_db=float(snr_db), codeword=c, device=eng.device) for f, c in zip(frames, words)]
+        else:
+            rows = [_engine.awgn_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, scale=scale, shift=shift,
+                                     codeword=c, device=eng.device, rate_matching=cfg.rate_matching)
+                    for f, c in zip(frames, words)]
         llr = torch.cat(rows, dim=0) if rows else torch.empty((0, code.n), dtype=torch.float32, device=eng.device)
         with torch.no_grad():
             res = eng.decode(llr, early_stop=True)

@@ -63,6 +63,10 @@ enter the C ABI of include/ldpc_hip.h (ldpc_decode / ldpc_decode_saving / ldpc_b
                  Device device) -> Tensor llr
      the counter-based BI-AWGN channel (ldpc_channel_awgn): fp32 LLRs [batch, n] of frames first_frame .. of stream
      (seed, stream_id), the same whatever block a frame is drawn in; needs no engine.
+  ldpc::sym_llr(int batch, int n, int seed, int stream_id, int first_frame, str scheme, bool rayleigh, float amp,
+                Tensor? interleaver, Tensor? codeword_packed, Device device) -> Tensor llr
+     the symbol channel (ldpc_channel_sym): max-log LLRs of Gray-mapped "bpsk" / "qpsk" / "qam16" / "qam64" / "qam256" symbols
+     over AWGN or per-symbol Rayleigh fading; codeword_packed is one packed word or [batch, ceil(n/8)] rows; needs no engine.
   ldpc::awgn_llr_mix(int batch, int n, int seed, int stream_id, int first_frame, Tensor scale_tab, Tensor shift_tab,
                      Tensor? codeword_packed, Device device) -> Tensor llr
      the same stream with the SNR point a function of the frame (ldpc_channel_awgn_mix): frame f is drawn with
@@ -159,6 +163,22 @@ def awgn_llr(batch: int, n: int, seed: int, stream_id: int, first_frame: int, sc
 
 @awgn_llr.register_fake
 def _(batch, n, seed, stream_id, first_frame, scale, shift, codeword_packed, device):
+    return torch.empty((batch, n), dtype=torch.float32, device=device)
+
+
+@torch.library.custom_op("ldpc::sym_llr", mutates_args=())
+def sym_llr(batch: int, n: int, seed: int, stream_id: int, first_frame: int, scheme: str, rayleigh: bool, amp: float,
+            interleaver: Optional[Tensor], codeword_packed: Optional[Tensor], device: torch.device) -> Tensor:
+    import engine
+    from modulation import Modulation
+    mod = Modulation(scheme, "rayleigh" if rayleigh else None,
+                     None if interleaver is None else interleaver.detach().cpu().numpy())
+    return engine.sym_llr(batch, n, seed=seed, stream_id=stream_id, first_frame=first_frame, modulation=mod, amp=amp,
+                          codeword=codeword_packed, device=device)
+
+
+@sym_llr.register_fake
+def _(batch, n, seed, stream_id, first_frame, scheme, rayleigh, amp, interleaver, codeword_packed, device):
     return torch.empty((batch, n), dtype=torch.float32, device=device)
 
 

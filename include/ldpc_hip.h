@@ -602,6 +602,73 @@ int ldpc_simulate_enc(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
                       int64_t capture, int64_t out_state[8], int64_t *out_diag /* host, or NULL when capture < 0 */,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- symbol channel: Gray-mapped QAM over AWGN or Rayleigh fading, max-log demapper -------------
+ * The channels above are binary-input AWGN.  The bit levels of a Gray-mapped 16- / 64- / 256-QAM symbol are unequal channels
+ * and not output-symmetric, so they need the per-frame codewords of the section above.  Everything above is unchanged.
+ *
+ * Modulation.  m = bits_per_symbol in {1, 2, 4, 6, 8}: BPSK, QPSK, 16-, 64-, 256-QAM, every constellation of unit average
+ * energy.  A frame of n bits is S = ceil(n / m) symbols.  Transmit index t = s * m + k is bit k of symbol s and carries the
+ * codeword bit of variable position[t] (an interleaver: a permutation of 0 .. n-1 on the device, which the caller vouches for;
+ * NULL is the identity).  Transmit indices >= n in the last symbol are pad bits: sent as 0, nothing is stored for them.
+ * For m >= 2 the first h = m / 2 bits of a symbol label the I axis and the next h the Q axis; m = 1 has an I axis (h = 1) only.
+ * An axis is Gray-labelled 2^h-PAM: level index i = gray_to_binary(b_0 .. b_{h-1}) with b_0 the most significant bit (the
+ * running XOR), integer amplitude a = (2^h - 1) - 2 i.  So b_0 = 0 is the positive half and a lone bit 0 is +1: the decoders'
+ * convention, bit 0 -> positive LLR.
+ *
+ * Noise stream.  Symbol s of frame f draws
+ *     (x0, x1, x2, x3) = Philox4x32-10(counter = (f & 0xffffffff, f >> 32, 0x40000000 | s, stream_id),
+ *                                      key = (seed & 0xffffffff, seed >> 32))
+ * The BI-AWGN stream's third counter word is a quad index below 2^29 + 256 and the information-bit stream sets the top bit, so
+ * the three are disjoint under one (seed, stream_id) as long as S < 2^29 (LDPC_ERR_UNSUPPORTED otherwise).
+ *     (zI, zQ) = the Box-Muller pair of (x0, x1) exactly as the noise stream above forms z[4q], z[4q+1]; m = 1 uses zI only
+ *     fading 0:  g = 1.0f (x2, x3 unused)
+ *     fading 1:  g = sqrtf(-logf(u(x2))): Rayleigh amplitude with E g^2 = 1, independent per symbol, known to the receiver
+ * A frame draws the same zI, zQ with and without fading.
+ *
+ * Received sample and demapper, all fp32, every multiply and add rounded on its own (no fused multiply-add).  `amp` is the
+ * constellation's half-spacing over the per-dimension noise standard deviation.  Per axis, with sent amplitude a:
+ *     e = g * amp;   v = e * (float)a + z
+ *     for every candidate a':  t = v - e * (float)a',  D(a') = t * t
+ *     bit k of the axis:       llr = 0.5f * (min_{a': b_k = 1} D - min_{a': b_k = 0} D)
+ * the max-log LLR, exact for BPSK and QPSK; llr[b][position[t]] receives it.  With N0 = 10^(-snr_db / 10) and Es = 1:
+ * BPSK has real noise of variance N0, amp = 1 / sqrt(N0); m >= 2 has N0 / 2 per dimension and half-spacing
+ * d = sqrt(3 / (2 (4^h - 1))), amp = d / sqrt(N0 / 2).  2 amp is the `scale` of ldpc_channel_awgn for m = 1 and m = 2, and QPSK
+ * at snr_db is, in law, the BI-AWGN channel at the same snr_db.
+ *
+ * ldpc_channel_sym : llr [batch][n] fp32 (device, 4-byte aligned) of frames first_frame .. first_frame + batch - 1.
+ *   codeword_stride = ceil(n / 8): one packed row per frame, as ldpc_encode_random writes them; 0: one word for every frame;
+ *   codewords_packed NULL: the all-zero word.  received, when not NULL: fp32 [batch][S][4] = (vI, vQ, e, 0.0f), 16-byte
+ *   aligned, vQ = 0.0f for m = 1 -- the samples for a constellation plot or a demapper of the caller's own.
+ *   LDPC_ERR_ARG for batch < 0, n < 1, a NULL mod, bits_per_symbol outside {1, 2, 4, 6, 8}, fading outside {0, 1}, amp not
+ *   finite or < 0, a stride other than 0 and ceil(n / 8); LDPC_ERR_UNSUPPORTED for S >= 2^29; then batch == 0 returns LDPC_OK
+ *   without touching a device pointer; then LDPC_ERR_ARG for a NULL or misaligned llr and a misaligned received.
+ *   Asynchronous on `stream`, allocates nothing, safe under stream capture.
+ *
+ * ldpc_simulate_sym : the loop of ldpc_simulate_enc with this channel.  Per block: ldpc_encode_random when e != NULL,
+ *   otherwise desc->codeword_packed (NULL: all-zero) for every frame; ldpc_channel_sym; ldpc_decode; the decisions XORed with
+ *   the codeword rows (e == NULL: the counters compare with the one word instead); the counters.  capture < 0: no diagnostics
+ *   (out_diag unused).  Records, replay and the independence of block and poll_blocks are those of ldpc_simulate_enc; a
+ *   recorded frame is drawn again by ldpc_encode_random and ldpc_channel_sym with batch = 1, first_frame = record[0].
+ *   desc->scale and desc->shift are ignored; desc->codeword_packed must be NULL when e != NULL.  float64 decoders:
+ *   LDPC_ERR_UNSUPPORTED.  workspace: ldpc_simulate_sym_workspace_bytes(d, block, capture).  Synchronous, as ldpc_simulate.
+ *
+ * Not provided: rate matching together with a modulation, the exact log-sum-exp demapper (`received` lets a caller write
+ * one), PSK above 4 points and APSK, block fading, training on this channel, fp64 LLRs. */
+typedef struct {
+    int32_t bits_per_symbol;      /* 1, 2, 4, 6, 8 */
+    int32_t fading;               /* 0 none, 1 Rayleigh per symbol */
+    float   amp;                  /* finite, >= 0 */
+    const int32_t *position;      /* device, n entries, or NULL */
+} ldpc_modulation;
+
+int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                     const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride,
+                     void *received /* or NULL */, void *stream);
+size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture);
+int ldpc_simulate_sym(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
+                      const ldpc_modulation *mod, int64_t capture, int64_t out_state[8], int64_t *out_diag,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
 /* sha256 (hex) over the sources and the compile recipe this library was built from, embedded at build time
