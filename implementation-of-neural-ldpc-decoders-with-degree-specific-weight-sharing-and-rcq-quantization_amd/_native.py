@@ -164,7 +164,7 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_simulate_rm", "ldpc_simulate_diag_rm",
                    "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode", "ldpc_encode_random",
                    "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc",
-                   "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym")
+                   "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym", "ldpc_channel_sym_mix")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -323,6 +323,8 @@ def load():
         mod = C.POINTER(ModulationDesc)
         lib.ldpc_channel_sym.restype = C.c_int
         lib.ldpc_channel_sym.argtypes = [vp, i64, i32, u64, u32, u64, mod, vp, i64, vp, vp]
+        lib.ldpc_channel_sym_mix.restype = C.c_int
+        lib.ldpc_channel_sym_mix.argtypes = [vp, i64, i32, u64, u32, u64, mod, vp, i32, vp, i64, vp, vp]
         lib.ldpc_simulate_sym_workspace_bytes.restype = C.c_size_t
         lib.ldpc_simulate_sym_workspace_bytes.argtypes = [vp, i64, i64]
         lib.ldpc_simulate_sym.restype = C.c_int

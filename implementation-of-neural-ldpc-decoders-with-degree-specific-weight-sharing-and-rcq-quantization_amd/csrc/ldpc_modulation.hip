@@ -1,6 +1,7 @@
 // ldpc_modulation.hip -- a symbol channel for the on-device Monte-Carlo path: Gray-mapped BPSK / QPSK / 16- / 64- / 256-QAM over
-// AWGN or per-symbol Rayleigh fading with a max-log demapper (ldpc_channel_sym) and the host loop of one SNR point on it
-// (ldpc_simulate_sym) of include/ldpc_hip.h.
+// AWGN or per-symbol Rayleigh fading with a max-log demapper (ldpc_channel_sym), the host loop of one SNR point on it
+// (ldpc_simulate_sym) and the training draw with one SNR point per frame and the sent bits as targets (ldpc_channel_sym_mix)
+// of include/ldpc_hip.h.
 //
 // Included by ldpc_hip.hip below ldpc_encode.hip (it uses ldpc_sim.hip's Philox rounds, uniforms, Box-Muller, counters and
 // workspace carving and ldpc_encode.hip's encoder launch and row XOR): still the one compiled unit.
@@ -161,19 +162,103 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__
     }
 }
 
+// sim_channel_sym with the SNR point a function of the frame and the sent bits as training targets (ldpc_channel_sym_mix):
+// amp = amp_tab[p], p = f mod K of the absolute frame index f = first_frame + b, the remainder taken as sim_channel_awgn_mix
+// takes it (p0 = first_frame mod K and Kinv = floor((2^32 - 1) / K) from the host, b <= 2^31 - 1 and K <= 4096 keep
+// r = b + p0 below 2^32, umulhi and one conditional subtraction).  The table read is issued before the Philox rounds and
+// hidden behind them; a wave covers 64 / S + 1 rows at most, so it is nearly wave-uniform, and 4096 floats stay in cache.
+// The lane-per-symbol mapping, the counters, the normals, the fading gain, sym_axis and the stores are sim_channel_sym's,
+// which is left as it is: a frame gets what that kernel gives it at amp = amp_tab[p], bit for bit.  targets, when not NULL,
+// receives the symbol's bits as 0.0f / 1.0f where the LLRs go: the lane holds them in `bits` already.  The two rows start at
+// unrelated addresses, so each output picks its store widths from its own address; pad bits are stored in neither.
+template <int M, bool FADING, bool PERM>
+__global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restrict__ llr, float *__restrict__ targets,
+                                                                 long long batch, int n, unsigned S, uint32_t k0, uint32_t k1,
+                                                                 uint32_t stream_id, unsigned long long first_frame,
+                                                                 unsigned p0, unsigned K, unsigned Kinv,
+                                                                 const float *__restrict__ amp_tab,
+                                                                 const int *__restrict__ pos, const uint8_t *__restrict__ cw,
+                                                                 long long cw_stride)
+{
+    constexpr int H = M == 1 ? 1 : M / 2;
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
+    const unsigned long long b0 = g0 / S;
+    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
+    const unsigned db = t / S;
+    const long long b = (long long)b0 + db;
+    const unsigned s = t - db * S;
+    if (b >= batch) return;
+    const unsigned r = (unsigned)b + p0;
+    unsigned pt = r - __umulhi(r, Kinv) * K;                                      // in [0, 2K), as in sim_channel_awgn_mix
+    if (pt >= K) pt -= K;                                                         // (first_frame + b) mod K
+    const float amp = amp_tab[pt];
+    const int j0 = (int)s * M;                                                    // < n <= 2^31 - 1
+    const int cnt = n - j0 < M ? n - j0 : M;
+    const int rb = (n + 7) >> 3;
+    const uint8_t *row = cw ? cw + (size_t)b * (size_t)cw_stride : nullptr;
+    int p[M];                                                                     // permuted path: the symbol's variables
+    (void)p; (void)rb;
+    unsigned bits = 0;                                                           // bit k of the symbol at bit k; pad bits 0
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k) {
+            p[k] = k < cnt ? pos[j0 + k] : 0;
+            if (row && k < cnt) bits |= ((unsigned)(row[p[k] >> 3] >> (p[k] & 7)) & 1u) << k;
+        }
+    } else if (row) {
+        const int byte = j0 >> 3, sh = j0 & 7;
+        unsigned w = row[byte];
+        if (M == 6 && byte + 1 < rb) w |= (unsigned)row[byte + 1] << 8;           // six bits from bit 4 or 6 on reach into the next byte
+        bits = (w >> sh) & ((1u << cnt) - 1u);
+    }
+    const unsigned long long f = first_frame + (unsigned long long)b;
+    uint32_t x[4];
+    philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), kSymCounterTag | s, stream_id, k0, k1, x);
+    float zI, zQ;
+    sim_box_muller(x[0], x[1], zI, zQ);
+    float g = 1.0f;
+    if (FADING) g = sqrtf(-logf(sim_uniform(x[2])));
+    const float e = g * amp;
+    float v[M];
+    sym_axis<H>(bits & ((1u << H) - 1u), e, zI, v);
+    if constexpr (M > 1) sym_axis<H>(bits >> H, e, zQ, v + H);
+    float *dst = llr + (size_t)b * (size_t)n;
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k)
+            if (k < cnt) dst[p[k]] = v[k];
+    } else {
+        sym_store<M>(dst + j0, v, cnt);
+    }
+    if (targets) {
+        float sent[M];
+#pragma unroll
+        for (int k = 0; k < M; ++k) sent[k] = ((bits >> k) & 1u) ? 1.0f : 0.0f;
+        float *tdst = targets + (size_t)b * (size_t)n;
+        if constexpr (PERM) {
+#pragma unroll
+            for (int k = 0; k < M; ++k)
+                if (k < cnt) tdst[p[k]] = sent[k];
+        } else {
+            sym_store<M>(tdst + j0, sent, cnt);
+        }
+    }
+}
+
 }  // namespace ldpc
 
 namespace {
 
-// the scalar part of a modulation descriptor (the position table is a device pointer: the caller vouches for it)
-int sym_mod_check(const ldpc_modulation *mod, int32_t n)
+// the scalar part of a modulation descriptor (the position table is a device pointer: the caller vouches for it); the mix
+// entry reads its amplitudes from a device table and passes check_amp = false
+int sym_mod_check(const ldpc_modulation *mod, int32_t n, bool check_amp = true)
 {
     if (!mod) return fail(LDPC_ERR_ARG, "NULL mod");
     const int32_t m = mod->bits_per_symbol;
     if (m != 1 && m != 2 && m != 4 && m != 6 && m != 8)
         return fail(LDPC_ERR_ARG, "bits_per_symbol must be 1, 2, 4, 6 or 8 (BPSK, QPSK, 16- / 64- / 256-QAM), got %d", m);
     if (mod->fading != 0 && mod->fading != 1) return fail(LDPC_ERR_ARG, "fading must be 0 (none) or 1 (Rayleigh per symbol), got %d", mod->fading);
-    if (!(std::isfinite(mod->amp) && mod->amp >= 0.0f)) return fail(LDPC_ERR_ARG, "amp must be finite and >= 0");
+    if (check_amp && !(std::isfinite(mod->amp) && mod->amp >= 0.0f)) return fail(LDPC_ERR_ARG, "amp must be finite and >= 0");
     if (((int64_t)n + m - 1) / m >= (int64_t)kSymMaxSymbols)
         return fail(LDPC_ERR_UNSUPPORTED, "a frame of %lld symbols: the symbol index must stay below 2^29", (long long)(((int64_t)n + m - 1) / m));
     return LDPC_OK;
@@ -223,6 +308,67 @@ int sim_channel_sym_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, 
     default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
     }
 #undef LDPC_SYM_CASE
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+struct SymMixArgs {
+    float *llr, *targets;
+    long long batch;
+    int n;
+    unsigned S;
+    uint32_t k0, k1, stream_id;
+    unsigned long long first_frame;
+    unsigned p0, K, Kinv;
+    const float *amp_tab;
+    const int *pos;
+    const uint8_t *cw;
+    long long cw_stride;
+};
+
+template <int M, bool FADING, bool PERM>
+void sym_mix_launch_one(dim3 grid, hipStream_t s, const SymMixArgs &a)
+{
+    hipLaunchKernelGGL((sim_channel_sym_mix<M, FADING, PERM>), grid, dim3(kSimBlock), 0, s, a.llr, a.targets, a.batch, a.n, a.S,
+                       a.k0, a.k1, a.stream_id, a.first_frame, a.p0, a.K, a.Kinv, a.amp_tab, a.pos, a.cw, a.cw_stride);
+}
+
+template <int M>
+void sym_mix_launch_m(bool fading, bool perm, dim3 grid, hipStream_t s, const SymMixArgs &a)
+{
+    if (fading) {
+        if (perm) sym_mix_launch_one<M, true, true>(grid, s, a);
+        else sym_mix_launch_one<M, true, false>(grid, s, a);
+    } else {
+        if (perm) sym_mix_launch_one<M, false, true>(grid, s, a);
+        else sym_mix_launch_one<M, false, false>(grid, s, a);
+    }
+}
+
+// one launch of sim_channel_sym_mix; mod has passed sym_mod_check, 1 <= n_points <= 4096 and batch <= 2^31 - 1
+int sim_channel_sym_mix_launch(float *llr, float *targets, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id,
+                               uint64_t first_frame, const ldpc_modulation *mod, const float *amp_tab, int32_t n_points,
+                               const uint8_t *cw, int64_t cw_stride, hipStream_t s)
+{
+    const int m = mod->bits_per_symbol;
+    const unsigned S = (unsigned)(((int64_t)n + m - 1) / m);
+    const unsigned long long syms = (unsigned long long)batch * S;
+    const unsigned long long blocks = (syms + kSimBlock - 1) / kSimBlock;
+    if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+    const dim3 grid((unsigned)blocks);
+    const bool perm = mod->position != nullptr, fading = mod->fading != 0;
+    const unsigned K = (unsigned)n_points;
+    const SymMixArgs a{llr, targets, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id,
+                       (unsigned long long)first_frame, (unsigned)(first_frame % K), K, 0xffffffffu / K, amp_tab,
+                       (const int *)mod->position, cw, (long long)cw_stride};
+    switch (m) {
+    case 1: sym_mix_launch_m<1>(fading, perm, grid, s, a); break;
+    case 2: sym_mix_launch_m<2>(fading, perm, grid, s, a); break;
+    case 4: sym_mix_launch_m<4>(fading, perm, grid, s, a); break;
+    case 6: sym_mix_launch_m<6>(fading, perm, grid, s, a); break;
+    case 8: sym_mix_launch_m<8>(fading, perm, grid, s, a); break;
+    default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+    }
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
@@ -332,6 +478,30 @@ int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_
     if (received && ((uintptr_t)received % 16) != 0) return fail(LDPC_ERR_ARG, "received must be 16-byte aligned");
     return sim_channel_sym_launch((float *)llr, batch, n, seed, stream_id, first_frame, mod, codewords_packed, codeword_stride,
                                   received, (hipStream_t)stream);
+}
+
+int ldpc_channel_sym_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         const ldpc_modulation *mod, const float *amp_tab, int32_t n_points, const uint8_t *codewords_packed,
+                         int64_t codeword_stride, void *targets, void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = sym_mod_check(mod, n, false)) return rc;
+    if (codeword_stride != 0 && codeword_stride != ((int64_t)n + 7) / 8)
+        return fail(LDPC_ERR_ARG, "codeword_stride must be 0 (one codeword) or ceil(n / 8) = %lld (one packed row per frame)",
+                    (long long)(((int64_t)n + 7) / 8));
+    if (n_points < 1 || n_points > 4096) return fail(LDPC_ERR_ARG, "n_points must be in 1 .. 4096");
+    if (batch > INT32_MAX) return fail(LDPC_ERR_ARG, "batch > 2^31 - 1");
+    if (batch > 0 && first_frame > (uint64_t)0 - (uint64_t)batch)       // 2^64 - batch: p is not continuous across the wrap
+        return fail(LDPC_ERR_ARG, "first_frame + batch wraps the 64-bit frame index");
+    if (batch > 0 && !amp_tab) return fail(LDPC_ERR_ARG, "NULL amp_tab");
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    if (targets && ((uintptr_t)targets % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "targets must be 4-byte aligned");
+    if (((uintptr_t)amp_tab % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "amp_tab must be 4-byte aligned");
+    return sim_channel_sym_mix_launch((float *)llr, (float *)targets, batch, n, seed, stream_id, first_frame, mod, amp_tab,
+                                      n_points, codewords_packed, codeword_stride, (hipStream_t)stream);
 }
 
 size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture)

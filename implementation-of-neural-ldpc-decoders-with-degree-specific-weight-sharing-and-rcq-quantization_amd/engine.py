@@ -271,6 +271,54 @@ def awgn_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_fra
     return out
 
 
+def sym_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, modulation, snr_db=None, amp=None,
+                codeword=None, device=None, want_targets: bool = False):
+    """``sym_llr`` with the SNR point a function of the frame (ldpc_channel_sym_mix): frame
+    f = first_frame + b is drawn at point f % K of a table of K points and gets, bit for bit, what ``sym_llr`` gives frame f at
+    that point, whatever block it is drawn in (``mix_points`` tells which point a frame has).  Give snr_db, a sequence of K
+    values of Es/N0 (the table is ``modulation.amp_table(snr_db)``), or amp: a 1-D sequence, or a contiguous float32 tensor on
+    the device, whose entries are then the caller's responsibility.  codeword as in ``sym_llr``.  want_targets: ->
+    (llr, targets), targets fp32 [batch, n] = the bits that were sent as 0.0 / 1.0, written by the same kernel: what
+    ``model.joint_posterior_loss(llr, targets)`` takes."""
+    mod = _check_modulation(modulation)
+    if (snr_db is None) == (amp is None):
+        raise ValueError("with a modulation give either snr_db or amp")
+    values = mod.amp_table(snr_db) if amp is None else amp
+    if isinstance(values, torch.Tensor):
+        n_points = values.numel()
+    else:
+        host = np.asarray(values, dtype=np.float64)
+        if host.ndim != 1:
+            raise ValueError("amp must be a 1-D sequence")
+        if not (np.isfinite(host).all() and (host >= 0.0).all()):
+            raise ValueError("amp must be finite and >= 0 at every point")
+        n_points = host.size
+    if not 1 <= n_points <= MIX_MAX_POINTS:
+        raise ValueError(f"the number of SNR points must be in 1 .. {MIX_MAX_POINTS}, got {n_points}")
+    batch, n = int(batch), int(n)
+    if batch < 0 or n < 1:
+        raise ValueError("batch must be >= 0 and n >= 1")
+    if batch > 2 ** 31 - 1:
+        raise ValueError("batch must be <= 2^31 - 1")
+    dev = _require_gpu(device)
+    amp_tab = _mix_table(values, "amp", dev)
+    rows = isinstance(codeword, torch.Tensor) and codeword.dim() == 2
+    cw = _codeword_rows(codeword, batch, n, dev) if rows else _channel_codeword(codeword, n, dev)
+    desc, _keep = mod.native(0.0, n, dev)
+    lib = nat.load()
+    out = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    targets = torch.empty((batch, n), dtype=torch.float32, device=dev) if want_targets else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(lib.ldpc_channel_sym_mix(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
+                                           int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), C.byref(desc),
+                                           C.c_void_p(amp_tab.data_ptr()), n_points,
+                                           None if cw is None else C.c_void_p(cw.data_ptr()), (n + 7) // 8 if rows else 0,
+                                           None if targets is None else C.c_void_p(targets.data_ptr()), C.c_void_p(stream)),
+                  "ldpc_channel_sym_mix")
+    return (out, targets) if want_targets else out
+
+
 SIM_COUNTERS = ("frames", "frame_errors", "bit_errors", "iterations", "done", "blocks_seen")
 ERROR_FRAME_DTYPE = np.dtype([("frame", np.uint64), ("wrong_bits", np.int64), ("iterations", np.int64), ("undetected", np.int64)])
 

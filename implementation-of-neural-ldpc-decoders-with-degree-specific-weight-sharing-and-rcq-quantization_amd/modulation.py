@@ -2,7 +2,8 @@
 Symbol modulation for the on-device Monte-Carlo path: Gray-mapped BPSK / QPSK / 16- / 64- / 256-QAM of unit average energy over
 AWGN or per-symbol Rayleigh fading, demapped with the max-log rule (ldpc_channel_sym of include/ldpc_hip.h; the definition is in
 INTEGRATION.md 6f and DESIGN.md 3j).  ``Modulation`` is the host-side description; ``engine.sym_llr``,
-``DecodeEngine.simulate(modulation=...)`` and ``SimulationConfig(channel="device", modulation=...)`` take it.
+``DecodeEngine.simulate(modulation=...)`` and ``SimulationConfig(channel="device", modulation=...)`` take it, and so do the
+training draw ``engine.sym_llr_mix`` and ``PosteriorJointTrainer(modulation=...)`` (ldpc_channel_sym_mix).
 """
 
 from __future__ import annotations
@@ -66,6 +67,14 @@ class Modulation:
         if self.bits_per_symbol == 1:
             return 1.0 / math.sqrt(n0)
         return half_spacing(self.bits_per_symbol) / math.sqrt(n0 / 2.0)
+
+    def amp_table(self, snr_db) -> np.ndarray:
+        """float32 [K]: ``amp`` of each of the K points of snr_db (Es/N0), computed in double and then cast -- entry p is exactly
+        the value ``engine.sym_llr(snr_db=snr_db[p])`` hands the kernel; the table of ``engine.sym_llr_mix``"""
+        snr = np.asarray(snr_db, dtype=np.float64)
+        if snr.ndim != 1:
+            raise ValueError("snr_db must be a 1-D sequence of SNR points")
+        return np.array([self.amp(float(s)) for s in snr], dtype=np.float64).astype(np.float32)
 
     def symbols(self, n: int) -> int:
         """S = ceil(n / m): symbols of a frame of n bits"""

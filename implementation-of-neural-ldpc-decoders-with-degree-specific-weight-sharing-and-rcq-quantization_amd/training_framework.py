@@ -30,7 +30,9 @@ field and changes nothing.
 Addition, stated: `PosteriorJointTrainer.train_stream` is the same loop without a dataset.  The reference trains on one
 fixed set of 1000 host-drawn frames and never reads its own `snr_step`; `train_stream` draws fresh frames every step from
 the counter-based device noise stream, each mini-batch holding every point of the grid snr_range / snr_step in equal share
-(engine.awgn_llr_mix), reproducible bit for bit from (seed, step).
+(engine.awgn_llr_mix), reproducible bit for bit from (seed, step).  `PosteriorJointTrainer(..., modulation=, codeword=)` puts
+that loop on the symbol channel: Gray-mapped QAM over AWGN or Rayleigh fading with a fresh random codeword per frame, the
+LLRs and the targets of a block from one kernel (engine.sym_llr_mix).
 """
 
 from __future__ import annotations
@@ -93,8 +95,9 @@ def stream_first_frame(g: int, batch_size: int, rank: int = 0, world: int = 1) -
 
 
 class _StreamBlocks:
-    """what `_pass` iterates over in stream training: blocks (first_frame, frames) drawn one by one as (llr, None) -- None is
-    the all-zero codeword -- with `drawn()` called after each block"""
+    """what `_pass` iterates over in stream training: blocks (first_frame, frames) drawn one by one, with `drawn()` called after
+    each block.  `draw` returns the block's LLRs, yielded as (llr, None) -- None is the all-zero codeword -- or the pair
+    (llr, targets) of a draw on per-frame codewords, yielded as it is"""
 
     def __init__(self, blocks, draw, drawn=None):
         self.blocks, self.draw, self.drawn = list(blocks), draw, drawn
@@ -104,10 +107,10 @@ class _StreamBlocks:
 
     def __iter__(self):
         for first, frames in self.blocks:
-            llr = self.draw(first, frames)
+            block = self.draw(first, frames)
             if self.drawn is not None:
                 self.drawn()
-            yield llr, None
+            yield block if isinstance(block, tuple) else (block, None)
 
 
 def _plot_series(panels, figsize, save_path):
@@ -129,12 +132,33 @@ def _plot_series(panels, figsize, save_path):
     plt.show()
 
 
-class PosteriorJointTrainer:
+class _TrainerType(type):
+    """the call ``PosteriorJointTrainer(model, config, *, rate_matching=None, modulation=None, codeword=None)``.  `__init__`
+    keeps the parameter list it has had since rate matching, which callers inspect and subclasses replace; the two
+    symbol-channel keywords are taken here and set on the finished trainer by `_set_symbol_channel`, which refuses what
+    cannot be trained."""
+
+    def __call__(cls, *args, modulation=None, codeword=None, **kwargs):     # the rest is `__init__`'s, a subclass's included
+        trainer = super().__call__(*args, **kwargs)
+        if modulation is not None or codeword is not None:
+            trainer._set_symbol_channel(modulation, codeword)
+        return trainer
+
+
+class PosteriorJointTrainer(metaclass=_TrainerType):
     """Adam on the BCE of the posterior the decoder returns (default), or -- config.joint_posterior_loss -- on the
     weighted sum of every iteration's posterior BCE with the paper's posterior-local gradient; then the history also
     holds each epoch's per-iteration training losses (`train_iteration_losses`, one [T] list per epoch).
     rate_matching (keyword only, a rate_matching.RateMatching): the profile `train_stream` draws its training and validation
-    frames through -- punctured bits enter the decoder as +0.0, shortened ones as +short_llr; `train` does not use it."""
+    frames through -- punctured bits enter the decoder as +0.0, shortened ones as +short_llr; `train` does not use it.
+    modulation (keyword only, a modulation.Modulation): `train_stream` draws its frames on the symbol channel instead
+    (engine.sym_llr_mix: Gray-mapped BPSK .. 256-QAM over AWGN or Rayleigh fading, max-log LLRs, snr_range read as Es/N0) and
+    trains against the bits that were sent.  codeword (with a modulation only): None, the all-zero word (BPSK and QPSK only:
+    from 16-QAM up it sends one corner point and the bit levels are not output-symmetric); "random", a fresh codeword per frame
+    (engine.encode_random on the code's graph); or a 0/1 array of length n, one word for every frame.  `train`, the
+    host-drawn BI-AWGN dataset, refuses a trainer with a modulation."""
+
+    modulation, codeword = None, None                 # the symbol channel of train_stream: set by _set_symbol_channel
 
     def __init__(self, model: nn.Module, config: TrainingConfig, *, rate_matching=None):
         self.model, self.config = model, config
@@ -143,6 +167,7 @@ class PosteriorJointTrainer:
             if not isinstance(rate_matching, RateMatching):
                 raise ValueError("rate_matching must be a rate_matching.RateMatching")
         self.rate_matching = rate_matching
+        self._stream_encoder = None                   # train_stream under codeword="random": (graph, codes.Encoder)
         self.device = torch.device(config.device)
         self.model.to(self.device)
         self.optimizer = optim.Adam(self.model.parameters(), lr=config.learning_rate)
@@ -160,6 +185,33 @@ class PosteriorJointTrainer:
         # model.parameters(): Adam keeps its state per parameter in that parameter's dtype)
         self.quantizer_params: List[List[Tuple[float, float]]] = []
         logger.info("trainer ready: %d trainable scalars", sum(p.numel() for p in model.parameters()))
+
+    def _set_symbol_channel(self, modulation, codeword):
+        """the keywords `modulation` and `codeword` of the constructor call, checked against the rest of the trainer"""
+        config, rate_matching = self.config, self.rate_matching
+        if modulation is None:
+            if codeword is not None:
+                raise ValueError("codeword needs a modulation: per-frame codewords on the BI-AWGN stream are not provided "
+                                 "(Modulation('qpsk') is that channel in law at the same snr_db)")
+        else:
+            from modulation import Modulation
+            if not isinstance(modulation, Modulation):
+                raise ValueError("modulation must be a modulation.Modulation")
+            if rate_matching is not None:
+                raise ValueError("rate_matching together with modulation is not provided (DESIGN.md section 3j)")
+            if config.llr_convention != "decoder":
+                raise ValueError("modulation maps bit 0 to the positive half: llr_convention must be 'decoder'")
+            if isinstance(codeword, str):
+                if codeword != "random":
+                    raise ValueError(f"codeword must be None, 'random' or a 0/1 array, got {codeword!r}")
+            elif codeword is not None:
+                codeword = np.asarray(codeword)
+                if codeword.ndim != 1 or not np.isin(codeword, (0, 1)).all():
+                    raise ValueError("codeword must be None, 'random' or a 0/1 array of length n")
+            elif modulation.bits_per_symbol >= 4:
+                raise ValueError(f"{modulation.scheme} with the all-zero codeword sends one corner point only and its bit "
+                                 f"levels are not output-symmetric: train with codeword='random'")
+        self.modulation, self.codeword = modulation, codeword
 
     # ---- data ------------------------------------------------------------------------------------------
     def generate_training_data(self, code: LDPCCode, num_samples: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -245,6 +297,9 @@ class PosteriorJointTrainer:
         return self._pass(val_loader, train=False)
 
     def train(self, code: LDPCCode, num_train_samples: int = 1000, num_val_samples: int = 200) -> Dict[str, List[float]]:
+        if self.modulation is not None:
+            raise ValueError("train draws its dataset on the host as all-zero BI-AWGN frames: a trainer with a modulation "
+                             "trains with train_stream")
         bs = self.config.batch_size
         train_loader = DataLoader(TensorDataset(*self.generate_training_data(code, num_train_samples)), batch_size=bs, shuffle=True)
         val_loader = DataLoader(TensorDataset(*self.generate_training_data(code, num_val_samples)), batch_size=bs, shuffle=False)
@@ -279,6 +334,10 @@ class PosteriorJointTrainer:
         config.data_parallel with an initialised process group); the transmitted codeword is all zero; with the trainer's
         rate_matching the draw is engine.awgn_llr_mix(..., rate_matching=...), the same frames with the profile applied.  A run is reproducible
         bit for bit from (seed, step); with config.seed None a seed is drawn once, kept in self.stream_seed and logged.
+        With the trainer's modulation the draw of a block is instead engine.encode_random(Encoder.from_graph(graph), frames,
+        seed, stream_id, first_frame) under codeword="random", then engine.sym_llr_mix(..., want_targets=True) at the table
+        modulation.amp_table(grid), the grid read as Es/N0: the block is (llr, targets) and loss, accuracy and validation are
+        computed against the bits that were sent; steps, streams and frame ranges are the same.
         After each epoch frames 0 .. val_frames - 1 of stream val_stream_id are validated, the same frames every epoch.
         -> the history of `train` plus val_losses, val_accuracies, snr_points (the grid) and val_fer_per_point (per epoch,
         the frame-error rate of each of the K points; nan for a point no validation frame falls on)."""
@@ -298,12 +357,36 @@ class PosteriorJointTrainer:
         world, rank = 1, 0
         if cfg.data_parallel and torch.distributed.is_available() and torch.distributed.is_initialized():
             world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
-        scale_tab, shift_tab = engine.awgn_mix_tables(grid, cfg.llr_convention, self.device)
+        if self.modulation is None:
+            scale_tab, shift_tab = engine.awgn_mix_tables(grid, cfg.llr_convention, self.device)
 
-        def draw(stream_id):
-            return lambda first, frames: engine.awgn_llr_mix(frames, code.n, seed=self.stream_seed, stream_id=stream_id,
-                                                             first_frame=first, scale=scale_tab, shift=shift_tab,
-                                                             device=scale_tab.device, rate_matching=self.rate_matching)
+            def draw(stream_id):
+                return lambda first, frames: engine.awgn_llr_mix(frames, code.n, seed=self.stream_seed, stream_id=stream_id,
+                                                                 first_frame=first, scale=scale_tab, shift=shift_tab,
+                                                                 device=scale_tab.device, rate_matching=self.rate_matching)
+        else:                         # the symbol channel: the encoder, the amp table and the one word are built once per call
+            mod, dev = self.modulation, engine._require_gpu(self.device)
+            mod.check(code.n)
+            amp_tab = engine._mix_table(mod.amp_table(grid), "amp", dev)
+            random = isinstance(self.codeword, str)
+            encoder = None
+            if random:                # kept across calls on one graph: its device copy is cached on the encoder object
+                graph = code.tanner_graph()
+                if self._stream_encoder is None or self._stream_encoder[0] is not graph:
+                    from codes import Encoder
+                    self._stream_encoder = (graph, Encoder.from_graph(graph))
+                encoder = self._stream_encoder[1]
+            one = None if random or self.codeword is None else engine.pack_codeword(self.codeword, code.n, dev)
+
+            def draw(stream_id):
+                def block(first, frames):
+                    cw = one
+                    if random:
+                        cw = engine.encode_random(encoder, frames, seed=self.stream_seed, stream_id=stream_id,
+                                                  first_frame=first, device=dev)
+                    return engine.sym_llr_mix(frames, code.n, seed=self.stream_seed, stream_id=stream_id, first_frame=first,
+                                              modulation=mod, amp=amp_tab, codeword=cw, device=dev, want_targets=True)
+                return block
 
         def step_drawn():
             self.stream_step += 1

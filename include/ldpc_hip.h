@@ -652,8 +652,22 @@ int ldpc_simulate_enc(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
  *   desc->scale and desc->shift are ignored; desc->codeword_packed must be NULL when e != NULL.  float64 decoders:
  *   LDPC_ERR_UNSUPPORTED.  workspace: ldpc_simulate_sym_workspace_bytes(d, block, capture).  Synchronous, as ldpc_simulate.
  *
+ * ldpc_channel_sym_mix : ldpc_channel_sym with the SNR point a function of the frame, for training: frame
+ *   f = first_frame + b is drawn at amp = amp_tab[f mod n_points] (amp_tab: fp32 [n_points] on the device, 4-byte aligned,
+ *   1 <= n_points <= 4096, its entries the caller's responsibility; batch <= 2^31 - 1; mod->amp is ignored) and receives, bit
+ *   for bit, what ldpc_channel_sym gives it at that amp, whatever block it is drawn in: every run of n_points consecutive
+ *   frames holds each point once, as under ldpc_channel_awgn_mix.  Codeword arguments as in ldpc_channel_sym.  targets, when
+ *   not NULL: fp32 [batch][n] (device, 4-byte aligned), targets[b][j] = 0.0f / 1.0f, the codeword bit of variable j that frame
+ *   b sent (all +0.0f for the all-zero word) -- the `targets` of the ldpc_train_joint* entry points, written by the lane that
+ *   sends the bit.  Nothing is stored for pad bits in either output.
+ *   LDPC_ERR_ARG for batch < 0, n < 1, a NULL mod, bits_per_symbol outside {1, 2, 4, 6, 8}, fading outside {0, 1}, a stride
+ *   other than 0 and ceil(n / 8), n_points outside 1 .. 4096, batch > 2^31 - 1, first_frame + batch beyond 2^64, a NULL
+ *   amp_tab with batch > 0; LDPC_ERR_UNSUPPORTED for S >= 2^29; then batch == 0 returns LDPC_OK without touching a device
+ *   pointer; then LDPC_ERR_ARG for a NULL or misaligned llr, a misaligned targets and a misaligned amp_tab.
+ *   Asynchronous on `stream`, allocates nothing, safe under stream capture.
+ *
  * Not provided: rate matching together with a modulation, the exact log-sum-exp demapper (`received` lets a caller write
- * one), PSK above 4 points and APSK, block fading, training on this channel, fp64 LLRs. */
+ * one), PSK above 4 points and APSK, block fading, a training step that fuses this draw into the decode, fp64 LLRs. */
 typedef struct {
     int32_t bits_per_symbol;      /* 1, 2, 4, 6, 8 */
     int32_t fading;               /* 0 none, 1 Rayleigh per symbol */
@@ -664,6 +678,10 @@ typedef struct {
 int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
                      const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride,
                      void *received /* or NULL */, void *stream);
+int ldpc_channel_sym_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         const ldpc_modulation *mod, const float *amp_tab, int32_t n_points,
+                         const uint8_t *codewords_packed, int64_t codeword_stride,
+                         void *targets /* or NULL */, void *stream);
 size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture);
 int ldpc_simulate_sym(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
                       const ldpc_modulation *mod, int64_t capture, int64_t out_state[8], int64_t *out_diag,
