@@ -30,6 +30,7 @@ LDPC_F32, LDPC_F64 = 0, 1
 C2V_NMS, C2V_RCQ, C2V_OMS, C2V_SPA = 0, 1, 2, 3
 MODE_AUTO, MODE_STREAM, MODE_RESIDENT, MODE_SWEEPS, MODE_GATHER, MODE_PAIR = 0, 1, 2, 3, 4, 5
 SCHED_FLOODING, SCHED_LAYERED_REF, SCHED_LAYERED = 0, 1, 2
+DEMAP_MAXLOG, DEMAP_EXACT = 0, 1
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-ffp-contract=off",       # the reference never fuses llr + alpha*sum
@@ -164,7 +165,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_simulate_rm", "ldpc_simulate_diag_rm",
                    "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode", "ldpc_encode_random",
                    "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc",
-                   "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym", "ldpc_channel_sym_mix")
+                   "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym", "ldpc_channel_sym_mix",
+                   "ldpc_demap_sym", "ldpc_channel_sym_dm", "ldpc_channel_sym_mix_dm", "ldpc_simulate_sym_dm")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -329,6 +331,14 @@ def load():
         lib.ldpc_simulate_sym_workspace_bytes.argtypes = [vp, i64, i64]
         lib.ldpc_simulate_sym.restype = C.c_int
         lib.ldpc_simulate_sym.argtypes = [vp, C.POINTER(SimDesc), vp, mod, i64, vp, vp, vp, C.c_size_t, vp]
+        lib.ldpc_demap_sym.restype = C.c_int
+        lib.ldpc_demap_sym.argtypes = [vp, i64, i32, mod, i32, vp, vp]
+        lib.ldpc_channel_sym_dm.restype = C.c_int
+        lib.ldpc_channel_sym_dm.argtypes = [vp, i64, i32, u64, u32, u64, mod, vp, i64, vp, i32, vp]
+        lib.ldpc_channel_sym_mix_dm.restype = C.c_int
+        lib.ldpc_channel_sym_mix_dm.argtypes = [vp, i64, i32, u64, u32, u64, mod, vp, i32, vp, i64, vp, i32, vp]
+        lib.ldpc_simulate_sym_dm.restype = C.c_int
+        lib.ldpc_simulate_sym_dm.argtypes = [vp, C.POINTER(SimDesc), vp, mod, i32, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p

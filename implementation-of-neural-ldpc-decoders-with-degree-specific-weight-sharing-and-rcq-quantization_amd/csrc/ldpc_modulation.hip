@@ -15,6 +15,12 @@
 //   (zI, zQ) = sim_box_muller(x0, x1);  g = 1.0f, or sqrtf(-logf(u(x2))) under Rayleigh fading;  e = g * amp
 //   per axis: v = e * (float)a + z;  D(a') = (v - e * (float)a')^2;  llr_k = 0.5f * (min_{b_k = 1} D - min_{b_k = 0} D)
 // Every multiply and add is rounded on its own: no fmaf is written here and the unit is built with -ffp-contract=off.
+//
+// Demappers.  LDPC_DEMAP_MAXLOG is the rule above.  LDPC_DEMAP_EXACT (sym_axis_exact, the EXACT instantiations) adds the
+// log-sum-exp correction of include/ldpc_hip.h to it, each set normalised by its own minimum m_b:
+//   S_b = sum_{a': b_k = b} expf(-0.5f * (D(a') - m_b)) in ascending level index;  llr_k = 0.5f * (m1 - m0) + (logf(S_0) - logf(S_1))
+// For h = 1 both sums are 1.0f and the rule is max-log bit for bit: the host sends m <= 2 to the max-log instantiations.
+// sym_demap applies either rule to received samples (vI, vQ, e, 0) that a caller hands in (ldpc_demap_sym).
 
 namespace ldpc {
 
@@ -101,11 +107,134 @@ __device__ inline float sym_axis(unsigned bits, float e, float z, float *llr)
     return v;
 }
 
+// the axis of a received sample: sym_axis from v on -- the same 2^H distances in the same operations and the same masked
+// minima, so a sample that sim_channel_sym stored demaps to the LLRs that kernel stored, bit for bit
+template <int H>
+__device__ inline void sym_demap_axis(float v, float e, float *llr)
+{
+    constexpr int L = 1 << H;
+    float D[L];
+#pragma unroll
+    for (int c = 0; c < L; ++c) {
+        const float ec = e * (float)((L - 1) - 2 * c);
+        const float t = v - ec;
+        D[c] = t * t;
+    }
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        float m0 = INFINITY, m1 = INFINITY;
+#pragma unroll
+        for (int c = 0; c < L; ++c) {
+            const int gray = c ^ (c >> 1);
+            if ((gray >> (H - 1 - k)) & 1) m1 = fminf(m1, D[c]);
+            else m0 = fminf(m0, D[c]);
+        }
+        const float d = m1 - m0;
+        llr[k] = 0.5f * d;
+    }
+}
+
+// the exact (log-MAP) rule on the distances of sym_axis: the max-log LLR plus logf(S_0) - logf(S_1), S_b the sum over the
+// levels with b_k = b of expf(-0.5f * (D - m_b)) in ascending level index.  Each set is normalised by its own minimum, so
+// 1 <= S_b <= L / 2 and nothing underflows into logf(0).  H * 2^H expf and 2 H logf per axis; D stays in registers (every
+// index is a compile-time constant after unrolling).
+template <int H>
+__device__ inline void sym_demap_axis_exact(float v, float e, float *llr)
+{
+    constexpr int L = 1 << H;
+    float D[L];
+#pragma unroll
+    for (int c = 0; c < L; ++c) {
+        const float ec = e * (float)((L - 1) - 2 * c);
+        const float t = v - ec;
+        D[c] = t * t;
+    }
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        float m0 = INFINITY, m1 = INFINITY;
+#pragma unroll
+        for (int c = 0; c < L; ++c) {
+            const int gray = c ^ (c >> 1);                                        // label of level c, b_0 at bit H - 1
+            if ((gray >> (H - 1 - k)) & 1) m1 = fminf(m1, D[c]);
+            else m0 = fminf(m0, D[c]);
+        }
+        float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+        for (int c = 0; c < L; ++c) {
+            const int gray = c ^ (c >> 1);
+            if ((gray >> (H - 1 - k)) & 1) {
+                const float x = D[c] - m1;
+                s1 = s1 + expf(-0.5f * x);
+            } else {
+                const float x = D[c] - m0;
+                s0 = s0 + expf(-0.5f * x);
+            }
+        }
+        const float d = m1 - m0;
+        const float corr = logf(s0) - logf(s1);
+        llr[k] = 0.5f * d + corr;
+    }
+}
+
+// sym_axis with the exact rule: the same level, the same ea and the same v = ea + z, then sym_demap_axis_exact
+template <int H>
+__device__ inline float sym_axis_exact(unsigned bits, float e, float z, float *llr)
+{
+    constexpr int L = 1 << H;
+    unsigned i = 0, run = 0;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        run ^= (bits >> k) & 1u;
+        i = (i << 1) | run;
+    }
+    const int a = (L - 1) - 2 * (int)i;
+    const float ea = e * (float)a;
+    const float v = ea + z;
+    sym_demap_axis_exact<H>(v, e, llr);
+    return v;
+}
+
+// LLRs from received samples (ldpc_demap_sym): one lane per symbol with the lane-to-(frame, symbol) arithmetic of
+// sim_channel_sym, one 16-byte load of (vI, vQ, e, 0), the axis rule on (vI, e) and (vQ, e), and that kernel's stores: the
+// lane's M floats of row b, or the pos[] scatter.  256-thread workgroups, no LDS, no random numbers; pad bits are not stored.
+template <int M, bool PERM, bool EXACT>
+__global__ __launch_bounds__(kSimBlock) void sym_demap(float *__restrict__ llr, long long batch, int n, unsigned S,
+                                                       const int *__restrict__ pos, const float4 *__restrict__ received)
+{
+    constexpr int H = M == 1 ? 1 : M / 2;
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
+    const unsigned long long b0 = g0 / S;
+    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
+    const unsigned db = t / S;
+    const long long b = (long long)b0 + db;
+    const unsigned s = t - db * S;
+    if (b >= batch) return;
+    const int j0 = (int)s * M;                                                    // < n <= 2^31 - 1
+    const int cnt = n - j0 < M ? n - j0 : M;
+    const float4 r = received[(size_t)b * S + s];
+    float v[M];
+    if constexpr (EXACT) {
+        sym_demap_axis_exact<H>(r.x, r.z, v);
+        if constexpr (M > 1) sym_demap_axis_exact<H>(r.y, r.z, v + H);
+    } else {
+        sym_demap_axis<H>(r.x, r.z, v);
+        if constexpr (M > 1) sym_demap_axis<H>(r.y, r.z, v + H);
+    }
+    float *dst = llr + (size_t)b * (size_t)n;
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k)
+            if (k < cnt) dst[pos[j0 + k]] = v[k];
+    } else {
+        sym_store<M>(dst + j0, v, cnt);
+    }
+}
+
 // One lane per symbol; consecutive lanes hold consecutive symbols of the [batch][S] block, the lane-to-(frame, symbol)
 // arithmetic of sim_channel_awgn.  256-thread workgroups, no LDS.  Identity path (PERM false): the lane owns floats
 // s * M .. s * M + M - 1 of row b.  Permuted path: bit k of the symbol is the codeword bit of variable pos[s * M + k], and its
 // LLR goes there with a 4-byte store.  cw_stride 0: one codeword for every frame; cw NULL: the all-zero word.
-template <int M, bool FADING, bool PERM>
+template <int M, bool FADING, bool PERM, bool EXACT>
 __global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__ llr, long long batch, int n, unsigned S,
                                                              uint32_t k0, uint32_t k1, uint32_t stream_id,
                                                              unsigned long long first_frame, float amp,
@@ -148,9 +277,14 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__
     if (FADING) g = sqrtf(-logf(sim_uniform(x[2])));
     const float e = g * amp;
     float v[M];
-    const float vI = sym_axis<H>(bits & ((1u << H) - 1u), e, zI, v);
-    float vQ = 0.0f;
-    if constexpr (M > 1) vQ = sym_axis<H>(bits >> H, e, zQ, v + H);
+    float vI, vQ = 0.0f;
+    if constexpr (EXACT) {
+        vI = sym_axis_exact<H>(bits & ((1u << H) - 1u), e, zI, v);
+        if constexpr (M > 1) vQ = sym_axis_exact<H>(bits >> H, e, zQ, v + H);
+    } else {
+        vI = sym_axis<H>(bits & ((1u << H) - 1u), e, zI, v);
+        if constexpr (M > 1) vQ = sym_axis<H>(bits >> H, e, zQ, v + H);
+    }
     if (received) received[(size_t)b * S + s] = make_float4(vI, vQ, e, 0.0f);
     float *dst = llr + (size_t)b * (size_t)n;
     if constexpr (PERM) {
@@ -171,7 +305,7 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__
 // which is left as it is: a frame gets what that kernel gives it at amp = amp_tab[p], bit for bit.  targets, when not NULL,
 // receives the symbol's bits as 0.0f / 1.0f where the LLRs go: the lane holds them in `bits` already.  The two rows start at
 // unrelated addresses, so each output picks its store widths from its own address; pad bits are stored in neither.
-template <int M, bool FADING, bool PERM>
+template <int M, bool FADING, bool PERM, bool EXACT>
 __global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restrict__ llr, float *__restrict__ targets,
                                                                  long long batch, int n, unsigned S, uint32_t k0, uint32_t k1,
                                                                  uint32_t stream_id, unsigned long long first_frame,
@@ -220,8 +354,13 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restri
     if (FADING) g = sqrtf(-logf(sim_uniform(x[2])));
     const float e = g * amp;
     float v[M];
-    sym_axis<H>(bits & ((1u << H) - 1u), e, zI, v);
-    if constexpr (M > 1) sym_axis<H>(bits >> H, e, zQ, v + H);
+    if constexpr (EXACT) {
+        sym_axis_exact<H>(bits & ((1u << H) - 1u), e, zI, v);
+        if constexpr (M > 1) sym_axis_exact<H>(bits >> H, e, zQ, v + H);
+    } else {
+        sym_axis<H>(bits & ((1u << H) - 1u), e, zI, v);
+        if constexpr (M > 1) sym_axis<H>(bits >> H, e, zQ, v + H);
+    }
     float *dst = llr + (size_t)b * (size_t)n;
     if constexpr (PERM) {
 #pragma unroll
@@ -250,36 +389,50 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restri
 namespace {
 
 // the scalar part of a modulation descriptor (the position table is a device pointer: the caller vouches for it); the mix
-// entry reads its amplitudes from a device table and passes check_amp = false
-int sym_mod_check(const ldpc_modulation *mod, int32_t n, bool check_amp = true)
+// entry reads its amplitudes from a device table and passes check_amp = false; ldpc_demap_sym reads the gain out of the
+// samples and ignores fading as well
+int sym_mod_check(const ldpc_modulation *mod, int32_t n, bool check_amp = true, bool check_fading = true)
 {
     if (!mod) return fail(LDPC_ERR_ARG, "NULL mod");
     const int32_t m = mod->bits_per_symbol;
     if (m != 1 && m != 2 && m != 4 && m != 6 && m != 8)
         return fail(LDPC_ERR_ARG, "bits_per_symbol must be 1, 2, 4, 6 or 8 (BPSK, QPSK, 16- / 64- / 256-QAM), got %d", m);
-    if (mod->fading != 0 && mod->fading != 1) return fail(LDPC_ERR_ARG, "fading must be 0 (none) or 1 (Rayleigh per symbol), got %d", mod->fading);
+    if (check_fading && mod->fading != 0 && mod->fading != 1)
+        return fail(LDPC_ERR_ARG, "fading must be 0 (none) or 1 (Rayleigh per symbol), got %d", mod->fading);
     if (check_amp && !(std::isfinite(mod->amp) && mod->amp >= 0.0f)) return fail(LDPC_ERR_ARG, "amp must be finite and >= 0");
     if (((int64_t)n + m - 1) / m >= (int64_t)kSymMaxSymbols)
         return fail(LDPC_ERR_UNSUPPORTED, "a frame of %lld symbols: the symbol index must stay below 2^29", (long long)(((int64_t)n + m - 1) / m));
     return LDPC_OK;
 }
 
-template <int M, bool FADING>
+int sym_demapper_check(int32_t demapper)
+{
+    if (demapper != LDPC_DEMAP_MAXLOG && demapper != LDPC_DEMAP_EXACT)
+        return fail(LDPC_ERR_ARG, "demapper must be LDPC_DEMAP_MAXLOG (0) or LDPC_DEMAP_EXACT (1), got %d", demapper);
+    return LDPC_OK;
+}
+
+// the EXACT instantiations exist for m >= 4 only: one bit per axis has one level per set, both sums are 1.0f and the exact
+// rule is the max-log rule bit for bit
+inline bool sym_exact(int32_t demapper, int m) { return demapper == LDPC_DEMAP_EXACT && m >= 4; }
+
+template <int M, bool FADING, bool EXACT>
 void sym_launch_perm(bool perm, dim3 grid, hipStream_t s, float *llr, long long batch, int n, unsigned S, uint32_t k0, uint32_t k1,
                      uint32_t stream_id, unsigned long long first_frame, float amp, const int *pos, const uint8_t *cw,
                      long long cw_stride, float4 *received)
 {
     if (perm)
-        hipLaunchKernelGGL((sim_channel_sym<M, FADING, true>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, k0, k1, stream_id,
+        hipLaunchKernelGGL((sim_channel_sym<M, FADING, true, EXACT>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, k0, k1, stream_id,
                            first_frame, amp, pos, cw, cw_stride, received);
     else
-        hipLaunchKernelGGL((sim_channel_sym<M, FADING, false>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, k0, k1, stream_id,
+        hipLaunchKernelGGL((sim_channel_sym<M, FADING, false, EXACT>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, k0, k1, stream_id,
                            first_frame, amp, pos, cw, cw_stride, received);
 }
 
-// one launch of sim_channel_sym; mod has passed sym_mod_check
+// one launch of sim_channel_sym; mod has passed sym_mod_check and demapper sym_demapper_check
 int sim_channel_sym_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
-                           const ldpc_modulation *mod, const uint8_t *cw, int64_t cw_stride, void *received, hipStream_t s)
+                           const ldpc_modulation *mod, int32_t demapper, const uint8_t *cw, int64_t cw_stride, void *received,
+                           hipStream_t s)
 {
     const int m = mod->bits_per_symbol;
     const unsigned S = (unsigned)(((int64_t)n + m - 1) / m);
@@ -288,26 +441,33 @@ int sim_channel_sym_launch(float *llr, int64_t batch, int32_t n, uint64_t seed, 
     if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
     const dim3 grid((unsigned)blocks);
     const bool perm = mod->position != nullptr, fading = mod->fading != 0;
-#define LDPC_SYM_CASE(M)                                                                                                          \
+#define LDPC_SYM_ARGS                                                                                                             \
+    perm, grid, s, llr, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id,                           \
+        (unsigned long long)first_frame, mod->amp, (const int *)mod->position, cw, (long long)cw_stride, (float4 *)received
+#define LDPC_SYM_CASE(M, EXACT)                                                                                                   \
     case M:                                                                                                                       \
-        if (fading)                                                                                                               \
-            sym_launch_perm<M, true>(perm, grid, s, llr, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32),      \
-                                     stream_id, (unsigned long long)first_frame, mod->amp, (const int *)mod->position, cw,        \
-                                     (long long)cw_stride, (float4 *)received);                                                   \
-        else                                                                                                                      \
-            sym_launch_perm<M, false>(perm, grid, s, llr, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32),     \
-                                      stream_id, (unsigned long long)first_frame, mod->amp, (const int *)mod->position, cw,       \
-                                      (long long)cw_stride, (float4 *)received);                                                  \
+        if (fading) sym_launch_perm<M, true, EXACT>(LDPC_SYM_ARGS);                                                               \
+        else sym_launch_perm<M, false, EXACT>(LDPC_SYM_ARGS);                                                                     \
         break;
-    switch (m) {
-        LDPC_SYM_CASE(1)
-        LDPC_SYM_CASE(2)
-        LDPC_SYM_CASE(4)
-        LDPC_SYM_CASE(6)
-        LDPC_SYM_CASE(8)
-    default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+    if (sym_exact(demapper, m)) {
+        switch (m) {
+            LDPC_SYM_CASE(4, true)
+            LDPC_SYM_CASE(6, true)
+            LDPC_SYM_CASE(8, true)
+        default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+        }
+    } else {
+        switch (m) {
+            LDPC_SYM_CASE(1, false)
+            LDPC_SYM_CASE(2, false)
+            LDPC_SYM_CASE(4, false)
+            LDPC_SYM_CASE(6, false)
+            LDPC_SYM_CASE(8, false)
+        default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+        }
     }
 #undef LDPC_SYM_CASE
+#undef LDPC_SYM_ARGS
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
 }
@@ -326,29 +486,30 @@ struct SymMixArgs {
     long long cw_stride;
 };
 
-template <int M, bool FADING, bool PERM>
+template <int M, bool FADING, bool PERM, bool EXACT>
 void sym_mix_launch_one(dim3 grid, hipStream_t s, const SymMixArgs &a)
 {
-    hipLaunchKernelGGL((sim_channel_sym_mix<M, FADING, PERM>), grid, dim3(kSimBlock), 0, s, a.llr, a.targets, a.batch, a.n, a.S,
+    hipLaunchKernelGGL((sim_channel_sym_mix<M, FADING, PERM, EXACT>), grid, dim3(kSimBlock), 0, s, a.llr, a.targets, a.batch, a.n, a.S,
                        a.k0, a.k1, a.stream_id, a.first_frame, a.p0, a.K, a.Kinv, a.amp_tab, a.pos, a.cw, a.cw_stride);
 }
 
-template <int M>
+template <int M, bool EXACT>
 void sym_mix_launch_m(bool fading, bool perm, dim3 grid, hipStream_t s, const SymMixArgs &a)
 {
     if (fading) {
-        if (perm) sym_mix_launch_one<M, true, true>(grid, s, a);
-        else sym_mix_launch_one<M, true, false>(grid, s, a);
+        if (perm) sym_mix_launch_one<M, true, true, EXACT>(grid, s, a);
+        else sym_mix_launch_one<M, true, false, EXACT>(grid, s, a);
     } else {
-        if (perm) sym_mix_launch_one<M, false, true>(grid, s, a);
-        else sym_mix_launch_one<M, false, false>(grid, s, a);
+        if (perm) sym_mix_launch_one<M, false, true, EXACT>(grid, s, a);
+        else sym_mix_launch_one<M, false, false, EXACT>(grid, s, a);
     }
 }
 
-// one launch of sim_channel_sym_mix; mod has passed sym_mod_check, 1 <= n_points <= 4096 and batch <= 2^31 - 1
+// one launch of sim_channel_sym_mix; mod has passed sym_mod_check, demapper sym_demapper_check, 1 <= n_points <= 4096 and
+// batch <= 2^31 - 1
 int sim_channel_sym_mix_launch(float *llr, float *targets, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id,
-                               uint64_t first_frame, const ldpc_modulation *mod, const float *amp_tab, int32_t n_points,
-                               const uint8_t *cw, int64_t cw_stride, hipStream_t s)
+                               uint64_t first_frame, const ldpc_modulation *mod, int32_t demapper, const float *amp_tab,
+                               int32_t n_points, const uint8_t *cw, int64_t cw_stride, hipStream_t s)
 {
     const int m = mod->bits_per_symbol;
     const unsigned S = (unsigned)(((int64_t)n + m - 1) / m);
@@ -361,13 +522,64 @@ int sim_channel_sym_mix_launch(float *llr, float *targets, int64_t batch, int32_
     const SymMixArgs a{llr, targets, (long long)batch, (int)n, S, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id,
                        (unsigned long long)first_frame, (unsigned)(first_frame % K), K, 0xffffffffu / K, amp_tab,
                        (const int *)mod->position, cw, (long long)cw_stride};
-    switch (m) {
-    case 1: sym_mix_launch_m<1>(fading, perm, grid, s, a); break;
-    case 2: sym_mix_launch_m<2>(fading, perm, grid, s, a); break;
-    case 4: sym_mix_launch_m<4>(fading, perm, grid, s, a); break;
-    case 6: sym_mix_launch_m<6>(fading, perm, grid, s, a); break;
-    case 8: sym_mix_launch_m<8>(fading, perm, grid, s, a); break;
-    default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+    if (sym_exact(demapper, m)) {
+        switch (m) {
+        case 4: sym_mix_launch_m<4, true>(fading, perm, grid, s, a); break;
+        case 6: sym_mix_launch_m<6, true>(fading, perm, grid, s, a); break;
+        case 8: sym_mix_launch_m<8, true>(fading, perm, grid, s, a); break;
+        default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+        }
+    } else {
+        switch (m) {
+        case 1: sym_mix_launch_m<1, false>(fading, perm, grid, s, a); break;
+        case 2: sym_mix_launch_m<2, false>(fading, perm, grid, s, a); break;
+        case 4: sym_mix_launch_m<4, false>(fading, perm, grid, s, a); break;
+        case 6: sym_mix_launch_m<6, false>(fading, perm, grid, s, a); break;
+        case 8: sym_mix_launch_m<8, false>(fading, perm, grid, s, a); break;
+        default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
+template <int M, bool EXACT>
+void sym_demap_launch_one(bool perm, dim3 grid, hipStream_t s, float *llr, long long batch, int n, unsigned S, const int *pos,
+                          const float4 *received)
+{
+    if (perm) hipLaunchKernelGGL((sym_demap<M, true, EXACT>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, pos, received);
+    else hipLaunchKernelGGL((sym_demap<M, false, EXACT>), grid, dim3(kSimBlock), 0, s, llr, batch, n, S, pos, received);
+}
+
+// one launch of sym_demap; mod has passed sym_mod_check and demapper sym_demapper_check
+int sym_demap_launch(float *llr, int64_t batch, int32_t n, const ldpc_modulation *mod, int32_t demapper, const void *received,
+                     hipStream_t s)
+{
+    const int m = mod->bits_per_symbol;
+    const unsigned S = (unsigned)(((int64_t)n + m - 1) / m);
+    const unsigned long long syms = (unsigned long long)batch * S;
+    const unsigned long long blocks = (syms + kSimBlock - 1) / kSimBlock;
+    if (blocks > 0x7fffffffull) return fail(LDPC_ERR_UNSUPPORTED, "batch too large for one launch");
+    const dim3 grid((unsigned)blocks);
+    const bool perm = mod->position != nullptr;
+    const int *pos = (const int *)mod->position;
+    const float4 *rec = (const float4 *)received;
+    if (sym_exact(demapper, m)) {
+        switch (m) {
+        case 4: sym_demap_launch_one<4, true>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        case 6: sym_demap_launch_one<6, true>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        case 8: sym_demap_launch_one<8, true>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+        }
+    } else {
+        switch (m) {
+        case 1: sym_demap_launch_one<1, false>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        case 2: sym_demap_launch_one<2, false>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        case 4: sym_demap_launch_one<4, false>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        case 6: sym_demap_launch_one<6, false>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        case 8: sym_demap_launch_one<8, false>(perm, grid, s, llr, (long long)batch, (int)n, S, pos, rec); break;
+        default: return fail(LDPC_ERR_ARG, "bits_per_symbol %d", m);
+        }
     }
     HIP_TRY(hipGetLastError());
     return LDPC_OK;
@@ -377,7 +589,7 @@ int sim_channel_sym_mix_launch(float *llr, float *targets, int64_t batch, int32_
 // ldpc_decode, the decisions XORed with the codeword rows (one codeword: the counters compare against it themselves), the
 // existing counters.
 int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
-                      int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
+                      int32_t demapper, int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
                       void *stream)
 {
     const bool diagnostics = capture >= 0;
@@ -390,6 +602,7 @@ int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
     if (d->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "ldpc_simulate_sym draws fp32 LLRs: float64 decoders are not supported");
     if (d->g->n < 1) return fail(LDPC_ERR_ARG, "n < 1");
     if (int rc = sym_mod_check(mod, d->g->n)) return rc;
+    if (int rc = sym_demapper_check(demapper)) return rc;
     if (e && e->g.n != d->g->n) return fail(LDPC_ERR_ARG, "the encoder has n = %d, the decoder n = %d", e->g.n, d->g->n);
     if (e && e->device != d->g->device) return fail(LDPC_ERR_ARG, "encoder and decoder live on different devices");
     if (!workspace) return fail(LDPC_ERR_ARG, "NULL workspace");
@@ -429,8 +642,8 @@ int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
             const uint64_t first = desc->first_frame + (uint64_t)drawn;
             if (e)
                 if (int rc = enc_launch(e, frames, 1, desc->seed, desc->stream_id, first, nullptr, cw, nullptr, s)) return rc;
-            if (int rc = sim_channel_sym_launch(llr, frames, n, desc->seed, desc->stream_id, first, mod, e ? cw : one, e ? rb : 0,
-                                                nullptr, s))
+            if (int rc = sim_channel_sym_launch(llr, frames, n, desc->seed, desc->stream_id, first, mod, demapper, e ? cw : one,
+                                                e ? rb : 0, nullptr, s))
                 return rc;
             if (int rc = ldpc_decode(d, llr, frames, 1, nullptr, nullptr, iters, success, packed, base + w.o_dec, w.dec_bytes, s))
                 return rc;
@@ -462,13 +675,14 @@ int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
 
 extern "C" {
 
-int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
-                     const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride, void *received,
-                     void *stream)
+int ldpc_channel_sym_dm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                        const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride, void *received,
+                        int32_t demapper, void *stream)
 {
     if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
     if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
     if (int rc = sym_mod_check(mod, n)) return rc;
+    if (int rc = sym_demapper_check(demapper)) return rc;
     if (codeword_stride != 0 && codeword_stride != ((int64_t)n + 7) / 8)
         return fail(LDPC_ERR_ARG, "codeword_stride must be 0 (one codeword) or ceil(n / 8) = %lld (one packed row per frame)",
                     (long long)(((int64_t)n + 7) / 8));
@@ -476,17 +690,42 @@ int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_
     if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
     if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
     if (received && ((uintptr_t)received % 16) != 0) return fail(LDPC_ERR_ARG, "received must be 16-byte aligned");
-    return sim_channel_sym_launch((float *)llr, batch, n, seed, stream_id, first_frame, mod, codewords_packed, codeword_stride,
-                                  received, (hipStream_t)stream);
+    return sim_channel_sym_launch((float *)llr, batch, n, seed, stream_id, first_frame, mod, demapper, codewords_packed,
+                                  codeword_stride, received, (hipStream_t)stream);
 }
 
-int ldpc_channel_sym_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
-                         const ldpc_modulation *mod, const float *amp_tab, int32_t n_points, const uint8_t *codewords_packed,
-                         int64_t codeword_stride, void *targets, void *stream)
+int ldpc_channel_sym(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                     const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride, void *received,
+                     void *stream)
+{
+    return ldpc_channel_sym_dm(llr, batch, n, seed, stream_id, first_frame, mod, codewords_packed, codeword_stride, received,
+                               LDPC_DEMAP_MAXLOG, stream);
+}
+
+int ldpc_demap_sym(void *llr, int64_t batch, int32_t n, const ldpc_modulation *mod, int32_t demapper, const void *received,
+                   void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = sym_mod_check(mod, n, false, false)) return rc;
+    if (int rc = sym_demapper_check(demapper)) return rc;
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    if (!received) return fail(LDPC_ERR_ARG, "NULL received");
+    if (((uintptr_t)received % 16) != 0) return fail(LDPC_ERR_ARG, "received must be 16-byte aligned");
+    return sym_demap_launch((float *)llr, batch, n, mod, demapper, received, (hipStream_t)stream);
+}
+
+int ldpc_channel_sym_mix_dm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                            const ldpc_modulation *mod, const float *amp_tab, int32_t n_points,
+                            const uint8_t *codewords_packed, int64_t codeword_stride, void *targets, int32_t demapper,
+                            void *stream)
 {
     if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
     if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
     if (int rc = sym_mod_check(mod, n, false)) return rc;
+    if (int rc = sym_demapper_check(demapper)) return rc;
     if (codeword_stride != 0 && codeword_stride != ((int64_t)n + 7) / 8)
         return fail(LDPC_ERR_ARG, "codeword_stride must be 0 (one codeword) or ceil(n / 8) = %lld (one packed row per frame)",
                     (long long)(((int64_t)n + 7) / 8));
@@ -500,8 +739,16 @@ int ldpc_channel_sym_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uin
     if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
     if (targets && ((uintptr_t)targets % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "targets must be 4-byte aligned");
     if (((uintptr_t)amp_tab % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "amp_tab must be 4-byte aligned");
-    return sim_channel_sym_mix_launch((float *)llr, (float *)targets, batch, n, seed, stream_id, first_frame, mod, amp_tab,
-                                      n_points, codewords_packed, codeword_stride, (hipStream_t)stream);
+    return sim_channel_sym_mix_launch((float *)llr, (float *)targets, batch, n, seed, stream_id, first_frame, mod, demapper,
+                                      amp_tab, n_points, codewords_packed, codeword_stride, (hipStream_t)stream);
+}
+
+int ldpc_channel_sym_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         const ldpc_modulation *mod, const float *amp_tab, int32_t n_points, const uint8_t *codewords_packed,
+                         int64_t codeword_stride, void *targets, void *stream)
+{
+    return ldpc_channel_sym_mix_dm(llr, batch, n, seed, stream_id, first_frame, mod, amp_tab, n_points, codewords_packed,
+                                   codeword_stride, targets, LDPC_DEMAP_MAXLOG, stream);
 }
 
 size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, int64_t capture)
@@ -509,12 +756,20 @@ size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, i
     return ldpc_simulate_enc_workspace_bytes(d, block, capture);
 }
 
+int ldpc_simulate_sym_dm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
+                         int32_t demapper, int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace,
+                         size_t workspace_bytes, void *stream)
+{
+    LDPC_NOTHROW(simulate_sym_impl(d, desc, e, mod, demapper, capture < 0 ? -1 : capture, out_state, out_diag, workspace,
+                                   workspace_bytes, stream))
+}
+
 int ldpc_simulate_sym(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
                       int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
                       void *stream)
 {
-    LDPC_NOTHROW(simulate_sym_impl(d, desc, e, mod, capture < 0 ? -1 : capture, out_state, out_diag, workspace, workspace_bytes,
-                                   stream))
+    return ldpc_simulate_sym_dm(d, desc, e, mod, LDPC_DEMAP_MAXLOG, capture, out_state, out_diag, workspace, workspace_bytes,
+                                stream);
 }
 
 }  // extern "C"

@@ -151,13 +151,14 @@ def _symbol_amp(modulation, snr_db, amp) -> float:
 
 def sym_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: int = 0, modulation, snr_db: Optional[float] = None,
             amp: Optional[float] = None, codeword=None, device=None, want_received: bool = False):
-    """Max-log LLRs [batch, n] fp32 of frames first_frame .. first_frame + batch - 1 sent as Gray-mapped symbols of `modulation`
-    (a modulation.Modulation) over AWGN or per-symbol Rayleigh fading (ldpc_channel_sym; defined in include/ldpc_hip.h and
-    INTEGRATION.md 6f): frame f gets the same noise and fading whatever block it is drawn in.  Give snr_db (Es/N0) or amp, the
+    """LLRs [batch, n] fp32 of frames first_frame .. first_frame + batch - 1 sent as Gray-mapped symbols of `modulation`
+    (a modulation.Modulation) over AWGN or per-symbol Rayleigh fading, demapped by the modulation's demapper: max-log
+    (ldpc_channel_sym; defined in include/ldpc_hip.h and INTEGRATION.md 6f) or exact (ldpc_channel_sym_dm).
+    Frame f gets the same noise and fading whatever block it is drawn in.  Give snr_db (Es/N0) or amp, the
     constellation's half-spacing over the per-dimension noise standard deviation.  codeword: None (all zero), a 0/1 array of
     length n, a packed uint8 tensor, or a 2-D uint8 tensor [batch, ceil(n/8)] of one packed codeword per frame, as
     ``encode_random`` returns them.  want_received: -> (llr, received), received fp32 [batch, S, 4] = (vI, vQ, e, 0) per
-    symbol, e the fading gain times amp (vQ = 0 for BPSK) -- for a constellation plot or a demapper of your own."""
+    symbol, e the fading gain times amp (vQ = 0 for BPSK) -- for a constellation plot, for ``demap``, or a demapper of your own."""
     dev = _require_gpu(device)
     mod = _check_modulation(modulation)
     amp = _symbol_amp(mod, snr_db, amp)
@@ -172,12 +173,50 @@ def sym_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: i
     rec = torch.empty((batch, mod.symbols(n), 4), dtype=torch.float32, device=dev) if want_received else None
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(lib.ldpc_channel_sym(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
-                                       int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), C.byref(desc),
-                                       None if cw is None else C.c_void_p(cw.data_ptr()), (n + 7) // 8 if rows else 0,
-                                       None if rec is None else C.c_void_p(rec.data_ptr()), C.c_void_p(stream)),
-                  "ldpc_channel_sym")
+        args = (C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
+                int(first_frame) & (2 ** 64 - 1), C.byref(desc), None if cw is None else C.c_void_p(cw.data_ptr()),
+                (n + 7) // 8 if rows else 0, None if rec is None else C.c_void_p(rec.data_ptr()))
+        if mod.demapper == "exact":
+            nat.check(lib.ldpc_channel_sym_dm(*args, nat.DEMAP_EXACT, C.c_void_p(stream)), "ldpc_channel_sym_dm")
+        else:
+            nat.check(lib.ldpc_channel_sym(*args, C.c_void_p(stream)), "ldpc_channel_sym")
     return (out, rec) if want_received else out
+
+
+def demap(received, n: int, *, modulation, demapper: Optional[str] = None, device=None) -> torch.Tensor:
+    """LLRs [batch, n] fp32 from received samples (ldpc_demap_sym): `received` is a contiguous float32
+    tensor [batch, S, 4] = (vI, vQ, e, 0) per symbol on the device, S = ceil(n / m) -- what ``sym_llr(want_received=True)``
+    returns, or ``modulation.normalise_received`` of physical samples.  demapper "maxlog" | "exact"; None: the modulation's
+    own.  The modulation's fading is not used (e travels with the samples); its interleaver is honoured.  With "maxlog" the
+    samples of a ``sym_llr`` call give that call's LLRs bit for bit, with "exact" those of the same call under
+    ``Modulation(..., demapper="exact")``."""
+    mod = _check_modulation(modulation)
+    from modulation import DEMAPPERS
+    rule = mod.demapper if demapper is None else demapper
+    if not isinstance(rule, str) or rule not in DEMAPPERS:
+        raise ValueError(f"demapper must be None, 'maxlog' or 'exact', got {demapper!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    S = mod.symbols(n)
+    if (not isinstance(received, torch.Tensor) or received.dtype != torch.float32 or received.dim() != 3
+            or tuple(received.shape[1:]) != (S, 4) or not received.is_contiguous()):
+        raise ValueError(f"received must be a contiguous float32 tensor [batch, {S}, 4] = (vI, vQ, e, 0) per symbol")
+    want = None if device is None else torch.device(device)
+    if received.device.type != "cuda" or (want is not None and (want.type != "cuda" or want.index not in
+                                                                (None, received.device.index))):
+        raise ValueError(f"received must be on the GPU the call is for, got {received.device}"
+                         f"{'' if want is None else f' and device={want}'}")
+    dev = _require_gpu(received.device)
+    batch = int(received.shape[0])
+    desc, _keep = mod.native(0.0, n, dev)
+    lib = nat.load()
+    out = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nat.check(lib.ldpc_demap_sym(C.c_void_p(out.data_ptr()), batch, n, C.byref(desc), DEMAPPERS[rule],
+                                     C.c_void_p(received.data_ptr()), C.c_void_p(stream)), "ldpc_demap_sym")
+    return out
 
 
 MIX_MAX_POINTS = 4096     # ldpc_channel_awgn_mix: n_points <= 4096, batch <= 2^31 - 1 (the point index stays in 32 bits)
@@ -310,12 +349,14 @@ def sym_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_fram
     targets = torch.empty((batch, n), dtype=torch.float32, device=dev) if want_targets else None
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(lib.ldpc_channel_sym_mix(C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1),
-                                           int(stream_id) & (2 ** 32 - 1), int(first_frame) & (2 ** 64 - 1), C.byref(desc),
-                                           C.c_void_p(amp_tab.data_ptr()), n_points,
-                                           None if cw is None else C.c_void_p(cw.data_ptr()), (n + 7) // 8 if rows else 0,
-                                           None if targets is None else C.c_void_p(targets.data_ptr()), C.c_void_p(stream)),
-                  "ldpc_channel_sym_mix")
+        args = (C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
+                int(first_frame) & (2 ** 64 - 1), C.byref(desc), C.c_void_p(amp_tab.data_ptr()), n_points,
+                None if cw is None else C.c_void_p(cw.data_ptr()), (n + 7) // 8 if rows else 0,
+                None if targets is None else C.c_void_p(targets.data_ptr()))
+        if mod.demapper == "exact":
+            nat.check(lib.ldpc_channel_sym_mix_dm(*args, nat.DEMAP_EXACT, C.c_void_p(stream)), "ldpc_channel_sym_mix_dm")
+        else:
+            nat.check(lib.ldpc_channel_sym_mix(*args, C.c_void_p(stream)), "ldpc_channel_sym_mix")
     return (out, targets) if want_targets else out
 
 
@@ -951,9 +992,13 @@ class DecodeEngine:
             self._sim_ws = ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            nat.check(self._lib.ldpc_simulate_sym(self.handle, C.byref(desc), None if ne is None else ne.handle, C.byref(mdesc),
-                                                  capture if diagnostics else -1, nat.ptr(out), nat.ptr(words),
-                                                  C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)), "ldpc_simulate_sym")
+            head = (self.handle, C.byref(desc), None if ne is None else ne.handle, C.byref(mdesc))
+            tail = (capture if diagnostics else -1, nat.ptr(out), nat.ptr(words), C.c_void_p(ws.data_ptr()), ws.numel(),
+                    C.c_void_p(stream))
+            if mod.demapper == "exact":
+                nat.check(self._lib.ldpc_simulate_sym_dm(*head, nat.DEMAP_EXACT, *tail), "ldpc_simulate_sym_dm")
+            else:
+                nat.check(self._lib.ldpc_simulate_sym(*head, *tail), "ldpc_simulate_sym")
         res = {k: int(v) for k, v in zip(SIM_COUNTERS, out)}
         if diagnostics:
             res.update(parse_sim_diag(words, self.iters, capture))

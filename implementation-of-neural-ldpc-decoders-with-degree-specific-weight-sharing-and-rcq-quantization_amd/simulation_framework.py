@@ -35,8 +35,8 @@ Channel (``SimulationConfig.channel``):
             ``SimulationConfig.rate_matching`` (this channel only) punctures and shortens bits on the channel and restricts
             the error counters to its count mask; the bit error rate is then per counted bit.
             ``SimulationConfig.modulation`` (this channel only; a ``modulation.Modulation``) sends the bits as Gray-mapped BPSK /
-            QPSK / 16- / 64- / 256-QAM symbols over AWGN or per-symbol Rayleigh fading and demaps them with the max-log rule
-            (``engine.sym_llr``); ``snr_db`` is then Es/N0 of the symbol.  Not together with
+            QPSK / 16- / 64- / 256-QAM symbols over AWGN or per-symbol Rayleigh fading and demaps them with the modulation's
+            demapper, max-log or exact (``engine.sym_llr``, DESIGN.md sections 3j and 3l); ``snr_db`` is then Es/N0 of the symbol.  Not together with
             ``rate_matching``; from 16-QAM up it needs ``codeword="random"`` (or a codeword).
 """
 

@@ -152,7 +152,7 @@ class PosteriorJointTrainer(metaclass=_TrainerType):
     rate_matching (keyword only, a rate_matching.RateMatching): the profile `train_stream` draws its training and validation
     frames through -- punctured bits enter the decoder as +0.0, shortened ones as +short_llr; `train` does not use it.
     modulation (keyword only, a modulation.Modulation): `train_stream` draws its frames on the symbol channel instead
-    (engine.sym_llr_mix: Gray-mapped BPSK .. 256-QAM over AWGN or Rayleigh fading, max-log LLRs, snr_range read as Es/N0) and
+    (engine.sym_llr_mix: Gray-mapped BPSK .. 256-QAM over AWGN or Rayleigh fading, LLRs by the modulation's demapper, snr_range read as Es/N0) and
     trains against the bits that were sent.  codeword (with a modulation only): None, the all-zero word (BPSK and QPSK only:
     from 16-QAM up it sends one corner point and the bit levels are not output-symmetric); "random", a fresh codeword per frame
     (engine.encode_random on the code's graph); or a 0/1 array of length n, one word for every frame.  `train`, the

@@ -602,7 +602,7 @@ int ldpc_simulate_enc(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
                       int64_t capture, int64_t out_state[8], int64_t *out_diag /* host, or NULL when capture < 0 */,
                       void *workspace, size_t workspace_bytes, void *stream);
 
-/* ---- symbol channel: Gray-mapped QAM over AWGN or Rayleigh fading, max-log demapper -------------
+/* ---- symbol channel: Gray-mapped QAM over AWGN or Rayleigh fading, max-log and exact demappers -
  * The channels above are binary-input AWGN.  The bit levels of a Gray-mapped 16- / 64- / 256-QAM symbol are unequal channels
  * and not output-symmetric, so they need the per-frame codewords of the section above.  Everything above is unchanged.
  *
@@ -666,8 +666,38 @@ int ldpc_simulate_enc(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
  *   pointer; then LDPC_ERR_ARG for a NULL or misaligned llr, a misaligned targets and a misaligned amp_tab.
  *   Asynchronous on `stream`, allocates nothing, safe under stream capture.
  *
- * Not provided: rate matching together with a modulation, the exact log-sum-exp demapper (`received` lets a caller write
- * one), PSK above 4 points and APSK, block fading, a training step that fuses this draw into the decode, fp64 LLRs. */
+ * Demappers.  With L = 2^h candidate amplitudes a' per axis, D(a') as above and m_b = min_{a': b_k = b} D(a'), all fp32 and
+ * every operation rounded on its own:
+ *     LDPC_DEMAP_MAXLOG:  llr_k = 0.5f * (m1 - m0), the rule above -- what the entry points without a demapper argument use
+ *     LDPC_DEMAP_EXACT:   S_b = sum_{a': b_k = b} expf(-0.5f * (D(a') - m_b)), summed in ascending level index
+ *                         c_k = logf(S_0) - logf(S_1);   llr_k = 0.5f * (m1 - m0) + c_k
+ * the exact log-MAP LLR of the axis (the log-sum-exp rule).  Each set is normalised by its own minimum, so 1 <= S_b <= L / 2,
+ * |c_k| <= log(L / 2), and the exact LLR is the max-log LLR plus a bounded correction: finite wherever the max-log LLR is.
+ * (A form normalised once by the global minimum underflows: the far set's sum rounds to 0 and its logf to -inf.)  For h = 1
+ * (BPSK, QPSK) each set has one element, S_b = 1.0f, c_k = +0.0f and the exact rule is the max-log rule bit for bit.  With
+ * e = 0 every D is equal and the LLR is +0.0f, an erasure, under both.  expf and logf are the device library's (1 ulp).
+ *
+ * ldpc_demap_sym : LLRs from received samples.  received: fp32 [batch][S][4] = (vI, vQ, e, 0) on the device, 16-byte aligned,
+ *   the layout ldpc_channel_sym writes (vQ and the fourth word are not read for m = 1 / at all).  llr [batch][n] fp32 (device,
+ *   4-byte aligned) receives, at variable position[t], the LLR of transmit bit t under `demapper`; nothing is stored for pad
+ *   bits.  mod->amp and mod->fading are ignored (e travels with the samples); mod->position is honoured.  With
+ *   LDPC_DEMAP_MAXLOG the samples ldpc_channel_sym wrote give the LLRs it wrote, bit for bit; with LDPC_DEMAP_EXACT those
+ *   ldpc_channel_sym_dm wrote.
+ *   LDPC_ERR_ARG for batch < 0, n < 1, a NULL mod, bits_per_symbol outside {1, 2, 4, 6, 8}; LDPC_ERR_UNSUPPORTED for
+ *   S >= 2^29; LDPC_ERR_ARG for a demapper outside {0, 1}; then batch == 0 returns LDPC_OK without touching a device pointer;
+ *   then LDPC_ERR_ARG for a NULL or misaligned llr and a NULL or misaligned received.
+ *   Asynchronous on `stream`, allocates nothing, safe under stream capture.
+ *
+ * ldpc_channel_sym_dm, ldpc_channel_sym_mix_dm, ldpc_simulate_sym_dm : ldpc_channel_sym, ldpc_channel_sym_mix and
+ *   ldpc_simulate_sym with the demapper chosen (LDPC_ERR_ARG outside {0, 1}, checked after the modulation); the three entry
+ *   points without the argument are these with LDPC_DEMAP_MAXLOG.  Noise, fading, received samples, targets and workspace
+ *   sizes do not depend on the demapper.
+ *
+ * Not provided: rate matching together with a modulation, PSK above 4 points and APSK, block fading, a training step that
+ * fuses this draw into the decode, fp64 LLRs, a table-driven or globally normalised fast form of the exact rule, demapping
+ * with decoder feedback. */
+enum { LDPC_DEMAP_MAXLOG = 0, LDPC_DEMAP_EXACT = 1 };
+
 typedef struct {
     int32_t bits_per_symbol;      /* 1, 2, 4, 6, 8 */
     int32_t fading;               /* 0 none, 1 Rayleigh per symbol */
@@ -686,6 +716,18 @@ size_t ldpc_simulate_sym_workspace_bytes(const ldpc_decoder *d, int64_t block, i
 int ldpc_simulate_sym(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
                       const ldpc_modulation *mod, int64_t capture, int64_t out_state[8], int64_t *out_diag,
                       void *workspace, size_t workspace_bytes, void *stream);
+int ldpc_demap_sym(void *llr, int64_t batch, int32_t n, const ldpc_modulation *mod, int32_t demapper,
+                   const void *received, void *stream);
+int ldpc_channel_sym_dm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                        const ldpc_modulation *mod, const uint8_t *codewords_packed, int64_t codeword_stride,
+                        void *received /* or NULL */, int32_t demapper, void *stream);
+int ldpc_channel_sym_mix_dm(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                            const ldpc_modulation *mod, const float *amp_tab, int32_t n_points,
+                            const uint8_t *codewords_packed, int64_t codeword_stride,
+                            void *targets /* or NULL */, int32_t demapper, void *stream);
+int ldpc_simulate_sym_dm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
+                         const ldpc_modulation *mod, int32_t demapper, int64_t capture, int64_t out_state[8],
+                         int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream);
 
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
