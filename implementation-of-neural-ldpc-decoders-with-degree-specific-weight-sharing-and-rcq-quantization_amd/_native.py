@@ -43,7 +43,8 @@ class NativeEngineError(RuntimeError):
 
 # the one compiled unit first, then everything it includes
 SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
-           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_encode.hip", "ldpc_modulation.hip", "ldpc_resident_geom.h", "ldpc_plan.h")
+           "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_encode.hip", "ldpc_modulation.hip", "ldpc_constellation.hip",
+           "ldpc_resident_geom.h", "ldpc_plan.h")
 
 
 def _source_files():
@@ -145,6 +146,12 @@ class ModulationDesc(C.Structure):
     _fields_ = [("bits_per_symbol", C.c_int32), ("fading", C.c_int32), ("amp", C.c_float), ("position", C.c_void_p)]
 
 
+class ConstellationDesc(C.Structure):
+    """ldpc_constellation of include/ldpc_hip.h: ldpc_modulation's fields and the table of 2^m points (device pointer)"""
+    _fields_ = [("bits_per_symbol", C.c_int32), ("fading", C.c_int32), ("amp", C.c_float), ("position", C.c_void_p),
+                ("points", C.c_void_p)]
+
+
 # every symbol include/ldpc_hip.h declares (tests check the library exports them all) ...
 PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info", "ldpc_decoder_create",
                    "ldpc_decoder_set_mode", "ldpc_decoder_info",
@@ -166,7 +173,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_encoder_create", "ldpc_encoder_destroy", "ldpc_encode", "ldpc_encode_random",
                    "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc",
                    "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym", "ldpc_channel_sym_mix",
-                   "ldpc_demap_sym", "ldpc_channel_sym_dm", "ldpc_channel_sym_mix_dm", "ldpc_simulate_sym_dm")
+                   "ldpc_demap_sym", "ldpc_channel_sym_dm", "ldpc_channel_sym_mix_dm", "ldpc_simulate_sym_dm",
+                   "ldpc_channel_con", "ldpc_channel_con_mix", "ldpc_demap_con", "ldpc_simulate_con")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -339,6 +347,15 @@ def load():
         lib.ldpc_channel_sym_mix_dm.argtypes = [vp, i64, i32, u64, u32, u64, mod, vp, i32, vp, i64, vp, i32, vp]
         lib.ldpc_simulate_sym_dm.restype = C.c_int
         lib.ldpc_simulate_sym_dm.argtypes = [vp, C.POINTER(SimDesc), vp, mod, i32, i64, vp, vp, vp, C.c_size_t, vp]
+        con = C.POINTER(ConstellationDesc)
+        lib.ldpc_channel_con.restype = C.c_int
+        lib.ldpc_channel_con.argtypes = [vp, i64, i32, u64, u32, u64, con, vp, i64, vp, i32, vp]
+        lib.ldpc_channel_con_mix.restype = C.c_int
+        lib.ldpc_channel_con_mix.argtypes = [vp, i64, i32, u64, u32, u64, con, vp, i32, vp, i64, vp, i32, vp]
+        lib.ldpc_demap_con.restype = C.c_int
+        lib.ldpc_demap_con.argtypes = [vp, i64, i32, con, i32, vp, vp]
+        lib.ldpc_simulate_con.restype = C.c_int
+        lib.ldpc_simulate_con.argtypes = [vp, C.POINTER(SimDesc), vp, con, i32, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p

@@ -1800,6 +1800,9 @@ int ldpc_decode_capped(const ldpc_decoder *d, const void *llr, int64_t batch, in
 // ---- symbol channel: Gray-mapped QAM, Rayleigh fading, max-log demapper, one SNR point on it (ldpc_channel_sym / ldpc_simulate_sym)
 #include "ldpc_modulation.hip"
 
+// ---- constellation channel: a table of up to 64 labelled points, joint max-log / exact demapper (ldpc_channel_con / ldpc_demap_con / ldpc_simulate_con)
+#include "ldpc_constellation.hip"
+
 extern "C" {
 
 int ldpc_debug_key4(const float *values, int64_t count, float beta, const float thresholds4[4], uint8_t *keys_float,

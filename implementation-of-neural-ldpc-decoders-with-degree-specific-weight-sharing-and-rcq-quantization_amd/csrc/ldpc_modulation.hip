@@ -70,6 +70,52 @@ __device__ inline void sym_store(float *dst, const float (&v)[M], int cnt)
     }
 }
 
+// the lane's (frame, symbol): one lane per symbol, consecutive lanes hold consecutive symbols of the [batch][S] block -- the
+// lane-to-(frame, symbol) arithmetic of sim_channel_awgn.  b may lie past the block: the caller returns then.
+__device__ inline void sym_lane(unsigned S, long long &b, unsigned &s)
+{
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
+    const unsigned long long b0 = g0 / S;
+    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
+    const unsigned db = t / S;
+    b = (long long)b0 + db;
+    s = t - db * S;
+}
+
+// the symbol's bits out of the frame's packed codeword row (NULL: the all-zero word), bit k of the symbol at bit k, pad bits 0.
+// Permuted path: p[k] = pos[j0 + k] is the variable of bit k (0 for a pad bit).  Identity path: cnt bits from bit j0 of the row on.
+template <int M, bool PERM>
+__device__ inline unsigned sym_bits(const uint8_t *row, const int *pos, int j0, int cnt, int rb, int (&p)[M])
+{
+    unsigned bits = 0;
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k) {
+            p[k] = k < cnt ? pos[j0 + k] : 0;
+            if (row && k < cnt) bits |= ((unsigned)(row[p[k] >> 3] >> (p[k] & 7)) & 1u) << k;
+        }
+    } else if (row) {
+        const int byte = j0 >> 3, sh = j0 & 7;
+        unsigned w = row[byte];
+        if ((M & (M - 1)) != 0 && byte + 1 < rb) w |= (unsigned)row[byte + 1] << 8;   // M = 3, 5, 6: a run can reach into the next byte
+        bits = (w >> sh) & ((1u << cnt) - 1u);
+    }
+    return bits;
+}
+
+// the lane's M values into row dst: the pos[] scatter, or the run of floats j0 .. j0 + cnt - 1
+template <int M, bool PERM>
+__device__ inline void sym_put(float *dst, const int (&p)[M], int j0, int cnt, const float (&v)[M])
+{
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k)
+            if (k < cnt) dst[p[k]] = v[k];
+    } else {
+        sym_store<M>(dst + j0, v, cnt);
+    }
+}
+
 // one axis of H bits: `bits` holds b_k at bit k (b_0, the most significant label bit, at bit 0).  Sends the labelled amplitude
 // through v = e * a + z, forms the 2^H squared distances once and takes the H masked minima out of them.
 template <int H>
@@ -202,12 +248,9 @@ __global__ __launch_bounds__(kSimBlock) void sym_demap(float *__restrict__ llr, 
                                                        const int *__restrict__ pos, const float4 *__restrict__ received)
 {
     constexpr int H = M == 1 ? 1 : M / 2;
-    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
-    const unsigned long long b0 = g0 / S;
-    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
-    const unsigned db = t / S;
-    const long long b = (long long)b0 + db;
-    const unsigned s = t - db * S;
+    long long b;
+    unsigned s;
+    sym_lane(S, b, s);
     if (b >= batch) return;
     const int j0 = (int)s * M;                                                    // < n <= 2^31 - 1
     const int cnt = n - j0 < M ? n - j0 : M;
@@ -242,32 +285,17 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__
                                                              long long cw_stride, float4 *__restrict__ received)
 {
     constexpr int H = M == 1 ? 1 : M / 2;
-    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
-    const unsigned long long b0 = g0 / S;
-    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
-    const unsigned db = t / S;
-    const long long b = (long long)b0 + db;
-    const unsigned s = t - db * S;
+    long long b;
+    unsigned s;
+    sym_lane(S, b, s);
     if (b >= batch) return;
     const int j0 = (int)s * M;                                                    // < n <= 2^31 - 1
     const int cnt = n - j0 < M ? n - j0 : M;
     const int rb = (n + 7) >> 3;
     const uint8_t *row = cw ? cw + (size_t)b * (size_t)cw_stride : nullptr;
     int p[M];                                                                     // permuted path: the symbol's variables
-    (void)p; (void)rb;
-    unsigned bits = 0;                                                           // bit k of the symbol at bit k; pad bits 0
-    if constexpr (PERM) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-            p[k] = k < cnt ? pos[j0 + k] : 0;
-            if (row && k < cnt) bits |= ((unsigned)(row[p[k] >> 3] >> (p[k] & 7)) & 1u) << k;
-        }
-    } else if (row) {
-        const int byte = j0 >> 3, sh = j0 & 7;
-        unsigned w = row[byte];
-        if (M == 6 && byte + 1 < rb) w |= (unsigned)row[byte + 1] << 8;           // six bits from bit 4 or 6 on reach into the next byte
-        bits = (w >> sh) & ((1u << cnt) - 1u);
-    }
+    (void)p;
+    const unsigned bits = sym_bits<M, PERM>(row, pos, j0, cnt, rb, p);            // bit k of the symbol at bit k; pad bits 0
     const unsigned long long f = first_frame + (unsigned long long)b;
     uint32_t x[4];
     philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), kSymCounterTag | s, stream_id, k0, k1, x);
@@ -287,13 +315,7 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym(float *__restrict__
     }
     if (received) received[(size_t)b * S + s] = make_float4(vI, vQ, e, 0.0f);
     float *dst = llr + (size_t)b * (size_t)n;
-    if constexpr (PERM) {
-#pragma unroll
-        for (int k = 0; k < M; ++k)
-            if (k < cnt) dst[p[k]] = v[k];
-    } else {
-        sym_store<M>(dst + j0, v, cnt);
-    }
+    sym_put<M, PERM>(dst, p, j0, cnt, v);
 }
 
 // sim_channel_sym with the SNR point a function of the frame and the sent bits as training targets (ldpc_channel_sym_mix):
@@ -315,12 +337,9 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restri
                                                                  long long cw_stride)
 {
     constexpr int H = M == 1 ? 1 : M / 2;
-    const unsigned long long g0 = (unsigned long long)blockIdx.x * kSimBlock;     // first symbol of the workgroup: uniform
-    const unsigned long long b0 = g0 / S;
-    const unsigned t = (unsigned)(g0 - b0 * S) + threadIdx.x;                     // < S + 256 < 2^29 + 256
-    const unsigned db = t / S;
-    const long long b = (long long)b0 + db;
-    const unsigned s = t - db * S;
+    long long b;
+    unsigned s;
+    sym_lane(S, b, s);
     if (b >= batch) return;
     const unsigned r = (unsigned)b + p0;
     unsigned pt = r - __umulhi(r, Kinv) * K;                                      // in [0, 2K), as in sim_channel_awgn_mix
@@ -331,20 +350,8 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restri
     const int rb = (n + 7) >> 3;
     const uint8_t *row = cw ? cw + (size_t)b * (size_t)cw_stride : nullptr;
     int p[M];                                                                     // permuted path: the symbol's variables
-    (void)p; (void)rb;
-    unsigned bits = 0;                                                           // bit k of the symbol at bit k; pad bits 0
-    if constexpr (PERM) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-            p[k] = k < cnt ? pos[j0 + k] : 0;
-            if (row && k < cnt) bits |= ((unsigned)(row[p[k] >> 3] >> (p[k] & 7)) & 1u) << k;
-        }
-    } else if (row) {
-        const int byte = j0 >> 3, sh = j0 & 7;
-        unsigned w = row[byte];
-        if (M == 6 && byte + 1 < rb) w |= (unsigned)row[byte + 1] << 8;           // six bits from bit 4 or 6 on reach into the next byte
-        bits = (w >> sh) & ((1u << cnt) - 1u);
-    }
+    (void)p;
+    const unsigned bits = sym_bits<M, PERM>(row, pos, j0, cnt, rb, p);            // bit k of the symbol at bit k; pad bits 0
     const unsigned long long f = first_frame + (unsigned long long)b;
     uint32_t x[4];
     philox4x32_10((uint32_t)f, (uint32_t)(f >> 32), kSymCounterTag | s, stream_id, k0, k1, x);
@@ -362,8 +369,8 @@ __global__ __launch_bounds__(kSimBlock) void sim_channel_sym_mix(float *__restri
         if constexpr (M > 1) sym_axis<H>(bits >> H, e, zQ, v + H);
     }
     float *dst = llr + (size_t)b * (size_t)n;
-    if constexpr (PERM) {
-#pragma unroll
+    if constexpr (PERM) {                                                         // sym_put, written out: through the helper the
+#pragma unroll                                                                    // permuted exact forms take two more VGPRs
         for (int k = 0; k < M; ++k)
             if (k < cnt) dst[p[k]] = v[k];
     } else {
@@ -587,10 +594,13 @@ int sym_demap_launch(float *llr, int64_t batch, int32_t n, const ldpc_modulation
 
 // simulate_enc_impl's loop with the symbol channel: encode_random (or the descriptor's one codeword), sim_channel_sym,
 // ldpc_decode, the decisions XORed with the codeword rows (one codeword: the counters compare against it themselves), the
-// existing counters.
-int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
-                      int32_t demapper, int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
-                      void *stream)
+// existing counters.  The channel is a parameter (ldpc_simulate_con runs the same loop on a constellation table):
+// check(n) validates its descriptor where sym_mod_check / sym_demapper_check stand, channel(llr, frames, first, cw, stride, s)
+// is the one launch of a block.
+template <class Check, class Channel>
+int simulate_symbols_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const char *what, Check check,
+                          Channel channel, int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace,
+                          size_t workspace_bytes, void *stream)
 {
     const bool diagnostics = capture >= 0;
     if (!d || !desc || !out_state) return fail(LDPC_ERR_ARG, "NULL decoder / descriptor / out_state");
@@ -599,10 +609,9 @@ int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
     if (e && desc->codeword_packed) return fail(LDPC_ERR_ARG, "codeword_packed must be NULL with an encoder: the codewords are drawn per frame");
     if (desc->block < 1) return fail(LDPC_ERR_ARG, "block < 1");
     if (desc->poll_blocks < 1) return fail(LDPC_ERR_ARG, "poll_blocks < 1");
-    if (d->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "ldpc_simulate_sym draws fp32 LLRs: float64 decoders are not supported");
+    if (d->dtype != LDPC_F32) return fail(LDPC_ERR_UNSUPPORTED, "%s draws fp32 LLRs: float64 decoders are not supported", what);
     if (d->g->n < 1) return fail(LDPC_ERR_ARG, "n < 1");
-    if (int rc = sym_mod_check(mod, d->g->n)) return rc;
-    if (int rc = sym_demapper_check(demapper)) return rc;
+    if (int rc = check(d->g->n)) return rc;
     if (e && e->g.n != d->g->n) return fail(LDPC_ERR_ARG, "the encoder has n = %d, the decoder n = %d", e->g.n, d->g->n);
     if (e && e->device != d->g->device) return fail(LDPC_ERR_ARG, "encoder and decoder live on different devices");
     if (!workspace) return fail(LDPC_ERR_ARG, "NULL workspace");
@@ -642,9 +651,7 @@ int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
             const uint64_t first = desc->first_frame + (uint64_t)drawn;
             if (e)
                 if (int rc = enc_launch(e, frames, 1, desc->seed, desc->stream_id, first, nullptr, cw, nullptr, s)) return rc;
-            if (int rc = sim_channel_sym_launch(llr, frames, n, desc->seed, desc->stream_id, first, mod, demapper, e ? cw : one,
-                                                e ? rb : 0, nullptr, s))
-                return rc;
+            if (int rc = channel(llr, frames, first, e ? (const uint8_t *)cw : one, e ? rb : 0, s)) return rc;
             if (int rc = ldpc_decode(d, llr, frames, 1, nullptr, nullptr, iters, success, packed, base + w.o_dec, w.dec_bytes, s))
                 return rc;
             if (e) {
@@ -669,6 +676,22 @@ int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
     }
     for (int k = 0; k < 8; ++k) out_state[k] = host.p[k];
     return LDPC_OK;
+}
+
+int simulate_sym_impl(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_modulation *mod,
+                      int32_t demapper, int64_t capture, int64_t out_state[8], int64_t *out_diag, void *workspace, size_t workspace_bytes,
+                      void *stream)
+{
+    return simulate_symbols_impl(
+        d, desc, e, "ldpc_simulate_sym",
+        [&](int32_t n) {
+            if (int rc = sym_mod_check(mod, n)) return rc;
+            return sym_demapper_check(demapper);
+        },
+        [&](float *llr, int64_t frames, uint64_t first, const uint8_t *cw, int64_t stride, hipStream_t s) {
+            return sim_channel_sym_launch(llr, frames, d->g->n, desc->seed, desc->stream_id, first, mod, demapper, cw, stride, nullptr, s);
+        },
+        capture, out_state, out_diag, workspace, workspace_bytes, stream);
 }
 
 }  // namespace

@@ -143,6 +143,12 @@ def _check_modulation(modulation):
     return modulation
 
 
+def _is_constellation(modulation) -> bool:
+    """a modulation.Constellation: the table-driven entry points (ldpc_*_con) instead of the separable ones (ldpc_*_sym)"""
+    from modulation import Constellation
+    return isinstance(modulation, Constellation)
+
+
 def _symbol_amp(modulation, snr_db, amp) -> float:
     if (snr_db is None) == (amp is None):
         raise ValueError("with a modulation give either snr_db or amp")
@@ -158,7 +164,9 @@ def sym_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: i
     constellation's half-spacing over the per-dimension noise standard deviation.  codeword: None (all zero), a 0/1 array of
     length n, a packed uint8 tensor, or a 2-D uint8 tensor [batch, ceil(n/8)] of one packed codeword per frame, as
     ``encode_random`` returns them.  want_received: -> (llr, received), received fp32 [batch, S, 4] = (vI, vQ, e, 0) per
-    symbol, e the fading gain times amp (vQ = 0 for BPSK) -- for a constellation plot, for ``demap``, or a demapper of your own."""
+    symbol, e the fading gain times amp (vQ = 0 for BPSK) -- for a constellation plot, for ``demap``, or a demapper of your own.
+    A modulation.Constellation sends the points of its table and is demapped jointly over all of them (ldpc_channel_con;
+    INTEGRATION.md 6i); amp is then 1 / sigma, sigma the per-dimension noise standard deviation."""
     dev = _require_gpu(device)
     mod = _check_modulation(modulation)
     amp = _symbol_amp(mod, snr_db, amp)
@@ -176,7 +184,10 @@ def sym_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: i
         args = (C.c_void_p(out.data_ptr()), batch, n, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1),
                 int(first_frame) & (2 ** 64 - 1), C.byref(desc), None if cw is None else C.c_void_p(cw.data_ptr()),
                 (n + 7) // 8 if rows else 0, None if rec is None else C.c_void_p(rec.data_ptr()))
-        if mod.demapper == "exact":
+        if _is_constellation(mod):
+            from modulation import DEMAPPERS
+            nat.check(lib.ldpc_channel_con(*args, DEMAPPERS[mod.demapper], C.c_void_p(stream)), "ldpc_channel_con")
+        elif mod.demapper == "exact":
             nat.check(lib.ldpc_channel_sym_dm(*args, nat.DEMAP_EXACT, C.c_void_p(stream)), "ldpc_channel_sym_dm")
         else:
             nat.check(lib.ldpc_channel_sym(*args, C.c_void_p(stream)), "ldpc_channel_sym")
@@ -189,7 +200,7 @@ def demap(received, n: int, *, modulation, demapper: Optional[str] = None, devic
     returns, or ``modulation.normalise_received`` of physical samples.  demapper "maxlog" | "exact"; None: the modulation's
     own.  The modulation's fading is not used (e travels with the samples); its interleaver is honoured.  With "maxlog" the
     samples of a ``sym_llr`` call give that call's LLRs bit for bit, with "exact" those of the same call under
-    ``Modulation(..., demapper="exact")``."""
+    ``Modulation(..., demapper="exact")``.  A modulation.Constellation goes through ldpc_demap_con."""
     mod = _check_modulation(modulation)
     from modulation import DEMAPPERS
     rule = mod.demapper if demapper is None else demapper
@@ -214,8 +225,9 @@ def demap(received, n: int, *, modulation, demapper: Optional[str] = None, devic
     out = torch.empty((batch, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        nat.check(lib.ldpc_demap_sym(C.c_void_p(out.data_ptr()), batch, n, C.byref(desc), DEMAPPERS[rule],
-                                     C.c_void_p(received.data_ptr()), C.c_void_p(stream)), "ldpc_demap_sym")
+        fn, name = (lib.ldpc_demap_con, "ldpc_demap_con") if _is_constellation(mod) else (lib.ldpc_demap_sym, "ldpc_demap_sym")
+        nat.check(fn(C.c_void_p(out.data_ptr()), batch, n, C.byref(desc), DEMAPPERS[rule],
+                     C.c_void_p(received.data_ptr()), C.c_void_p(stream)), name)
     return out
 
 
@@ -353,7 +365,10 @@ def sym_llr_mix(batch: int, n: int, *, seed: int, stream_id: int = 0, first_fram
                 int(first_frame) & (2 ** 64 - 1), C.byref(desc), C.c_void_p(amp_tab.data_ptr()), n_points,
                 None if cw is None else C.c_void_p(cw.data_ptr()), (n + 7) // 8 if rows else 0,
                 None if targets is None else C.c_void_p(targets.data_ptr()))
-        if mod.demapper == "exact":
+        if _is_constellation(mod):
+            from modulation import DEMAPPERS
+            nat.check(lib.ldpc_channel_con_mix(*args, DEMAPPERS[mod.demapper], C.c_void_p(stream)), "ldpc_channel_con_mix")
+        elif mod.demapper == "exact":
             nat.check(lib.ldpc_channel_sym_mix_dm(*args, nat.DEMAP_EXACT, C.c_void_p(stream)), "ldpc_channel_sym_mix_dm")
         else:
             nat.check(lib.ldpc_channel_sym_mix(*args, C.c_void_p(stream)), "ldpc_channel_sym_mix")
@@ -995,7 +1010,10 @@ class DecodeEngine:
             head = (self.handle, C.byref(desc), None if ne is None else ne.handle, C.byref(mdesc))
             tail = (capture if diagnostics else -1, nat.ptr(out), nat.ptr(words), C.c_void_p(ws.data_ptr()), ws.numel(),
                     C.c_void_p(stream))
-            if mod.demapper == "exact":
+            if _is_constellation(mod):
+                from modulation import DEMAPPERS
+                nat.check(self._lib.ldpc_simulate_con(*head, DEMAPPERS[mod.demapper], *tail), "ldpc_simulate_con")
+            elif mod.demapper == "exact":
                 nat.check(self._lib.ldpc_simulate_sym_dm(*head, nat.DEMAP_EXACT, *tail), "ldpc_simulate_sym_dm")
             else:
                 nat.check(self._lib.ldpc_simulate_sym(*head, *tail), "ldpc_simulate_sym")

@@ -37,7 +37,9 @@ Channel (``SimulationConfig.channel``):
             ``SimulationConfig.modulation`` (this channel only; a ``modulation.Modulation``) sends the bits as Gray-mapped BPSK /
             QPSK / 16- / 64- / 256-QAM symbols over AWGN or per-symbol Rayleigh fading and demaps them with the modulation's
             demapper, max-log or exact (``engine.sym_llr``, DESIGN.md sections 3j and 3l); ``snr_db`` is then Es/N0 of the symbol.  Not together with
-            ``rate_matching``; from 16-QAM up it needs ``codeword="random"`` (or a codeword).
+            ``rate_matching``; from 16-QAM up it needs ``codeword="random"`` (or a codeword).  A ``modulation.Constellation``
+            (8-PSK, APSK, any table of up to 64 labelled points) is taken the same way and always
+            needs ``codeword="random"`` (or a codeword).
 """
 
 from __future__ import annotations
@@ -58,7 +60,7 @@ import torch
 from ldpc_decoder import BasicMinSumDecoder, LDPCCode
 from neural_2d_decoder import Neural2DMinSumDecoder, Neural2DOffsetMinSumDecoder
 from neural_minsum_decoder import NeuralMinSumDecoder, NeuralOffsetMinSumDecoder
-from modulation import Modulation
+from modulation import Constellation, Modulation
 from rate_matching import RateMatching
 from rcq_decoder import RCQMinSumDecoder, WeightedRCQDecoder
 
@@ -105,6 +107,9 @@ class SimulationConfig:
                 raise ValueError("rate_matching together with modulation is not provided (DESIGN.md section 3j)")
             if self.llr_convention != "decoder":
                 raise ValueError("modulation maps bit 0 to the positive half: llr_convention must be 'decoder'")
+            if isinstance(self.modulation, Constellation) and self.codeword is None:
+                raise ValueError(f"{self.modulation.scheme}: a constellation table has no guaranteed symmetry, so the all-zero "
+                                 f"codeword says nothing about the others: set codeword=\"random\" (or give a codeword)")
             if self.modulation.bits_per_symbol >= 4 and self.codeword is None:
                 raise ValueError(f"{self.modulation.scheme} with the all-zero codeword sends one corner point only and its bit "
                                  f"channels are not output-symmetric: set codeword=\"random\" (or give a codeword)")

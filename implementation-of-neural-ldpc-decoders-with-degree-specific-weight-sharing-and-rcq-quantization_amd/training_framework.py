@@ -194,7 +194,7 @@ class PosteriorJointTrainer(metaclass=_TrainerType):
                 raise ValueError("codeword needs a modulation: per-frame codewords on the BI-AWGN stream are not provided "
                                  "(Modulation('qpsk') is that channel in law at the same snr_db)")
         else:
-            from modulation import Modulation
+            from modulation import Constellation, Modulation
             if not isinstance(modulation, Modulation):
                 raise ValueError("modulation must be a modulation.Modulation")
             if rate_matching is not None:
@@ -208,6 +208,9 @@ class PosteriorJointTrainer(metaclass=_TrainerType):
                 codeword = np.asarray(codeword)
                 if codeword.ndim != 1 or not np.isin(codeword, (0, 1)).all():
                     raise ValueError("codeword must be None, 'random' or a 0/1 array of length n")
+            elif isinstance(modulation, Constellation):
+                raise ValueError(f"{modulation.scheme}: a constellation table has no guaranteed symmetry, so the all-zero codeword "
+                                 f"says nothing about the others: train with codeword=\"random\" (or give a codeword)")
             elif modulation.bits_per_symbol >= 4:
                 raise ValueError(f"{modulation.scheme} with the all-zero codeword sends one corner point only and its bit "
                                  f"levels are not output-symmetric: train with codeword='random'")

@@ -693,9 +693,9 @@ int ldpc_simulate_enc(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ld
  *   points without the argument are these with LDPC_DEMAP_MAXLOG.  Noise, fading, received samples, targets and workspace
  *   sizes do not depend on the demapper.
  *
- * Not provided: rate matching together with a modulation, PSK above 4 points and APSK, block fading, a training step that
- * fuses this draw into the decode, fp64 LLRs, a table-driven or globally normalised fast form of the exact rule, demapping
- * with decoder feedback. */
+ * Not provided: rate matching together with a modulation, block fading, a training step that fuses this draw into the
+ * decode, fp64 LLRs, a table-driven or globally normalised fast form of the exact rule, demapping with decoder feedback.
+ * (PSK above 4 points, APSK and every other labelled point set: the constellation channel below.) */
 enum { LDPC_DEMAP_MAXLOG = 0, LDPC_DEMAP_EXACT = 1 };
 
 typedef struct {
@@ -728,6 +728,74 @@ int ldpc_channel_sym_mix_dm(void *llr, int64_t batch, int32_t n, uint64_t seed, 
 int ldpc_simulate_sym_dm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
                          const ldpc_modulation *mod, int32_t demapper, int64_t capture, int64_t out_state[8],
                          int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- constellation channel: a table of up to 64 labelled points, demapped jointly over all points ----
+ * The symbol channel above rests on a Gray-labelled square grid that separates into two PAM axes.  This one takes the
+ * constellation as a table: 8-PSK, APSK, any labelling, rotated, shaped or learned point sets.  Everything above is unchanged.
+ *
+ * Constellation.  m = bits_per_symbol in 1 .. 6, `points` an fp32 table [2^m][2] = (xI, xQ) on the device, 8-byte aligned,
+ * whose contents the caller vouches for (finite; unit mean energy if `amp` is to mean what it means below).  The frame layout
+ * is the symbol channel's: S = ceil(n / m) symbols, transmit index t = s * m + k is bit k of symbol s and carries the codeword
+ * bit of variable position[t] (NULL: the identity), pad bits are sent as 0 and never stored.  The symbol's label is
+ * l = sum_k b_k 2^k (bit k of the symbol at bit k) and the sent point is points[l]: the labelling is the order of the table,
+ * nothing else.
+ *
+ * Noise stream: the symbol channel's, word for word -- Philox4x32-10 with counter (f lo, f hi, 0x40000000 | s, stream_id),
+ * (zI, zQ) the Box-Muller pair of (x0, x1), g = 1.0f or sqrtf(-logf(u(x2))) under fading, S < 2^29.  A table that holds a QAM
+ * grid sees the noise and fading that ldpc_channel_sym gives that scheme at the same (seed, stream_id, frame).  The noise is
+ * complex for every m, m = 1 included.
+ *
+ * Received sample and distances, all fp32, every multiply and add rounded on its own (no fused multiply-add):
+ *     e  = g * amp
+ *     vI = (e * xI_l) + zI;   vQ = (e * xQ_l) + zQ
+ *     for every candidate c = 0 .. 2^m - 1:  tI = vI - (e * xI_c);  tQ = vQ - (e * xQ_c);  D_c = (tI * tI) + (tQ * tQ)
+ *     m_b(k) = min over c with bit k of c equal to b of D_c
+ *     LDPC_DEMAP_MAXLOG:  llr_k = 0.5f * (m_1 - m_0)
+ *     LDPC_DEMAP_EXACT:   S_b = sum_{c: bit k of c = b} expf(-0.5f * (D_c - m_b)), summed in ascending c
+ *                         llr_k = 0.5f * (m_1 - m_0) + (logf(S_0) - logf(S_1))
+ * the normalisation and summation order of the exact rule above: 1 <= S_b <= 2^(m-1), so |correction| <= (m - 1) log 2.  For
+ * m = 1 the exact rule is the max-log rule bit for bit; e = 0 gives +0.0f under both.  `amp` is 1 / sigma, sigma = sqrt(N0 / 2)
+ * the per-dimension noise standard deviation: with Es = 1, amp = sqrt(2 * 10^(snr_db / 10)), for every m.
+ *
+ * ldpc_channel_con : ldpc_channel_sym_dm on the table.  llr, codewords_packed, codeword_stride, received ([batch][S][4] =
+ *   (vI, vQ, e, 0.0f), or NULL) and demapper as there.
+ *   LDPC_ERR_ARG for batch < 0, n < 1, a NULL con, bits_per_symbol outside 1 .. 6, a NULL points, fading outside {0, 1}, amp
+ *   not finite or < 0, a stride other than 0 and ceil(n / 8), a demapper outside {0, 1}; LDPC_ERR_UNSUPPORTED for S >= 2^29;
+ *   then batch == 0 returns LDPC_OK without touching a device pointer; then LDPC_ERR_ARG for a NULL or misaligned llr, a
+ *   misaligned received and a points that is not 8-byte aligned.
+ * ldpc_channel_con_mix : ldpc_channel_sym_mix_dm on the table: amp = amp_tab[f mod n_points] (con->amp is ignored), targets as
+ *   there; a frame receives, bit for bit, what ldpc_channel_con gives it at that amp.  Checks as ldpc_channel_con, with, after
+ *   the demapper: n_points outside 1 .. 4096, batch > 2^31 - 1, first_frame + batch beyond 2^64, a NULL amp_tab with
+ *   batch > 0; and a misaligned targets and amp_tab among the pointers.
+ * ldpc_demap_con : ldpc_demap_sym on the table.  con->amp and con->fading are ignored, con->position is honoured.  The samples
+ *   ldpc_channel_con wrote give, under the same demapper, the LLRs it wrote, bit for bit.  Checks: batch, n, con,
+ *   bits_per_symbol, points, demapper, S, batch == 0, then llr, received (NULL or not 16-byte aligned) and points.
+ * ldpc_simulate_con : the loop of ldpc_simulate_sym_dm with ldpc_channel_con as the channel; records, replay, workspace
+ *   (ldpc_simulate_sym_workspace_bytes) and everything else as there.
+ * The three channel entry points are asynchronous on `stream`, allocate nothing and are safe under stream capture.
+ *
+ * Not provided: more than 64 points, fp64, a reduced-search or table-driven fast form of the joint rule, iterative demapping,
+ * rate matching with a constellation, block fading, the standards' own APSK bit maps (pass the standard's table). */
+typedef struct {
+    int32_t bits_per_symbol;      /* m, 1 .. 6 */
+    int32_t fading;               /* 0 none, 1 Rayleigh per symbol */
+    float   amp;                  /* finite, >= 0 */
+    const int32_t *position;      /* device, n entries, or NULL */
+    const float   *points;        /* device fp32 [2^m][2] = (xI, xQ), 8-byte aligned; the caller vouches for its contents */
+} ldpc_constellation;
+
+int ldpc_channel_con(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                     const ldpc_constellation *con, const uint8_t *codewords_packed, int64_t codeword_stride,
+                     void *received /* or NULL */, int32_t demapper, void *stream);
+int ldpc_channel_con_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
+                         const ldpc_constellation *con, const float *amp_tab, int32_t n_points,
+                         const uint8_t *codewords_packed, int64_t codeword_stride,
+                         void *targets /* or NULL */, int32_t demapper, void *stream);
+int ldpc_demap_con(void *llr, int64_t batch, int32_t n, const ldpc_constellation *con, int32_t demapper,
+                   const void *received, void *stream);
+int ldpc_simulate_con(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
+                      const ldpc_constellation *con, int32_t demapper, int64_t capture, int64_t out_state[8],
+                      int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream);
 
 const char *ldpc_last_error(void);
 int ldpc_abi_version(void);
