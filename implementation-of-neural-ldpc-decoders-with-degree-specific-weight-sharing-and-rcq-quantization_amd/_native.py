@@ -174,7 +174,8 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_channel_awgn_cw", "ldpc_simulate_enc_workspace_bytes", "ldpc_simulate_enc",
                    "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym", "ldpc_channel_sym_mix",
                    "ldpc_demap_sym", "ldpc_channel_sym_dm", "ldpc_channel_sym_mix_dm", "ldpc_simulate_sym_dm",
-                   "ldpc_channel_con", "ldpc_channel_con_mix", "ldpc_demap_con", "ldpc_simulate_con")
+                   "ldpc_channel_con", "ldpc_channel_con_mix", "ldpc_demap_con", "ldpc_simulate_con",
+                   "ldpc_demap_con_prior")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
@@ -354,6 +355,8 @@ def load():
         lib.ldpc_channel_con_mix.argtypes = [vp, i64, i32, u64, u32, u64, con, vp, i32, vp, i64, vp, i32, vp]
         lib.ldpc_demap_con.restype = C.c_int
         lib.ldpc_demap_con.argtypes = [vp, i64, i32, con, i32, vp, vp]
+        lib.ldpc_demap_con_prior.restype = C.c_int
+        lib.ldpc_demap_con_prior.argtypes = [vp, i64, i32, con, i32, vp, vp, vp, C.c_float, vp]
         lib.ldpc_simulate_con.restype = C.c_int
         lib.ldpc_simulate_con.argtypes = [vp, C.POINTER(SimDesc), vp, con, i32, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int

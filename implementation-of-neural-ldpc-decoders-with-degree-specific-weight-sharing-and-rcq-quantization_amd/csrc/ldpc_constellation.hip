@@ -1,7 +1,8 @@
 // ldpc_constellation.hip -- the symbol channel on a constellation given as a table: up to 64 labelled points in the plane
 // (8-PSK, APSK, any labelling, rotated, shaped or learned sets) over AWGN or per-symbol Rayleigh fading, demapped jointly over
 // all points with the max-log or the exact rule (ldpc_channel_con), the training draw (ldpc_channel_con_mix), LLRs from
-// received samples (ldpc_demap_con) and one SNR point (ldpc_simulate_con) of include/ldpc_hip.h.
+// received samples (ldpc_demap_con), extrinsic LLRs from samples and a priori LLRs (ldpc_demap_con_prior) and one SNR point
+// (ldpc_simulate_con) of include/ldpc_hip.h.
 //
 // Included by ldpc_hip.hip below ldpc_modulation.hip: it uses that file's lane arithmetic (sym_lane), codeword bit extraction
 // (sym_bits), stores (sym_put / sym_store), counter tag, demapper check and simulate loop.  Still the one compiled unit.
@@ -127,6 +128,107 @@ __global__ __launch_bounds__(kSimBlock) void con_demap(float *__restrict__ llr, 
         for (int k = 0; k < M; ++k) p[k] = k < cnt ? pos[j0 + k] : 0;
     }
     sym_put<M, PERM>(llr + (size_t)b * (size_t)n, p, j0, cnt, v);
+}
+
+// extrinsic LLRs of one received sample given the a priori LLRs la[k] of its bits (ldpc_demap_con_prior).  A_c is the sum of
+// la over the set bits of c: one add per candidate onto the sum of c without its highest set bit, all indices compile-time
+// after unrolling.  Lam_c = D_c + 2.0f * A_c is D_c exactly when every la is +-0.0f, so the rule is then con_rule's bit for
+// bit.  con_rule itself is left alone: the kernels built on it compile to what they compiled to before.
+template <int M, bool EXACT>
+__device__ inline void con_rule_prior(float vI, float vQ, float e, const float2 *tab, const float (&la)[M], float (&llr)[M])
+{
+    constexpr int L = 1 << M;
+    float m0[M], m1[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) m0[k] = m1[k] = INFINITY;
+    float A[L];                                            // max-log: dead once Lam_c is formed;  exact: Lam_c takes its place
+    A[0] = 0.0f;
+#pragma unroll
+    for (int c = 1; c < L; ++c) {
+        const int h = 31 - __builtin_clz((unsigned)c);     // the highest set bit of c
+        A[c] = A[c - (1 << h)] + la[h];
+    }
+#pragma unroll
+    for (int c = 0; c < L; ++c) {
+        const float2 x = tab[c];
+        const float eI = e * x.x;
+        const float eQ = e * x.y;
+        const float tI = vI - eI;
+        const float tQ = vQ - eQ;
+        const float qI = tI * tI;
+        const float qQ = tQ * tQ;
+        const float d = qI + qQ;
+        const float a2 = 2.0f * A[c];
+        const float lam = d + a2;
+        if constexpr (EXACT) A[c] = lam;
+#pragma unroll
+        for (int k = 0; k < M; ++k) {
+            if ((c >> k) & 1) m1[k] = fminf(m1[k], lam);
+            else m0[k] = fminf(m0[k], lam);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        const float diff = m1[k] - m0[k];
+        if constexpr (EXACT) {
+            float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+            for (int c = 0; c < L; ++c) {
+                if ((c >> k) & 1) {
+                    const float x = A[c] - m1[k];
+                    s1 = s1 + expf(-0.5f * x);
+                } else {
+                    const float x = A[c] - m0[k];
+                    s0 = s0 + expf(-0.5f * x);
+                }
+            }
+            const float corr = logf(s0) - logf(s1);
+            const float post = 0.5f * diff + corr;
+            llr[k] = post - la[k];
+        } else {
+            llr[k] = 0.5f * diff - la[k];
+        }
+    }
+}
+
+// extrinsic LLRs from received samples and a priori LLRs (ldpc_demap_con_prior): con_demap with con_rule_prior.  A lane loads
+// the priors of its own symbol's variables only, all of them before its first store, and stores to those variables only: llr
+// may be prior or prior_sub themselves (none of the three is __restrict__).  Pad bits have the prior +0.0f.
+template <int M, bool PERM, bool EXACT>
+__global__ __launch_bounds__(kSimBlock) void con_demap_prior(float *llr, long long batch, int n, unsigned S,
+                                                             const int *__restrict__ pos, const float4 *__restrict__ received,
+                                                             const float2 *__restrict__ points, const float *prior,
+                                                             const float *prior_sub, float prior_scale)
+{
+    __shared__ float2 tab[1 << M];
+    con_stage<M>(tab, points);
+    long long b;
+    unsigned s;
+    sym_lane(S, b, s);
+    if (b >= batch) return;
+    const int j0 = (int)s * M;                                                    // < n <= 2^31 - 1
+    const int cnt = n - j0 < M ? n - j0 : M;
+    const float4 r = received[(size_t)b * S + s];
+    int p[M];
+    (void)p;
+    if constexpr (PERM) {
+#pragma unroll
+        for (int k = 0; k < M; ++k) p[k] = k < cnt ? pos[j0 + k] : 0;
+    }
+    const size_t row = (size_t)b * (size_t)n;
+    float la[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        la[k] = 0.0f;
+        if (k < cnt) {
+            const size_t j = row + (size_t)(PERM ? p[k] : j0 + k);
+            const float a = prior_sub ? prior[j] - prior_sub[j] : prior[j];
+            la[k] = prior_scale * a;
+        }
+    }
+    float v[M];
+    con_rule_prior<M, EXACT>(r.x, r.y, r.z, tab, la, v);
+    sym_put<M, PERM>(llr + row, p, j0, cnt, v);
 }
 
 // sim_channel_sym on a table: the same lanes, bits, counters and stores, con_send and con_rule where sym_axis stands
@@ -267,9 +369,11 @@ struct ConArgs {
     long long cw_stride;
     float4 *received;
     const float2 *points;
+    const float *prior, *prior_sub;
+    float prior_scale;
 };
 
-enum { kConChannel, kConMix, kConDemap };
+enum { kConChannel, kConMix, kConDemap, kConDemapPrior };
 
 template <int KIND, int M, bool FADING, bool PERM, bool EXACT>
 void con_launch_one(dim3 grid, hipStream_t s, const ConArgs &a)
@@ -281,17 +385,21 @@ void con_launch_one(dim3 grid, hipStream_t s, const ConArgs &a)
         hipLaunchKernelGGL((sim_channel_con_mix<M, FADING, PERM, EXACT>), grid, dim3(kSimBlock), 0, s, a.llr, a.targets, a.batch, a.n,
                            a.S, a.k0, a.k1, a.stream_id, a.first_frame, a.p0, a.K, a.Kinv, a.amp_tab, a.pos, a.cw, a.cw_stride,
                            a.points);
-    else
+    else if constexpr (KIND == kConDemap)
         hipLaunchKernelGGL((con_demap<M, PERM, EXACT>), grid, dim3(kSimBlock), 0, s, a.llr, a.batch, a.n, a.S, a.pos,
                            (const float4 *)a.received, a.points);
+    else
+        hipLaunchKernelGGL((con_demap_prior<M, PERM, EXACT>), grid, dim3(kSimBlock), 0, s, a.llr, a.batch, a.n, a.S, a.pos,
+                           (const float4 *)a.received, a.points, a.prior, a.prior_sub, a.prior_scale);
 }
 
 template <int KIND, int M, bool EXACT>
 void con_launch_m(bool fading, bool perm, dim3 grid, hipStream_t s, const ConArgs &a)
 {
-    if (KIND != kConDemap && fading) {                     // con_demap reads the gain out of the samples: one form for both
-        if (perm) con_launch_one<KIND, M, KIND != kConDemap, true, EXACT>(grid, s, a);
-        else con_launch_one<KIND, M, KIND != kConDemap, false, EXACT>(grid, s, a);
+    constexpr bool kDraws = KIND != kConDemap && KIND != kConDemapPrior;
+    if (kDraws && fading) {                                // the demappers read the gain out of the samples: one form for both
+        if (perm) con_launch_one<KIND, M, kDraws, true, EXACT>(grid, s, a);
+        else con_launch_one<KIND, M, kDraws, false, EXACT>(grid, s, a);
     } else {
         if (perm) con_launch_one<KIND, M, false, true, EXACT>(grid, s, a);
         else con_launch_one<KIND, M, false, false, EXACT>(grid, s, a);
@@ -415,6 +523,32 @@ int ldpc_demap_con(void *llr, int64_t batch, int32_t n, const ldpc_constellation
     a.llr = (float *)llr, a.batch = (long long)batch, a.n = (int)n;
     a.received = (float4 *)const_cast<void *>(received);
     return con_launch<kConDemap>(con, demapper, (hipStream_t)stream, a);
+}
+
+int ldpc_demap_con_prior(void *llr, int64_t batch, int32_t n, const ldpc_constellation *con, int32_t demapper,
+                         const void *received, const void *prior, const void *prior_sub, float prior_scale, void *stream)
+{
+    if (batch < 0) return fail(LDPC_ERR_ARG, "batch < 0");
+    if (n < 1) return fail(LDPC_ERR_ARG, "n < 1");
+    if (int rc = con_desc_check(con, false, false)) return rc;
+    if (int rc = sym_demapper_check(demapper)) return rc;
+    if (!std::isfinite(prior_scale)) return fail(LDPC_ERR_ARG, "prior_scale must be finite");
+    if (int rc = con_symbols_check(con, n)) return rc;
+    if (batch == 0) return LDPC_OK;
+    if (!llr) return fail(LDPC_ERR_ARG, "NULL llr");
+    if (((uintptr_t)llr % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "llr must be 4-byte aligned");
+    if (!received) return fail(LDPC_ERR_ARG, "NULL received");
+    if (((uintptr_t)received % 16) != 0) return fail(LDPC_ERR_ARG, "received must be 16-byte aligned");
+    if (prior && ((uintptr_t)prior % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "prior must be 4-byte aligned");
+    if (prior_sub && ((uintptr_t)prior_sub % sizeof(float)) != 0) return fail(LDPC_ERR_ARG, "prior_sub must be 4-byte aligned");
+    if (prior_sub && !prior) return fail(LDPC_ERR_ARG, "prior_sub without a prior");
+    if (int rc = con_points_check(con)) return rc;
+    ConArgs a{};
+    a.llr = (float *)llr, a.batch = (long long)batch, a.n = (int)n;
+    a.received = (float4 *)const_cast<void *>(received);
+    if (!prior) return con_launch<kConDemap>(con, demapper, (hipStream_t)stream, a);     // no priors: ldpc_demap_con's kernel
+    a.prior = (const float *)prior, a.prior_sub = (const float *)prior_sub, a.prior_scale = prior_scale;
+    return con_launch<kConDemapPrior>(con, demapper, (hipStream_t)stream, a);
 }
 
 int ldpc_simulate_con(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e, const ldpc_constellation *con,

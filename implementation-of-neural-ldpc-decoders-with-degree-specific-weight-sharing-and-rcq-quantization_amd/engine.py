@@ -35,6 +35,7 @@ class DecodeResult:
     iterations: torch.Tensor              # int32 [B]        1-based, T when not converged
     success: torch.Tensor                 # bool  [B]
     packed_bits: Optional[torch.Tensor] = None   # uint8 [B, ceil(n/8)]
+    rounds: Optional[torch.Tensor] = None        # int32 [B]        demapping rounds run (decode_iterative only)
 
 
 def _require_gpu(device) -> torch.device:
@@ -194,13 +195,21 @@ def sym_llr(batch: int, n: int, *, seed: int, stream_id: int = 0, first_frame: i
     return (out, rec) if want_received else out
 
 
-def demap(received, n: int, *, modulation, demapper: Optional[str] = None, device=None) -> torch.Tensor:
+def demap(received, n: int, *, modulation, demapper: Optional[str] = None, device=None, prior=None, prior_sub=None,
+          prior_scale: float = 1.0, out=None) -> torch.Tensor:
     """LLRs [batch, n] fp32 from received samples (ldpc_demap_sym): `received` is a contiguous float32
     tensor [batch, S, 4] = (vI, vQ, e, 0) per symbol on the device, S = ceil(n / m) -- what ``sym_llr(want_received=True)``
     returns, or ``modulation.normalise_received`` of physical samples.  demapper "maxlog" | "exact"; None: the modulation's
     own.  The modulation's fading is not used (e travels with the samples); its interleaver is honoured.  With "maxlog" the
     samples of a ``sym_llr`` call give that call's LLRs bit for bit, with "exact" those of the same call under
-    ``Modulation(..., demapper="exact")``.  A modulation.Constellation goes through ldpc_demap_con."""
+    ``Modulation(..., demapper="exact")``.  A modulation.Constellation goes through ldpc_demap_con.
+
+    prior / prior_sub / prior_scale / out (a modulation.Constellation only; ldpc_demap_con_prior): with
+    a priori LLRs La = prior_scale * (prior - prior_sub) of the frame's variables (prior_sub None: prior_scale * prior) the
+    result is the *extrinsic* LLR of every bit, what the samples and the other bits of its symbol say about it -- the demapper
+    of iterative demapping, fed with prior = a decoder's posterior and prior_sub = the LLRs that decoder was given.  Both are
+    contiguous fp32 [batch, n] tensors on the samples' device, finite.  out: a contiguous fp32 [batch, n] tensor on that device
+    to write into; it may be prior or prior_sub themselves.  Without any of the four the call is the one above."""
     mod = _check_modulation(modulation)
     from modulation import DEMAPPERS
     rule = mod.demapper if demapper is None else demapper
@@ -213,6 +222,25 @@ def demap(received, n: int, *, modulation, demapper: Optional[str] = None, devic
     if (not isinstance(received, torch.Tensor) or received.dtype != torch.float32 or received.dim() != 3
             or tuple(received.shape[1:]) != (S, 4) or not received.is_contiguous()):
         raise ValueError(f"received must be a contiguous float32 tensor [batch, {S}, 4] = (vI, vQ, e, 0) per symbol")
+    if isinstance(prior_scale, (bool, str)) or not np.isscalar(prior_scale) or not np.isreal(prior_scale):
+        raise ValueError(f"prior_scale must be a finite number, got {prior_scale!r}")
+    prior_scale = float(prior_scale)
+    if prior is not None or prior_sub is not None or out is not None or prior_scale != 1.0:
+        if (prior is not None or prior_sub is not None) and not _is_constellation(mod):
+            raise ValueError(f"priors need a modulation.Constellation: the separable Gray demapper of {mod.scheme!r} has no prior "
+                             f"form (Gray labels gain nothing from feedback); Constellation.from_modulation gives its table")
+        if prior_sub is not None and prior is None:
+            raise ValueError("prior_sub without a prior")
+        if not np.isfinite(prior_scale):
+            raise ValueError(f"prior_scale must be a finite number, got {prior_scale!r}")
+        if prior_scale != 1.0 and prior is None:
+            raise ValueError("prior_scale without a prior")
+        for name, t in (("prior", prior), ("prior_sub", prior_sub), ("out", out)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32
+                                  or tuple(t.shape) != (int(received.shape[0]), n) or not t.is_contiguous()
+                                  or t.device != received.device):
+                raise ValueError(f"{name} must be a contiguous float32 tensor [{int(received.shape[0])}, {n}] on the samples' "
+                                 f"device {received.device}")
     want = None if device is None else torch.device(device)
     if received.device.type != "cuda" or (want is not None and (want.type != "cuda" or want.index not in
                                                                 (None, received.device.index))):
@@ -222,9 +250,16 @@ def demap(received, n: int, *, modulation, demapper: Optional[str] = None, devic
     batch = int(received.shape[0])
     desc, _keep = mod.native(0.0, n, dev)
     lib = nat.load()
-    out = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((batch, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if prior is not None:
+            nat.check(lib.ldpc_demap_con_prior(C.c_void_p(out.data_ptr()), batch, n, C.byref(desc), DEMAPPERS[rule],
+                                               C.c_void_p(received.data_ptr()), C.c_void_p(prior.data_ptr()),
+                                               None if prior_sub is None else C.c_void_p(prior_sub.data_ptr()),
+                                               float(prior_scale), C.c_void_p(stream)), "ldpc_demap_con_prior")
+            return out
         fn, name = (lib.ldpc_demap_con, "ldpc_demap_con") if _is_constellation(mod) else (lib.ldpc_demap_sym, "ldpc_demap_sym")
         nat.check(fn(C.c_void_p(out.data_ptr()), batch, n, C.byref(desc), DEMAPPERS[rule],
                      C.c_void_p(received.data_ptr()), C.c_void_p(stream)), name)
@@ -812,6 +847,69 @@ class DecodeEngine:
                                                            p(bits), p(post), p(iters), p(succ), p(packed), p(ws),
                                                            ws.numel(), C.c_void_p(stream)), "ldpc_decode_capped")
         return DecodeResult(bits, post, iters, succ.bool(), packed)
+
+    def decode_iterative(self, received: torch.Tensor, *, modulation, rounds: int, demapper: Optional[str] = None,
+                         prior_scale: float = 1.0, early_stop: bool = True, want_bits: bool = True,
+                         want_posterior: bool = True, want_packed: bool = False, llr: Optional[torch.Tensor] = None) -> DecodeResult:
+        """Iterative demapping with decoder feedback (BICM-ID) on received samples [B, S, 4] of a
+        modulation.Constellation, fp32 engines only.  Round 1 is ``decode(demap(received))``.  Round r > 1 demaps again with the
+        decoder's extrinsic as the a priori LLRs, ``demap(received, prior=posterior_{r-1}, prior_sub=llr_{r-1},
+        prior_scale=prior_scale)``, and decodes those LLRs from scratch.  With early_stop a frame closes at the first round
+        whose decode reports success and keeps that round's outputs; its `iterations` is the sum over the rounds it ran; a frame
+        never closed has the last round's outputs and success False.  Without early_stop every frame runs every round and
+        reports the last.  The result is per frame: the still-open frames are compacted between rounds, which changes nothing
+        (a frame's demap and decode do not depend on its neighbours).  DecodeResult.rounds: int32 [B], rounds run.
+        llr: round 1's LLRs where the caller already has them -- what ``sym_llr(want_received=True)`` returned beside the
+        samples, i.e. ``demap(received)`` under the same demapper -- so that round 1 does not demap again; left unchanged."""
+        if self.dtype != torch.float32:
+            raise TypeError("decode_iterative needs an fp32 engine: the demapper's LLRs are fp32")
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or int(rounds) < 1:
+            raise ValueError(f"rounds must be an integer >= 1, got {rounds!r}")
+        rounds, n, dev = int(rounds), self.graph.n, self.device
+        if not _is_constellation(_check_modulation(modulation)):
+            raise ValueError("decode_iterative needs a modulation.Constellation (Constellation.from_modulation gives a named "
+                             "scheme's table)")
+        if not isinstance(received, torch.Tensor) or received.device != dev:
+            raise ValueError(f"received must be a tensor on the engine's device {dev}")
+        kw = dict(early_stop=early_stop, want_bits=want_bits, want_posterior=True, want_packed=want_packed)
+        own = llr is None                          # whether `llr` is this call's to overwrite
+        if own:
+            llr = demap(received, n, modulation=modulation, demapper=demapper)
+        elif (not isinstance(llr, torch.Tensor) or llr.dtype != torch.float32 or llr.device != dev or not llr.is_contiguous()
+              or received.dim() != 3 or tuple(llr.shape) != (int(received.shape[0]), n)):
+            raise ValueError(f"llr must be a contiguous float32 tensor [batch, {n}] on the engine's device: demap(received)")
+        res = self.decode(llr, **kw)
+        B = int(llr.shape[0])
+        out = DecodeResult(res.bits, res.posterior, res.iterations, res.success, res.packed_bits,
+                           torch.ones((B,), dtype=torch.int32, device=dev))
+        idx = None                                 # rows of `out` the current sub-batch holds; None: all of them
+        for _ in range(1, rounds):
+            if early_stop:                         # only the frames still open go on
+                keep = torch.nonzero(~res.success, as_tuple=False).reshape(-1)
+                if keep.numel() == 0:
+                    break
+                if keep.numel() != res.success.numel():
+                    received = received.index_select(0, keep)
+                    llr, own = llr.index_select(0, keep), True
+                    res.posterior = res.posterior.index_select(0, keep)
+                    idx = keep if idx is None else idx.index_select(0, keep)
+            # the decoder's extrinsic, posterior - llr, formed in the kernel; the new LLRs take the old ones' place
+            llr = demap(received, n, modulation=modulation, demapper=demapper, prior=res.posterior, prior_sub=llr,
+                        prior_scale=prior_scale, out=llr if own else None)
+            own = True
+            res = self.decode(llr, **kw)
+            rows = slice(None) if idx is None else idx
+            for name in ("bits", "posterior", "packed_bits", "success"):
+                if getattr(out, name) is not None:
+                    getattr(out, name)[rows] = getattr(res, name)
+            if early_stop:
+                out.iterations[rows] += res.iterations
+            else:
+                out.iterations[rows] = res.iterations
+            out.rounds[rows] += 1
+        if not want_posterior:
+            out.posterior = None
+        return out
 
     # ------------------------------------------------------------------ on-device Monte-Carlo
     def _packed_codeword(self, codeword) -> Optional[torch.Tensor]:

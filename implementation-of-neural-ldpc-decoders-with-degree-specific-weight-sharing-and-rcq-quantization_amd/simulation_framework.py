@@ -40,6 +40,10 @@ Channel (``SimulationConfig.channel``):
             ``rate_matching``; from 16-QAM up it needs ``codeword="random"`` (or a codeword).  A ``modulation.Constellation``
             (8-PSK, APSK, any table of up to 64 labelled points) is taken the same way and always
             needs ``codeword="random"`` (or a codeword).
+            ``SimulationConfig.iterative_demapping = K`` (this channel and a ``Constellation`` only; default 1) demaps every
+            frame up to K times, each round after the first with the decoder's extrinsic as a priori LLRs scaled by
+            ``demapping_feedback_scale`` (``DecodeEngine.decode_iterative``).  The average iteration count
+            is then the sum over the rounds a frame ran.  Not together with ``diagnostics`` / ``capture_errors``.
 """
 
 from __future__ import annotations
@@ -95,9 +99,30 @@ class SimulationConfig:
     # channel="device": Gray-mapped symbols over AWGN or Rayleigh fading, max-log demapper.  An init-only argument kept as a
     # plain attribute: the dataclass fields (and with them repr, ==, the reference's field list) stay the twenty above
     modulation: InitVar[Optional[Modulation]] = None
+    # channel="device" with a modulation.Constellation: demapping rounds per frame (1: demap once, today's path; K > 1:
+    # iterative demapping with decoder feedback, DecodeEngine.decode_iterative) and the scale of the fed-back extrinsic.
+    # Init-only and kept as plain attributes, as `modulation` is
+    iterative_demapping: InitVar[int] = 1
+    demapping_feedback_scale: InitVar[float] = 1.0
 
-    def __post_init__(self, modulation=None):
+    def __post_init__(self, modulation=None, iterative_demapping=1, demapping_feedback_scale=1.0):
         self.modulation = modulation
+        if isinstance(iterative_demapping, bool) or not isinstance(iterative_demapping, (int, np.integer)) \
+                or int(iterative_demapping) < 1:
+            raise ValueError(f"iterative_demapping must be an integer >= 1, got {iterative_demapping!r}")
+        self.iterative_demapping = int(iterative_demapping)
+        if isinstance(demapping_feedback_scale, (bool, str)) or not np.isscalar(demapping_feedback_scale) \
+                or not np.isreal(demapping_feedback_scale) or not np.isfinite(demapping_feedback_scale):
+            raise ValueError(f"demapping_feedback_scale must be a finite number, got {demapping_feedback_scale!r}")
+        self.demapping_feedback_scale = float(demapping_feedback_scale)
+        if self.iterative_demapping > 1:
+            if self.channel != "device" or not isinstance(self.modulation, Constellation):
+                raise ValueError("iterative_demapping > 1 needs channel='device' and a modulation.Constellation "
+                                 "(Constellation.from_modulation gives a named scheme's table)")
+            if self.diagnostics or int(self.capture_errors) > 0:
+                raise ValueError("iterative_demapping > 1 together with diagnostics or capture_errors is not provided: the "
+                                 "stop-iteration histogram has T + 1 bins and the iterations summed over the rounds do not "
+                                 "fit it (DESIGN.md section 3n)")
         if self.modulation is not None:
             if not isinstance(self.modulation, Modulation):
                 raise ValueError("modulation must be a modulation.Modulation")
@@ -363,6 +388,26 @@ class LDPSimulator:
             return _engine.awgn_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=first, scale=scale,
                                     shift=shift, codeword=cw, device=eng.device, rate_matching=rm)
 
+        if cfg.iterative_demapping > 1:
+            # iterative demapping: the Python block loop on every engine -- the samples of the same stream, rounds of
+            # demap and decode on them, the same counters fed with the iterations summed over the rounds
+            state = torch.zeros(8, dtype=torch.int64, device=eng.device)
+            drawn, host = 0, [0] * 8
+            while drawn < max_frames and not host[4]:
+                frames = min(block, max_frames - drawn)
+                if random:
+                    cw = _engine.encode_random(eng.encoder(), frames, seed=int(cfg.seed), stream_id=stream_id,
+                                               first_frame=drawn, device=eng.device)
+                llr, rec = _engine.sym_llr(frames, n, seed=int(cfg.seed), stream_id=stream_id, first_frame=drawn, modulation=mod,
+                                         snr_db=snr_db, codeword=cw, device=eng.device, want_received=True)
+                res = eng.decode_iterative(rec, modulation=mod, rounds=cfg.iterative_demapping,
+                                           prior_scale=cfg.demapping_feedback_scale, early_stop=True, want_bits=False,
+                                           want_posterior=False, want_packed=True, llr=llr)
+                eng.sim_count(state, res.packed_bits, res.iterations, max_frames=max_frames, max_errors=max_errors,
+                              codeword=cw)
+                host = state.tolist()
+                drawn += frames
+            return dict(zip(_engine.SIM_COUNTERS, host))
         if eng.info()["engine"] == "resident":
             if mod is not None:
                 return eng.simulate(seed=int(cfg.seed), stream_id=stream_id, snr_db=snr_db, modulation=mod, codeword=cw,
@@ -402,6 +447,8 @@ class LDPSimulator:
         """Draw the listed frames of the point at `snr_db` again -- stream indices, e.g. error_frames["frame"] of a run with
         this configuration (same seed, convention, codeword and rate_matching; channel="device") -- and decode them with early stop.
         -> {frames, llr [F, n], bits int32 [F, n], posterior [F, n], iterations int32 [F], success bool [F]} on the device.
+        Under iterative_demapping > 1 the frames go through the same rounds (DecodeEngine.decode_iterative): llr is round 1's,
+        iterations the sum over the rounds, and the dict also has `rounds` int32 [F] and `received` [F, S, 4], the samples.
         A frame has the same noise whatever block it was drawn in, so this reproduces the recorded failure exactly.  Under
         codeword="random" each frame's codeword is drawn again too and the dict has `codewords`: uint8 [F, ceil(n/8)], packed."""
         import engine as _engine
@@ -416,6 +463,24 @@ class LDPSimulator:
         frames = [int(f) for f in np.asarray(frames).reshape(-1)]
         words = [_engine.encode_random(eng.encoder(), 1, seed=int(cfg.seed), stream_id=stream_id, first_frame=f,
                                        device=eng.device) for f in frames] if random else [cw] * len(frames)
+        if cfg.iterative_demapping > 1:                    # the samples again, and the rounds on them
+            pairs = [_engine.sym_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, modulation=cfg.modulation,
+                                     snr_db=float(snr_db), codeword=c, device=eng.device, want_received=True)
+                     for f, c in zip(frames, words)]
+            S = cfg.modulation.symbols(code.n)
+            llr = (torch.cat([p[0] for p in pairs], dim=0) if pairs else
+                   torch.empty((0, code.n), dtype=torch.float32, device=eng.device))
+            rec = (torch.cat([p[1] for p in pairs], dim=0) if pairs else
+                   torch.empty((0, S, 4), dtype=torch.float32, device=eng.device))
+            with torch.no_grad():
+                res = eng.decode_iterative(rec, modulation=cfg.modulation, rounds=cfg.iterative_demapping,
+                                           prior_scale=cfg.demapping_feedback_scale, early_stop=True, llr=llr)
+            out = {"frames": frames, "llr": llr, "bits": res.bits, "posterior": res.posterior, "iterations": res.iterations,
+                   "success": res.success, "rounds": res.rounds, "received": rec}
+            if random:
+                out["codewords"] = (torch.cat(words, dim=0) if words else
+                                    torch.empty((0, (code.n + 7) // 8), dtype=torch.uint8, device=eng.device))
+            return out
         if cfg.modulation is not None:                     # the symbol channel draws a frame again just the same
             rows = [_engine.sym_llr(1, code.n, seed=int(cfg.seed), stream_id=stream_id, first_frame=f, modulation=cfg.modulation,
                                     snr_db=float(snr_db), codeword=c, device=eng.device) for f, c in zip(frames, words)]

@@ -774,8 +774,39 @@ int ldpc_simulate_sym_dm(const ldpc_decoder *d, const ldpc_sim_desc *desc, const
  *   (ldpc_simulate_sym_workspace_bytes) and everything else as there.
  * The three channel entry points are asynchronous on `stream`, allocate nothing and are safe under stream capture.
  *
- * Not provided: more than 64 points, fp64, a reduced-search or table-driven fast form of the joint rule, iterative demapping,
- * rate matching with a constellation, block fading, the standards' own APSK bit maps (pass the standard's table). */
+ * ldpc_demap_con_prior : ldpc_demap_con given a priori LLRs of the frame's variables, returning *extrinsic* LLRs -- the
+ *   demapper of iterative demapping with decoder feedback (BICM-ID).  Frame layout, labels, received = (vI, vQ, e, 0), the
+ *   distances D_c and the candidate order are ldpc_demap_con's; positive means bit 0.  `prior` and `prior_sub` are fp32
+ *   [batch][n] on the device in variable order.  For the symbol's bits k = 0 .. m-1, bit k carrying variable j_k, all fp32,
+ *   every operation rounded on its own (no fused multiply-add):
+ *     La_k  = prior_scale * (prior[j_k] - prior_sub[j_k])     (prior_sub == NULL: prior_scale * prior[j_k]);
+ *             +0.0f for the bits past n in the last symbol
+ *     A_c   = the sum over the set bits j of c, in ascending j and starting from 0.0f, of La_j
+ *             (= A_{c without its highest set bit} + La_{that bit}: the same roundings)
+ *     Lam_c = D_c + (2.0f * A_c)
+ *     M_b(k) = min over c with bit k of c equal to b of Lam_c
+ *     LDPC_DEMAP_MAXLOG:  llr_k = 0.5f * (M_1 - M_0) - La_k
+ *     LDPC_DEMAP_EXACT:   S_b = sum_{c: bit k of c = b, ascending c} expf(-0.5f * (Lam_c - M_b))
+ *                         llr_k = (0.5f * (M_1 - M_0) + (logf(S_0) - logf(S_1))) - La_k
+ *   The bit's own prior is subtracted at the end: the output is what the channel and the *other* bits of the symbol say about
+ *   bit k.  With every La +0.0f or -0.0f, Lam_c == D_c exactly and the result is ldpc_demap_con's under both rules, bit for
+ *   bit but for the sign of a zero: where ldpc_demap_con gives -0.0f (0.5f times a negative difference of the smallest
+ *   subnormal, which rounds to -0.0f) and the bit's prior is -0.0f, the final subtraction gives +0.0f.  With
+ *   prior == NULL the call *is* ldpc_demap_con (its kernel is launched; prior_scale is still checked).  For m = 1 the exact
+ *   rule is the max-log rule.  The priors must be finite: +-inf and NaN are outside the contract (inf - inf in Lam_c).
+ *   The decoder's extrinsic is its posterior minus what it was given: prior = the posterior, prior_sub = the LLRs it decoded.
+ *   Aliasing: llr may be `prior` or `prior_sub` itself (the same pointer, not an overlapping range).  A lane reads the priors
+ *   of its own symbol's variables, all before it stores, and stores to those variables only; that is safe as long as
+ *   `position` is a permutation of 0 .. n-1, which the caller vouches for as everywhere above.
+ *   Checks, in ldpc_demap_con's order: batch, n, con, bits_per_symbol, points, demapper, then a prior_scale that is not
+ *   finite, S, batch == 0, then llr, received (NULL or not 16-byte aligned), a prior that is not 4-byte aligned, a prior_sub
+ *   that is not 4-byte aligned, a prior_sub without a prior, and points.  Asynchronous on `stream`, allocates nothing, safe
+ *   under stream capture.
+ *
+ * Not provided: more than 64 points, fp64, a reduced-search or table-driven fast form of the joint rule, a prior form of the
+ * separable Gray demapper (ldpc_demap_sym: Gray labels gain nothing from feedback), decoder messages carried across
+ * demapping rounds, rate matching with a constellation, block fading, the standards' own APSK bit maps (pass the standard's
+ * table). */
 typedef struct {
     int32_t bits_per_symbol;      /* m, 1 .. 6 */
     int32_t fading;               /* 0 none, 1 Rayleigh per symbol */
@@ -793,6 +824,9 @@ int ldpc_channel_con_mix(void *llr, int64_t batch, int32_t n, uint64_t seed, uin
                          void *targets /* or NULL */, int32_t demapper, void *stream);
 int ldpc_demap_con(void *llr, int64_t batch, int32_t n, const ldpc_constellation *con, int32_t demapper,
                    const void *received, void *stream);
+int ldpc_demap_con_prior(void *llr, int64_t batch, int32_t n, const ldpc_constellation *con, int32_t demapper,
+                         const void *received, const void *prior /* fp32 [batch][n], or NULL */,
+                         const void *prior_sub /* fp32 [batch][n], or NULL */, float prior_scale, void *stream);
 int ldpc_simulate_con(const ldpc_decoder *d, const ldpc_sim_desc *desc, const ldpc_encoder *e /* or NULL */,
                       const ldpc_constellation *con, int32_t demapper, int64_t capture, int64_t out_state[8],
                       int64_t *out_diag, void *workspace, size_t workspace_bytes, void *stream);
