@@ -440,19 +440,71 @@ __device__ __forceinline__ void res_walk_edges(unsigned base, unsigned stride, i
         if (e < dc) f(base + (unsigned)e * stride, std::integral_constant<int, 1>{});
 }
 
+// How res_check_body_uniform walks a check's d_lo edges, a compile-time choice per instantiation like res_cpt_forms:
+// 0 is res_walk_edges in both passes (groups of four, every edge read twice).  kChkHold: the last 4 + (d_lo & 3) edges
+// are read as ONE group at the end of pass 1 and stay in registers, pass 2 starts with them -- select and write, no
+// read, no wait -- and reads only the edges in front of them; kChkBy8 walks those in groups of eight (a group of four
+// for the rest).  Degree 14 is [8][6] then [6 held][8]: three LDS round trips and 22 reads per phase instead of eight
+// and 28.  An instantiation takes a part only where it stays within the 80 VGPRs of six waves per SIMD with no more
+// scratch than without it (profiles/check_hold_compiler_report.txt).  With this compiler all three kernels of the
+// select form do (72, 79 and 74 VGPRs, no scratch); the table is where one that stops doing so goes back to 0.
+constexpr unsigned kChkHold = 1u;
+constexpr unsigned kChkBy8 = 2u;
+constexpr unsigned res_cpt_check_walk(int form, int nl)
+{
+    (void)form; (void)nl;
+    return kChkHold | kChkBy8;
+}
+
+// pass 1 on the K edges v[K0 .. K0+K-1] held in registers, in index order: pairs, an odd last one by the one-value step
+template <int FORM, int K0, int K, int N>
+__device__ __forceinline__ void res_absorb_held(float (&m1)[2], float (&m2)[2], uint32_t (&sacc)[2],
+                                                const Pack<float, 2> (&v)[N], float ninf)
+{
+    static_assert(K0 + K <= N, "edges of the array");
+#pragma unroll
+    for (int k = K0; k + 1 < K0 + K; k += 2) res_absorb2<FORM, 2>(m1, m2, sacc, v[k], v[k + 1], ninf);
+    if constexpr (K & 1) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            sacc[g] ^= __float_as_uint(v[K0 + K - 1].x[g]);
+            res_min2_step(m1[g], m2[g], v[K0 + K - 1].x[g], ninf);
+        }
+    }
+}
+// pass 2 on the same: edge k goes to addr + k * STRIDE.  An odd last edge is paired with itself, the copy's result dropped.
+template <unsigned STRIDE, int K0, int K, int N>
+__device__ __forceinline__ void res_select_held(unsigned addr, const Pack<float, 2> (&v)[N], const float (&m1)[2],
+                                                const uint32_t (&o1)[2], const uint32_t (&o2)[2], uint32_t sign_v)
+{
+    static_assert(K0 + K <= N, "edges of the array");
+#pragma unroll
+    for (int k = K0; k < K0 + K; k += 2) {
+        constexpr int last = K0 + K - 1;
+        const int k1 = k + 1 <= last ? k + 1 : k;
+        float y[4];
+        res_select4_out(y, v[k].x[0], v[k].x[1], v[k1].x[0], v[k1].x[1], m1[0], m1[1], o1[0], o2[0], o1[1], o2[1], sign_v);
+        lds_store<Pack<float, 2>>(addr + k * STRIDE, Pack<float, 2>{{y[0], y[1]}});
+        if (k1 != k) lds_store<Pack<float, 2>>(addr + k1 * STRIDE, Pack<float, 2>{{y[2], y[3]}});
+    }
+}
+
 // The check phase of the compact kernels (fp32 codeword pairs, no split checks) for a wave with d_lo >= 4, in the
 // one-beta-per-check form (normalised min-sum, RCQ with tau_0 == 0): the two passes of res_check_body below -- the same
-// arithmetic on the same edges in the same order, so every output is the same bits -- walked by res_walk_edges.  The
+// arithmetic on the same edges in the same order, so every output is the same bits -- walked by res_walk_edges or,
+// with WALK != 0, with the check's tail held between the passes (res_cpt_check_walk).  The
 // host marks every wave of a decoder with per-edge tables or other forms kChkPerLane.
-template <int FORM, int NL, int MS>
+template <int FORM, int NL, int MS, unsigned WALK>
 __device__ __forceinline__ void res_check_body_uniform(int p, int dc, unsigned cw, float b_check, const float (&th)[8],
                                                        const float *__restrict__ thr, int n_levels)
 {
     static_assert(FORM == FORM_NMS || FORM == FORM_RCQ, "forms with two outgoing magnitudes per check");
     static_assert(MS > 0, "compile-time row stride: the slots of a group are immediate offsets");
+    static_assert(WALK == 0 || (WALK & kChkHold), "groups of eight come with the held tail");
     constexpr int G = 2;
     using P = Pack<float, G>;
     constexpr unsigned stride = (unsigned)MS * G * (unsigned)sizeof(float);
+    static_assert(7 * stride < 65536u, "immediate offsets of a group of eight");
     const unsigned base = (unsigned)p * G * (unsigned)sizeof(float);
     const int d_lo = chk_lo(cw), spread = chk_spread(cw);
     float m1[G], m2[G];
@@ -463,6 +515,62 @@ __device__ __forceinline__ void res_check_body_uniform(int p, int dc, unsigned c
     for (int g = 0; g < G; ++g) {
         m1[g] = inf_of<float>(); m2[g] = inf_of<float>(); sacc[g] = 0;
     }
+    // the edges in front of the held tail: d_lo - 4 - (d_lo & 3) of them, a multiple of four, in groups of KB and one
+    // group of four; f as in res_walk_edges
+    constexpr int KB = (WALK & kChkBy8) ? 8 : 4;
+    const int rem = d_lo & 3, body = d_lo - 4 - rem;
+    auto walk_body = [&](auto &&f) -> unsigned {
+        unsigned addr = base;
+#pragma unroll 1
+        for (int t = 0; t + KB <= body; t += KB) {
+            f(addr, std::integral_constant<int, KB>{});
+            addr += KB * stride;
+        }
+        if constexpr (KB == 8) {
+            if (body & 4) {
+                f(addr, std::integral_constant<int, 4>{});
+                addr += 4 * stride;
+            }
+        }
+        return addr;
+    };
+    // the lanes of a mixed-degree wave with dc > d_lo: their remaining edges one at a time under the exec mask
+    auto walk_spread = [&](auto &&f) {
+#pragma unroll 1
+        for (int e = d_lo; e < d_lo + spread; ++e)
+            if (e < dc) f(base + (unsigned)e * stride, std::integral_constant<int, 1>{});
+    };
+    auto pass1 = [&](unsigned addr, auto kc) {
+        constexpr int K = decltype(kc)::value;
+        P v[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = lds_load<P>(addr + k * stride);
+        res_absorb_held<FORM, 0, K>(m1, m2, sacc, v, ninf);
+    };
+    P tl[7];                                          // the held tail: edges body .. d_lo-1, tl[4 ..] as far as rem says
+    unsigned ta = 0;
+    if constexpr (WALK != 0) {
+        ta = walk_body(pass1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tl[k] = lds_load<P>(ta + k * stride);
+        if (rem == 0) {
+            res_absorb_held<FORM, 0, 4>(m1, m2, sacc, tl, ninf);
+        } else if (rem == 1) {
+            tl[4] = lds_load<P>(ta + 4 * stride);
+            res_absorb_held<FORM, 0, 5>(m1, m2, sacc, tl, ninf);
+        } else if (rem == 2) {
+            tl[4] = lds_load<P>(ta + 4 * stride);
+            tl[5] = lds_load<P>(ta + 5 * stride);
+            res_absorb_held<FORM, 0, 6>(m1, m2, sacc, tl, ninf);
+        } else {
+            tl[4] = lds_load<P>(ta + 4 * stride);
+            tl[5] = lds_load<P>(ta + 5 * stride);
+            tl[6] = lds_load<P>(ta + 6 * stride);
+            res_absorb_held<FORM, 0, 7>(m1, m2, sacc, tl, ninf);
+        }
+        walk_spread(pass1);
+    }
+    if constexpr (WALK == 0)
     res_walk_edges(base, stride, d_lo, spread, dc, [&](unsigned addr, auto kc) {
         constexpr int K = decltype(kc)::value;
         P v[K];
@@ -499,6 +607,23 @@ __device__ __forceinline__ void res_check_body_uniform(int p, int dc, unsigned c
     }
     uint32_t sign_v = 0x80000000u;
     asm volatile("" : "+v"(sign_v));
+    if constexpr (WALK != 0) {
+        // the held tail first -- nothing to wait for -- then the edges in front of it, read again
+        res_select_held<stride, 0, 4>(ta, tl, m1, o1, o2, sign_v);
+        if (rem == 1) res_select_held<stride, 4, 1>(ta, tl, m1, o1, o2, sign_v);
+        else if (rem == 2) res_select_held<stride, 4, 2>(ta, tl, m1, o1, o2, sign_v);
+        else if (rem == 3) res_select_held<stride, 4, 3>(ta, tl, m1, o1, o2, sign_v);
+        auto pass2 = [&](unsigned addr, auto kc) {
+            constexpr int K = decltype(kc)::value;
+            P v[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) v[k] = lds_load<P>(addr + k * stride);
+            res_select_held<stride, 0, K>(addr, v, m1, o1, o2, sign_v);
+        };
+        walk_body(pass2);
+        walk_spread(pass2);
+        return;
+    }
     // every edge goes through res_select4_out (the constant in a VGPR); an odd edge is paired with a dummy pair whose
     // result is dropped
     res_walk_edges(base, stride, d_lo, spread, dc, [&](unsigned addr, auto kc) {
@@ -786,8 +911,9 @@ __device__ __forceinline__ void res_check_phase(const ResidentPlan &pl, unsigned
             // beta are all it needs.  A full wave runs with no lane mask at all, the last one is masked once for the whole
             // phase, a wave without checks leaves.
             const int lanes = chk_lanes(cw);
-            if (lanes == 64) res_check_body_uniform<FORM, NL, MS>(tid, dc_pre, cw, b_pre, th, thr, n_levels);
-            else if ((tid & 63) < lanes) res_check_body_uniform<FORM, NL, MS>(tid, dc_pre, cw, b_pre, th, thr, n_levels);
+            constexpr unsigned WALK = res_cpt_check_walk(FORM, NL);
+            if (lanes == 64) res_check_body_uniform<FORM, NL, MS, WALK>(tid, dc_pre, cw, b_pre, th, thr, n_levels);
+            else if ((tid & 63) < lanes) res_check_body_uniform<FORM, NL, MS, WALK>(tid, dc_pre, cw, b_pre, th, thr, n_levels);
             return;
         }
         // per-lane waves of these kernels: the form below on the lane's one check
