@@ -28,7 +28,7 @@ DEBUG_HEADER = os.path.join(os.path.dirname(_HERE), "include", "ldpc_hip_debug.h
 
 LDPC_F32, LDPC_F64 = 0, 1
 C2V_NMS, C2V_RCQ, C2V_OMS, C2V_SPA = 0, 1, 2, 3
-MODE_AUTO, MODE_STREAM, MODE_RESIDENT, MODE_SWEEPS, MODE_GATHER, MODE_PAIR = 0, 1, 2, 3, 4, 5
+MODE_AUTO, MODE_STREAM, MODE_RESIDENT, MODE_SWEEPS, MODE_GATHER, MODE_PAIR, MODE_BLOCK = 0, 1, 2, 3, 4, 5, 6
 SCHED_FLOODING, SCHED_LAYERED_REF, SCHED_LAYERED = 0, 1, 2
 DEMAP_MAXLOG, DEMAP_EXACT = 0, 1
 
@@ -44,7 +44,7 @@ class NativeEngineError(RuntimeError):
 # the one compiled unit first, then everything it includes
 SOURCES = ("ldpc_hip.hip", "ldpc_kernels.hip", "ldpc_resident.hip", "ldpc_train.hip", "ldpc_layered.hip",
            "ldpc_train_host.hip", "ldpc_sim.hip", "ldpc_encode.hip", "ldpc_modulation.hip", "ldpc_constellation.hip",
-           "ldpc_resident_geom.h", "ldpc_plan.h")
+           "ldpc_resident_geom.h", "ldpc_plan.h", "ldpc_layered_block.hip", "ldpc_layer_plan.h")
 
 
 def _source_files():
@@ -175,12 +175,12 @@ PRODUCT_EXPORTS = ("ldpc_graph_create", "ldpc_graph_destroy", "ldpc_graph_info",
                    "ldpc_channel_sym", "ldpc_simulate_sym_workspace_bytes", "ldpc_simulate_sym", "ldpc_channel_sym_mix",
                    "ldpc_demap_sym", "ldpc_channel_sym_dm", "ldpc_channel_sym_mix_dm", "ldpc_simulate_sym_dm",
                    "ldpc_channel_con", "ldpc_channel_con_mix", "ldpc_demap_con", "ldpc_simulate_con",
-                   "ldpc_demap_con_prior")
+                   "ldpc_demap_con_prior", "ldpc_graph_create_layered", "ldpc_graph_layers")
 # ... and the measurement / test hooks of include/ldpc_hip_debug.h (bench.py's per-kernel timing, the tests' state dumps)
 DEBUG_EXPORTS = ("ldpc_debug_sweep", "ldpc_debug_workspace_layout", "ldpc_debug_resident_c2v", "ldpc_debug_key4",
                  "ldpc_debug_compact_layout", "ldpc_debug_compact_checks", "ldpc_debug_compact_banks",
                  "ldpc_debug_resident_kernel", "ldpc_debug_boundary_kernels", "ldpc_debug_launch_geometry", "ldpc_debug_min2",
-                 "ldpc_debug_philox")
+                 "ldpc_debug_philox", "ldpc_debug_layer_plan")
 EXPORTS = PRODUCT_EXPORTS + DEBUG_EXPORTS
 
 _lib = None
@@ -210,6 +210,10 @@ def load():
         vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
         lib.ldpc_graph_create.restype = C.c_int
         lib.ldpc_graph_create.argtypes = [C.POINTER(vp), i32, i32, i32, vp, vp]
+        lib.ldpc_graph_create_layered.restype = C.c_int
+        lib.ldpc_graph_create_layered.argtypes = [C.POINTER(vp), i32, i32, i32, vp, vp, i32, vp]
+        lib.ldpc_graph_layers.restype = C.c_int
+        lib.ldpc_graph_layers.argtypes = [vp, vp, vp]
         lib.ldpc_graph_destroy.restype = None
         lib.ldpc_graph_destroy.argtypes = [vp]
         lib.ldpc_graph_info.restype = C.c_int
@@ -361,6 +365,8 @@ def load():
         lib.ldpc_simulate_con.argtypes = [vp, C.POINTER(SimDesc), vp, con, i32, i64, vp, vp, vp, C.c_size_t, vp]
         lib.ldpc_debug_philox.restype = C.c_int
         lib.ldpc_debug_philox.argtypes = [vp, i64, u64, u32, u64, i32, vp]
+        lib.ldpc_debug_layer_plan.restype = C.c_int
+        lib.ldpc_debug_layer_plan.argtypes = [i32, i32, i32, vp, vp, i32, vp, i32, vp]
         lib.ldpc_last_error.restype = C.c_char_p
         lib.ldpc_last_error.argtypes = []
         lib.ldpc_abi_version.restype = C.c_int

@@ -13,9 +13,18 @@ builder-generated IRA-style codes:
   CN {4:1441, 5:3239, 6:3600, 7:720}
 * ``small_96_48`` : n=96, m=48 test code with variable degrees {1,2,3,8}
 
+* ``qc_1944_972`` : n=1944, m=972 quasi-cyclic, mb=12, nb=24, Z=81, dual-diagonal parity part, check degrees 7 and 8,
+  no 4-cycles; its 12 block rows are declared as layers (``generate_qc_code``, seed 1944, ``_QC_SPECS``)
+
 Generated edge lists are committed under ``data/`` so every run (here and on
 the GPU box) decodes the very same graph; ``generate_ira_code`` is the script
-that made them (``python codes.py`` regenerates and verifies the files).
+that made them (``python codes.py`` regenerates and verifies the files).  The quasi-cyclic codes of ``_QC_SPECS`` have no
+file under ``data/``: ``generate_qc_code`` takes about two seconds, so ``load_graph`` builds them from their seed, once per
+process; the recorded edge list of ``qc_1944_972`` is a test vector (tests/golden/qc_1944_972.npz) that pins the generator.
+
+Layers: ``quasi_cyclic`` builds a QC code from any shift table, ``layered_order`` reorders the checks of any graph into
+variable-disjoint layers; both return graphs that carry ``layer_ptr`` (tanner_graph.py), which the block-parallel layered
+kernel reads.
 
 Construction: the last ``m`` columns are the IRA staircase (parity column p
 touches checks p and p+1; the last one only check m-1).  Information columns
@@ -169,8 +178,15 @@ _SPECS = {
 }
 
 
+# quasi-cyclic codes (generate_qc_code): ``qc_1944_972`` is mb = 12, nb = 24, Z = 81 -- eight information block columns of
+# degree 3 and four of degree 11 beside the dual-diagonal parity part, check degrees 7 and 8; layers = block rows
+_QC_SPECS = {
+    "qc_1944_972": dict(mb=12, nb=24, Z=81, info_degree_profile={3: 8, 11: 4}, seed=1944),
+}
+
+
 def code_names() -> Sequence[str]:
-    return tuple(_SPECS)
+    return tuple(_SPECS) + tuple(_QC_SPECS)
 
 
 def _path(name: str) -> str:
@@ -178,15 +194,135 @@ def _path(name: str) -> str:
 
 
 def save_graph(path: str, g: TannerGraph) -> None:
+    """A graph that declares layers also stores ``layer_ptr``; one without is written exactly as before."""
+    extra = {} if g.layer_ptr is None else {"layer_ptr": np.asarray(g.layer_ptr, dtype=np.int32)}
     np.savez_compressed(path, n=np.int32(g.n), m=np.int32(g.m),
-                        check_ptr=g.check_ptr, var_idx=g.var_idx.astype(np.uint16 if g.n <= 65535 else np.int32))
+                        check_ptr=g.check_ptr, var_idx=g.var_idx.astype(np.uint16 if g.n <= 65535 else np.int32), **extra)
+
+
+_QC_CACHE: Dict[str, TannerGraph] = {}
 
 
 def load_graph(name_or_path: str) -> TannerGraph:
-    """Load a committed edge list (``data/<name>.npz``)."""
+    """Load a committed edge list (``data/<name>.npz``, or any path), with its layers when the file has them; a name of
+    ``_QC_SPECS`` is generated from its seed (once per process: later calls return the same graph object)."""
+    if name_or_path in _QC_SPECS and not os.path.exists(name_or_path):
+        if name_or_path not in _QC_CACHE:
+            _QC_CACHE[name_or_path] = generate_qc_code(**_QC_SPECS[name_or_path])
+        return _QC_CACHE[name_or_path]
     path = name_or_path if os.path.exists(name_or_path) else _path(name_or_path)
     with np.load(path, allow_pickle=False) as z:
-        return TannerGraph.from_csr(int(z["n"]), z["check_ptr"], z["var_idx"].astype(np.int32))
+        g = TannerGraph.from_csr(int(z["n"]), z["check_ptr"], z["var_idx"].astype(np.int32))
+        return g.with_layers(z["layer_ptr"]) if "layer_ptr" in z.files else g
+
+
+# ---------------------------------------------------------------------------- quasi-cyclic and layer-ordered codes
+def quasi_cyclic(shifts, Z: int) -> TannerGraph:
+    """The quasi-cyclic code of a shift matrix: ``shifts`` int [mb, nb], a value < 0 is the Z x Z zero block, a value
+    s >= 0 the Z x Z identity shifted by s (row z has its one in column (z + s) mod Z).  Checks are ordered block row by
+    block row; the checks of a block row share no variable, so the graph declares them as its layers:
+    ``layer_ptr = [0, Z, 2Z, ...]``.  A caller with a standard's shift table (802.11n, 5G NR) passes it here."""
+    S = np.asarray(shifts)
+    if S.ndim != 2 or not np.issubdtype(S.dtype, np.integer):
+        raise ValueError("shifts must be an integer array [mb, nb]")
+    Z = int(Z)
+    if Z < 1:
+        raise ValueError("Z must be >= 1")
+    mb, nb = S.shape
+    br, bc = np.nonzero(S >= 0)
+    z = np.arange(Z, dtype=np.int64)
+    rows = (br[:, None] * Z + z[None, :]).ravel()
+    cols = (bc[:, None] * Z + (z[None, :] + S[br, bc][:, None].astype(np.int64)) % Z).ravel()
+    g = TannerGraph(nb * Z, mb * Z, rows, cols)
+    return g.with_layers(np.arange(mb + 1, dtype=np.int64) * Z) if mb else g
+
+
+def layered_order(graph: TannerGraph, max_layer: Optional[int] = None):
+    """Reorder the checks of any graph into layers.  First-fit colouring of the checks in ascending order (a check goes to
+    the first layer none of whose checks shares a variable with it and that holds fewer than ``max_layer`` checks, when
+    given); the rows are then re-emitted layer by layer, ascending inside a layer.  -> (graph2, perm): ``graph2`` carries
+    the layers and its row i is row ``perm[i]`` of ``graph``.
+
+    It is the same code with the same codewords -- encoders, channels and error counters need nothing, and the result of
+    a FLOODING decode does not depend on the order of the checks.  It is a DIFFERENT layered decoder: the layered
+    schedule walks the checks in order, so another order gives other messages, posteriors and iteration counts."""
+    if max_layer is not None and int(max_layer) < 1:
+        raise ValueError("max_layer must be >= 1")
+    cap = None if max_layer is None else int(max_layer)
+    var_layers = [set() for _ in range(graph.n)]
+    members = []                                        # layer -> checks, ascending
+    first_open = 0                                      # layers below are full
+    for i in range(graph.m):
+        vs = graph.var_idx[graph.check_ptr[i]:graph.check_ptr[i + 1]]
+        taken = set()
+        for v in vs:
+            taken |= var_layers[int(v)]
+        l = first_open
+        while l < len(members) and (l in taken or (cap is not None and len(members[l]) >= cap)):
+            l += 1
+        if l == len(members):
+            members.append([])
+        members[l].append(i)
+        for v in vs:
+            var_layers[int(v)].add(l)
+        while cap is not None and first_open < len(members) and len(members[first_open]) >= cap:
+            first_open += 1
+    perm = np.asarray([i for layer in members for i in layer], dtype=np.int64)
+    new_row = np.empty(graph.m, dtype=np.int64)
+    new_row[perm] = np.arange(graph.m)
+    g2 = TannerGraph(graph.n, graph.m, new_row[graph.check_of_edge], graph.var_idx)
+    ptr = np.concatenate([[0], np.cumsum([len(layer) for layer in members])]).astype(np.int64)
+    return (g2.with_layers(ptr) if graph.m else g2), perm.astype(np.int32)
+
+
+def generate_qc_code(mb: int, nb: int, Z: int, info_degree_profile: Dict[int, int], seed: int = 0,
+                     max_draws: int = 10000) -> TannerGraph:
+    """Seeded quasi-cyclic code with a dual-diagonal parity part.  The last mb block columns are the parity part: parity
+    block column i sits in block rows i and i + 1 (the last one in row mb - 1 only) at shift 0, so H has full rank.  The
+    nb - mb information block columns follow ``info_degree_profile`` {block-column degree: count}, highest degree first;
+    a column takes the block rows that hold the fewest entries so far (ties in seeded random order), so the check degrees
+    come out even.  The shifts of a column are redrawn until it closes no 4-cycle with the columns before it; the
+    finished graph is verified with ``four_cycles() == 0``."""
+    kb = nb - mb
+    if kb < 1 or mb < 1 or sum(info_degree_profile.values()) != kb:
+        raise ValueError("info_degree_profile must cover exactly nb - mb block columns")
+    if max(info_degree_profile) > mb or min(info_degree_profile) < 1:
+        raise ValueError("a block column's degree must be in 1 .. mb")
+    rng = np.random.default_rng(seed)
+    S = np.full((mb, nb), -1, dtype=np.int64)
+    for i in range(mb):
+        S[i, kb + i] = 0
+        if i + 1 < mb:
+            S[i + 1, kb + i] = 0
+    load = (S >= 0).sum(axis=1)
+
+    def closes_cycle(col, done):
+        ra = np.flatnonzero(S[:, col] >= 0)
+        for b in done:
+            common = ra[S[ra, b] >= 0]
+            d = (S[common, col] - S[common, b]) % Z
+            if np.unique(d).size != d.size:            # two common rows with the same shift difference: a 4-cycle
+                return True
+        return False
+
+    done = list(range(kb, nb))
+    degs = [d for d, cnt in sorted(info_degree_profile.items(), reverse=True) for _ in range(cnt)]
+    for col, d in enumerate(degs):
+        order = rng.permutation(mb)
+        rows = order[np.argsort(load[order], kind="stable")[:d]]
+        for _ in range(max_draws):
+            S[:, col] = -1
+            S[rows, col] = rng.integers(0, Z, size=d)
+            if not closes_cycle(col, done):
+                break
+        else:
+            raise RuntimeError(f"no 4-cycle-free shifts for block column {col} at Z = {Z}")
+        load[rows] += 1
+        done.append(col)
+    g = quasi_cyclic(S, Z)
+    if g.four_cycles() != 0:
+        raise RuntimeError("generated QC code has 4-cycles")
+    return g
 
 
 def load_code(name: str, max_iterations: int = 50):
@@ -338,16 +474,23 @@ class Encoder:
 
 if __name__ == "__main__":  # regenerate + verify the committed edge lists
     os.makedirs(_DATA_DIR, exist_ok=True)
-    for name, spec in _SPECS.items():
-        g = generate_ira_code(**spec)
+    for name, spec in list(_SPECS.items()) + list(_QC_SPECS.items()):
+        g = generate_qc_code(**spec) if name in _QC_SPECS else generate_ira_code(**spec)
         dvs = dict(zip(*np.unique(g.dv, return_counts=True)))
         dcs = dict(zip(*np.unique(g.dc, return_counts=True)))
         print(name, "n", g.n, "m", g.m, "E", g.E, "dv", dvs, "dc", dcs,
               "4-cycles", g.four_cycles() if g.E < 10000 else "n/a")
         p = _path(name)
+        if name in _QC_SPECS:      # no file under data/: the recorded edge list is the test vector tests/golden/<name>.npz
+            p = os.path.join(os.path.dirname(_DATA_DIR), os.pardir, "tests", "golden", name + ".npz")
+            if not os.path.exists(p):
+                print("   no recorded edge list to compare with")
+                continue
         if os.path.exists(p):
             old = load_graph(p)
-            same = np.array_equal(old.check_ptr, g.check_ptr) and np.array_equal(old.var_idx, g.var_idx)
+            same = np.array_equal(old.check_ptr, g.check_ptr) and np.array_equal(old.var_idx, g.var_idx) and \
+                (old.layer_ptr is None) == (g.layer_ptr is None) and \
+                (g.layer_ptr is None or np.array_equal(old.layer_ptr, g.layer_ptr))
             print("   committed file", "matches" if same else "DIFFERS (not overwritten)")
         else:
             save_graph(p, g)

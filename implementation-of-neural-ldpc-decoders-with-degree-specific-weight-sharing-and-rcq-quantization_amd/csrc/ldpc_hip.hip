@@ -9,12 +9,14 @@
 #include "ldpc_resident.hip"
 #include "ldpc_train.hip"
 #include "ldpc_layered.hip"
+#include "ldpc_layered_block.hip"
 #include "ldpc_plan.h"
 
 #include <algorithm>
 #include <climits>
 #include <mutex>
 #include <set>
+#include <string>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -81,6 +83,7 @@ struct ldpc_graph : HostGraph {   // the host copies (ldpc_plan.h) and their dev
     int *check_ptr = nullptr, *var_idx = nullptr, *var_ptr = nullptr, *csc_edge = nullptr;
     int *wide_checks = nullptr;    // checks of degree > kWideCheck (cn_sweep_wide splits each over a block)
     int n_wide = 0;
+    std::vector<int> h_layer_ptr;  // ldpc_graph_create_layered: [n_layers + 1], validated; empty: the graph declares no layers
     GraphDev dev() const { return GraphDev{n, m, E, check_ptr, var_idx, var_ptr, csc_edge}; }
 };
 
@@ -135,13 +138,40 @@ struct ldpc_decoder {
     bool beta_unit = false;        // every beta is 1.0 (fp32): the layered RCQ kernels skip the weight
     int *lay_oms_slot = nullptr;   // layered offset min-sum: check-side alpha slot of each plan entry, and the table in plan
     float *lay_oms = nullptr;      // order, as lay_slot / lay_beta
+    // block-parallel layered decode (ldpc_layered_block.hip): LDPC_SCHED_LAYERED on a graph that declares layers
+    bool blk_ok = false;
+    std::string blk_why;           // why LDPC_MODE_BLOCK is refused (blk_ok == false)
+    BlockPlan blk{};
+    size_t blk_lds = 0;
+    int blk_threads = 0;
+    double blk_mean_layer = 0.0;   // m / L: what the AUTO rule reads
+    int *blk_layer_ptr = nullptr, *blk_entry_base = nullptr, *blk_deg = nullptr;
+    uint32_t *blk_off = nullptr;
+    int *blk_slot = nullptr;       // beta slot of each plan entry (-1: hole), and beta in plan order [T][entries]
+    float *blk_beta = nullptr;
+    int *blk_oms_slot = nullptr;   // the offset form's check-side alpha, likewise
+    float *blk_oms = nullptr;
 };
 
 namespace {
 
+// Block-parallel layered kernel: LDPC_MODE_BLOCK forces it.  LDPC_MODE_AUTO would take it when the mean layer size reaches
+// kBlkAutoMinMeanLayer.  profiles/block_layered_timing.jsonl (tools/time_block_layered.py, 65536 codewords, T = 10): on one
+// base matrix lifted at Z = 1 .. 81 the block kernel first beats the sequential LDS kernel at Z = 16 (1.28x; 3.2x at 32, 5.1x
+// at 81, far outside the spread of five repetitions), but on the layer-ordered (1998,1512) graph -- mean layer 24.3, layers of
+// 1 .. 40 checks of degree 13-14 -- it loses (NMS 0.98x, W-RCQ 0.57x).  The mean layer size alone does not name the winner,
+// so the constant stays "never": AUTO does exactly what it did before and the kernel is reached with LDPC_MODE_BLOCK only.
+constexpr double kBlkAutoMinMeanLayer = 1e300;
+bool use_block(const ldpc_decoder *d)
+{
+    return d->blk_ok && (d->mode == LDPC_MODE_BLOCK || (d->mode == LDPC_MODE_AUTO && d->blk_mean_layer >= kBlkAutoMinMeanLayer));
+}
 bool use_resident(const ldpc_decoder *d) { return d->res_ok && (d->mode == LDPC_MODE_AUTO || d->mode == LDPC_MODE_RESIDENT); }
 // layered schedule: the LDS-resident kernel unless a streaming mode is forced (then layered_rcq / layered_minsum, posteriors in HBM)
-bool use_layered_lds(const ldpc_decoder *d) { return d->lay_ok && (d->mode == LDPC_MODE_AUTO || d->mode == LDPC_MODE_RESIDENT); }
+bool use_layered_lds(const ldpc_decoder *d)
+{
+    return d->lay_ok && !use_block(d) && (d->mode == LDPC_MODE_AUTO || d->mode == LDPC_MODE_RESIDENT);
+}
 // streaming engine, RCQ: one fused kernel per iteration (cn_gather) unless the two-sweep form is forced
 // streaming forms of an fp32 RCQ decoder, best first: code pair (4E + 4n bytes per iteration), fused gather, two sweeps
 bool use_pair(const ldpc_decoder *d) { return d->pair_ok && d->mode != LDPC_MODE_SWEEPS && d->mode != LDPC_MODE_GATHER; }
@@ -1397,6 +1427,95 @@ int decode_layered_lds(const ldpc_decoder *d, const void *llr, int64_t batch, in
     return LDPC_OK;
 }
 
+// ---- block-parallel layered decode: plan (ldpc_layer_plan.h) and launch -------------------------------------------
+// the decoder's beta table (and the offset form's check-side alpha) in plan order, enqueued on `s` after the table's upload
+int gather_block_tables(const ldpc_decoder *d, bool beta, bool oms, hipStream_t s)
+{
+    if (!d->blk_ok || d->T == 0) return LDPC_OK;
+    const int entries = d->blk.entries;
+    const long long cnt = (long long)entries * d->T;
+    if (beta && d->blk_beta) {
+        hipLaunchKernelGGL(lay_beta_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, (const float *)d->beta, d->n_beta,
+                           (const int *)d->blk_slot, entries, d->T, d->blk_beta);
+        HIP_TRY(hipGetLastError());
+    }
+    if (oms && d->blk_oms) {
+        hipLaunchKernelGGL(lay_beta_gather, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, (const float *)d->oms_alpha,
+                           d->n_oms_alpha, (const int *)d->blk_oms_slot, entries, d->T, d->blk_oms);
+        HIP_TRY(hipGetLastError());
+    }
+    return LDPC_OK;
+}
+
+int build_block_plan(ldpc_decoder *d, const ldpc_decoder_desc *desc)
+{
+    const ldpc_graph *g = d->g;
+    d->blk_ok = false;
+    if (g->h_layer_ptr.empty()) { d->blk_why = "the graph declares no layers (ldpc_graph_create_layered)"; return LDPC_OK; }
+    if (d->dtype != LDPC_F32) { d->blk_why = "the block-parallel layered kernel is fp32 only"; return LDPC_OK; }
+    if (d->schedule != LDPC_SCHED_LAYERED) { d->blk_why = "the block-parallel kernel runs LDPC_SCHED_LAYERED only"; return LDPC_OK; }
+    if (d->form == LDPC_C2V_SPA) { d->blk_why = "the sum-product form has no layered schedule"; return LDPC_OK; }
+    const bool rcq = d->form == LDPC_C2V_RCQ;
+    const int L = (int)g->h_layer_ptr.size() - 1;
+    LayerPlan p = layer_plan(g->n, g->m, g->h_check_ptr.data(), g->h_var_idx.data(), L, g->h_layer_ptr.data(),
+                             rcq ? kBlkRcq : kBlkMinSum);
+    if (!p.ok) { d->blk_why = p.why; return LDPC_OK; }
+    int rc = upload(&d->blk_layer_ptr, p.layer_ptr.data(), p.layer_ptr.size());
+    if (!rc) rc = upload(&d->blk_entry_base, p.entry_base.data(), p.entry_base.size());
+    if (!rc) rc = upload(&d->blk_deg, p.deg.data(), p.deg.size());
+    if (!rc) rc = upload(&d->blk_off, p.off.data(), p.off.size());
+    std::vector<int> slot((size_t)p.entries, -1);
+    for (int k = 0; k < p.entries; ++k)
+        if (p.edge_of_entry[k] >= 0) slot[k] = desc->beta_slot[p.edge_of_entry[k]];
+    if (!rc) rc = upload(&d->blk_slot, slot.data(), slot.size());
+    if (!rc) rc = upload(&d->blk_beta, (const float *)nullptr, slot.size() * (size_t)std::max(d->T, 1));
+    if (!rc && d->form == LDPC_C2V_OMS && d->oms_alpha) {
+        for (int k = 0; k < p.entries; ++k)
+            if (p.edge_of_entry[k] >= 0) slot[k] = desc->oms_alpha_slot[p.edge_of_entry[k]];
+        rc = upload(&d->blk_oms_slot, slot.data(), slot.size());
+        if (!rc) rc = upload(&d->blk_oms, (const float *)nullptr, slot.size() * (size_t)std::max(d->T, 1));
+    }
+    if (rc) return rc;
+    d->blk = BlockPlan{p.n, p.m, p.L, p.W, p.G, p.lpc, p.row_words, p.rec_off, p.entries, d->blk_layer_ptr, d->blk_entry_base,
+                       d->blk_deg, d->blk_off, d->blk_beta, d->blk_oms};
+    d->blk_lds = p.lds_bytes;
+    d->blk_threads = p.threads;
+    d->blk_mean_layer = (double)p.m / (double)p.L;
+    d->blk_ok = true;
+    rc = gather_block_tables(d, true, true, nullptr);
+    if (!rc) HIP_TRY(hipStreamSynchronize(nullptr));
+    return rc;
+}
+
+int decode_block(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t early_stop, int32_t *bits,
+                 void *posterior, int32_t *iterations, uint8_t *success, uint8_t *packed_bits, void *stream)
+{
+    DeviceGuard guard(d->g->device);
+    hipStream_t s = (hipStream_t)stream;
+    const BlockPlan &pl = d->blk;
+    const unsigned blocks = (unsigned)((batch + pl.G - 1) / pl.G);
+#define LDPC_BLK_K(FORM_, ES_, AUX_)                                                                                 \
+    do {                                                                                                             \
+        auto kfn = layered_block_lds<FORM_, ES_, AUX_>;                                                              \
+        if (int rc_ = allow_full_lds((const void *)kfn, d->g->device)) return rc_;                                   \
+        hipLaunchKernelGGL(kfn, dim3(blocks), dim3((unsigned)d->blk_threads), d->blk_lds, s, pl, (const float *)llr, \
+                           (long long)batch, (const float *)d->thresholds, d->n_levels, (const int *)d->q_of_iter_dev, \
+                           capped_T(d), bits, (float *)posterior, iterations, success, packed_bits);                \
+    } while (0)
+#define LDPC_BLK_ES(FORM_, AUX_)                                                                                     \
+    do {                                                                                                             \
+        if (early_stop) LDPC_BLK_K(FORM_, true, AUX_); else LDPC_BLK_K(FORM_, false, AUX_);                          \
+    } while (0)
+    if (d->form == LDPC_C2V_RCQ) { if (d->beta_unit) LDPC_BLK_ES(FORM_RCQ, false); else LDPC_BLK_ES(FORM_RCQ, true); }
+    else if (d->form == LDPC_C2V_NMS) LDPC_BLK_ES(FORM_NMS, false);
+    else if (pl.oms_lay) LDPC_BLK_ES(FORM_OMS, true);
+    else LDPC_BLK_ES(FORM_OMS, false);
+#undef LDPC_BLK_ES
+#undef LDPC_BLK_K
+    HIP_TRY(hipGetLastError());
+    return LDPC_OK;
+}
+
 }  // namespace
 
 // =========================================================================================== C ABI
@@ -1478,6 +1597,36 @@ int ldpc_graph_create(ldpc_graph **out, int32_t n, int32_t m, int32_t E, const i
                       const int32_t *var_idx)
 {
     LDPC_NOTHROW(graph_create_impl(out, n, m, E, check_ptr, var_idx))
+}
+
+static int graph_create_layered_impl(ldpc_graph **out, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                                     const int32_t *var_idx, int32_t n_layers, const int32_t *layer_ptr)
+{
+    if (!out) return fail(LDPC_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    {
+        HostGraph probe;                                             // validates the CSR before the partition reads it
+        if (int rc = graph_host_build(&probe, n, m, E, check_ptr, var_idx)) return rc;
+    }
+    const std::string bad = layer_partition_error(n, m, check_ptr, var_idx, n_layers, layer_ptr);
+    if (!bad.empty()) return fail(LDPC_ERR_ARG, "%s", bad.c_str());
+    if (int rc = graph_create_impl(out, n, m, E, check_ptr, var_idx)) return rc;
+    (*out)->h_layer_ptr.assign(layer_ptr, layer_ptr + n_layers + 1);
+    return LDPC_OK;
+}
+
+int ldpc_graph_create_layered(ldpc_graph **out, int32_t n, int32_t m, int32_t E, const int32_t *check_ptr,
+                              const int32_t *var_idx, int32_t n_layers, const int32_t *layer_ptr)
+{
+    LDPC_NOTHROW(graph_create_layered_impl(out, n, m, E, check_ptr, var_idx, n_layers, layer_ptr))
+}
+
+int ldpc_graph_layers(const ldpc_graph *g, int32_t *n_layers, int32_t *layer_ptr_out)
+{
+    if (!g || !n_layers) return fail(LDPC_ERR_ARG, "NULL argument");
+    *n_layers = g->h_layer_ptr.empty() ? 0 : (int32_t)g->h_layer_ptr.size() - 1;
+    if (layer_ptr_out && !g->h_layer_ptr.empty()) std::copy(g->h_layer_ptr.begin(), g->h_layer_ptr.end(), layer_ptr_out);
+    return LDPC_OK;
 }
 
 void ldpc_graph_destroy(ldpc_graph *g)
@@ -1636,6 +1785,7 @@ static int decoder_create_impl(ldpc_decoder **out, const ldpc_graph *g, const ld
     // the sum-product form has the two-sweep streaming engine only: no LDS-resident plan is built for it
     if (!rc && d->schedule == LDPC_SCHED_FLOODING && d->form != LDPC_C2V_SPA) rc = build_resident_plan(d, desc);
     if (!rc) rc = build_layered_plan(d, desc);
+    if (!rc) rc = build_block_plan(d, desc);
     if (rc) {
         ldpc_decoder_destroy(d);
         return rc;
@@ -1652,7 +1802,9 @@ int ldpc_decoder_create(ldpc_decoder **out, const ldpc_graph *g, const ldpc_deco
 int ldpc_decoder_set_mode(ldpc_decoder *d, int32_t mode)
 {
     if (!d) return fail(LDPC_ERR_ARG, "NULL decoder");
-    if (mode < LDPC_MODE_AUTO || mode > LDPC_MODE_PAIR) return fail(LDPC_ERR_ARG, "bad mode");
+    if (mode < LDPC_MODE_AUTO || mode > LDPC_MODE_BLOCK) return fail(LDPC_ERR_ARG, "bad mode");
+    if (mode == LDPC_MODE_BLOCK && !d->blk_ok)
+        return fail(LDPC_ERR_UNSUPPORTED, "LDPC_MODE_BLOCK: %s", d->blk_why.c_str());
     if (d->form == LDPC_C2V_SPA && (mode == LDPC_MODE_RESIDENT || mode == LDPC_MODE_GATHER || mode == LDPC_MODE_PAIR))
         return fail(LDPC_ERR_UNSUPPORTED, "the sum-product form (LDPC_C2V_SPA) has the two-sweep streaming engine only "
                                           "(LDPC_MODE_AUTO / STREAM / SWEEPS): no LDS-resident, fused or code-pair form");
@@ -1677,6 +1829,7 @@ int ldpc_decoder_info(const ldpc_decoder *d, int32_t out4[4])
     out4[3] = d->res_ok ? (int32_t)d->res_lds : 0;
     if (d->resc_ok) { out4[2] = kResCptThreads; out4[3] = (int32_t)d->resc_lds; }   // the fixed-T decode's compact geometry
     if (d->lay_ok) { out4[1] = d->lay.cw; out4[2] = kWave; out4[3] = (int32_t)d->lay_lds; }   // layered: codewords per (one-wave) workgroup
+    if (use_block(d)) { out4[0] = LDPC_MODE_BLOCK; out4[1] = d->blk.G; out4[2] = d->blk_threads; out4[3] = (int32_t)d->blk_lds; }
     return LDPC_OK;
 }
 
@@ -1692,6 +1845,7 @@ int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alph
         HIP_TRY(hipMemcpyAsync(d->beta, beta, rows * d->n_beta * es, hipMemcpyHostToDevice, s));
         beta_table_flags(d, beta);
         if (int rc = gather_layered_beta(d, s)) return rc;
+        if (int rc = gather_block_tables(d, true, false, s)) return rc;
     }
     if (alpha) {
         HIP_TRY(hipMemcpyAsync(d->alpha, alpha, rows * d->n_alpha * es, hipMemcpyHostToDevice, s));
@@ -1701,6 +1855,7 @@ int ldpc_decoder_set_weights(ldpc_decoder *d, const void *beta, const void *alph
         if (!d->oms_alpha) return fail(LDPC_ERR_ARG, "decoder was created without oms_alpha");
         HIP_TRY(hipMemcpyAsync(d->oms_alpha, oms_alpha, rows * d->n_oms_alpha * es, hipMemcpyHostToDevice, s));
         if (int rc = gather_layered_oms(d, s)) return rc;
+        if (int rc = gather_block_tables(d, false, true, s)) return rc;
     }
     return LDPC_OK;
 }
@@ -1740,6 +1895,8 @@ void ldpc_decoder_destroy(ldpc_decoder *d)
     for (void *p : d->res_bufs) (void)hipFree(p);
     (void)hipFree(d->gat_meta); (void)hipFree(d->gat_nbr); (void)hipFree(d->lay_off);
     (void)hipFree(d->lay_slot); (void)hipFree(d->lay_beta); (void)hipFree(d->lay_oms_slot); (void)hipFree(d->lay_oms);
+    (void)hipFree(d->blk_layer_ptr); (void)hipFree(d->blk_entry_base); (void)hipFree(d->blk_deg); (void)hipFree(d->blk_off);
+    (void)hipFree(d->blk_slot); (void)hipFree(d->blk_beta); (void)hipFree(d->blk_oms_slot); (void)hipFree(d->blk_oms);
     (void)hipFree(d->beta_inv_ptr); (void)hipFree(d->beta_inv_items); (void)hipFree(d->alpha_inv_ptr);
     (void)hipFree(d->alpha_inv_items); (void)hipFree(d->oms_inv_ptr); (void)hipFree(d->oms_inv_items);
     delete d;
@@ -1748,7 +1905,7 @@ void ldpc_decoder_destroy(ldpc_decoder *d)
 size_t ldpc_decoder_workspace_bytes(const ldpc_decoder *d, int64_t batch)
 {
     if (!d || batch < 0) return 0;
-    if (use_resident(d) || use_layered_lds(d)) return kAlign;   // the LDS-resident engines keep their state in LDS
+    if (use_resident(d) || use_layered_lds(d) || use_block(d)) return kAlign;   // the LDS-resident engines keep their state in LDS
     return carve(d, batch, nullptr).total;
 }
 
@@ -1764,6 +1921,8 @@ int ldpc_decode(const ldpc_decoder *d, const void *llr, int64_t batch, int32_t e
     if (((uintptr_t)workspace % kAlign) != 0) return fail(LDPC_ERR_ARG, "workspace must be %zu-byte aligned", kAlign);
     if (use_resident(d))
         return decode_resident(d, llr, batch, early_stop, bits, posterior, iterations, success, packed_bits, nullptr, stream);
+    if (use_block(d))
+        return decode_block(d, llr, batch, early_stop, bits, posterior, iterations, success, packed_bits, stream);
     if (use_layered_lds(d))
         return decode_layered_lds(d, llr, batch, early_stop, bits, posterior, iterations, success, packed_bits, stream);
     const Workspace w = carve(d, batch, workspace);
@@ -1832,7 +1991,7 @@ int ldpc_debug_min2(const float *values, int64_t rows, int32_t d, float *m12_cha
 int ldpc_debug_workspace_layout(const ldpc_decoder *d, int64_t batch, int32_t max_iterations, int64_t out8[8])
 {
     if (!d || !out8 || batch <= 0) return fail(LDPC_ERR_ARG, "bad argument");
-    if (use_resident(d) || use_layered_lds(d)) return fail(LDPC_ERR_ARG, "workspace layout exists only in LDPC_MODE_STREAM");
+    if (use_resident(d) || use_layered_lds(d) || use_block(d)) return fail(LDPC_ERR_ARG, "workspace layout exists only in LDPC_MODE_STREAM");
     char *base = reinterpret_cast<char *>(kAlign);   // any non-null base: only differences are used
     const Workspace w = carve(d, batch, base);
     out8[0] = w.vec; out8[1] = w.tiles;
@@ -1965,7 +2124,7 @@ int ldpc_debug_boundary_kernels(const ldpc_decoder *d, int64_t batch, int32_t ma
     if (batch <= 0) return fail(LDPC_ERR_ARG, "batch must be >= 1");
     if (saving) {
         if (int rc = train_supported(d)) return rc;                   // ldpc_decode_saving streams whatever the mode
-    } else if (use_resident(d) || use_layered_lds(d))
+    } else if (use_resident(d) || use_layered_lds(d) || use_block(d))
         return fail(LDPC_ERR_UNSUPPORTED, "the LDS-resident kernels read and write the caller's rows element by element");
     IterCap cap(max_iterations > 0 ? max_iterations : INT_MAX);      // as ldpc_decode_capped; <= 0: the decoder's T
     const BoundaryKernels k = boundary_kernels(d, pick_vec(d, batch), capped_T(d), saving != 0, llr, posterior, bits);
@@ -1974,11 +2133,34 @@ int ldpc_debug_boundary_kernels(const ldpc_decoder *d, int64_t batch, int32_t ma
     return LDPC_OK;
 }
 
+static int debug_layer_plan_impl(int32_t n, int32_t m, int32_t E, const int32_t *check_ptr, const int32_t *var_idx,
+                                 int32_t n_layers, const int32_t *layer_ptr, int32_t kind, int64_t out8[8])
+{
+    if (!out8) return fail(LDPC_ERR_ARG, "NULL argument");
+    if (kind != kBlkMinSum && kind != kBlkRcq) return fail(LDPC_ERR_ARG, "kind must be 0 (min-sum) or 1 (RCQ)");
+    HostGraph probe;
+    if (int rc = graph_host_build(&probe, n, m, E, check_ptr, var_idx)) return rc;
+    const std::string bad = layer_partition_error(n, m, check_ptr, var_idx, n_layers, layer_ptr);
+    if (!bad.empty()) return fail(LDPC_ERR_ARG, "%s", bad.c_str());
+    const LayerPlan p = layer_plan(n, m, check_ptr, var_idx, n_layers, layer_ptr, kind);
+    std::fill(out8, out8 + 8, (int64_t)0);
+    if (!p.ok) { (void)fail(LDPC_OK, "%s", p.why.c_str()); return LDPC_OK; }
+    const int64_t out[8] = {1, p.G, p.lpc, p.threads, (int64_t)p.lds_bytes, (int64_t)p.row_words, p.entries, p.W};
+    std::copy(out, out + 8, out8);
+    return LDPC_OK;
+}
+
+int ldpc_debug_layer_plan(int32_t n, int32_t m, int32_t E, const int32_t *check_ptr, const int32_t *var_idx,
+                          int32_t n_layers, const int32_t *layer_ptr, int32_t kind, int64_t out8[8])
+{
+    LDPC_NOTHROW(debug_layer_plan_impl(n, m, E, check_ptr, var_idx, n_layers, layer_ptr, kind, out8))
+}
+
 int ldpc_debug_launch_geometry(const ldpc_decoder *d, int64_t batch, int64_t out8[8])
 {
     if (!d || !out8) return fail(LDPC_ERR_ARG, "NULL argument");
     if (batch <= 0) return fail(LDPC_ERR_ARG, "batch must be >= 1");
-    if (use_resident(d) || use_layered_lds(d))
+    if (use_resident(d) || use_layered_lds(d) || use_block(d))
         return fail(LDPC_ERR_UNSUPPORTED, "the LDS-resident kernels have no tiles: launch geometry exists only on the streaming engine");
     const Workspace w = carve(d, batch, nullptr);
     const bool flooding = d->schedule == LDPC_SCHED_FLOODING;      // the layered kernels check the syndrome themselves
@@ -2004,7 +2186,7 @@ int ldpc_debug_sweep(const ldpc_decoder *d, int64_t batch, int32_t which, int32_
 {
     if (!d || !workspace || batch <= 0) return fail(LDPC_ERR_ARG, "bad argument");
     if (iter < 0 || iter >= d->T) return fail(LDPC_ERR_ARG, "iter outside [0, T)");
-    if (use_resident(d) || use_layered_lds(d)) return fail(LDPC_ERR_ARG, "debug sweeps need LDPC_MODE_STREAM");
+    if (use_resident(d) || use_layered_lds(d) || use_block(d)) return fail(LDPC_ERR_ARG, "debug sweeps need LDPC_MODE_STREAM");
     const Workspace w = carve(d, batch, workspace);
     if (w.total > workspace_bytes) return fail(LDPC_ERR_WORKSPACE, "workspace too small");
     DeviceGuard guard(d->g->device);

@@ -453,8 +453,14 @@ class _NativeGraph:
         with torch.cuda.device(device):
             cp = np.ascontiguousarray(graph.check_ptr, dtype=np.int32)
             vi = np.ascontiguousarray(graph.var_idx, dtype=np.int32)
-            nat.check(lib.ldpc_graph_create(C.byref(self.handle), graph.n, graph.m, graph.E,
-                                            nat.ptr(cp), nat.ptr(vi)), "ldpc_graph_create")
+            lp = getattr(graph, "layer_ptr", None)
+            if lp is None:
+                nat.check(lib.ldpc_graph_create(C.byref(self.handle), graph.n, graph.m, graph.E,
+                                                nat.ptr(cp), nat.ptr(vi)), "ldpc_graph_create")
+            else:       # a graph that declares layers (TannerGraph.with_layers): the block-parallel layered kernel may run on it
+                lp = np.ascontiguousarray(lp, dtype=np.int32)
+                nat.check(lib.ldpc_graph_create_layered(C.byref(self.handle), graph.n, graph.m, graph.E, nat.ptr(cp),
+                                                        nat.ptr(vi), lp.size - 1, nat.ptr(lp)), "ldpc_graph_create_layered")
         self._lib = lib
 
     def __del__(self):
@@ -655,14 +661,15 @@ class DecodeEngine:
 
     # ------------------------------------------------------------------ engine choice
     _MODES = {"auto": nat.MODE_AUTO, "stream": nat.MODE_STREAM, "resident": nat.MODE_RESIDENT, "sweeps": nat.MODE_SWEEPS,
-              "gather": nat.MODE_GATHER, "pair": nat.MODE_PAIR}
+              "gather": nat.MODE_GATHER, "pair": nat.MODE_PAIR, "block": nat.MODE_BLOCK}
 
     def set_mode(self, mode: str):
         """'auto' (LDS-resident fused kernel when the code qualifies, else streaming), 'stream' (HBM-streaming
         engine; fp32 RCQ decoders run its cheapest applicable form: 1-byte codes both ways ('pair'), else the fused
         one-kernel-per-iteration form ('gather')), 'sweeps' (streaming, always one kernel per sweep with fp32
         variable->check rows), 'gather' / 'pair' (force that RCQ form; error when the decoder does not qualify),
-        'resident' -- every choice gives identical results."""
+        'resident', 'block' (the block-parallel layered kernel: a layered decoder on a graph that declares layers; error
+        otherwise) -- every choice gives identical results."""
         nat.check(self._lib.ldpc_decoder_set_mode(self.handle, self._MODES[mode]), "ldpc_decoder_set_mode")
         with self._ws_lock:
             self._ws.clear()
@@ -671,15 +678,16 @@ class DecodeEngine:
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.int32)
         nat.check(self._lib.ldpc_decoder_info(self.handle, nat.ptr(out)), "ldpc_decoder_info")
-        resident = int(out[0]) == nat.MODE_RESIDENT
+        block = int(out[0]) == nat.MODE_BLOCK          # LDS-resident too: the block-parallel layered kernel
+        resident = int(out[0]) == nat.MODE_RESIDENT or block
         if self.schedule == nat.SCHED_FLOODING:
             kernel = "resident" if resident else {3: "sweeps", 4: "cn_gather", 5: "code_pair"}[int(out[0])]
         else:   # the layered schedules: LDS-resident walk (ldpc_layered.hip) or the HBM-streaming one (layered_rcq / layered_minsum)
             paper = self.schedule == nat.SCHED_LAYERED
             if self.c2v_form != nat.C2V_RCQ:      # the min-sum forms: check records in LDS, or fp32 messages in HBM
-                kernel = "layered_minsum_lds" if resident else "layered_minsum"
+                kernel = "layered_block_lds" if block else "layered_minsum_lds" if resident else "layered_minsum"
             else:
-                kernel = ("layered_paper_lds" if paper else "layered_lds") if resident else \
+                kernel = "layered_block_lds" if block else ("layered_paper_lds" if paper else "layered_lds") if resident else \
                          ("layered_rcq<paper>" if paper else "layered_rcq<ref>")
         # workgroups per CU as LDS (160 KiB) and the wave slots (32 per CU) allow; 0 on the streaming engine
         threads, lds = int(out[2]), int(out[3])
@@ -700,8 +708,11 @@ class DecodeEngine:
         if resident and self.schedule == nat.SCHED_FLOODING:
             kernels = {"fixed_T": self._resident_kernel(False), "early_stop": self._resident_kernel(True)}
         form = {nat.C2V_NMS: "NMS", nat.C2V_RCQ: "RCQ", nat.C2V_OMS: "OMS", nat.C2V_SPA: "SPA"}[self.c2v_form]
-        return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream"}[int(out[0])], "kernel": kernel, "form": form,
-                "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair"}[int(out[0])],
+        n_layers = C.c_int32(0)
+        nat.check(self._lib.ldpc_graph_layers(self._ng.handle, C.byref(n_layers), None), "ldpc_graph_layers")
+        return {"engine": {2: "resident", 3: "stream", 4: "stream", 5: "stream", 6: "resident"}[int(out[0])], "kernel": kernel, "form": form,
+                "stream_form": {2: None, 3: "two-sweeps", 4: "fused-rcq-iteration", 5: "rcq-code-pair", 6: None}[int(out[0])],
+                "layers": int(n_layers.value),
                 "codewords_per_workgroup": int(out[1]),
                 "threads_per_workgroup": threads, "lds_bytes": lds, "workgroups_per_cu": per_cu,
                 "compact_plan": plan, "resident_kernel": kernels}

@@ -16,6 +16,10 @@ has to preserve -- the *neighbour order*:
 
 Edge ids are CSR positions.  ``csc_edge[var_ptr[j] + k]`` is the CSR edge id of
 the k-th (ascending check index) neighbour of variable ``j``.
+
+Layers (optional): ``layer_ptr`` partitions the checks into runs of consecutive checks in CSR order whose variable
+sets are pairwise disjoint.  The checks of such a run may be updated in any order, or all at once, by a layered decoder
+(the block-parallel kernel, csrc/ldpc_layered_block.hip); a graph without ``layer_ptr`` behaves as it always did.
 """
 
 from __future__ import annotations
@@ -27,7 +31,7 @@ class TannerGraph:
     """Immutable CSR+CSC view of a binary parity-check matrix (host, int32)."""
 
     __slots__ = ("n", "m", "E", "check_ptr", "var_idx", "var_ptr", "csc_edge",
-                 "check_of_edge", "dc", "dv", "__weakref__")
+                 "check_of_edge", "dc", "dv", "layer_ptr", "__weakref__")
 
     def __init__(self, n: int, m: int, rows: np.ndarray, cols: np.ndarray):
         rows = np.asarray(rows, dtype=np.int64).ravel()
@@ -48,6 +52,7 @@ class TannerGraph:
         if E >= 2**31 - 1:
             raise ValueError("too many edges for int32 edge ids")
         self.n, self.m, self.E = int(n), int(m), E
+        self.layer_ptr = None        # int32 [L + 1] when the graph declares layers (with_layers)
         self.dc = np.bincount(rows, minlength=m).astype(np.int32)
         self.dv = np.bincount(cols, minlength=n).astype(np.int32)
         self.check_ptr = np.zeros(m + 1, dtype=np.int32)
@@ -76,6 +81,40 @@ class TannerGraph:
         m = check_ptr.size - 1
         rows = np.repeat(np.arange(m, dtype=np.int64), np.diff(check_ptr))
         return cls(n, m, rows, np.asarray(var_idx, dtype=np.int64))
+
+    # ------------------------------------------------------------------ layers
+    def with_layers(self, layer_ptr) -> "TannerGraph":
+        """A graph with the same edges that declares the layers ``layer_ptr`` (int [L + 1], from 0 to m, strictly
+        ascending): layer l is the checks layer_ptr[l] .. layer_ptr[l + 1] - 1, and no two of them share a variable.
+        ValueError for a malformed pointer, and for a shared variable (the message names the first offending layer and
+        the variable)."""
+        lp = np.asarray(layer_ptr)
+        if lp.ndim != 1 or lp.size < 1 or not np.issubdtype(lp.dtype, np.integer):
+            raise ValueError("layer_ptr must be a 1-D integer array [L + 1]")
+        lp = lp.astype(np.int64)
+        if lp[0] != 0 or lp[-1] != self.m:
+            raise ValueError(f"layer_ptr must start at 0 and end at m = {self.m}, got {int(lp[0])} .. {int(lp[-1])}")
+        if np.any(np.diff(lp) <= 0):
+            bad = int(np.flatnonzero(np.diff(lp) <= 0)[0])
+            raise ValueError(f"layer_ptr must be strictly ascending (layer {bad} is empty or reversed)")
+        for l in range(lp.size - 1):
+            vs = self.var_idx[self.check_ptr[lp[l]]:self.check_ptr[lp[l + 1]]]
+            if vs.size > 1:
+                srt = np.sort(vs)
+                dup = np.flatnonzero(srt[1:] == srt[:-1])
+                if dup.size:
+                    raise ValueError(f"layer {l} (checks {int(lp[l])} .. {int(lp[l + 1]) - 1}) is not variable-disjoint: "
+                                     f"variable {int(srt[dup[0]])} is in two of its checks")
+        g = TannerGraph.__new__(TannerGraph)
+        for name in TannerGraph.__slots__:
+            if name not in ("__weakref__", "layer_ptr"):
+                setattr(g, name, getattr(self, name))
+        g.layer_ptr = lp.astype(np.int32)
+        return g
+
+    @property
+    def n_layers(self) -> int:
+        return 0 if self.layer_ptr is None else int(self.layer_ptr.size - 1)
 
     # ------------------------------------------------------------------ helpers
     def to_dense(self, dtype=np.int8) -> np.ndarray:
@@ -118,3 +157,22 @@ class TannerGraph:
                 for b in range(a + 1, len(vs)):
                     cnt[(int(vs[a]), int(vs[b]))] += 1
         return sum(1 for v in cnt.values() if v >= 2)
+
+
+def disjoint_runs(graph: TannerGraph) -> np.ndarray:
+    """The greedy partition of the checks, in CSR order, into maximal runs of consecutive variable-disjoint checks: a new
+    layer starts at the first check that shares a variable with one of the current run.  -> layer_ptr int32 [L + 1]
+    (``graph.with_layers(disjoint_runs(graph))`` opts any graph in; on an IRA staircase every run has length 1).
+    Deterministic; an empty graph gives [0]."""
+    stamp = np.full(graph.n, -1, dtype=np.int64)       # layer that last touched the variable
+    ptr = [0]
+    layer = 0
+    for i in range(graph.m):
+        vs = graph.var_idx[graph.check_ptr[i]:graph.check_ptr[i + 1]]
+        if i > ptr[-1] and np.any(stamp[vs] == layer):
+            ptr.append(i)
+            layer += 1
+        stamp[vs] = layer
+    if graph.m:
+        ptr.append(graph.m)
+    return np.asarray(ptr, dtype=np.int32)

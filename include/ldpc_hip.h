@@ -107,7 +107,11 @@ enum {
  * edge -- from which each lane recomputes R; same qualification as above) and streaming (R as fp32 per edge in the workspace).
  * Gradients: ldpc_train_joint_layered (posterior joint training with a posterior-local gradient, below) and nothing else --
  * ldpc_decode_saving, ldpc_backward and ldpc_train_joint return LDPC_ERR_UNSUPPORTED.  LAYERED_REF with these forms is
- * unsupported (the reference has no such path), as is a float64 layered decoder. */
+ * unsupported (the reference has no such path), as is a float64 layered decoder.
+ * LAYERED on a graph that declares layers (ldpc_graph_create_layered) has a third kernel with the same results, the
+ * block-parallel one (LDPC_MODE_BLOCK): the checks of a layer share no variable, so it updates them all at once -- its dependent chain
+ * per iteration is the number of layers, not the number of checks.  All three forms (NMS, OMS, RCQ weighted or not); LAYERED_REF,
+ * sum-product and float64 do not have it. */
 enum { LDPC_SCHED_FLOODING = 0, LDPC_SCHED_LAYERED_REF = 1, LDPC_SCHED_LAYERED = 2 };
 
 typedef struct ldpc_graph ldpc_graph;      /* Tanner graph, CSR + CSC, device resident */
@@ -119,6 +123,17 @@ typedef struct ldpc_decoder ldpc_decoder;  /* graph + weight tables + quantiser 
  * ascending inside a check.  The CSC permutation is derived inside. */
 int ldpc_graph_create(ldpc_graph **out, int32_t n, int32_t m, int32_t n_edges,
                       const int32_t *check_ptr, const int32_t *var_idx);
+/* ldpc_graph_create plus a partition of the checks into LAYERS: layer l is the checks layer_ptr[l] .. layer_ptr[l + 1] - 1
+ * (layer_ptr [n_layers + 1] host memory, from 0 to m, strictly ascending), consecutive in CSR order and pairwise
+ * variable-disjoint -- the block rows of a quasi-cyclic code, or any code after a layer ordering of its checks.  LDPC_ERR_ARG
+ * for a malformed layer_ptr and for a layer two of whose checks share a variable (the message names the layer and the
+ * variable).  The graph decodes exactly as one made by ldpc_graph_create under every mode that exists there; the layers
+ * are read by LDPC_MODE_BLOCK only. */
+int ldpc_graph_create_layered(ldpc_graph **out, int32_t n, int32_t m, int32_t n_edges,
+                              const int32_t *check_ptr, const int32_t *var_idx,
+                              int32_t n_layers, const int32_t *layer_ptr);
+/* *n_layers = the number of declared layers (0: created without); layer_ptr_out: NULL or room for n_layers + 1 entries */
+int ldpc_graph_layers(const ldpc_graph *g, int32_t *n_layers, int32_t *layer_ptr_out);
 void ldpc_graph_destroy(ldpc_graph *g);
 /* n, m, E, max check degree, max variable degree */
 int ldpc_graph_info(const ldpc_graph *g, int32_t out5[5]);
@@ -166,11 +181,19 @@ int ldpc_decoder_create(ldpc_decoder **out, const ldpc_graph *g, const ldpc_deco
  *   RESIDENT : one fused kernel, messages in LDS for all T iterations; fp32 codes with
  *              dv <= 8 whose state fits 160 KiB of LDS (e.g. the (1998,1512) code); for the layered schedule: the
  *              LDS-resident layered kernel (see LDPC_SCHED_LAYERED_REF)
- * AUTO (default) takes RESIDENT when the code qualifies, else STREAM. */
+ *   BLOCK    : the block-parallel layered kernel: LDPC_SCHED_LAYERED, fp32, on a graph created with layers
+ *              (ldpc_graph_create_layered) whose checks have at most 64 edges and whose per-codeword state (posteriors and
+ *              check records or message codes) fits LDS.  G codewords per workgroup in LDS, a thread per check of the current
+ *              layer and codeword, one barrier per layer.  LDPC_ERR_UNSUPPORTED, with the reason, for a graph without layers,
+ *              a float64 decoder, another schedule and a state that does not fit.  RESIDENT keeps meaning the sequential
+ *              LDS kernels and STREAM the streaming walk on such a graph too.
+ * AUTO (default) takes RESIDENT when the code qualifies, else STREAM.  AUTO never takes BLOCK: measured, it wins from a mean
+ * layer size of 16 on quasi-cyclic codes (5x at Z = 81) but loses on a layer-ordered irregular code at 24, so no threshold on
+ * the layer size alone is safe yet (DESIGN.md 3f'); ask for it with LDPC_MODE_BLOCK. */
 enum { LDPC_MODE_AUTO = 0, LDPC_MODE_STREAM = 1, LDPC_MODE_RESIDENT = 2, LDPC_MODE_SWEEPS = 3, LDPC_MODE_GATHER = 4,
-       LDPC_MODE_PAIR = 5 };
+       LDPC_MODE_PAIR = 5, LDPC_MODE_BLOCK = 6 };
 int ldpc_decoder_set_mode(ldpc_decoder *d, int32_t mode);
-/* out4 = { engine and form a decode would use now (LDPC_MODE_RESIDENT, or the streaming form LDPC_MODE_PAIR /
+/* out4 = { engine and form a decode would use now (LDPC_MODE_RESIDENT, LDPC_MODE_BLOCK, or the streaming form LDPC_MODE_PAIR /
  * LDPC_MODE_GATHER / LDPC_MODE_SWEEPS), codewords per workgroup, threads per
  * workgroup, LDS bytes per workgroup } -- the last three 0 when the code does not qualify; the geometry of a
  * fixed-iteration decode where it has one of its own (the compact resident kernel) */

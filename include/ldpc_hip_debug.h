@@ -133,6 +133,14 @@ int ldpc_debug_min2(const float *values, int64_t rows, int32_t d, float *m12_cha
 int ldpc_debug_philox(uint32_t *out4, int64_t count, uint64_t seed, uint32_t stream_id, uint64_t first_frame,
                       int32_t quads_per_frame, void *stream);
 
+/* The block-parallel layered decode's planner (csrc/ldpc_layer_plan.h) on a bare graph and layer partition; host only, no
+ * device is touched.  kind 0: the min-sum forms (check records), 1: RCQ (code bytes).  LDPC_ERR_ARG for an invalid CSR or
+ * partition.  out8 = { qualifies, codewords per workgroup, lanes per codeword, threads per workgroup, LDS bytes per
+ * workgroup, dwords of a codeword's row, plan entries, mask words per check record } -- the geometry ldpc_decoder_info
+ * reports under LDPC_MODE_BLOCK; all but the first 0 when the code does not qualify (ldpc_last_error says why). */
+int ldpc_debug_layer_plan(int32_t n, int32_t m, int32_t n_edges, const int32_t *check_ptr, const int32_t *var_idx,
+                          int32_t n_layers, const int32_t *layer_ptr, int32_t kind, int64_t out8[8]);
+
 #ifdef __cplusplus
 }
 #endif
